@@ -24,6 +24,13 @@ halo really travels over RCCL: a run that fell back to the host-staged transport
 `--weak` instead grows the system with N (--bodies per GPU, "scaling": "weak", `value` = N x global timesteps/s); the
 BBPGD iteration count grows with the system, which that line folds into what reads as a scaling curve -- so both lines
 also carry `constraint_updates_per_sec` (contacts x iterations per second), which does not.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, `--dump-outputs` if asked, the line
+(`roofline` and `cpu_baseline` are null).  `--full` adds everything else, as extra work after the timed steps or inside
+them: per-kernel HIP-event timing of the two sweeps in the timed steps and the roofline built on it (with the committed
+PMC traffic and a measured stream ceiling), the stage breakdown, the relaxed-packing figures, the CPU baseline, the
+narrow-phase arithmetic A/B of `--mixed`, the transport A/B and per-rank paths of N > 1.
+`--dump-outputs DIR` writes what the last timed step handed its caller as float64 .npy files (see dump_outputs).
 """
 import argparse
 import json
@@ -172,19 +179,25 @@ def measured_ceiling(roof, extra):
     return gbs
 
 
-def parse():
+def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure (roofline, stage breakdown, relaxed packing, CPU "
+                        "baseline, --mixed narrow-phase A/B, N > 1 transport A/B); off: set-up, warm-up, timed steps, line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64, a fixed "
+                        "seeded sample, original body numbering; single-GPU paths)")
     p.add_argument("--bodies", type=int, default=1_000_000, help="spherocylinders per GPU (default: configs[2])")
     p.add_argument("--buffer", type=float, default=0.1, help="search buffer added to every AABB")
     p.add_argument("--tol", type=float, default=1e-5)
     p.add_argument("--max-iters", type=int, default=10000)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--no-reorder", dest="reorder", action="store_false", help="skip the per-step Z-order reordering")
     p.add_argument("--reorder-cell", type=float, default=3.0, help="lattice edge of the Morton keys")
-    p.add_argument("--cpu-iters", type=int, default=12, help="BBPGD iterations timed on the host cores")
+    p.add_argument("--cpu-iters", type=int, default=12, help="--full: BBPGD iterations timed on the host cores")
     p.add_argument("--weak", action="store_true",
                    help="N > 1: --bodies rods PER GPU (one system of N x --bodies, weak scaling) instead of the default, "
                         "BASELINE configs[3] as written: ONE system of --bodies rods partitioned over the N GPUs")
@@ -197,7 +210,8 @@ def parse():
                    help="N > 1: the per-iteration velocity halo through grouped ncclSend / ncclRecv instead of the "
                         "node's IPC-mapped inboxes")
     p.add_argument("--no-transport-ab", action="store_true",
-                   help="N > 1: skip the untimed A/B of the transport mechanisms after the timed steps (`transport_ab`)")
+                   help="N > 1, --full: skip the untimed A/B of the transport mechanisms after the timed steps "
+                        "(`transport_ab`)")
     p.add_argument("--allow-host-transport", action="store_true",
                    help="print a line even when the halo is staged through host memory (gloo) instead of RCCL; "
                         "without it such a run exits with code 3")
@@ -208,8 +222,9 @@ def parse():
     p.add_argument("--cold-tier-any-size", action="store_true",
                    help="cold tier even below the size (1.5M contacts) from which it pays -- for tests of the accounting")
     p.add_argument("--relaxed-steps", type=int, default=2,
-                   help="N = 1: after the headline steps, advance the packing by this many full steps and time --steps "
-                        "more from THAT state (labelled `relaxed_packing`; SURVEY 8d.3 allows one relaxation pre-pass)")
+                   help="N = 1, --full: after the headline steps, advance the packing by this many full steps and time "
+                        "--steps more from THAT state (labelled `relaxed_packing`; SURVEY 8d.3 allows one relaxation "
+                        "pre-pass)")
     p.add_argument("--mixed", action="store_true",
                    help="BASELINE configs[4] instead of the headline workload: --bodies bodies, one third each spheres "
                         "(r 0.5), spherocylinders (r 0.5, L 2) and ellipsoids (0.8, 0.5, 0.4), random orientations, "
@@ -226,7 +241,12 @@ def parse():
     p.add_argument("--friction", type=float, default=None,
                    help="BUILD EXTENSION, parity unpinned: Coulomb coefficient of the cone-complementarity solver "
                         "(the reference has no frictional solver; default = its frictionless LCP).  N = 1 only.")
-    return p.parse_args()
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or args.distributed):
+        p.error("--dump-outputs covers the single-GPU paths only")
+    return args
 
 
 def launch_plan(gpus, env, argv, device_count=None):
@@ -256,6 +276,47 @@ def launch_plan(gpus, env, argv, device_count=None):
         port = sk.getsockname()[1]
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(gpus),
             "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
+
+
+DUMP_BODIES = 1 << 15            # bodies in the --dump-outputs sample
+DUMP_MAX_CONTACTS = 1_500_000    # contact rows (32 B each) at most: every dump stays under 64 MB
+DUMP_SEED = 20240613
+
+
+def dump_outputs(path, st, perm, last):
+    """--dump-outputs: what the last timed step handed its caller, in the ORIGINAL body numbering (the step's Z-order
+    permutation undone) and a canonical contact order, so that two builds of the project compare file for file.  A fixed,
+    seeded sample: DUMP_BODIES bodies and every contact that touches one of them (at most DUMP_MAX_CONTACTS rows, in
+    order).  All float64:
+      body_ids (S,)            the sampled bodies' original indices, ascending
+      center (S, 3), quat (S, 4)   their state after the step's Euler update
+      contact_pairs (K, 2)     (lower, higher) original indices of each contact, rows ascending
+      contact_sep (K,)         signed separation of the pair
+      contact_impulse (K,)     the solve's multiplier (normal impulse) of the pair
+      step (3,)                contacts, BBPGD iterations, residual of the step"""
+    os.makedirs(path, exist_ok=True)
+    n = st.center.shape[0]
+    dev = st.center.device
+    ids = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_BODIES), replace=False))
+    # perm[k] = original index of the body at position k; pos[i] = position of original body i
+    orig = torch.arange(n, device=dev) if perm is None else perm.long()
+    pos = torch.empty(n, dtype=torch.long, device=dev)
+    pos[orig] = torch.arange(n, device=dev)
+    at = pos[torch.from_numpy(ids).to(dev)]
+    out = {"body_ids": ids, "center": st.center[at].cpu().numpy(), "quat": st.quat[at].cpu().numpy()}
+    pairs = orig[st.contact_pairs.long()]
+    lo, hi = pairs.min(dim=1).values, pairs.max(dim=1).values
+    picked = torch.zeros(n, dtype=torch.bool, device=dev)
+    picked[torch.from_numpy(ids).to(dev)] = True
+    sel = torch.nonzero(picked[lo] | picked[hi]).flatten()
+    lo, hi = lo[sel].cpu().numpy(), hi[sel].cpu().numpy()
+    rows = np.lexsort((hi, lo))[:DUMP_MAX_CONTACTS]
+    out["contact_pairs"] = np.stack([lo[rows], hi[rows]], axis=1)
+    out["contact_sep"] = st.contacts["sep"][sel].cpu().numpy()[rows]
+    out["contact_impulse"] = st.lam[sel].cpu().numpy()[rows]
+    out["step"] = np.array([last.num_contacts, last.num_iters, last.residual])
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def main():
@@ -317,12 +378,14 @@ def main():
         stepper.tiering = 3
     pristine = stepper.snapshot()
     prof = dict(body_ms=0.0, con_ms=0.0, iters=0)
+    last = {}
 
     def one_step(timed_kernels, timed_stages=False):
         stepper.restore(pristine)
+        last["perm"] = None
         if args.reorder:
             # the synthetic input is in random order; the Z-order body reordering operator is part of the step
-            stepper.reorder_bodies(cell_size=args.reorder_cell, lo=[0.0, 0.0, 0.0])
+            last["perm"] = stepper.reorder_bodies(cell_size=args.reorder_cell, lo=[0.0, 0.0, 0.0])
         stepper.profile_next = timed_kernels
         st = stepper.step(integrate=True, force_rebuild=True, timed=timed_stages)
         if timed_kernels and args.friction is None:
@@ -345,24 +408,70 @@ def main():
         one_step(False)
     sync()
     t0 = time.perf_counter()
-    stats = [one_step(True) for _ in range(args.steps)]
+    stats = [one_step(args.full) for _ in range(args.steps)]   # --full: HIP-event timing of the sweeps (roofline)
     sync()
     elapsed = time.perf_counter() - t0
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, stepper, last["perm"], stats[-1])
 
+    contacts = stats[-1].num_contacts
+    iters = [s.num_iters for s in stats]
+    ms_per_step = 1e3 * elapsed / args.steps
+    value = world * args.steps / elapsed
+    roof, extra, relaxed, cpu, stage_ms = None, {}, None, None, None
+    if args.full:
+        roof, extra, relaxed, cpu, stage_ms = full_figures(args, b, stepper, pristine, prof, one_step, n, contacts,
+                                                           iters, dist)
+
+    if rank == 0:
+        out = {
+            "metric": METRIC,
+            "value": round(value, 4), "unit": "timesteps/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "configs[2]: %.3gM spherocylinders r=0.5 L=2 at 40%% volume fraction, random packing, "
+                                   "AABB+%.2g neighbour list, frictionless LCP tol %.0e" % (n / 1e6, args.buffer, args.tol),
+                       "bodies_per_gpu": n, "bodies_total": n, "contacts_per_gpu": contacts, "contacts_total": contacts,
+                       "bbpgd_iters_per_step": iters, "converged": [bool(s.converged) for s in stats],
+                       "parallelism": "single GPU (N > 1: the same system, hilbert domain decomposition with RCCL halo)"},
+            "contact_pairs_per_sec": round(world * contacts * args.steps / elapsed, 1),
+            "bbpgd_iterations_per_sec": round(world * sum(iters) / elapsed, 1),
+            # contacts x iterations per second: the rate that stays comparable when the iteration count changes
+            "constraint_updates_per_sec": round(world * contacts * sum(iters) / elapsed, 1),
+            "roofline": roof, "cpu_baseline": cpu,
+        }
+        if args.full:
+            out.update({
+                "stage_ms": {k: round(v, 3) for k, v in stage_ms.items()},
+                "relaxed_packing": relaxed,
+                # cold tier of the solve (time only, same iterates): share of contacts swept in full over the tiered
+                # iterations
+                "cold_tier": prof.get("tier"),
+            })
+        if args.friction is not None:  # never the default line: an extension without a reference to pin it on
+            out["metric"] = "timesteps/sec, 10^6 spherocylinders per GPU, FRICTIONAL cone-complementarity contact (build extension)"
+            out["config"]["workload"] = out["config"]["workload"].replace(
+                "frictionless LCP", "EXTENSION (parity unpinned): Coulomb friction mu = %g as a cone complementarity "
+                "problem (%s)," % (args.friction, args.friction_method.upper()))
+        out.update(extra)
+        print(json.dumps(out))
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def full_figures(args, b, stepper, pristine, prof, one_step, n, contacts, iters, dist):
+    """--full, after the timed steps of the headline line: the stage breakdown, the roofline of the two sweeps, the
+    relaxed-packing figures and the CPU baseline.  Returns (roofline, extra roofline entries, relaxed, cpu, stage_ms)."""
     # contacts the body sweep's masks flag at the end of the solve: not (x == 0 and 0 <= g < inf)
     active = None
     if args.friction is None and stepper.lam is not None and getattr(stepper, "grad", None) is not None:
         lam_t, g_t = stepper.lam, stepper.grad
         active = int((~((lam_t == 0) & (g_t >= 0) & torch.isfinite(g_t))).sum().item())
     stage_ms = one_step(False, timed_stages=True).timings_ms  # one extra, untimed step for the stage breakdown
-    contacts = stats[-1].num_contacts
-    iters = [s.num_iters for s in stats]
-    ms_per_step = 1e3 * elapsed / args.steps
-    value = world * args.steps / elapsed
 
     # ---- roofline of the dominant sweep of the fused BBPGD iteration (see kernel_bytes) -----------------------------
     roof, extra = None, {}
@@ -422,41 +531,11 @@ def main():
                                  "bbpgd_iters_per_step": [s.num_iters for s in tstats],
                                  "converged": [bool(s.converged) for s in tstats]}
 
-    # ---- CPU baseline: the oracle (CPU restatement of the reference path) on this box's host cores, rank 0 ---------
+    # ---- CPU baseline: the oracle (CPU restatement of the reference path) on this box's host cores ------------------
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline and args.friction is None:
+    if not args.no_cpu_baseline and args.friction is None:
         cpu = cpu_baseline(b, stepper, args, int(np.mean(iters)))
-
-    if rank == 0:
-        out = {
-            "metric": METRIC,
-            "value": round(value, 4), "unit": "timesteps/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "configs[2]: %.3gM spherocylinders r=0.5 L=2 at 40%% volume fraction, random packing, "
-                                   "AABB+%.2g neighbour list, frictionless LCP tol %.0e" % (n / 1e6, args.buffer, args.tol),
-                       "bodies_per_gpu": n, "bodies_total": n, "contacts_per_gpu": contacts, "contacts_total": contacts,
-                       "bbpgd_iters_per_step": iters, "converged": [bool(s.converged) for s in stats],
-                       "parallelism": "single GPU (N > 1: the same system, hilbert domain decomposition with RCCL halo)"},
-            "contact_pairs_per_sec": round(world * contacts * args.steps / elapsed, 1),
-            "bbpgd_iterations_per_sec": round(world * sum(iters) / elapsed, 1),
-            # contacts x iterations per second: the rate that stays comparable when the iteration count changes
-            "constraint_updates_per_sec": round(world * contacts * sum(iters) / elapsed, 1),
-            "roofline": roof, "cpu_baseline": cpu,
-            "stage_ms": {k: round(v, 3) for k, v in stage_ms.items()},
-            "relaxed_packing": relaxed,
-            # cold tier of the solve (time only, same iterates): share of contacts swept in full over the tiered iterations
-            "cold_tier": prof.get("tier"),
-        }
-        if args.friction is not None:  # never the default line: an extension without a reference to pin it on
-            out["metric"] = "timesteps/sec, 10^6 spherocylinders per GPU, FRICTIONAL cone-complementarity contact (build extension)"
-            out["config"]["workload"] = out["config"]["workload"].replace(
-                "frictionless LCP", "EXTENSION (parity unpinned): Coulomb friction mu = %g as a cone complementarity "
-                "problem (%s)," % (args.friction, args.friction_method.upper()))
-        out.update(extra)
-        print(json.dumps(out))
-    if dist is not None:
-        dist.destroy_process_group()
+    return roof, extra, relaxed, cpu, stage_ms
 
 
 def main_mixed(args, ops, pipeline, synth, dev):
@@ -473,11 +552,13 @@ def main_mixed(args, ops, pipeline, synth, dev):
         st.work_mapping = (args.xcd_tile, args.lanes_per_body)
     pristine = st.snapshot()
     prof = dict(body_ms=0.0, con_ms=0.0, iters=0)
+    last = {}
 
     def one_step(timed_kernels, timed_stages=False):
         st.restore(pristine)
+        last["perm"] = None
         if args.reorder:
-            st.reorder_bodies(cell_size=args.reorder_cell, lo=[0.0, 0.0, 0.0])
+            last["perm"] = st.reorder_bodies(cell_size=args.reorder_cell, lo=[0.0, 0.0, 0.0])
         st.profile_next = timed_kernels
         s = st.step(integrate=True, force_rebuild=True, timed=timed_stages)
         if timed_kernels:
@@ -493,14 +574,41 @@ def main_mixed(args, ops, pipeline, synth, dev):
         one_step(False)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    stats = [one_step(True) for _ in range(args.steps)]
+    stats = [one_step(args.full) for _ in range(args.steps)]   # --full: HIP-event timing of the sweeps (roofline)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, st, last["perm"], stats[-1])
+    contacts, iters = stats[-1].num_contacts, [s.num_iters for s in stats]
+    out = {
+        "metric": "timesteps/sec, 10^6 mixed sphere / spherocylinder / ellipsoid bodies, frictionless LCP contact (BBPGD)",
+        "value": round(args.steps / elapsed, 4), "unit": "timesteps/s", "n_gpus": 1, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "configs[4] on one GPU: %.3gM bodies, one third each spheres r=0.5, spherocylinders r=0.5 L=2, "
+                               "ellipsoids (0.8, 0.5, 0.4), random orientations, %.0f%% volume fraction, AABB+%.2g neighbour "
+                               "list, class-binned narrow phase (L-BFGS ellipsoid distances), frictionless LCP tol %.0e"
+                               % (n / 1e6, 100 * args.mixed_phi, args.buffer, args.tol),
+                   "bodies_per_gpu": n, "contacts_per_gpu": contacts, "bbpgd_iters_per_step": iters,
+                   "converged": [bool(s.converged) for s in stats], "parallelism": "single GPU"},
+        "contact_pairs_per_sec": round(contacts * args.steps / elapsed, 1),
+        "bbpgd_iterations_per_sec": round(sum(iters) / elapsed, 1),
+        "roofline": None, "cpu_baseline": None,
+    }
+    if args.full:
+        out.update(full_figures_mixed(args, ops, b, st, pristine, prof, one_step, n, contacts, iters))
+    out["ellipsoid_aabb"] = ("reference (centre -/+ q*radii, compute_aabb.hpp:82-103: not conservative for general "
+                             "orientations)")
+    print(json.dumps(out))
+
+
+def full_figures_mixed(args, ops, b, st, pristine, prof, one_step, n, contacts, iters):
+    """--full, after the timed steps of the --mixed line: stage breakdown, the fp64-vector roofline of the narrow phase
+    with both arithmetics side by side, the roofline of the two sweeps, the CPU baseline.  Returns the line's entries."""
     active = None   # contacts the body sweep's masks flag at the end of the solve (as in the headline line)
     if st.lam is not None and getattr(st, "grad", None) is not None:
         active = int((~((st.lam == 0) & (st.grad >= 0) & torch.isfinite(st.grad))).sum().item())
     stage_ms = one_step(False, timed_stages=True).timings_ms
-    contacts, iters = stats[-1].num_contacts, [s.num_iters for s in stats]
     # The narrow phase of this config is NOT bandwidth bound: the E-E class runs the reference's 9-start L-BFGS
     # shared-normal minimisation, ~10^3 objective evaluations per pair (S-E and R-E, build extensions without a reference
     # routine, are closed-form since round 3 and report no evaluations).  Its roofline is the fp64 vector rate:
@@ -553,26 +661,13 @@ def main_mixed(args, ops, pipeline, synth, dev):
             attach_traffic(roof, extra, dom, oth, n, args.buffer, name="traffic_mixed.json")
         measured_ceiling(roof, extra)
     out = {
-        "metric": "timesteps/sec, 10^6 mixed sphere / spherocylinder / ellipsoid bodies, frictionless LCP contact (BBPGD)",
-        "value": round(args.steps / elapsed, 4), "unit": "timesteps/s", "n_gpus": 1, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "configs[4] on one GPU: %.3gM bodies, one third each spheres r=0.5, spherocylinders r=0.5 L=2, "
-                               "ellipsoids (0.8, 0.5, 0.4), random orientations, %.0f%% volume fraction, AABB+%.2g neighbour "
-                               "list, class-binned narrow phase (L-BFGS ellipsoid distances), frictionless LCP tol %.0e"
-                               % (n / 1e6, 100 * args.mixed_phi, args.buffer, args.tol),
-                   "bodies_per_gpu": n, "contacts_per_gpu": contacts, "bbpgd_iters_per_step": iters,
-                   "converged": [bool(s.converged) for s in stats], "parallelism": "single GPU"},
-        "contact_pairs_per_sec": round(contacts * args.steps / elapsed, 1),
-        "bbpgd_iterations_per_sec": round(sum(iters) / elapsed, 1),
         "roofline": roof,
         "cpu_baseline": None if args.no_cpu_baseline else cpu_baseline_mixed(b, st, pristine, args, int(np.mean(iters))),
         "stage_ms": {k: round(v, 3) for k, v in stage_ms.items()},
         "narrow_phase_roofline": ell_roof,
-        "ellipsoid_aabb": "reference (centre -/+ q*radii, compute_aabb.hpp:82-103: not conservative for general orientations)",
     }
     out.update(extra)
-    print(json.dumps(out))
+    return out
 
 
 def transport_ab(st, comm, dist, one_step, rank, world, steps=2):
@@ -693,7 +788,7 @@ def main_distributed(args, rank, world, dist, ops, synth, dev):
         one_step(False)
     sync()
     t0 = time.perf_counter()
-    stats = [one_step(True) for _ in range(args.steps)]
+    stats = [one_step(args.full) for _ in range(args.steps)]   # --full: per-phase and per-sweep timing (roofline)
     sync()
     elapsed = time.perf_counter() - t0
     t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
@@ -715,8 +810,9 @@ def main_distributed(args, rank, world, dist, ops, synth, dev):
                                              kin="rigid" if args.mixed else "rod")
     timed_prof = dict(st.prof)
     timed_phase_ms = dict(st.phase_ms)
-    paths = [None] * world   # what every rank's solve actually used during the timed steps
-    dist.all_gather_object(paths, (timed_prof.get("halo_path", "?"), timed_prof.get("record_path", "?")))
+    paths = [None] * world   # what every rank's solve actually used during the timed steps (--full: profiled)
+    if args.full:
+        dist.all_gather_object(paths, (timed_prof.get("halo_path", "?"), timed_prof.get("record_path", "?")))
 
     def finish(ab):
         if rank == 0:
@@ -754,25 +850,28 @@ def main_distributed(args, rank, world, dist, ops, synth, dev):
                        "transport": comm.transport,
                        # the per-iteration 5-double record: slots in the ranks' device memory, or the transport's all-gather
                        "reduction_records": "mailbox" if comm.mailbox else "all-gather",
-                       "velocity_halo": "IPC-mapped inboxes" if comm.halo_ipc_active() else "grouped send / recv",
-                       # ... and what the library reports every rank's solves USED in the timed steps
-                       "paths_active_per_rank": [{"halo": h, "records": r} for h, r in paths]},
+                       "velocity_halo": "IPC-mapped inboxes" if comm.halo_ipc_active() else "grouped send / recv"},
             "contact_pairs_per_sec": round(contacts_global * args.steps / elapsed, 1),
             "bbpgd_iterations_per_sec": round(sum(iters) / elapsed, 1),
             # contacts x iterations per second over all ranks: separates the growth of the BBPGD iteration count with
             # the system size (algorithmic) from what the halo and the all-gather cost per iteration
             "constraint_updates_per_sec": round(contacts_global * sum(iters) / elapsed, 1),
-            "halo_wait_ms_per_iteration": round(timed_prof.get("halo_wait_ms", 0.0) / max(1, timed_prof["iters"]), 4),
-            "record_ms_per_iteration": round(timed_prof.get("record_ms", 0.0) / max(1, timed_prof["iters"]), 4),
-            # host wall time per phase of the last step on rank 0 (each phase ends with a device sync)
-            "stage_ms": {k: round(v, 3) for k, v in timed_phase_ms.items() if k != "start"},
             "roofline": roof, "cpu_baseline": None,
         }
+        if args.full:
+            # ... and what the library reports every rank's solves USED in the timed steps
+            out["config"]["paths_active_per_rank"] = [{"halo": h, "records": r} for h, r in paths]
+            out.update({
+                "halo_wait_ms_per_iteration": round(timed_prof.get("halo_wait_ms", 0.0) / max(1, timed_prof["iters"]), 4),
+                "record_ms_per_iteration": round(timed_prof.get("record_ms", 0.0) / max(1, timed_prof["iters"]), 4),
+                # host wall time per phase of the last step on rank 0 (each phase ends with a device sync)
+                "stage_ms": {k: round(v, 3) for k, v in timed_phase_ms.items() if k != "start"},
+            })
         out.update(extra)
     # ---- untimed: the transport mechanisms side by side.  The line must come out whatever happens in here (this is the
     # first code that ever runs these mechanisms between real GPUs): an exception is recorded in its place, and a
     # watchdog prints the line without it if a rank gets stuck in a collective
-    if world > 1 and not args.no_transport_ab:
+    if world > 1 and args.full and not args.no_transport_ab:
         import threading
 
         def give_up():

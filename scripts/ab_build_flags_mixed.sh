@@ -5,7 +5,7 @@ for flags in "$@"; do
   export MHIP_EXTRA_HIPCC_FLAGS="$flags"
   python3 -m mundy_amd.build > /dev/null 2>&1 || { echo "build failed for [$flags]"; continue; }
   for rep in $(seq $REPS); do
-    python3 bench.py --mixed --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "
+    python3 bench.py --full --mixed --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][0])
 o = d.get('k_body') or d.get('k_constraint')

@@ -2,7 +2,7 @@
 # same-box A/B of two builds of the tree: _ab_old/ (a worktree of the commit to compare against, built) and the tree itself
 for rep in 1 2 3; do
   for t in _ab_old .; do
-    ( cd $t && python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --relaxed-steps 2 2>/dev/null | python3 -c "
+    ( cd $t && python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --relaxed-steps 2 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][0])
 print('$t', 'ms/step %.2f' % d['ms_per_step'], 'relaxed ms/step %.2f' % d['relaxed_packing']['ms_per_step'], 'k_body %.4f' % d['roofline']['avg_launch_ms'], 'k_constraint %.4f' % d['k_constraint']['avg_launch_ms'])" )

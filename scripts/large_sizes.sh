@@ -1,8 +1,8 @@
 #!/bin/bash
 # the headline workload at 4 x and 16 x its size on one GPU (same density, same tolerance)
-echo "# \`python3 bench.py --bodies N --steps 1 --warmup 0 --no-cpu-baseline --relaxed-steps 0\` on one MI355X: the headline workload at 4 x and 16 x its size (same density, same tolerance)"
+echo "# \`python3 bench.py --full --bodies N --steps 1 --warmup 0 --no-cpu-baseline --relaxed-steps 0\` on one MI355X: the headline workload at 4 x and 16 x its size (same density, same tolerance)"
 for n in 4000000 16000000; do
-  timeout -k 10 500 python3 bench.py --bodies $n --steps 1 --warmup 0 --no-cpu-baseline --relaxed-steps 0 2>/dev/null | python3 -c "
+  timeout -k 10 500 python3 bench.py --full --bodies $n --steps 1 --warmup 0 --no-cpu-baseline --relaxed-steps 0 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][0])
 r, o = d['roofline'], d.get('k_constraint') or d.get('k_body')

@@ -14,7 +14,7 @@ cd /tmp
 i=0
 for SET in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_LEVEL_sum" "TCC_EA0_RDREQ_32B_sum TCC_BUBBLE_sum" "TCC_EA0_RDREQ_DRAM_CREDIT_STALL_sum TCC_TAG_STALL_sum" "TCC_CYCLE_sum TCC_BUSY_sum" "TCC_REQ_sum TCC_STREAMING_REQ_sum" "TCC_HIT_sum TCC_MISS_sum" "TCP_PENDING_STALL_CYCLES_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_TCC_READ_REQ_sum TCP_TCR_TCP_STALL_CYCLES_sum" "TA_TA_BUSY_sum TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum TA_FLAT_READ_WAVEFRONTS_sum" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  rocprofv3 --pmc $SET --output-format csv -T --kernel-include-regex "k_constraint|k_body|k_copy" -d "$OUT/p$i" -- python3 "$BENCH" --steps 1 --warmup 0 --no-cpu-baseline --relaxed-steps 0 --max-iters 400 $EXTRA > "$OUT/p$i.json" 2> "$OUT/p$i.err" || { echo "pass $i ($SET) failed"; tail -3 "$OUT/p$i.err"; }
+  rocprofv3 --pmc $SET --output-format csv -T --kernel-include-regex "k_constraint|k_body|k_copy" -d "$OUT/p$i" -- python3 "$BENCH" --full --steps 1 --warmup 0 --no-cpu-baseline --relaxed-steps 0 --max-iters 400 $EXTRA > "$OUT/p$i.json" 2> "$OUT/p$i.err" || { echo "pass $i ($SET) failed"; tail -3 "$OUT/p$i.err"; }
   echo "pass $i done: $SET"
 done
 cd - > /dev/null

@@ -1,5 +1,5 @@
-import sys, numpy as np, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mundy_amd import ops, pipeline, synth
 dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
 b = synth.spherocylinders(1_000_000)

@@ -25,7 +25,7 @@ def find(sub, pat):
 
 
 EXTRA = " ".join(sys.argv[2:])
-print("# rocprofv3 summary of `python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline%s` (kernel trace + stats)" % ((" " + EXTRA) if EXTRA else ""))
+print("# rocprofv3 summary of `python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline%s` (kernel trace + stats)" % ((" " + EXTRA) if EXTRA else ""))
 try:
     line = open(os.path.join(out, "bench_trace.json")).read().strip().splitlines()[-1]
     print("bench line (profiled run):", line)

@@ -34,6 +34,18 @@ def test_launch_plan(bench, capsys):
     assert bench.launch_plan(2, {"MUNDY_BENCH_BACKEND": "gloo"}, argv, device_count=1) is not None
 
 
+def test_plain_run_is_the_default_and_the_new_options_are_checked(bench):
+    a = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 5, 2)
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    for argv in (["--steps", "0"], ["--warmup", "-1"], ["--gpus", "2", "--dump-outputs", "out"],
+                 ["--distributed", "--dump-outputs", "out"]):
+        with pytest.raises(SystemExit) as e:
+            bench.parse(argv)
+        assert e.value.code == 2, argv
+
+
 def test_gpus_2_without_a_launcher_starts_two_ranks_or_fails_loudly():
     # in this container there is no GPU: the ranks that get started each say so and the run ends non-zero; on a box
     # with fewer GPUs than asked for the parent refuses before starting anything.  Either way: no JSON line.

@@ -1,19 +1,21 @@
-"""bench.py's output contract on a small workload: one JSON line on stdout with the driver's keys, the roofline and
-cpu_baseline objects, and sane values."""
+"""bench.py's output contract on a small workload: one JSON line on stdout with the driver's keys and sane values; with
+--full also the roofline and cpu_baseline objects and the other figures beyond the headline."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(extra):
+def _run(extra, full=True):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bodies", "30000", "--steps", "2", "--warmup",
-                        "1", "--cpu-iters", "2"] + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "1", "--cpu-iters", "2"] + (["--full"] if full else []) + extra,
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -69,6 +71,34 @@ def test_default_line_has_the_contract_keys(tier):
     assert c["kind"] == "port" and c["cores"] >= 1 and 0.0 < c["value"] < d["value"]
 
 
+@pytest.mark.parametrize("workload", [[], ["--mixed"]], ids=["rods", "mixed"])
+def test_plain_line_is_lean_and_dumps_the_last_step(tmp_path, workload):
+    # without --full: set-up, warm-up, the timed steps, the line -- nothing measured beyond the headline
+    d = _run(workload + ["--dump-outputs", str(tmp_path / "a")], full=False)
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
+        assert key in d, key
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "timesteps/s" and d["dtype"] == "f64"
+    assert d["value"] == pytest.approx(1e3 / d["ms_per_step"], rel=1e-3)
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    for key in ("stage_ms", "relaxed_packing", "cold_tier", "k_body", "k_constraint"):
+        assert key not in d, key
+    assert len(d["config"]["bbpgd_iters_per_step"]) == 2 and all(d["config"]["converged"])
+    # the outputs of the last timed step: float64, well under 64 MB, in the original body numbering
+    a = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert set(a) == {"body_ids", "center", "quat", "contact_pairs", "contact_sep", "contact_impulse", "step"}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))) < 64 << 20
+    assert a["center"].shape == (len(a["body_ids"]), 3) and a["quat"].shape == (len(a["body_ids"]), 4)
+    assert list(a["step"][:2]) == [d["config"]["contacts_per_gpu"], d["config"]["bbpgd_iters_per_step"][-1]]
+    assert len(a["contact_pairs"]) > 0 and (a["contact_pairs"][:, 0] < a["contact_pairs"][:, 1]).all()
+    assert np.isin(a["contact_pairs"], a["body_ids"]).any(axis=1).all()
+    # every step starts from the same input: another run with other step counts leaves the same bits
+    _run(workload + ["--dump-outputs", str(tmp_path / "b"), "--steps", "1", "--warmup", "0"], full=False)
+    for k, v in a.items():
+        assert np.array_equal(v, np.load(str(tmp_path / "b" / (k + ".npy")))), k
+
+
 def test_friction_extension_line_is_labelled():
     d = _run(["--friction", "0.3", "--no-cpu-baseline"])
     assert "EXTENSION" in d["config"]["workload"] and "build extension" in d["metric"]
@@ -80,7 +110,7 @@ def test_friction_extension_line_is_labelled():
 
 def test_mixed_line_names_configs4():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mixed", "--bodies", "9000", "--steps", "1",
-                        "--warmup", "0"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--warmup", "0", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert "configs[4]" in d["config"]["workload"] and "mixed" in d["metric"]
@@ -143,8 +173,8 @@ def test_gpus_2_without_a_launcher_prints_a_two_rank_line():
     # path goes through the inboxes, the records through the mailbox), which is why the host transport is allowed.
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bodies", "40000", "--steps", "1",
-                        "--warmup", "1", "--allow-host-transport"], capture_output=True, text=True, timeout=600, cwd=ROOT,
-                       env=dict(env, MUNDY_BENCH_BACKEND="gloo"))
+                        "--warmup", "1", "--allow-host-transport", "--full"], capture_output=True, text=True, timeout=600,
+                       cwd=ROOT, env=dict(env, MUNDY_BENCH_BACKEND="gloo"))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
