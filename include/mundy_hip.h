@@ -138,6 +138,21 @@ int mhip_contact_spherocylinders_periodic(size_t c, const int32_t* pairs, const 
                                           const double* box /*[host] 3*/, double* sep, double* normal, double* cp1,
                                           double* cp2, double* ra, double* rb, double* s, double* t,
                                           mhip_stream_t stream);
+/* Hertzian soft contact, per linker (c = (i, j), sep and normal from the contact routines above):
+ *   R* = r_i r_j / (r_i + r_j)     E* = E_i E_j / (E_j - E_j nu_i^2 + E_i - E_i nu_j^2)
+ *   force[c] = (4/3) E* sqrt(R*) (-sep)^1.5 if sep < 0, else +0.0
+ * in the reference's association.  force[c] is the magnitude the contact operator takes as x (mhip_contact_op_body_sweep:
+ * body i receives -force n, body j +force n).  radius [n] = sphere radius or rod radius (not the bounding radius).
+ * youngs_modulus / poisson_ratio [n] per body, or NULL: then the scalar stands for every body (E > 0, 0 < nu < 1;
+ * per-body arrays must satisfy the same).  *max_overlap [device, 1 double] = max(0, -sep) over the list (+0.0 for an
+ * empty list), order independent.  A pair index outside [0, n) gives NaN and is never dereferenced.
+ * Replaces: EvaluateLinkerPotentials with the Hertzian contact kernels,
+ *           .../evaluate_linker_potentials/kernels/SphereSphereHertzianContact.cpp:198-219,
+ *           SphereSpherocylinderHertzianContact.cpp:203-219, SpherocylinderSpherocylinderHertzianContact.cpp:205-219
+ *           (called from scrap/parameter_interface/alens/tests/performance_tests/Bacteria.cpp:755-804). */
+int mhip_hertz_contact_force(size_t c, size_t n, const int32_t* pairs, const double* sep, const double* radius,
+                             const double* youngs_modulus, double youngs_modulus_scalar, const double* poisson_ratio,
+                             double poisson_ratio_scalar, double* force, double* max_overlap, mhip_stream_t stream);
 
 /* Mixed shapes (BASELINE configs[4]): kind[n] = 0 sphere, 1 spherocylinder, 2 ellipsoid; shape[n][3] = (r,-,-) /
  * (r,L,-) / (r1,r2,r3); quat is ignored for spheres.  compute_aabb dispatches on kind (compute_aabb.hpp:72-127) and
@@ -362,6 +377,14 @@ int mhip_contact_op_destroy(mhip_contact_op_t handle);
  * allocation in the steady state of a time loop); this frees that set. */
 int mhip_release_cached_workspaces(void);
 int mhip_contact_op_apply(mhip_contact_op_t handle, const double* x, double* y, mhip_stream_t stream);
+/* The body sweep of apply without its constraint sweep: the velocity rows U = M D x of a caller-given x [C] (one
+ * non-negative force magnitude per contact: body i receives -x_c n_c, body j +x_c n_c, at the operator's lever arms),
+ * read with mhip_contact_op_body_velocity.  Same incidence index and fixed-order double-double sums as apply; a body
+ * whose contacts all carry x = 0 gets a zero row.  The rods' angular rows are formed too.
+ * Replaces: LinkerPotentialForceReduction (.../linker_potential_force_reduction/kernels/Spherocylinder.cpp:173-207 --
+ *           force and torque (cp - x_body) x F summed per body) followed by compute_generalized_velocity
+ *           (scrap/parameter_interface/alens/tests/performance_tests/Bacteria.cpp:806-848, dry drag). */
+int mhip_contact_op_body_sweep(mhip_contact_op_t handle, const double* x, mhip_stream_t stream);
 /* Per-kernel timing of the fused solver (measurement support, no effect on results): when enabled,
  * mhip_bbpgd_solve_contact brackets the k_body / k_constraint launches of every 8th iteration with HIP events on
  * `stream` and accumulates their device durations.  get_profile returns the totals in milliseconds and the number of timed iterations

@@ -10,7 +10,9 @@
 //                       convex::KokkosBackend, convex.hpp:141-285), CQPPProblem, LCPProblem, to_cqpp, PGDConfig,
 //                       SolveResult, PGDState, PGDStrategy, BBStepStrategy, LinfNormProjected{Diff,Gradient}Residual,
 //                       make_*, solve_cqpp, solve_lcp -- same names, argument meaning and error behaviour
-//   mundy_hip::ContactOperator   the matrix-free LinearOp with `void apply(x, y) const` (convex.hpp:133-136)
+//   mundy_hip::ContactOperator   the matrix-free LinearOp with `void apply(x, y) const` (convex.hpp:133-136); its body
+//                       sweep alone is linker_potential_force_reduction / compute_generalized_velocity (soft contact)
+//   mundy_hip::linkers  evaluate_linker_potentials: the Hertzian contact force per linker (Bacteria.cpp:755-804)
 //
 // Functors cannot cross a C ABI, so the convex spaces and residual policies are tag types that map to enums; a
 // user-defined LinearOp only needs `void apply(const DeviceVector&, DeviceVector&) const` on device vectors.
@@ -755,6 +757,31 @@ class GenNeighborLinks {  // mundy_mesh/GenNeighborLinkers.hpp:294-866 (builder 
 
 }  // namespace mesh
 
+// ---- linker potentials ----------------------------------------------------------------------------------------------------
+namespace linkers {
+
+/// Material of the Hertzian contact: per-body arrays [num_bodies], or null for the scalar (the reference's defaults,
+/// Bacteria.cpp:1213-1214)
+struct HertzMaterial {
+  double youngs_modulus = 1000.0;
+  double poisson_ratio = 0.3;
+  const double* youngs_modulus_per_body = nullptr;
+  const double* poisson_ratio_per_body = nullptr;
+};
+
+/// EvaluateLinkerPotentials with the Hertzian contact kernels (.../evaluate_linker_potentials/kernels/
+/// *HertzianContact.cpp): force [C] = (4/3) E* sqrt(R*) (-sep)^1.5 per overlapping linker, +0.0 otherwise;
+/// max_overlap [device, 1] = max(0, -sep).  radius = sphere / rod radius (mhip_hertz_contact_force).
+inline void evaluate_linker_potentials(size_t num_linkers, size_t num_bodies, const int32_t* pairs, const double* sep,
+                                       const double* radius, const HertzMaterial& material, double* force,
+                                       double* max_overlap, mhip_stream_t stream = nullptr) {
+  check(mhip_hertz_contact_force(num_linkers, num_bodies, pairs, sep, radius, material.youngs_modulus_per_body,
+                                 material.youngs_modulus, material.poisson_ratio_per_body, material.poisson_ratio,
+                                 force, max_overlap, stream));
+}
+
+}  // namespace linkers
+
 // ---- contact operator (a LinearOp with apply(x, y)) ---------------------------------------------------------------------
 class ContactOperator {
  public:
@@ -787,6 +814,17 @@ class ContactOperator {
     check(mhip_contact_op_refresh_rods(h_, normal, rods.arc_s, rods.arc_t, rods.segments, stream));
   }
   void apply(const DeviceVector& x, DeviceVector& y) const { check(mhip_contact_op_apply(h_, x.data(), y.data(), nullptr)); }
+  /// LinkerPotentialForceReduction followed by compute_generalized_velocity (Bacteria.cpp:755-848): the velocity rows
+  /// U = M D f of per-linker force magnitudes f [C] (body i gets -f n, body j +f n) -- the body sweep of apply alone
+  void linker_potential_force_reduction(const double* force, mhip_stream_t stream = nullptr) const {
+    check(mhip_contact_op_body_sweep(h_, force, stream));
+  }
+  /// [num_bodies][6] (U, W) of the last apply / body sweep / solve (device pointer, valid in stream order)
+  const double* compute_generalized_velocity() const {
+    const double* v = nullptr;
+    check(mhip_contact_op_body_velocity(h_, &v));
+    return v;
+  }
   mhip_contact_op_t handle() const { return h_; }
 
  private:

@@ -3,7 +3,10 @@
 // scrap/lcp_spheres/NgpLcp.cpp:835-920; scrap/.../Bacteria.cpp:1013-1110).  Host code only sequences kernels:
 //   [Z-order reorder] -> compute_aabb -> GenNeighborLinks::generate -> segment records -> contact_spherocylinders
 //   -> ContactOperator (rod-compressed) -> solve_lcp (fused BBPGD) -> body velocities -> Euler + quaternion update
-// All arrays stay on the device; the only host reads are the pair count and the solver's convergence polls.
+// Opt-in soft contact (SpherocylinderStepper::set_hertz_contact): the solve is replaced by the Hertz force per linker
+// and the operator's body sweep on it, U = M D f (Bacteria.cpp:755-848).
+// All arrays stay on the device; the only host reads are the pair count and the solver's convergence polls (Hertz
+// mode: the largest overlap).
 #pragma once
 #include <chrono>
 #include <memory>
@@ -26,6 +29,7 @@ struct StepStats {
   unsigned num_iters = 0;
   double residual = 0.0;
   bool converged = false, rebuilt = false;
+  double max_overlap = 0.0;  // Hertz mode: max(0, -sep) over the step's contacts (what dt is chosen from)
 };
 
 class SpherocylinderStepper {
@@ -62,24 +66,27 @@ class SpherocylinderStepper {
     op_.reset();
   }
 
+  /// Hertzian soft contact instead of the LCP (opt-in; the LCP is the default): each step evaluates the Hertz force
+  /// per linker (rod radius, E > 0, 0 < nu < 1 for every body) and sums it per body through the operator's body sweep
+  /// -- no solve (num_iters = 0, converged).  The reference's production loop: Bacteria.cpp:755-848, :1033-1080.
+  void set_hertz_contact(double youngs_modulus = 1000.0, double poisson_ratio = 0.3) {
+    if (!(youngs_modulus > 0.0 && youngs_modulus < HUGE_VAL) || !(poisson_ratio > 0.0 && poisson_ratio < 1.0))
+      throw std::invalid_argument("set_hertz_contact: E must be finite and > 0, 0 < nu < 1");
+    hertz_ = true;
+    material_.youngs_modulus = youngs_modulus;
+    material_.poisson_ratio = poisson_ratio;
+  }
+
   StepStats step(bool integrate = true, bool force_rebuild = false) {
     StepStats st;
-    check(mhip_compute_aabb_spherocylinders(n_, center_.data(), quat_.data(), radius_.data(), length_.data(),
-                                            aabb_.data(), nullptr));
-    st.rebuilt = links_.generate(n_, aabb_.data(), center_.data(), brad_.data(), nullptr, force_rebuild);
-    if (st.rebuilt) links_.links_into(pairs_);
-    const size_t C = links_.num_links();
-    st.num_contacts = C;
-    check(mhip_spherocylinder_segments(n_, center_.data(), quat_.data(), radius_.data(), length_.data(), seg_.data(),
-                                       nullptr));
-    double *sep = workspace(w_sep_, C), *normal = workspace(w_normal_, 3 * C), *s = workspace(w_s_, C),
-           *t = workspace(w_t_, C);
-    if (periodic_)
-      check(mhip_contact_spherocylinders_periodic(C, pairs_.data(), seg_.data(), center_.data(), box_, sep, normal,
-                                                  nullptr, nullptr, nullptr, nullptr, s, t, nullptr));
-    else
-      check(mhip_contact_spherocylinders(C, pairs_.data(), seg_.data(), nullptr, sep, normal, nullptr, nullptr,
-                                         nullptr, nullptr, s, t, nullptr));
+    double *sep = nullptr, *normal = nullptr, *s = nullptr, *t = nullptr;
+    const size_t C = contacts(st, force_rebuild, sep, normal, s, t);
+    if (hertz_) {
+      double* f = workspace(lambda_, C);
+      double* mx = workspace(w_mx_, 1);
+      linkers::evaluate_linker_potentials(C, n_, pairs_.data(), sep, radius_.data(), material_, f, mx);
+      num_lambda_ = C;
+    }
     // the operator follows the contact list: rebuilt with it, otherwise only its geometry is refreshed
     if (st.rebuilt || !op_)
       op_.reset(new ContactOperator(C, n_, pairs_.data(), normal, ContactOperator::Rods{s, t, seg_.data()},
@@ -87,21 +94,15 @@ class SpherocylinderStepper {
     else
       op_->refresh(normal, ContactOperator::Rods{s, t, seg_.data()});
     ContactOperator& op = *op_;
-    double *x = workspace(lambda_, C), *g = workspace(w_g_, C), *x_tmp = workspace(w_xt_, C),
-           *g_tmp = workspace(w_gt_, C);
-    check(mhip_fill(C, x, 0.0, nullptr));  // lambda = 0 (NgpLcp.cpp:890-891)
-    num_lambda_ = C;
-    const mhip_space lcp{MHIP_SPACE_LOWER_BOUND, 0.0, 0.0};
-    const mhip_pgd_config pc{cfg_.max_iters, cfg_.tol, MHIP_RESIDUAL_PROJECTED_DIFF};
-    mhip_solve_result res{};
-    check(mhip_bbpgd_solve_contact(op.handle(), sep, &lcp, &pc, x, g, x_tmp, g_tmp, &res, nullptr));
-    st.num_iters = res.num_iters;
-    st.residual = res.residual;
-    st.converged = res.converged != 0;
+    if (hertz_) {
+      op.linker_potential_force_reduction(lambda_.data());
+      st.converged = true;
+      check(mhip_memcpy_d2h(&st.max_overlap, w_mx_.data(), sizeof(double), nullptr));
+    } else {
+      solve(op, C, sep, st);
+    }
     if (integrate) {
-      const double* vel = nullptr;
-      check(mhip_contact_op_body_velocity(op.handle(), &vel));
-      check(mhip_integrate_euler(n_, dt_, vel, center_.data(), quat_.data(), nullptr));
+      check(mhip_integrate_euler(n_, dt_, op.compute_generalized_velocity(), center_.data(), quat_.data(), nullptr));
       // wrap_rigid_inplace(Spherocylinder): the centre goes back into the box (periodicity.hpp:1094-1113)
       if (periodic_) check(mhip_wrap_rigid(n_, box_, center_.data(), nullptr));
     }
@@ -112,12 +113,49 @@ class SpherocylinderStepper {
   size_t num_bodies() const { return n_; }
   const DeviceVector& center() const { return center_; }
   const DeviceVector& quat() const { return quat_; }
-  /// multipliers of the last step: the first num_lambda() entries (the buffer only ever grows)
+  /// multipliers of the last step (Hertz mode: the linker forces): the first num_lambda() entries (the buffer only
+  /// ever grows)
   const DeviceVector& lambda() const { return lambda_; }
   size_t num_lambda() const { return num_lambda_; }
   const DeviceArray<int32_t>& pairs() const { return pairs_; }
 
  private:
+  /// compute_aabb -> neighbour list (rebuild rule) -> segments -> narrow phase; returns the number of contacts
+  size_t contacts(StepStats& st, bool force_rebuild, double*& sep, double*& normal, double*& s, double*& t) {
+    check(mhip_compute_aabb_spherocylinders(n_, center_.data(), quat_.data(), radius_.data(), length_.data(),
+                                            aabb_.data(), nullptr));
+    st.rebuilt = links_.generate(n_, aabb_.data(), center_.data(), brad_.data(), nullptr, force_rebuild);
+    if (st.rebuilt) links_.links_into(pairs_);
+    const size_t C = links_.num_links();
+    st.num_contacts = C;
+    check(mhip_spherocylinder_segments(n_, center_.data(), quat_.data(), radius_.data(), length_.data(), seg_.data(),
+                                       nullptr));
+    sep = workspace(w_sep_, C);
+    normal = workspace(w_normal_, 3 * C);
+    s = workspace(w_s_, C);
+    t = workspace(w_t_, C);
+    if (periodic_)
+      check(mhip_contact_spherocylinders_periodic(C, pairs_.data(), seg_.data(), center_.data(), box_, sep, normal,
+                                                  nullptr, nullptr, nullptr, nullptr, s, t, nullptr));
+    else
+      check(mhip_contact_spherocylinders(C, pairs_.data(), seg_.data(), nullptr, sep, normal, nullptr, nullptr,
+                                         nullptr, nullptr, s, t, nullptr));
+    return C;
+  }
+  /// the LCP: fused BBPGD from lambda = 0 (NgpLcp.cpp:890-891)
+  void solve(ContactOperator& op, size_t C, const double* sep, StepStats& st) {
+    double *x = workspace(lambda_, C), *g = workspace(w_g_, C), *x_tmp = workspace(w_xt_, C),
+           *g_tmp = workspace(w_gt_, C);
+    check(mhip_fill(C, x, 0.0, nullptr));
+    num_lambda_ = C;
+    const mhip_space lcp{MHIP_SPACE_LOWER_BOUND, 0.0, 0.0};
+    const mhip_pgd_config pc{cfg_.max_iters, cfg_.tol, MHIP_RESIDUAL_PROJECTED_DIFF};
+    mhip_solve_result res{};
+    check(mhip_bbpgd_solve_contact(op.handle(), sep, &lcp, &pc, x, g, x_tmp, g_tmp, &res, nullptr));
+    st.num_iters = res.num_iters;
+    st.residual = res.residual;
+    st.converged = res.converged != 0;
+  }
   void gather(DeviceVector& a, size_t width) {
     check(mhip_gather_rows(n_, width, perm_.data(), a.data(), tmp_.data(), nullptr));
     check(mhip_deep_copy(width * n_, a.data(), tmp_.data(), nullptr));
@@ -128,8 +166,10 @@ class SpherocylinderStepper {
   double box_[3] = {0.0, 0.0, 0.0};
   convex::PGDConfig<double> cfg_;
   DeviceVector center_, quat_, radius_, length_, mob_t_, mob_r_, brad_, aabb_, seg_, tmp_, lambda_;
-  DeviceVector w_sep_, w_normal_, w_s_, w_t_, w_g_, w_xt_, w_gt_;  // per-step workspaces (grow-only)
+  DeviceVector w_sep_, w_normal_, w_s_, w_t_, w_g_, w_xt_, w_gt_, w_mx_;  // per-step workspaces (grow-only)
   size_t num_lambda_ = 0;
+  bool hertz_ = false;
+  linkers::HertzMaterial material_;
   DeviceArray<int32_t> perm_, pairs_;
   mesh::GenNeighborLinks links_;
   std::unique_ptr<ContactOperator> op_;

@@ -98,6 +98,7 @@ SIGNATURES = {
     "mhip_ellipsoid_last_evaluations": [C.POINTER(C.c_ulonglong), _vp],
     "mhip_contact_mixed_periodic": [_sz] + [_vp] * 5 + [C.POINTER(_d)] + [_vp] * 6 + [C.POINTER(_sz), _vp],
     "mhip_contact_spherocylinders_periodic": [_sz, _vp, _vp, _vp, C.POINTER(_d)] + [_vp] * 9,
+    "mhip_hertz_contact_force": [_sz, _sz, _vp, _vp, _vp, _vp, _d, _vp, _d, _vp, _vp, _vp],
     "mhip_contact_spheres": [_sz, _vp, _vp, _vp, C.POINTER(_d), _vp, _vp, _vp],
     "mhip_contact_spherocylinders": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mhip_broadphase_create": [C.POINTER(_vp)],
@@ -131,6 +132,7 @@ SIGNATURES = {
     "mhip_contact_op_refresh_rods": [_vp, _vp, _vp, _vp, _vp, _vp],
     "mhip_contact_op_destroy": [_vp],
     "mhip_contact_op_apply": [_vp, _vp, _vp, _vp],
+    "mhip_contact_op_body_sweep": [_vp, _vp, _vp],
     "mhip_contact_op_body_velocity": [_vp, C.POINTER(_vp)],
     "mhip_contact_op_set_profiling": [_vp, _i],
     "mhip_contact_op_set_tiering": [_vp, _i],

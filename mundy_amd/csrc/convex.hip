@@ -3606,6 +3606,16 @@ int mhip_contact_op_apply(mhip_contact_op_t op, const double* x, double* y, mhip
                               grid_for(op->view.C), s);
 }
 
+// The body sweep of apply alone: the velocity rows U = M D x of a caller-given x (the linker forces of a soft-contact
+// step), no constraint sweep.  The X_APPLY sweep writes the rods' angular rows as well, so body_velocity is complete.
+int mhip_contact_op_body_sweep(mhip_contact_op_t op, const double* x, mhip_stream_t stream) {
+  MHIP_REQUIRE(op != nullptr, MHIP_ERR_INVALID_ARGUMENT, "operator handle is null");
+  MHIP_REQUIRE(op->view.C == 0 || x, MHIP_ERR_INVALID_ARGUMENT, "x must not be null");
+  MHIP_REQUIRE(!op->stage.active, MHIP_ERR_RUNTIME, "a staged solve is in progress");
+  const Space none{MHIP_SPACE_UNCONSTRAINED, 0, 0};
+  return op_launch_body(op, X_APPLY, x, x, nullptr, nullptr, none, as_stream(stream));
+}
+
 int mhip_contact_op_sizes(mhip_contact_op_t op, size_t* num_constraints, size_t* num_bodies) {
   MHIP_REQUIRE(op != nullptr, MHIP_ERR_INVALID_ARGUMENT, "operator handle is null");
   if (num_constraints) *num_constraints = op->view.C;

@@ -286,6 +286,36 @@ def contact_spherocylinders(pairs, seg, center, want_points=True, out=None, arms
     return out
 
 
+def _material(value, n, name, lo, hi):
+    """a per-body material parameter: a number (checked here, on the host) -> (None, value); a tensor [n] -> (tensor, 0)"""
+    if isinstance(value, torch.Tensor):
+        if value.dim() != 1 or value.shape[0] != n:
+            raise ValueError("%s must be a number or a tensor of shape [%d], got %s" % (name, n, tuple(value.shape)))
+        return value, 0.0
+    v = float(value)
+    if not (lo < v < hi):
+        raise ValueError("%s must lie in (%g, %g), got %r" % (name, lo, hi, value))
+    return None, v
+
+
+def hertz_contact_force(pairs, sep, radius, youngs_modulus=1000.0, poisson_ratio=0.3, out=None, max_overlap=None):
+    """Hertzian soft contact per linker (EvaluateLinkerPotentials, Bacteria.cpp:755-804; mhip_hertz_contact_force):
+    f_c = (4/3) E* sqrt(R*) (-sep_c)^1.5 for sep_c < 0, else +0.0.  radius [n] = sphere / rod radius (not the bounding
+    radius); youngs_modulus (E > 0) and poisson_ratio (0 < nu < 1) are numbers or per-body tensors [n] (defaults:
+    Bacteria.cpp:1213-1214).  Returns (f [C], max_overlap [1] device tensor = max(0, -sep))."""
+    c, n = pairs.shape[0], radius.shape[0]
+    E, E0 = _material(youngs_modulus, n, "youngs_modulus", 0.0, float("inf"))
+    nu, nu0 = _material(poisson_ratio, n, "poisson_ratio", 0.0, 1.0)
+    f = _new(sep, c) if out is None else out
+    mx = _new(sep, 1) if max_overlap is None else max_overlap
+    capi.check(capi.load().mhip_hertz_contact_force(c, n, _ptr(pairs, torch.int32, 2, name="pairs"), _ptr(sep, name="sep"),
+                                                    _ptr(radius, name="radius"),
+                                                    _ptr(E, allow_none=True, name="youngs_modulus"), E0,
+                                                    _ptr(nu, allow_none=True, name="poisson_ratio"), nu0,
+                                                    _ptr(f, name="out"), _ptr(mx, name="max_overlap"), _stream()))
+    return f, mx
+
+
 # ---- broad phase (GenNeighborLinks, mundy_mesh/GenNeighborLinkers.hpp:294-866) ---------------------------------------
 class GenNeighborLinks:
     """Builder-style mirror of mundy::mesh::GenNeighborLinks: set_* -> concretize() -> generate().
@@ -593,6 +623,19 @@ class ContactOperator:
         y = torch.empty_like(x) if y is None else y
         capi.check(capi.load().mhip_contact_op_apply(self._h, _ptr(x), _ptr(y), _stream()))
         return y
+
+    def body_sweep(self, x):
+        """the velocity rows (U, W) = M D x of per-contact force magnitudes x [C] (body i gets -x n, body j +x n): the
+        body sweep alone, no constraint sweep (LinkerPotentialForceReduction + compute_generalized_velocity,
+        mhip_contact_op_body_sweep); body_velocity() reads them"""
+        if tuple(x.shape) != (self.num_constraints,):
+            raise ValueError("x must have shape [%d], got %s" % (self.num_constraints, tuple(x.shape)))
+        capi.check(capi.load().mhip_contact_op_body_sweep(self._h, _ptr(x, name="x"), _stream()))
+
+    def body_velocity_of(self, x):
+        """[N, 6] (U, W) = M D x (body_sweep, then a copy of the rows)"""
+        self.body_sweep(x)
+        return self.body_velocity()
 
     def body_velocity(self):
         """[N, 6] (U, W) of the last evaluated iterate -- a view of handle-owned memory; clone to keep."""

@@ -7,6 +7,13 @@ scrap/parameter_interface/alens/tests/performance_tests/Bacteria.cpp:755-805):
                  -> resolve_collisions: BBPGD on the LCP  0 <= dt D^T M D lambda + sep  _|_  lambda >= 0
                  -> Euler update x += dt U (and q <- rotate(q, W dt) for rods)
 
+contact_model="hertz" replaces the solve by the reference's Hertzian soft-contact force (the same app's contact stage,
+Bacteria.cpp:755-848; scrap/lcp_spheres/NGPSpheres2.cpp:192-240):
+
+    ... -> signed separation + contact normal -> Hertz force per linker (EvaluateLinkerPotentials)
+        -> force / torque summed per body and dry drag U = M D f (LinkerPotentialForceReduction +
+           compute_generalized_velocity: the contact operator's body sweep, no solve) -> Euler update
+
 Everything is device resident; host logic here only sequences library calls.
 """
 from dataclasses import dataclass, field
@@ -25,6 +32,7 @@ class StepStats:
     residual: float = 0.0
     converged: bool = False
     timings_ms: dict = field(default_factory=dict)
+    max_overlap: float = 0.0  # contact_model="hertz": max(0, -sep) over the step's contacts (what dt is chosen from)
 
 
 class ContactStepper:
@@ -33,12 +41,30 @@ class ContactStepper:
     def __init__(self, kind, center, radius, quat=None, length=None, *, dt=5e-3, viscosity=1e-3, search_buffer=0.25,
                  search_kind=ops.SEARCH_AABB, periodic_box=None, cfg=None, warm_start=False, mob_trans=None,
                  mob_rot=None, rod_kinematics=True, kinds=None, shape=None, friction=None, contact_cutoff=None,
-                 conservative_ellipsoid_box=False, friction_method="apgd"):
+                 conservative_ellipsoid_box=False, friction_method="apgd", contact_model="lcp", youngs_modulus=1000.0,
+                 poisson_ratio=0.3):
         """kind = "sphere" | "spherocylinder" | "mixed".  Mixed systems (BASELINE configs[4]) pass kinds [n] int32
         (0 sphere, 1 spherocylinder, 2 ellipsoid) and shape [n, 3] = (r,-,-) / (r,L,-) / (r1,r2,r3) instead of
-        radius / length."""
+        radius / length.
+        contact_model = "lcp" (default: hard contact, BBPGD) | "hertz" (soft contact, no solve; spheres and rods only).
+        youngs_modulus (E > 0) and poisson_ratio (0 < nu < 1): numbers or per-body tensors [n], Hertz mode only
+        (defaults: Bacteria.cpp:1213-1214)."""
         if kind not in ("sphere", "spherocylinder", "mixed"):
             raise ValueError("kind must be 'sphere', 'spherocylinder' or 'mixed'")
+        if contact_model not in ("lcp", "hertz"):
+            raise ValueError("contact_model must be 'lcp' or 'hertz'")
+        self.contact_model = contact_model
+        if contact_model == "hertz":  # (checked before anything reaches the device)
+            for what, v in (("friction", friction), ("contact_cutoff", contact_cutoff)):
+                if v is not None:
+                    raise ValueError("contact_model='hertz' takes no %s (the LCP path's options)" % what)
+            if warm_start:
+                raise ValueError("contact_model='hertz' has no solve to warm-start")
+            if kind == "mixed" and kinds is not None and bool((kinds == 2).any()):
+                raise ValueError("contact_model='hertz' has no ellipsoid contact (the reference has no such kernel)")
+            ops._material(youngs_modulus, center.shape[0], "youngs_modulus", 0.0, float("inf"))
+            ops._material(poisson_ratio, center.shape[0], "poisson_ratio", 0.0, 1.0)
+        self.youngs_modulus, self.poisson_ratio = youngs_modulus, poisson_ratio
         if kind == "spherocylinder" and (quat is None or length is None):
             raise ValueError("spherocylinders need quat and length")
         if kind == "mixed" and (quat is None or kinds is None or shape is None):
@@ -200,6 +226,9 @@ class ContactStepper:
         return bool((g >= -self.cfg.tol).all())
 
     def resolve_collisions(self, rebuilt):
+        if self.contact_model == "hertz":
+            self.contact_pairs = self.links.pairs
+            return self._hertz(rebuilt, lambda name: None)
         if self.contact_cutoff is not None and self.friction is None:
             self.full_contacts = self.contacts
             pairs, self.contacts, dropped = self._compact_contacts()
@@ -253,6 +282,36 @@ class ContactStepper:
         self.lam, self.grad = x, g
         return res
 
+    def _contact_radius(self):
+        """the radius the Hertz model takes: the sphere / rod radius, not the bounding radius"""
+        return self.shape[:, 0].contiguous() if self.kind == "mixed" else self.radius
+
+    def _hertz(self, rebuilt, mark):
+        """soft contact: per-linker Hertz force, then the operator's body sweep on it -- U = M D f (no solve)"""
+        c, pairs = self.contacts, self.links.pairs
+        self.lam, self.max_overlap = ops.hertz_contact_force(pairs, c["sep"], self._contact_radius(),
+                                                             self.youngs_modulus, self.poisson_ratio)
+        mark("hertz_force")
+        # the operator follows the neighbour list: built on a rebuild, its geometry refreshed otherwise
+        reuse = not rebuilt and self.op is not None and self.op.num_constraints == pairs.shape[0]
+        if self.op is not None and not reuse:
+            self.op.close()
+        if self.kind == "spherocylinder" and self.rod_kinematics:
+            if reuse:
+                self.op.refresh(c["normal"], rod=(c["s"], c["t"], self.seg))
+            else:
+                self.op = ops.ContactOperator(pairs, c["normal"], self.mob_trans, self.dt, mob_rot=self.mob_rot,
+                                              rod=(c["s"], c["t"], self.seg), priority=c["sep"])
+        elif reuse:
+            self.op.refresh(c["normal"], ra=c.get("ra"), rb=c.get("rb"))
+        else:
+            self.op = ops.ContactOperator(pairs, c["normal"], self.mob_trans, self.dt, ra=c.get("ra"), rb=c.get("rb"),
+                                          mob_rot=self.mob_rot, priority=c["sep"])
+        mark("operator")
+        self.op.body_sweep(self.lam)
+        mark("body_sweep")
+        return ops.SolveResult(num_iters=0, residual=0.0, converged=True)
+
     def integrate(self):
         vel = self.op.body_velocity()
         ops.integrate_euler(self.dt, vel, self.center, self.quat)
@@ -279,13 +338,19 @@ class ContactStepper:
         mark("broadphase")
         self.compute_contacts()
         mark("narrowphase")
-        res = self.resolve_collisions(st.rebuilt)
-        mark("solve")
+        if self.contact_model == "hertz":  # (stages: hertz_force, operator, body_sweep)
+            res = self._hertz(st.rebuilt, mark)
+            self.contact_pairs = self.links.pairs
+        else:
+            res = self.resolve_collisions(st.rebuilt)
+            mark("solve")
         if integrate:
             self.integrate()
         mark("integrate")
         st.num_contacts = self.contact_pairs.shape[0]
         st.num_iters, st.residual, st.converged = res.num_iters, res.residual, res.converged
+        if self.contact_model == "hertz":
+            st.max_overlap = float(self.max_overlap.item())
         if timed:
             torch.cuda.synchronize()
             for (_, a), (name, b) in zip(ev[:-1], ev[1:]):
