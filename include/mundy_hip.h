@@ -605,21 +605,24 @@ int mhip_contact_spheres_triclinic(size_t c, const int32_t* pairs, const double*
  * The lattice has 2^b cells per axis, b = the largest of 4..8 with 8^b <= 8 n (the code space stays within 8 codes per
  * body: 128 cells per axis at 10^6 bodies); lattice coordinates floor((c - lo) / cell_size) are clamped to
  * [0, 2^b - 1], so bodies outside that cube share the boundary cells (a locality heuristic there, exact Z-order inside).
+ * The clamp is applied to the floored double before the integer conversion: a coordinate below 0 or NaN gives cell 0,
+ * one above 2^b - 1 or +inf gives 2^b - 1 (the same rule for mhip_curve_order / mhip_curve_keys).
  * ---------------------------------------------------------------------------------------------------------------- */
 int mhip_morton_order(size_t n, const double* center, const double* lo /*[host] 3*/, double cell_size, int32_t* perm,
                       mhip_stream_t stream);
 /* The same reordering along any lattice curve given as a table: key_table [device, (2^level)^3 int32, indexed
  * [ix][iy][iz]] = visiting index of the cell.  With the table of mundy::math::hilbert_3d (mundy/math/src/mundy_math/
  * Hilbert.hpp:48-83; mundy_amd.distributed.hilbert_key_table generates it with that recursion) this is the Hilbert
- * order used for the domain decomposition.  Cells: floor((c - lo) / (hi - lo) * 2^level) clamped to the lattice;
- * ties by index.  level <= 8. */
+ * order used for the domain decomposition.  Cells: floor((c - lo) / (hi - lo) * 2^level) clamped to the lattice as
+ * above (NaN -> 0); ties by index.  level <= 8. */
 int mhip_curve_order(size_t n, const double* center, const double* lo /*[host] 3*/, const double* hi /*[host] 3*/,
                      int level, const int32_t* key_table, int32_t* perm, mhip_stream_t stream);
 /* keys[i] = key_table entry of body i's cell (the value mhip_curve_order sorts by): the Hilbert position of the cell --
  * what the work-weighted domain decomposition cuts and what decides a body's owner when it migrates */
 int mhip_curve_keys(size_t n, const double* center, const double* lo /*[host] 3*/, const double* hi /*[host] 3*/,
                     int level, const int32_t* key_table, uint32_t* keys, mhip_stream_t stream);
-/* perm = the stable ascending order of n 64-bit keys (radix sort, 8 bits per pass): perm[k] = index of the k-th key */
+/* perm = the stable ascending order of n unsigned 64-bit keys (radix sort, 8 bits per pass): perm[k] = index of the
+ * k-th key.  keys is not modified. */
 int mhip_sort_by_key_u64(size_t n, const uint64_t* keys, int32_t* perm, mhip_stream_t stream);
 /* dst[k][0..width) = src[perm[k]][0..width)  for rows of `width` doubles */
 int mhip_gather_rows(size_t n, size_t width, const int32_t* perm, const double* src, double* dst, mhip_stream_t stream);
@@ -772,8 +775,10 @@ int mhip_ghost_exchange(mhip_comm_t comm, size_t width, const double* records /*
  *                           steppers: by cell key, ties by entity id -- the order a single rank would have).
  * Small helpers of that bookkeeping:
  *   mhip_body_work_weights  weights[k] = 1 + number of pairs that contain local body first + k, k < count
- *   mhip_compose_keys_u64   out[i] = major[i] << shift | (uint64) minor[i]  (cell key, then entity id: minor is an
- *                           integer-valued double below 2^shift)
+ *   mhip_compose_keys_u64   out[i] = major[i] << shift | (uint64) minor[i]  (cell key, then entity id).  Precondition,
+ *                           not checked on the device: every minor[i] is an integer-valued double in [0, 2^shift);
+ *                           another value overwrites key bits or is truncated.  The steppers use shift 40 and refuse
+ *                           entity ids outside [0, 2^40) when they are given.
  *   mhip_fill_sequence      dst[i] = first + i
  * ---------------------------------------------------------------------------------------------------------------- */
 int mhip_hilbert_key_table(int level, int32_t* table /*[host] (2^level)^3*/);

@@ -9,7 +9,10 @@
 // mode: the largest overlap).
 #pragma once
 #include <chrono>
+#include <cmath>
 #include <memory>
+#include <stdexcept>
+#include <string>
 
 #include "mundy_hip/adapter.hpp"
 
@@ -205,7 +208,19 @@ class DistributedSpherocylinderStepper {
   /// ids the bodies keep for life (integer-valued, below 2^40); default: the global position at construction
   void set_entity_ids(const std::vector<double>& ids) {
     if (ids.size() != n_) throw std::invalid_argument("set_entity_ids: one id per owned body");
+    check_entity_ids(ids);
     entity_ = DeviceVector(ids);
+  }
+  /// throws std::invalid_argument unless every id is an integer in [0, 2^40): rebalance() orders the owned bodies by
+  /// (cell key << 40) | id (mhip_compose_keys_u64), which a larger, negative or fractional id would corrupt
+  static void check_entity_ids(const std::vector<double>& ids) {
+    constexpr double kBound = 1099511627776.0;  // 2^40
+    for (size_t i = 0; i < ids.size(); ++i) {
+      const double e = ids[i];
+      if (!(e >= 0.0 && e < kBound && e == std::floor(e)))  // NaN and +-inf fail too
+        throw std::invalid_argument("set_entity_ids: entity ids must be integers in [0, 2^40); id " +
+                                    std::to_string(e) + " at index " + std::to_string(i) + " is not");
+    }
   }
   /// The lattice the ownership is cut on: (2^level)^3 cells over [lo, hi], visited along mundy::math::hilbert_3d
   /// (Hilbert.hpp:48-83).  Needed by rebalance() / step(..., migrate = true).

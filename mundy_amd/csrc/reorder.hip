@@ -17,15 +17,19 @@ __device__ inline unsigned spread3(unsigned v) {  // 10 bits -> every third bit
   return v;
 }
 
+// lattice coordinate of a floored position f on [0, maxc]: clamped in double BEFORE the integer conversion (converting a
+// double outside the int range, +-inf or NaN is undefined behaviour); NaN goes to cell 0 (it fails `f > 0`)
+__device__ inline int lattice_coord(double f, int maxc) {
+  const double m = static_cast<double>(maxc);
+  return static_cast<int>(!(f > 0.0) ? 0.0 : (f < m ? f : m));
+}
+
 __device__ inline unsigned morton_code(const double* __restrict__ center, size_t i, V3 lo, double inv_cell, int bits) {
   const V3 c = load3(center, i);
   const int maxc = (1 << bits) - 1;
-  int ix = static_cast<int>(floor((c.x - lo.x) * inv_cell));
-  int iy = static_cast<int>(floor((c.y - lo.y) * inv_cell));
-  int iz = static_cast<int>(floor((c.z - lo.z) * inv_cell));
-  ix = ix < 0 ? 0 : (ix > maxc ? maxc : ix);
-  iy = iy < 0 ? 0 : (iy > maxc ? maxc : iy);
-  iz = iz < 0 ? 0 : (iz > maxc ? maxc : iz);
+  const int ix = lattice_coord(floor((c.x - lo.x) * inv_cell), maxc);
+  const int iy = lattice_coord(floor((c.y - lo.y) * inv_cell), maxc);
+  const int iz = lattice_coord(floor((c.z - lo.z) * inv_cell), maxc);
   return spread3((unsigned)ix) | (spread3((unsigned)iy) << 1) | (spread3((unsigned)iz) << 2);
 }
 
@@ -47,12 +51,9 @@ __global__ void __launch_bounds__(kBlock)
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const V3 c = load3(center, i);
     const double nsd = static_cast<double>(ns);  // ((c - lo) / span) * ns, the host partitioner's expression
-    double fx = floor((c.x - lo.x) / span.x * nsd), fy = floor((c.y - lo.y) / span.y * nsd),
-           fz = floor((c.z - lo.z) / span.z * nsd);
-    fx = fx < 0.0 ? 0.0 : (fx > maxc ? (double)maxc : fx);  // clamp before the integer conversion
-    fy = fy < 0.0 ? 0.0 : (fy > maxc ? (double)maxc : fy);
-    fz = fz < 0.0 ? 0.0 : (fz > maxc ? (double)maxc : fz);
-    const int ix = static_cast<int>(fx), iy = static_cast<int>(fy), iz = static_cast<int>(fz);
+    const int ix = lattice_coord(floor((c.x - lo.x) / span.x * nsd), maxc),
+              iy = lattice_coord(floor((c.y - lo.y) / span.y * nsd), maxc),
+              iz = lattice_coord(floor((c.z - lo.z) / span.z * nsd), maxc);
     const unsigned m = static_cast<unsigned>(key_table[((size_t)ix * ns + iy) * ns + iz]);
     code[i] = m;
     atomicAdd(&hist[m], 1);

@@ -85,6 +85,28 @@ def hilbert_order(center, lo, hi, level=6):
     return np.argsort(key, kind="stable")
 
 
+ENTITY_ID_BITS = 40   # the owned set is ordered by (cell key << 40) | entity id
+
+
+def checked_entity_ids(entity_id):
+    """entity_id as float64, or ValueError unless every id is an integer in [0, 2^40): a larger id would overwrite bits
+    of the cell key it is composed with, a negative one all of them, and a fraction would be cut off"""
+    bound = 1 << ENTITY_ID_BITS
+    e = torch.as_tensor(entity_id)
+    if e.dtype == torch.bool or e.is_complex():
+        raise ValueError("entity ids must be integers in [0, 2^40), got dtype %s" % e.dtype)
+    if e.is_floating_point():
+        e = e.to(torch.float64)
+        bad = ~((e >= 0) & (e < float(bound)) & (e == torch.floor(e)))     # NaN and +-inf fail too
+    else:
+        bad = (e < 0) | (e >= bound)
+    if e.numel() and bool(bad.any()):
+        k = int(torch.nonzero(bad.reshape(-1))[0])
+        raise ValueError("entity ids must be integers in [0, 2^40): id %r at index %d is not"
+                         % (e.reshape(-1)[k].item(), k))
+    return e.to(torch.float64)
+
+
 def partition_ranges(n_total, world):
     """equal contiguous ranges of the curve order: rank r owns global ids [start[r], start[r+1])"""
     base, rem = divmod(n_total, world)
@@ -389,6 +411,8 @@ class DistributedContactStepper:
         bodies migrate (rebalance / step(migrate=True)); recut_every: re-cut the curve by work every that many
         rebalances, 0 = keep the cuts."""
         from . import synth
+        if entity_id is not None:
+            entity_id = checked_entity_ids(entity_id)
         self.comm = comm or Comm()
         self.mixed = kind is not None
         if self.mixed:
@@ -407,7 +431,7 @@ class DistributedContactStepper:
         self.mob_r = torch.from_numpy(mr0).to(center.device)
         self.gid_first = int(gid_first)
         self.entity_id = (torch.arange(self.gid_first, self.gid_first + self.n, dtype=torch.float64, device=center.device)
-                          if entity_id is None else entity_id.to(torch.float64).contiguous())
+                          if entity_id is None else entity_id.to(center.device).contiguous())
         self.domain = None if domain is None else ([float(v) for v in np.broadcast_to(domain[0], 3)],
                                                    [float(v) for v in np.broadcast_to(domain[1], 3)])
         if not 1 <= int(curve_level) <= 7:

@@ -833,7 +833,8 @@ def hilbert_key_table(level):
 
 
 def sort_by_key(keys):
-    """stable ascending order of int64 keys (non-negative): int32 permutation (library radix sort)"""
+    """stable ascending order of unsigned 64-bit keys (int64 bit pattern: a negative int64 sorts after every
+    non-negative one): int32 permutation (library radix sort)"""
     perm = torch.empty(keys.shape[0], dtype=torch.int32, device=keys.device)
     capi.check(capi.load().mhip_sort_by_key_u64(keys.shape[0], _ptr(keys, torch.int64), _ptr(perm, torch.int32), _stream()))
     return perm

@@ -222,3 +222,67 @@ def test_direct_transport_negotiation_two_ranks_gloo(tmp_path):
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=dict(os.environ, MASTER_ADDR="127.0.0.1"))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     assert p.stdout.count("NEGOTIATE_OK") == 2
+
+
+def test_entity_ids_outside_the_composed_key_are_refused():
+    # the rebalance orders the owned bodies by (cell key << 40) | entity id: an id that is negative, 2^40 or above, not
+    # an integer or not finite would corrupt that key, so the stepper refuses it before any HIP call (CPU tensors here)
+    import pytest
+    import torch
+    from mundy_amd import distributed as D
+    n = 4
+    c, q = torch.zeros((n, 3), dtype=torch.float64), torch.zeros((n, 4), dtype=torch.float64)
+    r, ln = torch.full((n,), 0.5, dtype=torch.float64), torch.ones(n, dtype=torch.float64)
+    top = float((1 << 40) - 1)
+    bad = [[0.0, 1.0, 2.0, float(1 << 40)], [0.0, -1.0, 2.0, 3.0], [0.0, 1.5, 2.0, 3.0], [0.0, 1.0, float("nan"), 3.0],
+           [0.0, 1.0, float("inf"), 3.0], [0.0, 1.0, 2.0, 2.0 ** 60], [0.0, 1.0, 2.0, -0.5]]
+    for ids in bad:
+        with pytest.raises(ValueError, match=r"\[0, 2\^40\)"):
+            D.DistributedContactStepper(c, q, r, ln, 0, entity_id=torch.tensor(ids, dtype=torch.float64))
+    for ids in ([0, 1, 2, 1 << 40], [0, -1, 2, 3], [0, 1, 2, (1 << 53) + 1]):       # int64 ids: checked before conversion
+        with pytest.raises(ValueError, match=r"\[0, 2\^40\)"):
+            D.DistributedContactStepper(c, q, r, ln, 0, entity_id=torch.tensor(ids, dtype=torch.int64))
+    with pytest.raises(ValueError, match="dtype"):
+        D.checked_entity_ids(torch.tensor([True, False]))
+    # the largest ids pass unchanged, as float64, whatever integer or float type they come in
+    ok = [0, 1, (1 << 40) - 2, (1 << 40) - 1]
+    for t in (torch.tensor(ok, dtype=torch.int64), torch.tensor(ok, dtype=torch.float64), np.array(ok, dtype=np.int64)):
+        e = D.checked_entity_ids(t)
+        assert e.dtype == torch.float64 and e.tolist() == [0.0, 1.0, top - 1.0, top]
+    assert D.checked_entity_ids(torch.zeros(0)).shape == (0,)
+
+
+def test_cpp_set_entity_ids_refuses_ids_outside_the_composed_key(tmp_path):
+    # DistributedSpherocylinderStepper::set_entity_ids runs the same check on the host (check_entity_ids) before it
+    # copies anything to the device
+    import subprocess
+    from mundy_amd import build
+    libdir = os.path.dirname(build.build())
+    src = tmp_path / "ids.cpp"
+    src.write_text(r'''
+#include <cmath>
+#include <cstdio>
+#include <limits>
+#include <stdexcept>
+#include "mundy_hip/stepper.hpp"
+using S = mundy_hip::mech::DistributedSpherocylinderStepper;
+static int refused(std::vector<double> ids) {
+  try { S::check_entity_ids(ids); } catch (const std::invalid_argument& e) {
+    return std::string(e.what()).find("[0, 2^40)") != std::string::npos ? 1 : 2;
+  }
+  return 0;
+}
+int main() {
+  const double top = 1099511627775.0, inf = std::numeric_limits<double>::infinity();
+  const double bad[] = {top + 1.0, -1.0, 0.5, std::nan(""), inf, -inf, 1e300, -0.25};
+  for (double b : bad) std::printf("%d", refused({0.0, 1.0, b}));
+  std::printf(" %d %d\n", refused({0.0, 1.0, top - 1.0, top, -0.0}), refused({}));
+  return 0;
+}
+''')
+    exe = str(tmp_path / "ids")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", str(src), "-I", os.path.join(ROOT, "include"),
+                           "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath-link,/opt/rocm/lib",
+                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60, check=True).stdout.strip()
+    assert out == "11111111 0 0", out
