@@ -154,6 +154,34 @@ int mhip_hertz_contact_force(size_t c, size_t n, const int32_t* pairs, const dou
                              const double* youngs_modulus, double youngs_modulus_scalar, const double* poisson_ratio,
                              double poisson_ratio_scalar, double* force, double* max_overlap, mhip_stream_t stream);
 
+/* Growth and division of spherocylinders: the body population of the colony loop changes on the device
+ * (scrap/parameter_interface/alens/tests/performance_tests/Bacteria.cpp:1033-1080).  Per step, before the AABBs:
+ *   mhip_select_dividing  divide_bacteria's mark + partial_sum (:926-935, :243-254): parent_of [<= n] = ascending indices
+ *                         i with length[i] > division_length (strict: L == D and NaN never divide), by wavefront
+ *                         ballot + prefix sum; *num_born [host] (synchronises).  Birth k becomes row n + k.
+ *   mhip_divide_grow_spherocylinders
+ *                         subdivide_spherocylinders (:159-210) then grow_bacteria (:905-920) in one pass over [0, n).
+ *                         parent_of = the ascending list above.  For birth k of parent i, with t = q_i * zhat (the
+ *                         library's rod axis, not the app's q * xhat), cl = 0.5 L - r, s = r + 0.5 cl, off = t s:
+ *                         child row n + k = (c + off, q, r, cl + g), parent row i = (c - off, q, r, cl + g); every
+ *                         other body gets L + g, g = dt * growth_rate computed once.  box [host] 3 or NULL: the two
+ *                         new centres are wrapped into [0, L) as mhip_wrap_rigid does.  The arrays hold n + num_born
+ *                         rows; rows beyond are never written.  Every other per-body field of the parent is the
+ *                         caller's to copy: mhip_gather_rows(num_born, width, parent_of, src, src + n * width).
+ *   mhip_aabb_moved       check_update_neighbor_list (:710-741): *flag [host] = 1 iff some body's min or max corner
+ *                         moved since aabb_ref by d with dx*dx + dy*dy + dz*dz >= threshold^2 (left-to-right sum; NaN
+ *                         does not fire).  Synchronises.  aabb_ref is the snapshot of the last build: the reference
+ *                         accumulates per-step differences instead (:685-705), which is the same in exact arithmetic.
+ * Refused with MHIP_ERR_INVALID_ARGUMENT before any HIP call: dt, growth_rate or division_length negative or not
+ * finite, threshold negative or not finite, num_born > n, a null pointer that would be dereferenced. */
+int mhip_select_dividing(size_t n, const double* length, double division_length, int32_t* parent_of,
+                         size_t* num_born /*[host]*/, mhip_stream_t stream);
+int mhip_divide_grow_spherocylinders(size_t n, size_t num_born, const int32_t* parent_of, double dt,
+                                     double growth_rate, const double* box /*[host] 3 or NULL*/, double* center,
+                                     double* quat, double* radius, double* length, mhip_stream_t stream);
+int mhip_aabb_moved(size_t n, const double* aabb, const double* aabb_ref, double threshold, int* flag /*[host]*/,
+                    mhip_stream_t stream);
+
 /* Mixed shapes (BASELINE configs[4]): kind[n] = 0 sphere, 1 spherocylinder, 2 ellipsoid; shape[n][3] = (r,-,-) /
  * (r,L,-) / (r1,r2,r3); quat is ignored for spheres.  compute_aabb dispatches on kind (compute_aabb.hpp:72-127) and
  * also returns the bounding radii (compute_bounding_radius.hpp:61-93).  contact_mixed bins the pairs by shape class and

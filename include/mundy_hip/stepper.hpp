@@ -5,8 +5,11 @@
 //   -> ContactOperator (rod-compressed) -> solve_lcp (fused BBPGD) -> body velocities -> Euler + quaternion update
 // Opt-in soft contact (SpherocylinderStepper::set_hertz_contact): the solve is replaced by the Hertz force per linker
 // and the operator's body sweep on it, U = M D f (Bacteria.cpp:755-848).
+// Opt-in growth (SpherocylinderStepper::set_growth): the colony step of the same app (Bacteria.cpp:1033-1080) in front
+// of compute_aabb -- divide_bacteria (:926-966) -> grow_bacteria (:905-920) -- on a body population that lives in
+// grow-only device storage, with the rebuild rule of growing bodies (check_update_neighbor_list, :685-748).
 // All arrays stay on the device; the only host reads are the pair count and the solver's convergence polls (Hertz
-// mode: the largest overlap).
+// mode: the largest overlap; growth mode: the birth count and the corner-test flag).
 #pragma once
 #include <chrono>
 #include <cmath>
@@ -33,7 +36,16 @@ struct StepStats {
   double residual = 0.0;
   bool converged = false, rebuilt = false;
   double max_overlap = 0.0;  // Hertz mode: max(0, -sep) over the step's contacts (what dt is chosen from)
+  size_t num_born = 0;       // growth mode: bodies that divided this step (children are rows n_before + k)
 };
+
+/// grow-only storage that keeps its first `live` doubles: reallocates with headroom only when `need` does not fit
+inline void grow_keep(DeviceVector& a, size_t need, size_t live) {
+  if (a.size() >= need) return;
+  DeviceVector b(need + need / 8 + 16);
+  if (live) check(mhip_deep_copy(live, b.data(), a.data(), nullptr));
+  a = std::move(b);
+}
 
 class SpherocylinderStepper {
  public:
@@ -43,7 +55,8 @@ class SpherocylinderStepper {
                         const std::vector<double>& mob_trans, const std::vector<double>& mob_rot, double dt,
                         double search_buffer, convex::PGDConfig<double> cfg, const double* periodic_box = nullptr)
       : n_(radius.size()), dt_(dt), cfg_(cfg), center_(center), quat_(quat), radius_(radius), length_(length),
-        mob_t_(mob_trans), mob_r_(mob_rot), brad_(n_), aabb_(6 * n_), seg_(8 * n_), tmp_(4 * n_), perm_(n_) {
+        mob_t_(mob_trans), mob_r_(mob_rot), brad_(n_), aabb_(6 * n_), seg_(8 * n_), tmp_(4 * n_),
+        buffer_(search_buffer), perm_(n_) {
     check(mhip_bounding_radius_spherocylinders(n_, radius_.data(), length_.data(), brad_.data(), nullptr));
     links_.set_search_buffer(search_buffer).set_search_kind(MHIP_SEARCH_AABB);
     if (periodic_box) {  // orthorhombic periodic box [0, L): periodic search, nearest-image contacts, wrap_rigid
@@ -67,6 +80,7 @@ class SpherocylinderStepper {
     // the neighbour list and the operator's incidence index are in the old numbering
     links_.invalidate();
     op_.reset();
+    have_ref_ = false;
   }
 
   /// Hertzian soft contact instead of the LCP (opt-in; the LCP is the default): each step evaluates the Hertz force
@@ -80,8 +94,30 @@ class SpherocylinderStepper {
     material_.poisson_ratio = poisson_ratio;
   }
 
+  /// The bacterial colony step (Bacteria.cpp:1033-1080), opt-in: every step first divides the rods with length >
+  /// division_length (children appended as rows n + k, parent_of()[k] their parent) and grows every length by
+  /// dt * growth_rate, then rebuilds the list iff there were births, force_rebuild, or some AABB corner moved by
+  /// >= search_buffer since the last build -- the centre rule is not consulted.  Mobilities are carried as given
+  /// (children copy their parent's).  Buffers are sized max(capacity_hint, n + n/8 + 16) and grow with headroom.
+  void set_growth(double growth_rate, double division_length, size_t capacity_hint = 0) {
+    if (!(growth_rate >= 0.0 && growth_rate < HUGE_VAL))
+      throw std::invalid_argument("set_growth: growth_rate must be finite and >= 0");
+    if (!(division_length >= 0.0 && division_length < HUGE_VAL))
+      throw std::invalid_argument("set_growth: division_length must be finite and >= 0");
+    double rmax = 0.0;
+    for (double r : radius_.download()) rmax = r > rmax ? r : rmax;
+    if (division_length < 2.0 * rmax)
+      throw std::invalid_argument("set_growth: division_length < 2 * max(radius): a child would have no length");
+    growth_ = true;
+    rate_ = growth_rate;
+    division_ = division_length;
+    reserve(capacity_hint > n_ + n_ / 8 + 16 ? capacity_hint : n_ + n_ / 8 + 16);
+    have_ref_ = false;
+  }
+
   StepStats step(bool integrate = true, bool force_rebuild = false) {
     StepStats st;
+    if (growth_) st.num_born = grow_and_divide();
     double *sep = nullptr, *normal = nullptr, *s = nullptr, *t = nullptr;
     const size_t C = contacts(st, force_rebuild, sep, normal, s, t);
     if (hertz_) {
@@ -114,8 +150,12 @@ class SpherocylinderStepper {
   }
 
   size_t num_bodies() const { return n_; }
+  /// per-body arrays: the first num_bodies() rows (growth mode: the buffers hold spare rows beyond)
   const DeviceVector& center() const { return center_; }
   const DeviceVector& quat() const { return quat_; }
+  const DeviceVector& length() const { return length_; }
+  /// growth mode: the parents of the last step's births, ascending (the first num_born entries)
+  const DeviceArray<int32_t>& parent_of() const { return parent_of_; }
   /// multipliers of the last step (Hertz mode: the linker forces): the first num_lambda() entries (the buffer only
   /// ever grows)
   const DeviceVector& lambda() const { return lambda_; }
@@ -127,7 +167,20 @@ class SpherocylinderStepper {
   size_t contacts(StepStats& st, bool force_rebuild, double*& sep, double*& normal, double*& s, double*& t) {
     check(mhip_compute_aabb_spherocylinders(n_, center_.data(), quat_.data(), radius_.data(), length_.data(),
                                             aabb_.data(), nullptr));
-    st.rebuilt = links_.generate(n_, aabb_.data(), center_.data(), brad_.data(), nullptr, force_rebuild);
+    if (growth_) {
+      // check_update_neighbor_list (Bacteria.cpp:685-748) against the AABBs of the last build; births force a rebuild
+      int moved = 1;
+      if (have_ref_ && !force_rebuild && st.num_born == 0)
+        check(mhip_aabb_moved(n_, aabb_.data(), aabb_ref_.data(), buffer_, &moved, nullptr));
+      st.rebuilt = moved != 0 && links_.generate(n_, aabb_.data(), center_.data(), brad_.data(), nullptr, true);
+      if (st.rebuilt) {
+        grow_keep(aabb_ref_, 6 * n_, 0);
+        check(mhip_deep_copy(6 * n_, aabb_ref_.data(), aabb_.data(), nullptr));
+        have_ref_ = true;
+      }
+    } else {
+      st.rebuilt = links_.generate(n_, aabb_.data(), center_.data(), brad_.data(), nullptr, force_rebuild);
+    }
     if (st.rebuilt) links_.links_into(pairs_);
     const size_t C = links_.num_links();
     st.num_contacts = C;
@@ -159,6 +212,38 @@ class SpherocylinderStepper {
     st.residual = res.residual;
     st.converged = res.converged != 0;
   }
+  /// every per-body buffer holds at least `cap` rows (live rows kept)
+  void reserve(size_t cap) {
+    grow_keep(center_, 3 * cap, 3 * n_);
+    grow_keep(quat_, 4 * cap, 4 * n_);
+    grow_keep(radius_, cap, n_);
+    grow_keep(length_, cap, n_);
+    grow_keep(mob_t_, cap, n_);
+    grow_keep(mob_r_, cap, n_);
+    grow_keep(brad_, cap, n_);
+    grow_keep(aabb_, 6 * cap, 0);
+    grow_keep(seg_, 8 * cap, 0);
+    grow_keep(tmp_, 4 * cap, 0);
+    workspace(perm_, cap);
+  }
+  /// divide_bacteria -> grow_bacteria (Bacteria.cpp:926-966, :905-920) on the device; returns the birth count
+  size_t grow_and_divide() {
+    size_t nb = 0;
+    // sized before the selection and never reallocated after it: nb <= n_, and reserve() leaves parent_of_ alone, so
+    // the list the selection wrote is what the division and the row copies read
+    workspace(parent_of_, n_ ? n_ : 1);
+    check(mhip_select_dividing(n_, length_.data(), division_, parent_of_.data(), &nb, nullptr));
+    if (nb) reserve(n_ + nb);
+    check(mhip_divide_grow_spherocylinders(n_, nb, parent_of_.data(), dt_, rate_, periodic_ ? box_ : nullptr,
+                                           center_.data(), quat_.data(), radius_.data(), length_.data(), nullptr));
+    if (nb) {  // the other per-body fields of the parent go to the child
+      check(mhip_gather_rows(nb, 1, parent_of_.data(), mob_t_.data(), mob_t_.data() + n_, nullptr));
+      check(mhip_gather_rows(nb, 1, parent_of_.data(), mob_r_.data(), mob_r_.data() + n_, nullptr));
+      n_ += nb;
+    }
+    check(mhip_bounding_radius_spherocylinders(n_, radius_.data(), length_.data(), brad_.data(), nullptr));
+    return nb;
+  }
   void gather(DeviceVector& a, size_t width) {
     check(mhip_gather_rows(n_, width, perm_.data(), a.data(), tmp_.data(), nullptr));
     check(mhip_deep_copy(width * n_, a.data(), tmp_.data(), nullptr));
@@ -173,7 +258,10 @@ class SpherocylinderStepper {
   size_t num_lambda_ = 0;
   bool hertz_ = false;
   linkers::HertzMaterial material_;
-  DeviceArray<int32_t> perm_, pairs_;
+  bool growth_ = false, have_ref_ = false;
+  double rate_ = 0.0, division_ = 0.0, buffer_ = 0.0;
+  DeviceVector aabb_ref_;  // growth mode: the AABBs of the last build
+  DeviceArray<int32_t> perm_, pairs_, parent_of_;
   mesh::GenNeighborLinks links_;
   std::unique_ptr<ContactOperator> op_;
 };

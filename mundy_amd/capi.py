@@ -99,6 +99,9 @@ SIGNATURES = {
     "mhip_contact_mixed_periodic": [_sz] + [_vp] * 5 + [C.POINTER(_d)] + [_vp] * 6 + [C.POINTER(_sz), _vp],
     "mhip_contact_spherocylinders_periodic": [_sz, _vp, _vp, _vp, C.POINTER(_d)] + [_vp] * 9,
     "mhip_hertz_contact_force": [_sz, _sz, _vp, _vp, _vp, _vp, _d, _vp, _d, _vp, _vp, _vp],
+    "mhip_select_dividing": [_sz, _vp, _d, _vp, C.POINTER(_sz), _vp],
+    "mhip_divide_grow_spherocylinders": [_sz, _sz, _vp, _d, _d, C.POINTER(_d), _vp, _vp, _vp, _vp, _vp],
+    "mhip_aabb_moved": [_sz, _vp, _vp, _d, C.POINTER(_i), _vp],
     "mhip_contact_spheres": [_sz, _vp, _vp, _vp, C.POINTER(_d), _vp, _vp, _vp],
     "mhip_contact_spherocylinders": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mhip_broadphase_create": [C.POINTER(_vp)],

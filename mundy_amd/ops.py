@@ -85,8 +85,8 @@ def compute_aabb_segments(seg):
     return out
 
 
-def bounding_radius_spherocylinders(radius, length):
-    out = torch.empty_like(radius)
+def bounding_radius_spherocylinders(radius, length, out=None):
+    out = torch.empty_like(radius) if out is None else out
     capi.check(capi.load().mhip_bounding_radius_spherocylinders(radius.shape[0], _ptr(radius), _ptr(length),
                                                                 _ptr(out), _stream()))
     return out
@@ -481,6 +481,11 @@ class GenNeighborLinks:
         """the body numbering changed (reordering, migration): the next generate() rebuilds whatever the rebuild rule says"""
         self._generated = False
 
+    @property
+    def generated(self):
+        """True once generate() has built a list that invalidate() has not discarded since"""
+        return self._generated
+
     def generate(self, aabb, center, bounding_radius, force=False):
         if not self._concretized:
             raise RuntimeError("Cannot generate links before concretization.")  # :511
@@ -848,6 +853,71 @@ def select_contacts(sep, cutoff):
     capi.check(capi.load().mhip_select_contacts(sep.shape[0], _ptr(sep), float(cutoff), _ptr(kept, torch.int32),
                                                 C.byref(cnt), _stream()))
     return kept[:int(cnt.value)]
+
+
+# ---- growth and division of spherocylinders (Bacteria.cpp:905-966, :685-748) -------------------------------------------
+def _finite_nonneg(value, name):
+    v = float(value)
+    if not (v >= 0.0 and v < float("inf")):
+        raise ValueError("%s must be finite and >= 0, got %r" % (name, value))
+    return v
+
+
+def select_dividing(length, division_length):
+    """divide_bacteria's mark + partial_sum (mhip_select_dividing): (parent_of, num_born) -- int32 ascending indices of
+    the bodies with length > division_length (strict; NaN never divides); birth k becomes row n + k"""
+    D = _finite_nonneg(division_length, "division_length")
+    parent_of = torch.empty(length.shape[0], dtype=torch.int32, device=length.device)
+    cnt = C.c_size_t(0)
+    capi.check(capi.load().mhip_select_dividing(length.shape[0], _ptr(length, name="length"), D,
+                                                _ptr(parent_of, torch.int32), C.byref(cnt), _stream()))
+    nb = int(cnt.value)
+    return parent_of[:nb], nb
+
+
+def divide_grow_spherocylinders(n, parent_of, dt, growth_rate, center, quat, radius, length, box=None):
+    """subdivide_spherocylinders + grow_bacteria in place (mhip_divide_grow_spherocylinders): the first n rows are the
+    bodies before the step, parent_of [nb] the ascending list of select_dividing; rows [n, n + nb) receive the children.
+    Every array must hold at least n + nb rows; rows beyond are untouched.  box: 3 edge lengths of [0, L) or None."""
+    dt = _finite_nonneg(dt, "dt")
+    rate = _finite_nonneg(growth_rate, "growth_rate")
+    n, nb = int(n), int(parent_of.shape[0])
+    for name, t in (("center", center), ("quat", quat), ("radius", radius), ("length", length)):
+        if t.shape[0] < n + nb:
+            raise ValueError("%s holds %d rows, the step needs n + births = %d" % (name, t.shape[0], n + nb))
+    b = None
+    if box is not None:
+        tri, b = _cell(box)
+        if tri:
+            raise ValueError("growth takes an orthorhombic box (3 edge lengths)")
+    capi.check(capi.load().mhip_divide_grow_spherocylinders(
+        n, nb, _ptr(parent_of, torch.int32, name="parent_of"), dt, rate, b, _ptr(center, cols=3, name="center"),
+        _ptr(quat, cols=4, name="quat"), _ptr(radius, name="radius"), _ptr(length, name="length"), _stream()))
+
+
+def copy_parent_rows(parent_of, n, buf):
+    """rows [n, n + nb) of buf = rows parent_of of buf: every per-body field the parent hands to its child
+    (mhip_gather_rows on the same float64 storage, bits copied)"""
+    nb = int(parent_of.shape[0])
+    if nb == 0:
+        return buf
+    if buf.shape[0] < n + nb:
+        raise ValueError("buf holds %d rows, the step needs n + births = %d" % (buf.shape[0], n + nb))
+    width = buf[0].numel()
+    capi.check(capi.load().mhip_gather_rows(nb, width, _ptr(parent_of, torch.int32, name="parent_of"),
+                                            _ptr(buf, name="buf"), _ptr(buf[n:], name="buf"), _stream()))
+    return buf
+
+
+def aabb_moved(aabb, aabb_ref, threshold):
+    """check_update_neighbor_list (mhip_aabb_moved): True iff some min or max corner moved by |d|^2 >= threshold^2"""
+    thr = _finite_nonneg(threshold, "threshold")
+    if tuple(aabb_ref.shape) != tuple(aabb.shape):
+        raise ValueError("aabb_ref must have the shape of aabb %s, got %s" % (tuple(aabb.shape), tuple(aabb_ref.shape)))
+    flag = C.c_int(0)
+    capi.check(capi.load().mhip_aabb_moved(aabb.shape[0], _ptr(aabb, cols=6, name="aabb"),
+                                           _ptr(aabb_ref, cols=6, name="aabb_ref"), thr, C.byref(flag), _stream()))
+    return bool(flag.value)
 
 
 def gather_rows(perm, src):

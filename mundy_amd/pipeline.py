@@ -14,8 +14,17 @@ Bacteria.cpp:755-848; scrap/lcp_spheres/NGPSpheres2.cpp:192-240):
         -> force / torque summed per body and dry drag U = M D f (LinkerPotentialForceReduction +
            compute_generalized_velocity: the contact operator's body sweep, no solve) -> Euler update
 
+growth_rate= adds the colony step of the same app (Bacteria.cpp:1033-1080) in front of the AABBs:
+
+    divide_bacteria (rods longer than division_length split in two, children appended as rows n + k)
+        -> grow_bacteria (every length += dt * growth_rate) -> ... contact step as above
+    with the rebuild rule of growing bodies: births, or some AABB corner moved by >= the search buffer since the last
+    build (check_update_neighbor_list, :685-748) -- the centre rule is not consulted.
+
 Everything is device resident; host logic here only sequences library calls.
 """
+import math
+
 from dataclasses import dataclass, field
 
 import torch
@@ -33,6 +42,7 @@ class StepStats:
     converged: bool = False
     timings_ms: dict = field(default_factory=dict)
     max_overlap: float = 0.0  # contact_model="hertz": max(0, -sep) over the step's contacts (what dt is chosen from)
+    num_born: int = 0  # growth mode: bodies that divided this step (their children are rows n_before + k)
 
 
 class ContactStepper:
@@ -42,13 +52,19 @@ class ContactStepper:
                  search_kind=ops.SEARCH_AABB, periodic_box=None, cfg=None, warm_start=False, mob_trans=None,
                  mob_rot=None, rod_kinematics=True, kinds=None, shape=None, friction=None, contact_cutoff=None,
                  conservative_ellipsoid_box=False, friction_method="apgd", contact_model="lcp", youngs_modulus=1000.0,
-                 poisson_ratio=0.3):
+                 poisson_ratio=0.3, growth_rate=None, division_length=None, capacity=None, ids=None):
         """kind = "sphere" | "spherocylinder" | "mixed".  Mixed systems (BASELINE configs[4]) pass kinds [n] int32
         (0 sphere, 1 spherocylinder, 2 ellipsoid) and shape [n, 3] = (r,-,-) / (r,L,-) / (r1,r2,r3) instead of
         radius / length.
         contact_model = "lcp" (default: hard contact, BBPGD) | "hertz" (soft contact, no solve; spheres and rods only).
         youngs_modulus (E > 0) and poisson_ratio (0 < nu < 1): numbers or per-body tensors [n], Hertz mode only
-        (defaults: Bacteria.cpp:1213-1214)."""
+        (defaults: Bacteria.cpp:1213-1214).
+        growth_rate (None = off): the bacterial colony step (spherocylinders, SEARCH_AABB, either contact model, no
+        friction / cutoff / warm start).  Rods with length > division_length divide, every rod grows by dt *
+        growth_rate per step.  The stepper then owns grow-only storage of `capacity` rows (default n + n/8 + 16, grown
+        with headroom) of which center, quat, radius, length, bounding_radius, mob_*, per-body E / nu and ids (int64,
+        default arange(n)) are views of the first n rows; the caller's tensors are copied, not updated.  Default
+        mobilities use the rod radius (Bacteria.cpp:807-848), which growth does not change."""
         if kind not in ("sphere", "spherocylinder", "mixed"):
             raise ValueError("kind must be 'sphere', 'spherocylinder' or 'mixed'")
         if contact_model not in ("lcp", "hertz"):
@@ -65,6 +81,12 @@ class ContactStepper:
             ops._material(youngs_modulus, center.shape[0], "youngs_modulus", 0.0, float("inf"))
             ops._material(poisson_ratio, center.shape[0], "poisson_ratio", 0.0, 1.0)
         self.youngs_modulus, self.poisson_ratio = youngs_modulus, poisson_ratio
+        self.growth = growth_rate is not None
+        if self.growth:  # (checked before anything reaches the device)
+            self._check_growth(kind, search_kind, friction, contact_cutoff, warm_start, growth_rate, division_length,
+                               radius, quat, length, periodic_box, capacity, ids)
+        elif division_length is not None or capacity is not None or ids is not None:
+            raise ValueError("division_length, capacity and ids belong to growth mode: pass growth_rate")
         if kind == "spherocylinder" and (quat is None or length is None):
             raise ValueError("spherocylinders need quat and length")
         if kind == "mixed" and (quat is None or kinds is None or shape is None):
@@ -103,7 +125,8 @@ class ContactStepper:
             eff = self.bounding_radius
         else:
             self.bounding_radius = ops.bounding_radius_spherocylinders(radius, length)
-            eff = self.bounding_radius
+            # growth mode: the rod radius, constant while a rod grows (Bacteria.cpp:807-848)
+            eff = radius if self.growth else self.bounding_radius
             self.seg = torch.empty((n, 8), dtype=torch.float64, device=center.device)
         if mob_trans is None:
             mt, mr = synth.dry_mobility(eff.cpu().numpy(), viscosity=self.viscosity)
@@ -121,17 +144,154 @@ class ContactStepper:
         # the step is redone on the full list if one does not.
         self.contact_cutoff = None if contact_cutoff is None else float(contact_cutoff)
         self.cutoff_fallbacks = 0
+        self.ids = None
+        if self.growth:
+            self._init_growth(growth_rate, division_length, capacity, ids, search_buffer)
+
+    # -- growth mode (Bacteria.cpp:905-966, :685-748) ---------------------------------------------------------------
+    @staticmethod
+    def _check_growth(kind, search_kind, friction, contact_cutoff, warm_start, growth_rate, division_length, radius,
+                      quat, length, box, capacity, ids):
+        if kind != "spherocylinder":
+            raise ValueError("growth mode grows and divides spherocylinders only, not %r" % kind)
+        if search_kind != ops.SEARCH_AABB:
+            raise ValueError("growth mode needs search_kind=SEARCH_AABB (the corner rebuild rule bounds box gaps)")
+        if friction is not None or contact_cutoff is not None:
+            raise ValueError("growth mode takes no friction or contact_cutoff")
+        if warm_start:
+            raise ValueError("growth mode has no warm start: the constraint set changes with every birth")
+        if quat is None or length is None:
+            raise ValueError("spherocylinders need quat and length")
+        g = float(growth_rate)
+        if not (g >= 0.0 and g < math.inf):
+            raise ValueError("growth_rate must be finite and >= 0, got %r" % (growth_rate,))
+        if division_length is None:
+            raise ValueError("growth mode needs division_length")
+        D = float(division_length)
+        if not (D >= 0.0 and D < math.inf):
+            raise ValueError("division_length must be finite and >= 0, got %r" % (division_length,))
+        rmax = float(radius.max()) if radius.shape[0] else 0.0
+        if D < 2.0 * rmax:
+            raise ValueError("division_length %g < 2 * max(radius) = %g: a child's length 0.5 L - r would not be "
+                             "positive" % (D, 2.0 * rmax))
+        if box is not None:
+            import numpy as np
+            if np.asarray(box.cpu() if isinstance(box, torch.Tensor) else box).size != 3:
+                raise ValueError("growth mode takes an orthorhombic periodic box (3 edge lengths)")
+        if capacity is not None and int(capacity) < 0:
+            raise ValueError("capacity must be >= 0")
+        if ids is not None and (ids.dtype != torch.int64 or tuple(ids.shape) != (radius.shape[0],)):
+            raise ValueError("ids must be int64 of shape [n]")
+
+    def _per_body(self):
+        """the per-body arrays a body carries (and a child copies from its parent) in growth mode"""
+        names = ["center", "quat", "radius", "length", "bounding_radius", "mob_trans", "mob_rot", "ids"]
+        names += [k for k in ("youngs_modulus", "poisson_ratio") if isinstance(getattr(self, k), torch.Tensor)]
+        return names
+
+    def _init_growth(self, growth_rate, division_length, capacity, ids, search_buffer):
+        self.growth_rate, self.division_length = float(growth_rate), float(division_length)
+        self.search_buffer = float(search_buffer)
+        n = self.center.shape[0]
+        dev = self.center.device
+        if ids is None:
+            ids = torch.arange(n, dtype=torch.int64, device=dev)
+        self.ids = ids
+        self.next_id = int(ids.max()) + 1 if n else 0
+        self.n = n
+        self._cap = 0
+        self._store = {}
+        self._ensure_capacity(max(int(capacity or 0), n + n // 8 + 16), fresh=True)
+        self._aabb_ref = None  # the AABBs of the last build (corner rebuild rule)
+        self.last_parent_of = torch.empty(0, dtype=torch.int32, device=dev)
+
+    def _ensure_capacity(self, need, fresh=False):
+        """grow-only storage: a step whose births fit allocates nothing; otherwise new buffers with headroom, the live
+        rows copied over (the old ones stay alive as long as an operator still points into them)"""
+        if need <= self._cap:
+            return
+        cap = need if fresh else need + need // 8 + 16
+        n = self.n
+        for name in self._per_body() + ["seg"]:
+            old = getattr(self, name)
+            buf = torch.empty((cap,) + tuple(old.shape[1:]), dtype=old.dtype, device=self.center.device)
+            if name != "seg":
+                buf[:n].copy_(old[:n])
+            self._store[name] = buf
+        self._cap = cap
+        self._view()
+
+    def _view(self):
+        for name, buf in self._store.items():
+            setattr(self, name, buf[:self.n])
+
+    def grow_and_divide(self):
+        """divide_bacteria -> grow_bacteria (Bacteria.cpp:926-966, :905-920) on the device: returns the birth count.
+        Children are rows n + k with parent last_parent_of[k] and id next_id + k; the new bounding radii follow."""
+        n = self.n
+        parent_of, nb = ops.select_dividing(self.length, self.division_length)
+        if nb:
+            self._ensure_capacity(n + nb)
+        s = self._store
+        ops.divide_grow_spherocylinders(n, parent_of, self.dt, self.growth_rate, s["center"], s["quat"], s["radius"],
+                                        s["length"], box=self.box)
+        if nb:
+            for name in self._per_body():
+                if name not in ("center", "quat", "radius", "length", "bounding_radius", "ids"):
+                    ops.copy_parent_rows(parent_of, n, s[name])
+            s["ids"][n:n + nb] = torch.arange(self.next_id, self.next_id + nb, dtype=torch.int64,
+                                              device=self.center.device)
+            self.next_id += nb
+            self.n = n + nb
+            self._view()
+        # lengths changed: every bounding radius changes too
+        ops.bounding_radius_spherocylinders(self.radius, self.length, out=self.bounding_radius)
+        self.last_parent_of = parent_of
+        return nb
+
+    def _growth_links(self, births, force):
+        """the reference's rebuild rule of growing bodies: births, force, or an AABB corner moved by >= buffer since
+        the last build (check_update_neighbor_list, Bacteria.cpp:685-748)"""
+        rebuild = (force or births > 0 or self._aabb_ref is None or not self.links.generated or
+                   ops.aabb_moved(self.aabb, self._aabb_ref, self.search_buffer))
+        if rebuild:
+            self.links.generate(self.aabb, self.center, self.bounding_radius, force=True)
+            self._aabb_ref = self.aabb  # compute_aabb returns a fresh tensor each step: this is a snapshot
+        return rebuild
 
     # -- stages -----------------------------------------------------------------------------------------------------
     _BODY_ARRAYS = ("center", "radius", "quat", "length", "bounding_radius", "mob_trans", "mob_rot", "shape", "kinds")
 
     def snapshot(self):
-        """device copies of every per-body array (to restart a step from the same input)"""
+        """device copies of every per-body array (to restart a step from the same input); growth mode: and the body
+        count"""
+        if self.growth:
+            snap = {k: getattr(self, k).clone() for k in self._per_body()}
+            snap["_n"], snap["_next_id"] = self.n, self.next_id
+            return snap
         return {k: getattr(self, k).clone() for k in self._BODY_ARRAYS if getattr(self, k, None) is not None}
 
     def restore(self, snap):
+        if self.growth:
+            self._ensure_capacity(snap["_n"])
+            self.n, self.next_id = snap["_n"], snap["_next_id"]
+            for k in self._per_body():
+                self._store[k][:self.n].copy_(snap[k])
+            self._view()
+            self._forget_numbering()
+            return
         for k, v in snap.items():
             getattr(self, k).copy_(v)
+
+    def _forget_numbering(self):
+        """the neighbour list, the operator's incidence index and the multipliers are in an old numbering"""
+        self.links.invalidate()
+        if self.op is not None:
+            self.op.close()
+            self.op = None
+        self.lam = None
+        if self.growth:
+            self._aabb_ref = None
 
     def reorder_bodies(self, cell_size=None, lo=None, curve="morton", hi=None, level=7):
         """Space-filling-curve permutation of all per-body arrays by centre (what the reference's zmorton /
@@ -153,17 +313,13 @@ class ContactStepper:
             perm = ops.morton_order(self.center, lo, cell_size)
         else:
             raise ValueError("curve must be 'morton' or 'hilbert'")
-        for name in self._BODY_ARRAYS:
+        for name in (self._per_body() if self.growth else self._BODY_ARRAYS):
             t = getattr(self, name, None)
             if t is not None:
                 t.copy_(ops.gather_rows(perm, t) if t.dtype == torch.float64 else t[perm.long()])
         # the neighbour list, the operator's incidence index and the multipliers are in the old numbering: a reused list
         # would pair the wrong bodies unless the displacement test happened to fire, so force the rebuild
-        self.links.invalidate()
-        if self.op is not None:
-            self.op.close()
-            self.op = None
-        self.lam = None
+        self._forget_numbering()
         return perm
 
     def compute_aabb(self):
@@ -332,9 +488,16 @@ class ContactStepper:
                 ev.append((name, e))
 
         mark("start")
+        if self.growth:
+            st.num_born = self.grow_and_divide()
+            st.num_bodies = self.n
+            mark("grow_divide")
         self.compute_aabb()
         mark("aabb")
-        st.rebuilt = self.generate_neighbor_links(force=force_rebuild)
+        if self.growth:
+            st.rebuilt = self._growth_links(st.num_born, force_rebuild)
+        else:
+            st.rebuilt = self.generate_neighbor_links(force=force_rebuild)
         mark("broadphase")
         self.compute_contacts()
         mark("narrowphase")
