@@ -182,6 +182,55 @@ int mhip_divide_grow_spherocylinders(size_t n, size_t num_born, const int32_t* p
 int mhip_aabb_moved(size_t n, const double* aabb, const double* aabb_ref, double threshold, int* flag /*[host]*/,
                     mhip_stream_t stream);
 
+/* Bead-spring chains with thermal noise: the per-step kernels of the chromatin loop
+ * (scrap/.../NgpHP1.cpp:3802-3990, SpringsUpdated.cpp, BrownianMotion.cpp) that the contact step lacks.
+ *
+ * Spring set (a handle, built once): m springs (i, j) = pairs[s] between n bodies, all of one type.
+ *   MHIP_SPRING_HOOKEAN  r = rest length r0:  fm = k (L - r0) (1 / L)        (NgpHP1.cpp:1054-1069, its association)
+ *   MHIP_SPRING_FENE     r = r_max:           fm = k / (1 - q q), q = L / r_max
+ *     the force -grad U of U = -1/2 k r_max^2 ln(1 - (L / r_max)^2) (the potential HP1.cpp:3323-3333 weighs): attractive.
+ *     NgpHP1.cpp:1105-1122 applies the opposite sign; this library does not.  A spring with L >= r_max
+ *     (or L NaN) has no force: its term is NaN and it is counted in *overstretched.
+ *   with d = x_j - x_i, L = sqrt(d.d) (right fold), body i receives +fm d and body j -fm d.
+ * k [m] / r [m] per spring [host], or NULL: then the scalar stands for every spring.  pairs [m][2] int32 [host].
+ * create copies them, refuses (MHIP_ERR_INVALID_ARGUMENT, before any HIP call) an index outside [0, n), a spring from a
+ * body to itself, k < 0, r0 < 0, r_max <= 0 and anything not finite, builds the body -> spring incidence on the device
+ * and synchronises `stream`.
+ * force: force [n][3] is written for every body (no atomics on forces): each body adds its spring terms in ascending
+ * spring index from +0.0 (a body without springs gets +0.0 exactly); both ends of a spring evaluate d, L and fm d with
+ * the same operations, so they receive exactly negated vectors.  *overstretched [device, 1 int] = number of FENE springs
+ * without force; *max_length [device, 1 double] = the longest L (+0.0 without springs), order independent. */
+#define MHIP_SPRING_HOOKEAN 0
+#define MHIP_SPRING_FENE 1
+typedef struct mhip_springs* mhip_springs_t;
+int mhip_springs_create(mhip_springs_t* handle, size_t n, size_t m, const int32_t* pairs /*[host] m x 2*/, int type,
+                        const double* k /*[host] m or NULL*/, double k_scalar, const double* r /*[host] m or NULL*/,
+                        double r_scalar, mhip_stream_t stream);
+int mhip_springs_force(mhip_springs_t handle, const double* center, double* force, int* overstretched /*[device]*/,
+                       double* max_length /*[device]*/, mhip_stream_t stream);
+int mhip_springs_destroy(mhip_springs_t handle);
+/* Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11; the generator family of the reference's openrand::Philox):
+ * out[c] = the four 32-bit words of the bare generator at key (keys[c] lo32, hi32) and counter (counters[c] lo32,
+ * counters[c] hi32, block, 0): ten rounds, multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 /
+ * 0xBB67AE85.  Random123's known answers hold (counter 0, key 0 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8).  openrand's
+ * own stream (its key and counter layout) is not reproduced. */
+int mhip_philox4x32_10(size_t count, const uint64_t* keys, const uint64_t* counters, uint32_t block,
+                       uint32_t* out /*[count][4]*/, mhip_stream_t stream);
+/* Brownian velocity, per body: blocks 0 and 1 of Philox at (keys[b], counters[b]) give four normals, of which the
+ * first three are used; velocity[b][0..2] += sqrt(2 kt mob_trans[b] / dt) z (D = kT m_t, BrownianMotion.cpp:571,
+ * SpringsUpdated.cpp:578; NgpHP1.cpp:2157-2181 writes sqrt(sqrt(6 pi mu) r / dt)); counters[b] += 1.
+ * Uniform -> normal, per block of words (w0, w1, w2, w3):
+ *   m = (w0 << 21) | (w1 >> 11), m' = (w2 << 21) | (w3 >> 11)   (53-bit integers)
+ *   u1 = (m + 1) 2^-53 in (0, 1], u2 = m' 2^-53 in [0, 1)
+ *   z0 = sqrt(-2 ln u1) cos(2 pi u2), z1 = sqrt(-2 ln u1) sin(2 pi u2), 2 pi = 6.283185307179586
+ * Refused before any HIP call: kt negative or not finite, dt <= 0 or not finite. */
+int mhip_brownian_velocity(size_t n, const uint64_t* keys, uint64_t* counters /*in/out*/, double kt, double dt,
+                           const double* mob_trans, double* velocity /*[n][6]*/, mhip_stream_t stream);
+/* Dry drag of a per-body force: velocity[b] = (mob_trans[b] F_b, 0, 0, 0); force [n][3] or NULL (F = 0).  The
+ * U_ext = M F_ext of the chromatin step's resolve_collisions (NgpHP1.cpp:1488-1531). */
+int mhip_drag_velocity(size_t n, const double* mob_trans, const double* force, double* velocity /*[n][6]*/,
+                       mhip_stream_t stream);
+
 /* Mixed shapes (BASELINE configs[4]): kind[n] = 0 sphere, 1 spherocylinder, 2 ellipsoid; shape[n][3] = (r,-,-) /
  * (r,L,-) / (r1,r2,r3); quat is ignored for spheres.  compute_aabb dispatches on kind (compute_aabb.hpp:72-127) and
  * also returns the bounding radii (compute_bounding_radius.hpp:61-93).  contact_mixed bins the pairs by shape class and
@@ -413,6 +462,15 @@ int mhip_contact_op_apply(mhip_contact_op_t handle, const double* x, double* y, 
  *           force and torque (cp - x_body) x F summed per body) followed by compute_generalized_velocity
  *           (scrap/parameter_interface/alens/tests/performance_tests/Bacteria.cpp:806-848, dry drag). */
 int mhip_contact_op_body_sweep(mhip_contact_op_t handle, const double* x, mhip_stream_t stream);
+/* The transpose sweep alone: sep_dot [C] = D^T U of a caller-given velocity [N][6] (U, W) rows,
+ *   sep_dot_c = n_c . [(U_j + W_j x rb) - (U_i + W_i x ra)]
+ * with the operator's own kinematics (spheres, vector arms, rod arms).  It is apply's constraint sweep (X_APPLY) on the
+ * caller's rows with no dt factor, same expressions and rounding: dt * constraint_rate(body_velocity after body_sweep(x))
+ * == apply(x) bit for bit, and <x, D^T U> = <D x, U> to rounding.  Rod operators first form (U, W x u) rows in an
+ * operator workspace.  Refused while a staged solve is in progress.
+ * Replaces: sep += dt D^T U_ext of resolve_collisions (NgpHP1.cpp:1488-1531). */
+int mhip_contact_op_constraint_rate(mhip_contact_op_t handle, const double* velocity, double* sep_dot,
+                                    mhip_stream_t stream);
 /* Per-kernel timing of the fused solver (measurement support, no effect on results): when enabled,
  * mhip_bbpgd_solve_contact brackets the k_body / k_constraint launches of every 8th iteration with HIP events on
  * `stream` and accumulates their device durations.  get_profile returns the totals in milliseconds and the number of timed iterations

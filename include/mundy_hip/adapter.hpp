@@ -1129,6 +1129,58 @@ auto solve_cqpp(const Problem& prob, const Strategy& strat, typename Strategy::s
     return strat.result(state);
   }
 }
+// ---- mech: bead-spring chains with thermal noise (NgpHP1.cpp:3802-3990) --------------------------------------------------
+namespace mech {
+
+/// A spring set (mhip_springs_*): pairs [m][2], k / r per spring (host vectors, empty = the scalar for every spring);
+/// r is the rest length (Hookean) or r_max (FENE).  The body -> spring incidence is built on the device once.
+class Springs {
+ public:
+  Springs(size_t num_bodies, const std::vector<int32_t>& pairs, int type, const std::vector<double>& k, double k_scalar,
+          const std::vector<double>& r, double r_scalar, mhip_stream_t stream = nullptr)
+      : overstretched_(1), max_length_(1) {
+    check(mhip_springs_create(&h_, num_bodies, pairs.size() / 2, pairs.data(), type, k.empty() ? nullptr : k.data(),
+                              k_scalar, r.empty() ? nullptr : r.data(), r_scalar, stream));
+  }
+  ~Springs() { mhip_springs_destroy(h_); }
+  Springs(const Springs&) = delete;
+  Springs& operator=(const Springs&) = delete;
+  /// force [n][3] (device); the statistics stay on the device until read
+  void compute_forces(const double* center, double* force, mhip_stream_t stream = nullptr) {
+    check(mhip_springs_force(h_, center, force, overstretched_.data(), max_length_.data(), stream));
+  }
+  int overstretched() const { return overstretched_.download()[0]; }
+  double max_length() const { return max_length_.download()[0]; }
+  const int* overstretched_device() const { return overstretched_.data(); }
+  const double* max_length_device() const { return max_length_.data(); }
+  mhip_springs_t handle() const { return h_; }
+
+ private:
+  mhip_springs_t h_ = nullptr;
+  DeviceArray<int> overstretched_;
+  DeviceArray<double> max_length_;
+};
+
+/// compute_hookean_spring_forces (NgpHP1.cpp:1054-1069): force [n][3] of a Hookean spring set
+inline void compute_hookean_spring_forces(Springs& springs, const double* center, double* force,
+                                          mhip_stream_t stream = nullptr) {
+  springs.compute_forces(center, force, stream);
+}
+/// compute_fene_spring_forces: -grad of U = -1/2 k r_max^2 ln(1 - (L / r_max)^2) (attractive; NgpHP1.cpp:1105-1122
+/// applies the opposite sign).  Overstretched springs are counted in springs.overstretched().
+inline void compute_fene_spring_forces(Springs& springs, const double* center, double* force,
+                                       mhip_stream_t stream = nullptr) {
+  springs.compute_forces(center, force, stream);
+}
+/// compute_brownian_velocity (BrownianMotion.cpp:571 form): velocity[b][0..2] += sqrt(2 kt m_t / dt) z from Philox at
+/// (keys[b], counters[b]); counters advance by one
+inline void compute_brownian_velocity(size_t n, const uint64_t* keys, uint64_t* counters, double kt, double dt,
+                                      const double* mob_trans, double* velocity, mhip_stream_t stream = nullptr) {
+  check(mhip_brownian_velocity(n, keys, counters, kt, dt, mob_trans, velocity, stream));
+}
+
+}  // namespace mech
+
 /// solve_lcp (convex.hpp:839-845)
 template <class Problem, class Strategy>
 auto solve_lcp(const Problem& prob, const Strategy& strat, typename Strategy::state_t& state) ->

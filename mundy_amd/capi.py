@@ -13,6 +13,7 @@ SEARCH_SPHERES, SEARCH_AABB = 0, 1
 SEARCH_METHOD_AUTO, SEARCH_METHOD_GRID, SEARCH_METHOD_MORTON_LBVH = 0, 1, 2
 SPACE_UNCONSTRAINED, SPACE_LOWER_BOUND, SPACE_UPPER_BOUND, SPACE_BOUNDED = 0, 1, 2, 3
 RESIDUAL_PROJECTED_DIFF, RESIDUAL_PROJECTED_GRADIENT = 0, 1
+SPRING_HOOKEAN, SPRING_FENE = 0, 1
 
 
 class MhipError(RuntimeError):
@@ -102,6 +103,12 @@ SIGNATURES = {
     "mhip_select_dividing": [_sz, _vp, _d, _vp, C.POINTER(_sz), _vp],
     "mhip_divide_grow_spherocylinders": [_sz, _sz, _vp, _d, _d, C.POINTER(_d), _vp, _vp, _vp, _vp, _vp],
     "mhip_aabb_moved": [_sz, _vp, _vp, _d, C.POINTER(_i), _vp],
+    "mhip_springs_create": [C.POINTER(_vp), _sz, _sz, _vp, _i, _vp, _d, _vp, _d, _vp],
+    "mhip_springs_force": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "mhip_springs_destroy": [_vp],
+    "mhip_philox4x32_10": [_sz, _vp, _vp, C.c_uint32, _vp, _vp],
+    "mhip_brownian_velocity": [_sz, _vp, _vp, _d, _d, _vp, _vp, _vp],
+    "mhip_drag_velocity": [_sz, _vp, _vp, _vp, _vp],
     "mhip_contact_spheres": [_sz, _vp, _vp, _vp, C.POINTER(_d), _vp, _vp, _vp],
     "mhip_contact_spherocylinders": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mhip_broadphase_create": [C.POINTER(_vp)],
@@ -136,6 +143,7 @@ SIGNATURES = {
     "mhip_contact_op_destroy": [_vp],
     "mhip_contact_op_apply": [_vp, _vp, _vp, _vp],
     "mhip_contact_op_body_sweep": [_vp, _vp, _vp],
+    "mhip_contact_op_constraint_rate": [_vp, _vp, _vp, _vp],
     "mhip_contact_op_body_velocity": [_vp, C.POINTER(_vp)],
     "mhip_contact_op_set_profiling": [_vp, _i],
     "mhip_contact_op_set_tiering": [_vp, _i],

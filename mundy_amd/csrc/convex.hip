@@ -1969,6 +1969,16 @@ __global__ void __launch_bounds__(kBlock) k_rod_axes(size_t n, const double* __r
     store3(axis, i, V3{r[3], r[4], r[5]} - V3{r[0], r[1], r[2]});
   }
 }
+// (U, W) rows of a caller -> (U, Z = W x u) rows as the rod sweeps read them (the cross product k_body forms)
+__global__ void __launch_bounds__(kBlock) k_rate_rows(size_t n, const double* __restrict__ vel,
+                                                     const double* __restrict__ axis, double* __restrict__ out) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const V3 w{vel[6 * i + 3], vel[6 * i + 4], vel[6 * i + 5]};
+    const V3 z = cross(w, V3{axis[3 * i], axis[3 * i + 1], axis[3 * i + 2]});
+    out[6 * i] = vel[6 * i]; out[6 * i + 1] = vel[6 * i + 1]; out[6 * i + 2] = vel[6 * i + 2];
+    out[6 * i + 3] = z.x; out[6 * i + 4] = z.y; out[6 * i + 5] = z.z;
+  }
+}
 // (U, Z) rows + omega -> (U, W) rows for the integrator
 __global__ void __launch_bounds__(kBlock) k_assemble_velocity(size_t n, const double* __restrict__ vel,
                                                              const double* __restrict__ omega,
@@ -2369,6 +2379,7 @@ struct mhip_contact_op {
   hipStream_t last_stream = nullptr;
   DeviceBuffer inc_ptr, inc, cursor, vel, partials, state, scanws, half, axis, omega, vel_out;
   DeviceBuffer iterate;  // packed (x, g) ping-pong pair of the fused / staged solvers: 2 x C x 16 bytes
+  DeviceBuffer rate_rows;  // (U, W x u) rows of a caller's velocity (mhip_contact_op_constraint_rate, rods)
   DeviceBuffer body_mask, pos;  // activity masks of the packed LCP solves (see OpView)
   DeviceBuffer sort_tmp, sort_list;  // workspaces of the incidence-list sort
   DeviceBuffer aptr, aent, arec, snap_mask, acnt;  // active lists (see OpView)
@@ -3301,7 +3312,7 @@ int mhip_gemv(size_t n, const double* A, const double* x, double* y, mhip_stream
 // pinned state block, timing events -- are the same size step after step.  A destroyed operator therefore leaves them
 // in one process-wide spare set that the next create adopts: no hipMalloc / hipFree in the steady state (hipFree
 // alone cost 1.6 ms per step at 10^6 rods).  mhip_release_cached_workspaces() frees the spare set.
-constexpr int kOpBuffers = 30;
+constexpr int kOpBuffers = 31;
 struct OpWorkspaces {
   DeviceBuffer buf[kOpBuffers];
   SolverState* host_state = nullptr;
@@ -3315,7 +3326,7 @@ static DeviceBuffer* op_buffers(mhip_contact_op* op, int k) {
   DeviceBuffer* all[kOpBuffers] = {&op->inc_ptr, &op->inc,     &op->cursor,   &op->vel,      &op->partials, &op->state,
                                    &op->scanws,  &op->half,    &op->axis,     &op->omega,    &op->vel_out,  &op->iterate,
                                    &op->body_mask, &op->pos,   &op->sort_tmp, &op->sort_list, &op->aptr,    &op->aent,
-                                   &op->arec,    &op->snap_mask, &op->acnt,
+                                   &op->arec,    &op->snap_mask, &op->acnt,  &op->rate_rows,
                                    &op->tier.geo[0], &op->tier.geo[1], &op->tier.iter[0], &op->tier.iter[1],
                                    &op->tier.misc, &op->tier.vel2, &op->tier.drift, &op->tier.arm, &op->tier.xprev};
   return all[k];
@@ -3614,6 +3625,42 @@ int mhip_contact_op_body_sweep(mhip_contact_op_t op, const double* x, mhip_strea
   MHIP_REQUIRE(!op->stage.active, MHIP_ERR_RUNTIME, "a staged solve is in progress");
   const Space none{MHIP_SPACE_UNCONSTRAINED, 0, 0};
   return op_launch_body(op, X_APPLY, x, x, nullptr, nullptr, none, as_stream(stream));
+}
+
+// The constraint sweep of apply alone, on a velocity the caller gives: sep_dot = D^T U.  The operator's own view with
+// the caller's rows and dt = 1 (1.0 * sdot is sdot), so the same expressions round the same way as inside apply.
+int mhip_contact_op_constraint_rate(mhip_contact_op_t op, const double* velocity, double* sep_dot,
+                                    mhip_stream_t stream) {
+  MHIP_REQUIRE(op != nullptr, MHIP_ERR_INVALID_ARGUMENT, "operator handle is null");
+  MHIP_REQUIRE(op->view.C == 0 || (velocity && sep_dot), MHIP_ERR_INVALID_ARGUMENT, "velocity / sep_dot must not be null");
+  MHIP_REQUIRE(!op->stage.active, MHIP_ERR_RUNTIME, "a staged solve is in progress");
+  if (op->view.C == 0) return MHIP_SUCCESS;
+  hipStream_t s = as_stream(stream);
+  op->last_stream = s;
+  OpView v = op->view;
+  v.dt = 1.0;
+  v.vel = const_cast<double*>(velocity);  // read only in X_APPLY's constraint sweep
+  if (op->kin == KIN_ROD) {
+    const size_t N = op->view.N;
+    if (int e = op->rate_rows.reserve((6 * N + 2) * sizeof(double))) return e;
+    k_rate_rows<<<grid_for(N), kBlock, 0, s>>>(N, velocity, op->axis.as<double>(), op->rate_rows.as<double>());
+    v.vel = op->rate_rows.as<double>();
+  }
+  const Space none{MHIP_SPACE_UNCONSTRAINED, 0, 0};
+  // X_APPLY loads an iterate from X0 whose value it never uses: any readable array of >= C doubles (the half-edge
+  // records: 2 C records of >= 3 doubles) stands in
+  double* x0 = op->half.as<double>();
+  const SolverState* st = op->state.as<SolverState>();
+  double* parts = op->partials.as<double>();
+  const unsigned grid = grid_for(op->view.C);
+  if (op->kin == KIN_ROD)
+    k_constraint<X_APPLY, KIN_ROD, false><<<grid, kBlock, 0, s>>>(v, st, x0, nullptr, nullptr, sep_dot, nullptr, none, 0, parts);
+  else if (op->kin == KIN_RIGID)
+    k_constraint<X_APPLY, KIN_RIGID, false><<<grid, kBlock, 0, s>>>(v, st, x0, nullptr, nullptr, sep_dot, nullptr, none, 0, parts);
+  else
+    k_constraint<X_APPLY, KIN_TRANS, false><<<grid, kBlock, 0, s>>>(v, st, x0, nullptr, nullptr, sep_dot, nullptr, none, 0, parts);
+  MHIP_LAUNCH_CHECK();
+  return MHIP_SUCCESS;
 }
 
 int mhip_contact_op_sizes(mhip_contact_op_t op, size_t* num_constraints, size_t* num_bodies) {

@@ -637,6 +637,16 @@ class ContactOperator:
             raise ValueError("x must have shape [%d], got %s" % (self.num_constraints, tuple(x.shape)))
         capi.check(capi.load().mhip_contact_op_body_sweep(self._h, _ptr(x, name="x"), _stream()))
 
+    def constraint_rate(self, velocity, out=None):
+        """sep_dot [C] = D^T U of a velocity [N, 6] (U, W): n_c . [(U_j + W_j x rb) - (U_i + W_i x ra)] with this
+        operator's kinematics -- the adjoint of body_sweep, without apply's dt (mhip_contact_op_constraint_rate)"""
+        if tuple(velocity.shape) != (self.num_bodies, 6):
+            raise ValueError("velocity must have shape [%d, 6], got %s" % (self.num_bodies, tuple(velocity.shape)))
+        y = torch.empty(self.num_constraints, dtype=torch.float64, device=self._device) if out is None else out
+        capi.check(capi.load().mhip_contact_op_constraint_rate(self._h, _ptr(velocity, cols=6, name="velocity"),
+                                                               _ptr(y, name="out"), _stream()))
+        return y
+
     def body_velocity_of(self, x):
         """[N, 6] (U, W) = M D x (body_sweep, then a copy of the rows)"""
         self.body_sweep(x)
@@ -968,3 +978,134 @@ def unit_cell_inverse(cell):
 def integrate_euler(dt, velocity, center, quat=None):
     capi.check(capi.load().mhip_integrate_euler(center.shape[0], float(dt), _ptr(velocity, cols=6),
                                                 _ptr(center, cols=3), _ptr(quat, cols=4, allow_none=True), _stream()))
+
+
+# ---- bead-spring chains with thermal noise (NgpHP1.cpp:3802-3990, BrownianMotion.cpp, SpringsUpdated.cpp) ------------
+SPRING_TYPES = {"hookean": capi.SPRING_HOOKEAN, "fene": capi.SPRING_FENE}
+
+
+def _spring_param(value, m, name, positive):
+    """a per-spring parameter: a number -> (None, value); an array / tensor [m] -> (host float64 array, 0.0); checked
+    here on the host, as the library checks it again before any HIP call"""
+    import numpy as np
+    if isinstance(value, (torch.Tensor, np.ndarray, list, tuple)):
+        a = np.ascontiguousarray((value.detach().cpu().numpy() if isinstance(value, torch.Tensor) else
+                                  np.asarray(value)), dtype=np.float64)
+        if a.shape != (m,):
+            raise ValueError("%s must be a number or an array of shape [%d], got %s" % (name, m, a.shape))
+        vals = a
+    else:
+        a, vals = None, np.array([float(value)])
+    ok = np.isfinite(vals) & ((vals > 0.0) if positive else (vals >= 0.0))
+    if not ok.all():
+        raise ValueError("%s must be finite and %s 0, got %r" % (name, ">" if positive else ">=",
+                                                                 float(vals[~ok][0])))
+    return (a, 0.0) if a is not None else (None, float(vals[0]))
+
+
+def check_springs(pairs, kind, k, r, n):
+    """host-side validation of a spring set -> (pairs int32 [m, 2] host, type, k array / None, k0, r array / None, r0)"""
+    import numpy as np
+    if kind not in SPRING_TYPES:
+        raise ValueError("spring type must be 'hookean' or 'fene', got %r" % (kind,))
+    p = pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
+    if p.size == 0:
+        p = p.reshape(0, 2)
+    if p.ndim != 2 or p.shape[1] != 2 or not (p.dtype.kind in "iu" or p.size == 0):
+        raise ValueError("spring pairs must be integers of shape [m, 2], got %s %s" % (p.dtype, p.shape))
+    if p.size and (p.min() < 0 or p.max() >= n):
+        raise ValueError("spring pairs: an index outside [0, %d)" % n)
+    if p.size and (p[:, 0] == p[:, 1]).any():
+        raise ValueError("spring pairs: a spring from a body to itself (spring %d)" % int(np.argmax(p[:, 0] == p[:, 1])))
+    m = p.shape[0]
+    ka, k0 = _spring_param(k, m, "spring constant k", False)
+    fene = kind == "fene"
+    ra, r0 = _spring_param(r, m, "r_max" if fene else "rest length r0", fene)
+    return np.ascontiguousarray(p, dtype=np.int32), SPRING_TYPES[kind], ka, k0, ra, r0
+
+
+class Springs:
+    """A spring set between n bodies (mhip_springs_*): kind "hookean" (r = rest length) or "fene" (r = r_max); k and r
+    numbers or per-spring arrays.  force(center) -> (force [n, 3], overstretched [1] int32, max_length [1] float64), the
+    two statistics left on the device.  Every body sums its terms in ascending spring index from +0.0."""
+
+    def __init__(self, n, pairs, kind, k, r):
+        p, t, ka, k0, ra, r0 = check_springs(pairs, kind, k, r, n)
+        self.n, self.num_springs, self.kind = int(n), p.shape[0], kind
+        self.pairs, self.k, self.r = p, (ka if ka is not None else k0), (ra if ra is not None else r0)
+        h = C.c_void_p()
+        cp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        capi.check(capi.load().mhip_springs_create(C.byref(h), self.n, p.shape[0], cp(p), t, cp(ka), k0, cp(ra), r0,
+                                                   _stream()))
+        self._h = h
+
+    def force(self, center, out=None, stats=None):
+        """stats: an optional int32 [1] / float64 [1] pair (overstretched, max_length) to write into"""
+        if tuple(center.shape) != (self.n, 3):
+            raise ValueError("center must have shape [%d, 3], got %s" % (self.n, tuple(center.shape)))
+        f = torch.empty((self.n, 3), dtype=torch.float64, device=center.device) if out is None else out
+        if stats is None:
+            stats = (torch.empty(1, dtype=torch.int32, device=center.device),
+                     torch.empty(1, dtype=torch.float64, device=center.device))
+        over, mx = stats
+        capi.check(capi.load().mhip_springs_force(self._h, _ptr(center, cols=3, name="center"), _ptr(f, name="out"),
+                                                  C.c_void_p(over.data_ptr()), C.c_void_p(mx.data_ptr()), _stream()))
+        return f, over, mx
+
+    def close(self):
+        if getattr(self, "_h", None):
+            capi.load().mhip_springs_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _u64(t, name):
+    """int64 tensors carry the u64 keys / counters of the generator (bit patterns)"""
+    return _ptr(t, torch.int64, name=name)
+
+
+def philox4x32_10(keys, counters, block=0):
+    """the bare Philox4x32-10 (mhip_philox4x32_10): [count, 4] int32 holding the uint32 words at key (keys lo, hi) and
+    counter (counters lo, hi, block, 0); keys / counters are int64 tensors read as u64 bit patterns"""
+    b = int(block)
+    if not (0 <= b < 2 ** 32):
+        raise ValueError("block must be a uint32, got %r" % (block,))
+    if keys.shape != counters.shape or keys.dim() != 1:
+        raise ValueError("keys and counters must be 1-D of one shape")
+    out = torch.empty((keys.shape[0], 4), dtype=torch.int32, device=keys.device)
+    capi.check(capi.load().mhip_philox4x32_10(keys.shape[0], _u64(keys, "keys"), _u64(counters, "counters"), b,
+                                              _ptr(out, torch.int32), _stream()))
+    return out
+
+
+def brownian_velocity(keys, counters, kt, dt, mob_trans, velocity):
+    """velocity[:, :3] += sqrt(2 kt m_t / dt) z with z from Philox blocks 0 and 1 at (key, counter); counters += 1
+    (mhip_brownian_velocity).  keys / counters int64 [n] (counters updated in place), velocity [n, 6] in place."""
+    kt, dt = float(kt), float(dt)
+    if not (kt >= 0.0 and kt < float("inf")):
+        raise ValueError("kt must be finite and >= 0, got %r" % kt)
+    if not (dt > 0.0 and dt < float("inf")):
+        raise ValueError("dt must be finite and > 0, got %r" % dt)
+    n = keys.shape[0]
+    for name, t in (("counters", counters), ("mob_trans", mob_trans), ("velocity", velocity)):
+        if t.shape[0] != n:
+            raise ValueError("%s holds %d rows, keys %d" % (name, t.shape[0], n))
+    capi.check(capi.load().mhip_brownian_velocity(n, _u64(keys, "keys"), _u64(counters, "counters"), kt, dt,
+                                                  _ptr(mob_trans, name="mob_trans"),
+                                                  _ptr(velocity, cols=6, name="velocity"), _stream()))
+    return velocity
+
+
+def drag_velocity(mob_trans, force=None, out=None):
+    """[n, 6] (m_t F, 0) of a per-body force [n, 3] (None: F = 0) (mhip_drag_velocity)"""
+    n = mob_trans.shape[0]
+    v = torch.empty((n, 6), dtype=torch.float64, device=mob_trans.device) if out is None else out
+    capi.check(capi.load().mhip_drag_velocity(n, _ptr(mob_trans, name="mob_trans"),
+                                              _ptr(force, cols=3, allow_none=True, name="force"),
+                                              _ptr(v, cols=6, name="out"), _stream()))
+    return v

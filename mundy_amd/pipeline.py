@@ -21,6 +21,12 @@ growth_rate= adds the colony step of the same app (Bacteria.cpp:1033-1080) in fr
     with the rebuild rule of growing bodies: births, or some AABB corner moved by >= the search buffer since the last
     build (check_update_neighbor_list, :685-748) -- the centre rule is not consulted.
 
+springs= / brownian_kt= add the bead-spring chain step of the chromatin app (spheres only; NgpHP1.cpp:3802-3990):
+
+    ... -> broad phase -> spring forces F (+ external_force) -> U_ext = M F + U_brown
+        -> contacts, q = sep + dt D^T U_ext (ContactOperator.constraint_rate) -> solve (or Hertz f)
+        -> U = U_ext + M D lambda -> Euler update
+
 Everything is device resident; host logic here only sequences library calls.
 """
 import math
@@ -43,6 +49,7 @@ class StepStats:
     timings_ms: dict = field(default_factory=dict)
     max_overlap: float = 0.0  # contact_model="hertz": max(0, -sep) over the step's contacts (what dt is chosen from)
     num_born: int = 0  # growth mode: bodies that divided this step (their children are rows n_before + k)
+    max_spring_length: float = 0.0  # springs=: the longest spring at the start of the step
 
 
 class ContactStepper:
@@ -52,7 +59,8 @@ class ContactStepper:
                  search_kind=ops.SEARCH_AABB, periodic_box=None, cfg=None, warm_start=False, mob_trans=None,
                  mob_rot=None, rod_kinematics=True, kinds=None, shape=None, friction=None, contact_cutoff=None,
                  conservative_ellipsoid_box=False, friction_method="apgd", contact_model="lcp", youngs_modulus=1000.0,
-                 poisson_ratio=0.3, growth_rate=None, division_length=None, capacity=None, ids=None):
+                 poisson_ratio=0.3, growth_rate=None, division_length=None, capacity=None, ids=None, springs=None,
+                 brownian_kt=None, rng_keys=None, rng_counter=None):
         """kind = "sphere" | "spherocylinder" | "mixed".  Mixed systems (BASELINE configs[4]) pass kinds [n] int32
         (0 sphere, 1 spherocylinder, 2 ellipsoid) and shape [n, 3] = (r,-,-) / (r,L,-) / (r1,r2,r3) instead of
         radius / length.
@@ -64,7 +72,12 @@ class ContactStepper:
         growth_rate per step.  The stepper then owns grow-only storage of `capacity` rows (default n + n/8 + 16, grown
         with headroom) of which center, quat, radius, length, bounding_radius, mob_*, per-body E / nu and ids (int64,
         default arange(n)) are views of the first n rows; the caller's tensors are copied, not updated.  Default
-        mobilities use the rod radius (Bacteria.cpp:807-848), which growth does not change."""
+        mobilities use the rod radius (Bacteria.cpp:807-848), which growth does not change.
+        springs = (pairs [m, 2], "hookean" | "fene", k, r) and / or brownian_kt (kT >= 0): the chain step (spheres, no
+        growth, friction or cutoff; springs take no periodic box).  r is the rest length (Hookean) or r_max (FENE); k and
+        r numbers or per-spring arrays.  rng_keys (integers in [0, 2^63), default arange(n)) and rng_counter (default
+        0) key the Philox stream of each body; the counters advance by one per step.  step(external_force=) adds a
+        per-step [n, 3] force to the spring force."""
         if kind not in ("sphere", "spherocylinder", "mixed"):
             raise ValueError("kind must be 'sphere', 'spherocylinder' or 'mixed'")
         if contact_model not in ("lcp", "hertz"):
@@ -87,6 +100,12 @@ class ContactStepper:
                                radius, quat, length, periodic_box, capacity, ids)
         elif division_length is not None or capacity is not None or ids is not None:
             raise ValueError("division_length, capacity and ids belong to growth mode: pass growth_rate")
+        self.chain = springs is not None or brownian_kt is not None
+        if self.chain:  # (checked before anything reaches the device)
+            chain_spec = self._check_chain(kind, center.shape[0], periodic_box, friction, contact_cutoff, springs,
+                                           brownian_kt, rng_keys, rng_counter)
+        elif rng_keys is not None or rng_counter is not None:
+            raise ValueError("rng_keys and rng_counter key the Brownian noise: pass brownian_kt")
         if kind == "spherocylinder" and (quat is None or length is None):
             raise ValueError("spherocylinders need quat and length")
         if kind == "mixed" and (quat is None or kinds is None or shape is None):
@@ -147,6 +166,87 @@ class ContactStepper:
         self.ids = None
         if self.growth:
             self._init_growth(growth_rate, division_length, capacity, ids, search_buffer)
+        self.springs = self.rng_keys = self.rng_counter = None
+        if self.chain:
+            self._init_chain(*chain_spec)
+
+    # -- bead-spring chains with thermal noise (NgpHP1.cpp:3802-3990) ----------------------------------------------------
+    @staticmethod
+    def _check_chain(kind, n, box, friction, contact_cutoff, springs, kt, keys, counter):
+        import numpy as np
+        if kind != "sphere":
+            raise ValueError("springs and Brownian noise are wired for spheres only, not %r" % kind)
+        if friction is not None or contact_cutoff is not None:
+            raise ValueError("springs / brownian_kt take no friction or contact_cutoff")
+        if springs is not None and box is not None:
+            raise ValueError("springs take no periodic_box (the chains are unbounded; no minimum-image springs)")
+        spec = None
+        if springs is not None:
+            if not isinstance(springs, (tuple, list)) or len(springs) != 4:
+                raise ValueError("springs must be (pairs, 'hookean' | 'fene', k, r)")
+            pairs, skind, k, r = springs
+            p, _, ka, k0, ra, r0 = ops.check_springs(pairs, skind, k, r, n)
+            spec = (p, skind, ka if ka is not None else k0, ra if ra is not None else r0)
+        if kt is not None:
+            kt = float(kt)
+            if not (kt >= 0.0 and kt < math.inf):
+                raise ValueError("brownian_kt must be finite and >= 0, got %r" % (kt,))
+        elif keys is not None or counter is not None:
+            raise ValueError("rng_keys and rng_counter key the Brownian noise: pass brownian_kt")
+
+        def ints(t, name, hi):
+            if t is None:
+                return None
+            a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+            if a.dtype.kind not in "iu" or a.shape != (n,):
+                raise ValueError("%s must be integers of shape [%d], got %s %s" % (name, n, a.dtype, a.shape))
+            if a.size and (int(a.min()) < 0 or int(a.max()) >= hi):
+                raise ValueError("%s must lie in [0, 2^63)" % name)
+            return np.ascontiguousarray(a, dtype=np.int64)
+        return spec, kt, ints(keys, "rng_keys", 2 ** 63), ints(counter, "rng_counter", 2 ** 63)
+
+    def _init_chain(self, spec, kt, keys, counter):
+        n, dev = self.center.shape[0], self.center.device
+        self._spring_spec = spec
+        self.springs = ops.Springs(n, *spec) if spec is not None else None
+        self.brownian_kt = kt
+        self.rng_keys = (torch.arange(n, dtype=torch.int64, device=dev) if keys is None else
+                         torch.from_numpy(keys).to(dev))
+        self.rng_counter = (torch.zeros(n, dtype=torch.int64, device=dev) if counter is None else
+                            torch.from_numpy(counter).to(dev))
+        # [max_overlap, max_spring_length, overstretched (int32 in the low word)]: one read per step
+        self._chain_stats = torch.zeros(3, dtype=torch.float64, device=dev)
+        self.spring_force = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        self.u_ext = torch.zeros((n, 6), dtype=torch.float64, device=dev)
+        self.velocity = None
+
+    def _renumber_springs(self, perm):
+        """reorder_bodies: spring endpoints through the inverse permutation (spring order kept), new handle"""
+        import numpy as np
+        p, skind, k, r = self._spring_spec
+        pm = perm.cpu().numpy().astype(np.int64)
+        inv = np.empty(pm.shape[0], dtype=np.int64)
+        inv[pm] = np.arange(pm.shape[0])
+        self._spring_spec = (np.ascontiguousarray(inv[p], dtype=np.int32), skind, k, r)
+        self.springs.close()
+        self.springs = ops.Springs(self.center.shape[0], *self._spring_spec)
+
+    def external_velocity(self, external_force=None):
+        """U_ext = M (F_spring + F_ext) + U_brown into self.u_ext (the rng counters advance)"""
+        self._chain_stats.zero_()
+        force = None
+        if self.springs is not None:
+            force, _, _ = self.springs.force(self.center, out=self.spring_force,
+                                             stats=(self._chain_stats.view(torch.int32)[4:5], self._chain_stats[1:2]))
+            if external_force is not None:
+                ops.axpby(1.0, external_force.reshape(-1), 1.0, force.view(-1))
+        elif external_force is not None:
+            force = external_force
+        ops.drag_velocity(self.mob_trans, force, out=self.u_ext)
+        if self.brownian_kt is not None:
+            ops.brownian_velocity(self.rng_keys, self.rng_counter, self.brownian_kt, self.dt, self.mob_trans,
+                                  self.u_ext)
+        return self.u_ext
 
     # -- growth mode (Bacteria.cpp:905-966, :685-748) ---------------------------------------------------------------
     @staticmethod
@@ -260,7 +360,8 @@ class ContactStepper:
         return rebuild
 
     # -- stages -----------------------------------------------------------------------------------------------------
-    _BODY_ARRAYS = ("center", "radius", "quat", "length", "bounding_radius", "mob_trans", "mob_rot", "shape", "kinds")
+    _BODY_ARRAYS = ("center", "radius", "quat", "length", "bounding_radius", "mob_trans", "mob_rot", "shape", "kinds",
+                    "rng_keys", "rng_counter")
 
     def snapshot(self):
         """device copies of every per-body array (to restart a step from the same input); growth mode: and the body
@@ -317,6 +418,8 @@ class ContactStepper:
             t = getattr(self, name, None)
             if t is not None:
                 t.copy_(ops.gather_rows(perm, t) if t.dtype == torch.float64 else t[perm.long()])
+        if getattr(self, "springs", None) is not None:
+            self._renumber_springs(perm)
         # the neighbour list, the operator's incidence index and the multipliers are in the old numbering: a reused list
         # would pair the wrong bodies unless the displacement test happened to fire, so force the rebuild
         self._forget_numbering()
@@ -434,7 +537,12 @@ class ContactStepper:
         nc = pairs.shape[0]
         if rebuilt or self.lam is None or not self.warm_start or self.lam.shape[0] != nc:
             self.lam = torch.zeros(nc, dtype=torch.float64, device=self.center.device)  # NgpLcp.cpp:890-891
-        x, g, res = ops.solve_lcp(self.op, c["sep"], self.lam, self.cfg)
+        q = c["sep"]
+        if self.chain:  # q = sep + dt D^T U_ext (NgpHP1.cpp:1488-1531)
+            q = self.op.constraint_rate(self.u_ext)
+            ops.axpby(1.0, c["sep"], self.dt, q)
+            self.q = q
+        x, g, res = ops.solve_lcp(self.op, q, self.lam, self.cfg)
         self.lam, self.grad = x, g
         return res
 
@@ -446,7 +554,8 @@ class ContactStepper:
         """soft contact: per-linker Hertz force, then the operator's body sweep on it -- U = M D f (no solve)"""
         c, pairs = self.contacts, self.links.pairs
         self.lam, self.max_overlap = ops.hertz_contact_force(pairs, c["sep"], self._contact_radius(),
-                                                             self.youngs_modulus, self.poisson_ratio)
+                                                             self.youngs_modulus, self.poisson_ratio,
+                                                             max_overlap=self._chain_stats[0:1] if self.chain else None)
         mark("hertz_force")
         # the operator follows the neighbour list: built on a rebuild, its geometry refreshed otherwise
         reuse = not rebuilt and self.op is not None and self.op.num_constraints == pairs.shape[0]
@@ -470,6 +579,9 @@ class ContactStepper:
 
     def integrate(self):
         vel = self.op.body_velocity()
+        if self.chain:  # U = U_ext + U_contact
+            ops.axpby(1.0, self.u_ext.view(-1), 1.0, vel.view(-1))
+            self.velocity = vel
         ops.integrate_euler(self.dt, vel, self.center, self.quat)
         if self.box is not None:
             # wrap_rigid_inplace of a Sphere / Spherocylinder / Ellipsoid: the centre goes back into the box,
@@ -477,7 +589,13 @@ class ContactStepper:
             ops.wrap_rigid(self.box, self.center)
 
     # -- one timestep -------------------------------------------------------------------------------------------------
-    def step(self, integrate=True, force_rebuild=False, timed=False):
+    def step(self, integrate=True, force_rebuild=False, timed=False, external_force=None):
+        if external_force is not None:
+            if not self.chain:
+                raise ValueError("external_force belongs to the chain step: pass springs= or brownian_kt= (0.0: no noise)")
+            if tuple(external_force.shape) != (self.center.shape[0], 3):
+                raise ValueError("external_force must have shape [%d, 3], got %s" % (self.center.shape[0],
+                                                                                    tuple(external_force.shape)))
         st = StepStats(num_bodies=self.center.shape[0])
         ev = []
 
@@ -499,6 +617,9 @@ class ContactStepper:
         else:
             st.rebuilt = self.generate_neighbor_links(force=force_rebuild)
         mark("broadphase")
+        if self.chain:
+            self.external_velocity(external_force)
+            mark("springs_brownian")
         self.compute_contacts()
         mark("narrowphase")
         if self.contact_model == "hertz":  # (stages: hertz_force, operator, body_sweep)
@@ -512,7 +633,13 @@ class ContactStepper:
         mark("integrate")
         st.num_contacts = self.contact_pairs.shape[0]
         st.num_iters, st.residual, st.converged = res.num_iters, res.residual, res.converged
-        if self.contact_model == "hertz":
+        if self.chain:  # the one read of the step: (max_overlap, max_spring_length, overstretched)
+            h = self._chain_stats.cpu()
+            st.max_overlap, st.max_spring_length = float(h[0]), float(h[1])
+            over = int(h.view(torch.int32)[4])
+            if over:
+                raise RuntimeError("%d FENE spring(s) stretched to L >= r_max: no force (reduce dt)" % over)
+        elif self.contact_model == "hertz":
             st.max_overlap = float(self.max_overlap.item())
         if timed:
             torch.cuda.synchronize()

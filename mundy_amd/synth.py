@@ -113,3 +113,44 @@ def dry_mobility(radius, viscosity=1e-3, bounding_radius=None):
     For rods the effective radius is the bounding radius when given."""
     r = np.asarray(radius if bounding_radius is None else bounding_radius, dtype=np.float64)
     return 1.0 / (6.0 * np.pi * viscosity * r), 1.0 / (8.0 * np.pi * viscosity * r ** 3)
+
+
+def chains(num_chains, beads_per_chain, r0=1.0, radius=0.5, seed=1234, cell=None):
+    """Random-walk bead-spring chains (the chromatin model of NgpHP1.cpp with the numbers of its ngp_hp1.yaml: r = 0.5,
+    r0 = 1, k = 3, kT = 0.1, mu = 1, dt = 1e-3, skin 1.0).  Chain c walks inside its own cubic cell of a lattice (edge
+    `cell`, default ~ 2.5 radii of gyration + 2 r), bead to bead at distance exactly r0 in uniformly drawn directions,
+    redrawing any step that would leave the cell's interior shrunk by r: beads of different chains never overlap (beads
+    of one chain may).  Returns dict(center [n, 3], radius [n], pairs int32 [n - num_chains, 2] (bead b -> b + 1 along
+    each chain), chain [n] int32, plus the app's parameters k, kt, viscosity, dt, skin, r0)."""
+    rng = np.random.default_rng(seed)
+    B, M = int(beads_per_chain), int(num_chains)
+    if cell is None:
+        cell = 2.0 * radius + max(2.0 * r0, 2.5 * r0 * np.sqrt(max(B, 1) / 6.0) * 2.0)
+    side = int(np.ceil(M ** (1.0 / 3.0))) if M else 0
+    idx = np.arange(M)
+    lo = np.stack([idx % side, (idx // side) % side, idx // (side * side)], axis=1).astype(np.float64) * cell \
+        if M else np.zeros((0, 3))
+    inner_lo, inner_hi = lo + radius, lo + cell - radius
+    pos = np.empty((M, B, 3))
+    if B:
+        pos[:, 0] = lo + 0.5 * cell
+    for b in range(1, B):
+        prev = pos[:, b - 1]
+        nxt = np.empty_like(prev)
+        todo = np.ones(M, dtype=bool)
+        while todo.any():
+            k = int(todo.sum())
+            u = rng.normal(size=(k, 3))
+            u /= np.linalg.norm(u, axis=1, keepdims=True)
+            cand = prev[todo] + r0 * u
+            ok = ((cand >= inner_lo[todo]) & (cand <= inner_hi[todo])).all(axis=1)
+            sel = np.flatnonzero(todo)[ok]
+            nxt[sel] = cand[ok]
+            todo[sel] = False
+        pos[:, b] = nxt
+    center = np.ascontiguousarray(pos.reshape(-1, 3))
+    first = np.arange(M)[:, None] * B + np.arange(B - 1)[None, :] if B > 1 else np.zeros((M, 0), dtype=np.int64)
+    pairs = np.ascontiguousarray(np.stack([first.reshape(-1), first.reshape(-1) + 1], axis=1).astype(np.int32))
+    return dict(center=center, radius=np.full(M * B, float(radius)), pairs=pairs,
+                chain=np.repeat(np.arange(M, dtype=np.int32), B), k=3.0, kt=0.1, viscosity=1.0, dt=1e-3, skin=1.0,
+                r0=float(r0))
