@@ -446,9 +446,11 @@ def contact_op_apply(pairs, normal, ra, rb, mt, mr, dt, x, n_bodies, rod=None, b
 
 def solve_cqpp_contact(pairs, normal, ra, rb, mt, mr, dt, q, x0, space=(LOWER_BOUND, 0.0, 0.0),
                        resid_kind=RESID_PROJECTED_DIFF, max_iters=1000, tol=1e-8, threads=False, fast=False,
-                       rod=None):
+                       rod=None, previous=False):
     """BBPGD (convex.hpp:614-666) on A = dt D^T M D (NgpLcp.cpp:442-548).  threads=True runs the OpenMP baseline.
-    rod=(s, t, seg) solves with the rod-axis form of the spherocylinder operator (ContactOpRod, serial)."""
+    rod=(s, t, seg) solves with the rod-axis form of the spherocylinder operator (ContactOpRod, serial).
+    previous=True also returns the solver's (x_tmp, g_tmp) -- the previous iterate and its gradient as PGDState holds
+    them on return -- as a fourth element."""
     pairs = np.ascontiguousarray(pairs, dtype=np.int32)
     if rod is not None:
         assert not threads
@@ -463,7 +465,7 @@ def solve_cqpp_contact(pairs, normal, ra, rb, mt, mr, dt, q, x0, space=(LOWER_BO
             C.c_double(dt), _p(q), C.c_int(space[0]), C.c_double(space[1]), C.c_double(space[2]), C.c_int(resid_kind),
             C.c_uint(max_iters), C.c_double(tol), _p(x), _p(g), _p(x_tmp), _p(g_tmp), C.byref(it), C.byref(res),
             C.byref(conv))
-        return x, g, _result(it, res, conv)
+        return (x, g, _result(it, res, conv)) + (((x_tmp, g_tmp),) if previous else ())
     normal, mt, q = _f(normal), _f(mt), _f(q)
     ra = None if ra is None else _f(ra)
     rb = None if rb is None else _f(rb)
@@ -478,7 +480,7 @@ def solve_cqpp_contact(pairs, normal, ra, rb, mt, mr, dt, q, x0, space=(LOWER_BO
        _p(q), C.c_int(space[0]), C.c_double(space[1]), C.c_double(space[2]), C.c_int(resid_kind),
        C.c_uint(max_iters), C.c_double(tol), _p(x), _p(g), _p(x_tmp), _p(g_tmp), C.byref(it), C.byref(res),
        C.byref(conv))
-    return x, g, _result(it, res, conv)
+    return (x, g, _result(it, res, conv)) + (((x_tmp, g_tmp),) if previous else ())
 
 
 def solve_friction_contact(pairs, normal, ra, rb, mt, mr, dt, sep, mu, p0=None, max_iters=10000, tol=1e-5,
