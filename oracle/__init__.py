@@ -427,31 +427,38 @@ def _rod_args(rod, n_bodies):
     return _f(s), _f(t), seg
 
 
-def contact_op_apply(pairs, normal, ra, rb, mt, mr, dt, x, n_bodies, rod=None, body_velocity=False):
+def contact_op_apply(pairs, normal, ra, rb, mt, mr, dt, x, n_bodies, rod=None, body_velocity=False, parallel=False):
     """y = dt D^T M D x.  rod=(s, t, seg): the spherocylinder operator in rod-axis form (ContactOpRod) instead of the
-    vector arms ra, rb; body_velocity=True also returns the (U, W) rows [N][6] (rod form only)."""
+    vector arms ra, rb; body_velocity=True also returns the (U, W) rows [N][6] (rod form only).
+    parallel=True: the body-parallel form (OpenMP over bodies, each summing its contacts in ascending order), the same
+    bits as the serial form at any thread count."""
     pairs = np.ascontiguousarray(pairs, dtype=np.int32)
     y = np.empty(len(pairs))
     if rod is not None:
         s, t, seg = _rod_args(rod, n_bodies)
         vel = np.zeros((n_bodies, 6)) if body_velocity else None
-        lib().o_contact_op_apply_rod(C.c_size_t(len(pairs)), C.c_size_t(n_bodies), _p(pairs), _p(_f(normal)), _p(s),
-                                     _p(t), _p(seg), _p(_f(mt)), _p(_f(mr)), C.c_double(dt), _p(_f(x)), _p(y), _p(vel))
+        fn = lib().o_contact_op_apply_rod_par if parallel else lib().o_contact_op_apply_rod
+        fn(C.c_size_t(len(pairs)), C.c_size_t(n_bodies), _p(pairs), _p(_f(normal)), _p(s), _p(t), _p(seg), _p(_f(mt)),
+           _p(_f(mr)), C.c_double(dt), _p(_f(x)), _p(y), _p(vel))
         return (y, vel) if body_velocity else y
-    lib().o_contact_op_apply(C.c_size_t(len(pairs)), C.c_size_t(n_bodies), _p(pairs), _p(_f(normal)),
-                             _p(None if ra is None else _f(ra)), _p(None if rb is None else _f(rb)), _p(_f(mt)),
-                             _p(None if mr is None else _f(mr)), C.c_double(dt), _p(_f(x)), _p(y))
+    fn = lib().o_contact_op_apply_par if parallel else lib().o_contact_op_apply
+    fn(C.c_size_t(len(pairs)), C.c_size_t(n_bodies), _p(pairs), _p(_f(normal)), _p(None if ra is None else _f(ra)),
+       _p(None if rb is None else _f(rb)), _p(_f(mt)), _p(None if mr is None else _f(mr)), C.c_double(dt), _p(_f(x)),
+       _p(y))
     return y
 
 
 def solve_cqpp_contact(pairs, normal, ra, rb, mt, mr, dt, q, x0, space=(LOWER_BOUND, 0.0, 0.0),
                        resid_kind=RESID_PROJECTED_DIFF, max_iters=1000, tol=1e-8, threads=False, fast=False,
-                       rod=None, previous=False):
+                       rod=None, previous=False, parallel=False):
     """BBPGD (convex.hpp:614-666) on A = dt D^T M D (NgpLcp.cpp:442-548).  threads=True runs the OpenMP baseline.
     rod=(s, t, seg) solves with the rod-axis form of the spherocylinder operator (ContactOpRod, serial).
     previous=True also returns the solver's (x_tmp, g_tmp) -- the previous iterate and its gradient as PGDState holds
-    them on return -- as a fourth element."""
+    them on return -- as a fourth element.
+    parallel=True: the body-parallel operator and element-wise passes (contact_op_apply(parallel=True)), the same bits
+    as the serial solve at any thread count -- unlike threads=True, whose atomic scatter makes them timing dependent."""
     pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+    assert not (threads and parallel)
     if rod is not None:
         assert not threads
         mt, q = _f(mt), _f(q)
@@ -460,7 +467,8 @@ def solve_cqpp_contact(pairs, normal, ra, rb, mt, mr, dt, q, x0, space=(LOWER_BO
         x = _f(x0).copy()
         g, x_tmp, g_tmp = np.zeros(c), np.zeros(c), np.zeros(c)
         it, res, conv = C.c_uint(), C.c_double(), C.c_int()
-        lib(fast).o_solve_cqpp_contact_rod(
+        fn = lib(fast).o_solve_cqpp_contact_rod_par if parallel else lib(fast).o_solve_cqpp_contact_rod
+        fn(
             C.c_size_t(c), C.c_size_t(len(mt)), _p(pairs), _p(_f(normal)), _p(s), _p(t), _p(seg), _p(mt), _p(_f(mr)),
             C.c_double(dt), _p(q), C.c_int(space[0]), C.c_double(space[1]), C.c_double(space[2]), C.c_int(resid_kind),
             C.c_uint(max_iters), C.c_double(tol), _p(x), _p(g), _p(x_tmp), _p(g_tmp), C.byref(it), C.byref(res),
@@ -475,7 +483,7 @@ def solve_cqpp_contact(pairs, normal, ra, rb, mt, mr, dt, q, x0, space=(LOWER_BO
     g, x_tmp, g_tmp = np.zeros(c), np.zeros(c), np.zeros(c)
     it, res, conv = C.c_uint(), C.c_double(), C.c_int()
     L = lib(fast)
-    fn = L.o_solve_cqpp_contact_mt if threads else L.o_solve_cqpp_contact
+    fn = L.o_solve_cqpp_contact_mt if threads else (L.o_solve_cqpp_contact_par if parallel else L.o_solve_cqpp_contact)
     fn(C.c_size_t(c), C.c_size_t(len(mt)), _p(pairs), _p(normal), _p(ra), _p(rb), _p(mt), _p(mr), C.c_double(dt),
        _p(q), C.c_int(space[0]), C.c_double(space[1]), C.c_double(space[2]), C.c_int(resid_kind),
        C.c_uint(max_iters), C.c_double(tol), _p(x), _p(g), _p(x_tmp), _p(g_tmp), C.byref(it), C.byref(res),

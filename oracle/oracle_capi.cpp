@@ -27,6 +27,191 @@ inline void st_aabb(double* out, size_t i, const AABB& b) {
   }
 }
 std::vector<int32_t> g_pairs;
+
+// ---- body-parallel forms of the contact operators (the checker at 10^6 bodies) -------------------------------------
+// The same sums as ContactOp / ContactOpRod, one body per iteration of a parallel loop instead of a scatter in
+// contact order.  Each body walks its contacts through a CSR built by a stable counting sort of the 2C pair slots,
+// so it adds its terms in ascending contact order -- the order the serial scatter adds them to that body -- and every
+// Acc sees the same operands in the same order: the same bits as the serial form in either sum mode, at any thread
+// count.  The constraint sweep and the solver's element-wise passes are independent per element; the residual is a
+// max (order free); the two BB reductions stay serial (their Acc order is the serial one).  Unlike
+// o_solve_cqpp_contact_mt (the CPU baseline: atomics, plain sums) nothing here depends on thread timing.
+struct BodyIncidence {
+  std::vector<int64_t> start;  // [N + 1]
+  std::vector<int64_t> slot;   // [2C]: 2 c + side, side 0 = pairs[2c] (the i body), 1 = pairs[2c + 1]
+  BodyIncidence(const int32_t* pairs, size_t C, size_t N) : start(N + 1, 0), slot(2 * C) {
+    for (size_t e = 0; e < 2 * C; ++e) ++start[pairs[e] + 1];
+    for (size_t b = 0; b < N; ++b) start[b + 1] += start[b];
+    std::vector<int64_t> fill(start.begin(), start.end() - 1);
+    for (size_t e = 0; e < 2 * C; ++e) slot[fill[pairs[e]]++] = static_cast<int64_t>(e);
+  }
+};
+
+// fn(lo, hi) over [0, n) in fixed chunks, chunks in parallel
+template <class Fn>
+void for_chunks(size_t n, Fn&& fn) {
+  constexpr size_t kChunk = size_t{1} << 15;
+  const long nc = static_cast<long>((n + kChunk - 1) / kChunk);
+#pragma omp parallel for schedule(static)
+  for (long k = 0; k < nc; ++k) {
+    const size_t lo = static_cast<size_t>(k) * kChunk;
+    fn(lo, std::min(n, lo + kChunk));
+  }
+}
+
+// y[c] = dt sdot_c from the body rows U (+ Z or W): the constraint sweep of the serial operators, per contact
+struct ContactOpRodPar {
+  const int32_t* pairs;
+  const double *normal, *arc_s, *arc_t, *seg, *mt, *mr;
+  double dt;
+  size_t C, N;
+  const BodyIncidence& inc;
+  mutable std::vector<double> U, Z, Wv;
+  void operator()(const double* x, double* y) const {
+    U.resize(3 * N);
+    Z.resize(3 * N);
+    Wv.resize(3 * N);
+#pragma omp parallel for schedule(dynamic, 512)
+    for (size_t b = 0; b < N; ++b) {
+      Acc Fa[3], Sa[3];
+      for (int64_t k = inc.start[b]; k < inc.start[b + 1]; ++k) {
+        const int64_t e = inc.slot[k];
+        const size_t c = static_cast<size_t>(e >> 1);
+        const double lam = x[c];
+        const V3 n{normal[3 * c], normal[3 * c + 1], normal[3 * c + 2]};
+        const V3 f{lam * n.x, lam * n.y, lam * n.z};
+        if ((e & 1) == 0) {
+          const double ci = contact_arclength(arc_s[c]) - 0.5;
+          for (int d = 0; d < 3; ++d) {
+            Fa[d].add(-f[d]);
+            Sa[d].add(ci * (-f[d]));
+          }
+        } else {
+          const double cj = contact_arclength(arc_t[c]) - 0.5;
+          for (int d = 0; d < 3; ++d) {
+            Fa[d].add(f[d]);
+            Sa[d].add(cj * f[d]);
+          }
+        }
+      }
+      const double* r = seg + 8 * b;
+      const V3 u{r[3] - r[0], r[4] - r[1], r[5] - r[2]};
+      const V3 Fb{Fa[0].value(), Fa[1].value(), Fa[2].value()};
+      const V3 Sb{Sa[0].value(), Sa[1].value(), Sa[2].value()};
+      const V3 tq = cross(u, Sb);
+      const V3 w{mr[b] * tq.x, mr[b] * tq.y, mr[b] * tq.z};
+      const V3 z = cross(w, u);
+      for (int d = 0; d < 3; ++d) {
+        U[3 * b + d] = mt[b] * Fb[d];
+        Wv[3 * b + d] = w[d];
+        Z[3 * b + d] = z[d];
+      }
+    }
+#pragma omp parallel for schedule(static)
+    for (size_t c = 0; c < C; ++c) {
+      const int32_t i = pairs[2 * c], j = pairs[2 * c + 1];
+      const V3 n{normal[3 * c], normal[3 * c + 1], normal[3 * c + 2]};
+      const double ci = contact_arclength(arc_s[c]) - 0.5, cj = contact_arclength(arc_t[c]) - 0.5;
+      const V3 zi{Z[3 * i], Z[3 * i + 1], Z[3 * i + 2]}, zj{Z[3 * j], Z[3 * j + 1], Z[3 * j + 2]};
+      const V3 vi = V3{U[3 * i], U[3 * i + 1], U[3 * i + 2]} + zi * ci;
+      const V3 vj = V3{U[3 * j], U[3 * j + 1], U[3 * j + 2]} + zj * cj;
+      const double sdot = -n.x * (vi.x - vj.x) - n.y * (vi.y - vj.y) - n.z * (vi.z - vj.z);
+      y[c] = dt * sdot;
+    }
+  }
+};
+
+struct ContactOpPar {  // ContactOp: spheres (ra, rb, mr null) or vector lever arms
+  const int32_t* pairs;
+  const double *normal, *ra, *rb, *mt, *mr;
+  double dt;
+  size_t C, N;
+  const BodyIncidence& inc;
+  mutable std::vector<double> U, W;
+  void operator()(const double* x, double* y) const {
+    const bool rot = (ra && rb && mr);
+    U.resize(3 * N);
+    if (rot) W.resize(3 * N);
+#pragma omp parallel for schedule(dynamic, 512)
+    for (size_t b = 0; b < N; ++b) {
+      Acc Fa[3], Ta[3];
+      for (int64_t k = inc.start[b]; k < inc.start[b + 1]; ++k) {
+        const int64_t e = inc.slot[k];
+        const size_t c = static_cast<size_t>(e >> 1);
+        const double lam = x[c];
+        const V3 n{normal[3 * c], normal[3 * c + 1], normal[3 * c + 2]};
+        const V3 f{lam * n.x, lam * n.y, lam * n.z};
+        const bool first = (e & 1) == 0;
+        for (int d = 0; d < 3; ++d) Fa[d].add(first ? -f[d] : f[d]);
+        if (rot) {
+          const double* arm = first ? ra : rb;
+          const V3 t = cross(V3{arm[3 * c], arm[3 * c + 1], arm[3 * c + 2]}, f);
+          for (int d = 0; d < 3; ++d) Ta[d].add(first ? -t[d] : t[d]);
+        }
+      }
+      for (int d = 0; d < 3; ++d) {
+        U[3 * b + d] = mt[b] * Fa[d].value();
+        if (rot) W[3 * b + d] = mr[b] * Ta[d].value();
+      }
+    }
+#pragma omp parallel for schedule(static)
+    for (size_t c = 0; c < C; ++c) {
+      const int32_t i = pairs[2 * c], j = pairs[2 * c + 1];
+      const V3 n{normal[3 * c], normal[3 * c + 1], normal[3 * c + 2]};
+      V3 vi{U[3 * i], U[3 * i + 1], U[3 * i + 2]}, vj{U[3 * j], U[3 * j + 1], U[3 * j + 2]};
+      if (rot) {
+        const V3 a{ra[3 * c], ra[3 * c + 1], ra[3 * c + 2]}, b{rb[3 * c], rb[3 * c + 1], rb[3 * c + 2]};
+        const V3 wi{W[3 * i], W[3 * i + 1], W[3 * i + 2]}, wj{W[3 * j], W[3 * j + 1], W[3 * j + 2]};
+        vi = vi + cross(wi, a);
+        vj = vj + cross(wj, b);
+      }
+      const double sdot = -n.x * (vi.x - vj.x) - n.y * (vi.y - vj.y) - n.z * (vi.z - vj.z);
+      y[c] = dt * sdot;
+    }
+  }
+};
+
+// solve_cqpp (mundy_oracle.hpp) step for step, the element-wise passes and the residual over chunks in parallel
+template <class Op>
+SolveResult solve_cqpp_par(const Op& A, const double* q, const Space& sp, int resid_kind, unsigned max_iters,
+                           double tol, size_t n, double* x, double* g, double* x_tmp, double* g_tmp) {
+  auto par_residual = [&](const double* xx, const double* gg) {
+    // residual() of a chunk is max(v) (/ 1e-6): monotone in max(v), so the max over chunks is the serial value
+    std::vector<double> part((n + (size_t{1} << 15) - 1) >> 15, std::numeric_limits<double>::lowest());
+    for_chunks(n, [&](size_t lo, size_t hi) { part[lo >> 15] = residual(resid_kind, xx + lo, gg + lo, hi - lo, sp); });
+    if (part.empty()) return residual(resid_kind, xx, gg, 0, sp);
+    double mx = part[0];
+    for (double v : part)
+      if (v > mx) mx = v;
+    return mx;
+  };
+  auto par_copy = [&](const double* from, double* to) {
+    for_chunks(n, [&](size_t lo, size_t hi) { std::copy(from + lo, from + hi, to + lo); });
+  };
+  par_copy(x, x_tmp);
+  A(x_tmp, g_tmp);
+  for_chunks(n, [&](size_t lo, size_t hi) { axpby(1.0, q + lo, 1.0, g_tmp + lo, hi - lo); });
+  double res = par_residual(x_tmp, g_tmp);
+  double step = 1.0 / res;
+  unsigned iter = 0;
+  bool converged = (res <= tol);
+  if (converged) par_copy(g_tmp, g);
+  while (!(converged || iter >= max_iters)) {
+    for_chunks(n, [&](size_t lo, size_t hi) { wrapped_axpbyz(1.0, x_tmp + lo, -step, g_tmp + lo, x + lo, hi - lo, sp); });
+    A(x, g);
+    for_chunks(n, [&](size_t lo, size_t hi) { axpby(1.0, q + lo, 1.0, g + lo, hi - lo); });
+    res = par_residual(x, g);
+    if (res <= tol) {
+      converged = true;
+      break;
+    }
+    step = bb_step(x_tmp, g_tmp, x, g, n);  // serial: the Acc order of the serial solve
+    par_copy(x, x_tmp);
+    par_copy(g, g_tmp);
+    ++iter;
+  }
+  return {iter, res, converged ? 1 : 0};
+}
 }  // namespace
 
 extern "C" {
@@ -436,6 +621,51 @@ void o_scrap_resolve_collisions_rod(size_t C, size_t N, const int32_t* pairs, co
   *res = r.max_abs_projected_sep;
   *ite_count = r.ite_count;
   *max_speed = r.max_speed;
+}
+
+// body-parallel forms (BodyIncidence above): the bits of o_contact_op_apply[_rod] / o_solve_cqpp_contact[_rod]
+void o_contact_op_apply_rod_par(size_t C, size_t N, const int32_t* pairs, const double* normal, const double* arc_s,
+                                const double* arc_t, const double* seg, const double* mt, const double* mr, double dt,
+                                const double* x, double* y, double* body_velocity /* [N][6] = (U, W) or null */) {
+  const BodyIncidence inc(pairs, C, N);
+  ContactOpRodPar op{pairs, normal, arc_s, arc_t, seg, mt, mr, dt, C, N, inc, {}, {}, {}};
+  op(x, y);
+  if (body_velocity)
+    for (size_t b = 0; b < N; ++b)
+      for (int k = 0; k < 3; ++k) {
+        body_velocity[6 * b + k] = op.U[3 * b + k];
+        body_velocity[6 * b + 3 + k] = op.Wv[3 * b + k];
+      }
+}
+void o_solve_cqpp_contact_rod_par(size_t C, size_t N, const int32_t* pairs, const double* normal, const double* arc_s,
+                                  const double* arc_t, const double* seg, const double* mt, const double* mr,
+                                  double dt, const double* q, int kind, double lo, double hi, int resid_kind,
+                                  unsigned max_iters, double tol, double* x, double* g, double* x_tmp, double* g_tmp,
+                                  unsigned* num_iters, double* res, int* converged) {
+  const BodyIncidence inc(pairs, C, N);
+  ContactOpRodPar op{pairs, normal, arc_s, arc_t, seg, mt, mr, dt, C, N, inc, {}, {}, {}};
+  const SolveResult r = solve_cqpp_par(op, q, Space{kind, lo, hi}, resid_kind, max_iters, tol, C, x, g, x_tmp, g_tmp);
+  *num_iters = r.num_iters;
+  *res = r.residual;
+  *converged = r.converged;
+}
+void o_contact_op_apply_par(size_t C, size_t N, const int32_t* pairs, const double* normal, const double* ra,
+                            const double* rb, const double* mt, const double* mr, double dt, const double* x, double* y) {
+  const BodyIncidence inc(pairs, C, N);
+  ContactOpPar op{pairs, normal, ra, rb, mt, mr, dt, C, N, inc, {}, {}};
+  op(x, y);
+}
+void o_solve_cqpp_contact_par(size_t C, size_t N, const int32_t* pairs, const double* normal, const double* ra,
+                              const double* rb, const double* mt, const double* mr, double dt, const double* q,
+                              int kind, double lo, double hi, int resid_kind, unsigned max_iters, double tol,
+                              double* x, double* g, double* x_tmp, double* g_tmp, unsigned* num_iters, double* res,
+                              int* converged) {
+  const BodyIncidence inc(pairs, C, N);
+  ContactOpPar op{pairs, normal, ra, rb, mt, mr, dt, C, N, inc, {}, {}};
+  const SolveResult r = solve_cqpp_par(op, q, Space{kind, lo, hi}, resid_kind, max_iters, tol, C, x, g, x_tmp, g_tmp);
+  *num_iters = r.num_iters;
+  *res = r.residual;
+  *converged = r.converged;
 }
 
 // build extension (parity unpinned): frictional cone complementarity solve, serial
