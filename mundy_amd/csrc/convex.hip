@@ -16,6 +16,7 @@
 // post-conditions (which array holds what).
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "mhip_internal.hpp"
@@ -547,18 +548,9 @@ __device__ inline double iterate_x(size_t c, const double* __restrict__ xt, cons
 #ifndef MHIP_KBODY_FLAT
 #define MHIP_KBODY_FLAT 2
 #endif
-// 1: the sweep's early-fetched last words wait in LDS instead of registers (rods: 110 -> 96 VGPRs, 24 + 8 KB of LDS: FIVE
-// workgroups per CU with the chain still four levels long).  Measured, same box, three runs each
-// (profiles/r04_ab_experiments.txt): 0.0807 ms against 0.0772 -- a fifth resident workgroup makes the sweep SLOWER.  Off.
-#ifndef MHIP_KCON_DYN_LDS    // A/B only: the same for the packed constraint sweep
-#define MHIP_KCON_DYN_LDS 0
-#endif
-#ifndef MHIP_KBODY_DYN_LDS   // A/B only: unused dynamic LDS per workgroup of the flat sweep (caps the workgroups per CU)
-#define MHIP_KBODY_DYN_LDS 0
-#endif
-#ifndef MHIP_KBODY_STASH
-#define MHIP_KBODY_STASH 0
-#endif
+// (The sweep's early-fetched last words stay in registers.  Parked in LDS -- rods: 110 -> 96 VGPRs, 24 + 8 KB of LDS, FIVE
+// workgroups per CU with the chain still four levels long -- the sweep measured 0.0807 ms against 0.0772, same box, three
+// runs each (profiles/r04_ab_experiments.txt): a fifth resident workgroup makes it SLOWER.)
 #ifndef MHIP_KBODY_EARLY_FROM   // chunk size (x 256 entries) from which the sweep's last words are fetched at its top
 #define MHIP_KBODY_EARLY_FROM 3
 #endif
@@ -572,9 +564,6 @@ __device__ inline double iterate_x(size_t c, const double* __restrict__ xt, cons
 // entry in LDS, and the G lanes of a body then add up their body's slice of that image -- the double-double sums see
 // the same terms (rounded once: any order gives the same bits).  What the snapshot does not cover (entries that became
 // active since, lists beyond 64 entries, steps outside [0, finite]) takes the per-body chains as before.
-#ifdef MHIP_EXP_COUNT_MM
-__device__ unsigned long long g_dbg[4];
-#endif
 // TRACK (tiered solves): 0 = no drift bookkeeping; 1 = the drift is the difference of the body's new row and its row of
 // the previous iterate (an extra 48-byte read per body: free while the row tables live in the Infinity Cache, i.e. up
 // to ~1.7 * 10^6 bodies); 2 = the change of the force is accumulated beside the sums from +/-(lam - x_old) n of the
@@ -688,19 +677,6 @@ __global__ void __launch_bounds__(kBlock, MHIP_KBODY_WAVES)
       }
     }
   }
-#if MHIP_KBODY_STASH
-  // (A/B only, see MHIP_KBODY_STASH) ... parked in LDS until the end of the sweep: 64 B per body, 8 KB per workgroup
-  // (not with vector arms: their 36 KB image plus the stash would leave three workgroups per CU where there are four)
-  constexpr bool kStash = kEarlyTail && track_rows && KIN != KIN_RIGID;
-  __shared__ double2 stash[kStash ? 4 * (kBlock / G) : 1];
-  if (kStash && sub == 0) {
-    double2* mine = stash + 4 * (threadIdx.x / G);
-    mine[0] = o0;
-    mine[1] = o1;
-    mine[2] = o2;
-    mine[3] = make_double2(drift_old, fire_thr);
-  }
-#endif
   // The sweep is a chain of dependent accesses (row pointer -> incidence entry -> iterate of that contact -> record),
   // so what it waits on is latency, not bytes: each lane keeps U independent chains in flight, every level's U loads
   // issued back to back before the first use.  kk[u] = incidence slot or -1.
@@ -820,20 +796,11 @@ __global__ void __launch_bounds__(kBlock, MHIP_KBODY_WAVES)
 #pragma unroll
           for (int p = 0; p < FLATP; ++p)
             pit[p] = iterate_load<MODE, PACKED>(fe[p] >= 0 ? static_cast<size_t>(fe[p] >> 1) : 0, xt, gt);
-#ifdef MHIP_EXP_EXTRA_GATHER   // TIMING EXPERIMENT ONLY: a second gather of the same pattern (the other parity's pairs)
-          double2 pit2[FLATP];
-#pragma unroll
-          for (int p = 0; p < FLATP; ++p)
-            pit2[p] = iterate_load<MODE, PACKED>(fe[p] >= 0 ? static_cast<size_t>(fe[p] >> 1) : 0, (xt == X0) ? X1 : X0, gt);
-#endif
 #pragma unroll
           for (int p = 0; p < FLATP; ++p) {
             // (the iterate is USED unconditionally and the dead slot's value dropped by a select: with the use inside
             // `fe >= 0` the compiler sinks the gather into that branch and waits for it there with vmcnt(0))
-            double lam_live = iterate_value<MODE>(pit[p], step, step_is_zero, sp);
-#ifdef MHIP_EXP_EXTRA_GATHER
-            if (pit2[p].x == 1.2345e300) lam_live = 0.0;
-#endif
+            const double lam_live = iterate_value<MODE>(pit[p], step, step_is_zero, sp);
             const double lam = (fe[p] >= 0) ? lam_live : 0.0;
             // F_src += -lam n, F_tgt += +lam n  (NgpLcp.cpp:467-472): the products the per-body chains form, formed
             // here by the lane that holds the record (the same multiplications: the same bits)
@@ -888,18 +855,12 @@ __global__ void __launch_bounds__(kBlock, MHIP_KBODY_WAVES)
                 continue;
               }
               const V3 f{a0.x, a0.y, a1.x};
-#ifdef MHIP_EXP_PLAIN_SUMS   // TIMING EXPERIMENT ONLY (what the double-double sums of phase B cost): plain sums
-              Fdd.x.hi += f.x; Fdd.y.hi += f.y; Fdd.z.hi += f.z;
-              if (KIN == KIN_ROD) { Tdd.x.hi += a1.y * f.x; Tdd.y.hi += a1.y * f.y; Tdd.z.hi += a1.y * f.z; }
-              if (KIN == KIN_RIGID) { const double2 a2 = pl2[slot]; Tdd.x.hi += a1.y; Tdd.y.hi += a2.x; Tdd.z.hi += a2.y; }
-#else
               dd_add(Fdd, f);
               if (KIN == KIN_RIGID) {
                 const double2 a2 = pl2[slot];
                 dd_add(Tdd, V3{a1.y, a2.x, a2.y});
               }
               if (KIN == KIN_ROD) dd_add(Tdd, a1.y * f);  // S = sum coef f
-#endif
             }
           }
           __syncthreads();
@@ -918,19 +879,6 @@ __global__ void __launch_bounds__(kBlock, MHIP_KBODY_WAVES)
     if (head < 64) mm &= (1ull << head) - 1ull;
     if (op.aptr != nullptr) mm &= ~(kEarlySnap ? snap_early : op.snap_mask[b]);
     if (FLAT && !has_body) mm = 0ull;
-#ifdef MHIP_EXP_COUNT_MM   // DIAGNOSTIC BUILD ONLY: how many waves / lanes / entries take the per-body chains behind a snapshot
-    if (op.aptr != nullptr && FLAT) {
-      const bool any_lane = __any(mm != 0ull);
-      if ((threadIdx.x & 63) == 0) {
-        atomicAdd(&g_dbg[2], 1ull);
-        if (any_lane) atomicAdd(&g_dbg[0], 1ull);
-      }
-      if (mm != 0ull) {
-        atomicAdd(&g_dbg[1], 1ull);
-        atomicAdd(&g_dbg[3], (unsigned long long)__popcll(mm));
-      }
-    }
-#endif
     int32_t kk[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) kk[u] = -1;
@@ -978,16 +926,6 @@ __global__ void __launch_bounds__(kBlock, MHIP_KBODY_WAVES)
     }
   }
   if (sub != 0) return;
-#if MHIP_KBODY_STASH
-  if (kStash) {
-    const double2* mine = stash + 4 * (threadIdx.x / G);
-    o0 = mine[0];
-    o1 = mine[1];
-    o2 = mine[2];
-    drift_old = mine[3].x;
-    fire_thr = mine[3].y;
-  }
-#endif
   // (where it was not fetched at the top: asked for before the last arithmetic of the sweep)
   if (track_rows && !kEarlyTail) {
     const double* vel_old = op.vel_alt ? ((vel_new == op.vel) ? op.vel_alt : op.vel) : op.vel;
@@ -2433,6 +2371,20 @@ struct mhip_contact_op {
 
 namespace {
 
+// A run-time value becomes a template argument HERE: f(Const<V>{}) for the first V of the list equal to v, for the last
+// one when none is.  Inside f, `if constexpr` on decltype(arg)::value keeps the kernels of the branches not taken
+// uninstantiated.
+template <int V> using Const = std::integral_constant<int, V>;
+template <int V, int... Rest, class F>
+void pick(int v, F&& f) {
+  if constexpr (sizeof...(Rest) == 0) f(Const<V>{});
+  else if (v == V) f(Const<V>{});
+  else pick<Rest...>(v, f);
+}
+// the operator's kinematics as the KIN of the kernels
+template <class F>
+void with_kin(const mhip_contact_op* op, F&& f) { pick<KIN_ROD, KIN_RIGID, KIN_TRANS>(op->kin, f); }
+
 // Source of the body sweep's drift in tiered solves: 1 = difference of the two rows, 2 = accumulated in registers (see
 // k_body).  Auto (0): the row form while both row tables (96 B per body) stay well inside the 256 MiB Infinity Cache,
 // where its extra read is free and its smaller LDS image and register count pay; the register form beyond, and never
@@ -2467,47 +2419,32 @@ int op_launch_body(mhip_contact_op* op, int mode, const double* X0, const double
   // tracked sweeps: where the drift comes from (see k_body's TRACK) -- the register form exists for the default lane
   // layout of rods and spheres only (the vector-arm sweep needs the smaller image of the row form for its occupancy)
   const bool regs = op_drift_source(op) == 2;
-#define BODY_TRACKED(M, R, GG, UU, FP, LDS)                                                                    \
-  do {                                                                                                         \
-    if constexpr (GG == 2 && R != KIN_RIGID) {                                                                 \
-      if (regs) { k_body<M, R, GG, UU, true, 2, FP><<<grid, kBlock, LDS, s>>>(op->view, st, X0, X1, G0, G1, sp); break; } \
-    }                                                                                                          \
-    k_body<M, R, GG, UU, true, 1, FP><<<grid, kBlock, LDS, s>>>(op->view, st, X0, X1, G0, G1, sp);            \
-  } while (0)
-#define BODY4(M, R, GG, UU)                                                                        \
-  do {                                                                                             \
-    if (flatp == 3 && packed && M == X_SOLVE && op->view.aptr != nullptr && op->view.drift != nullptr) \
-      BODY_TRACKED(M, R, GG, UU, 3, MHIP_KBODY_DYN_LDS);                                           \
-    else if (flatp == 3 && packed && M == X_SOLVE && op->view.aptr != nullptr)                     \
-      k_body<M, R, GG, UU, true, 0, 3><<<grid, kBlock, MHIP_KBODY_DYN_LDS, s>>>(op->view, st, X0, X1, G0, G1, sp); \
-    else if (MHIP_KBODY_FLAT > 0 && packed && M == X_SOLVE && op->view.aptr != nullptr && op->view.drift != nullptr) \
-      BODY_TRACKED(M, R, GG, UU, MHIP_KBODY_FLAT, 0);                                              \
-    else if (MHIP_KBODY_FLAT > 0 && packed && M == X_SOLVE && op->view.aptr != nullptr)             \
-      k_body<M, R, GG, UU, true, 0, MHIP_KBODY_FLAT><<<grid, kBlock, 0, s>>>(op->view, st, X0, X1, G0, G1, sp); \
-    else if (packed && M == X_SOLVE && op->view.drift != nullptr)                                  \
-      BODY_TRACKED(M, R, GG, UU, 0, 0);                                                            \
-    else if (packed && M == X_SOLVE)                                                               \
-      k_body<M, R, GG, UU, true><<<grid, kBlock, 0, s>>>(op->view, st, X0, X1, G0, G1, sp);        \
-    else                                                                                           \
-      k_body<M, R, GG, UU, false><<<grid, kBlock, 0, s>>>(op->view, st, X0, X1, G0, G1, sp);       \
-  } while (0)
-#define BODY(M, R)                                    \
-  do {                                                \
-    if (G == 2) BODY4(M, R, 2, 2);                    \
-    else if (G == 1) BODY4(M, R, 1, 2);               \
-    else if (G == 8) BODY4(M, R, 8, 4);               \
-    else if (G == 16) BODY4(M, R, 16, 2);             \
-    else BODY4(M, R, 4, 4);                           \
-  } while (0)
-#define BODYK(K) \
-  do { if (mode == X_APPLY) BODY(X_APPLY, K); else if (mode == X_INIT) BODY(X_INIT, K); else BODY(X_SOLVE, K); } while (0)
-  if (op->kin == KIN_ROD) BODYK(KIN_ROD);
-  else if (op->kin == KIN_RIGID) BODYK(KIN_RIGID);
-  else BODYK(KIN_TRANS);
-#undef BODYK
-#undef BODY4
-#undef BODY_TRACKED
-#undef BODY
+  // Which k_body runs.  APPLY and INIT sweeps and unpacked solves: <PACKED = false, TRACK = 0, FLATP = 0>.  Packed
+  // X_SOLVE sweeps: <true, TRACK, FLATP> from the state of the view --
+  //   view.aptr   set (a snapshot of the active lists exists): FLATP = flatp      | null: FLATP = 0
+  //   view.drift  set (tiered solve, drift bookkeeping): TRACK = 2 where `regs` and the register form exists (two
+  //               lanes, not vector arms), else TRACK = 1                          | null: TRACK = 0
+  pick<X_APPLY, X_INIT, X_SOLVE>(mode, [&](auto m) { with_kin(op, [&](auto kin) { pick<1, 2, 8, 16, 4>(G, [&](auto g) {
+    constexpr int M = decltype(m)::value, K = decltype(kin)::value, GG = decltype(g)::value;
+    constexpr int UU = (GG == 4 || GG == 8) ? 4 : 2;  // independent chains per lane
+    auto launch = [&](auto pk, auto track, auto fp) {
+      k_body<M, K, GG, UU, decltype(pk)::value, decltype(track)::value, decltype(fp)::value>
+          <<<grid, kBlock, 0, s>>>(op->view, st, X0, X1, G0, G1, sp);
+    };
+    if constexpr (M == X_SOLVE) {
+      if (packed) {
+        pick<0, MHIP_KBODY_FLAT, 3>(op->view.aptr != nullptr ? flatp : 0, [&](auto fp) {
+          if (op->view.drift == nullptr) return launch(std::true_type{}, Const<0>{}, fp);
+          if constexpr (GG == 2 && K != KIN_RIGID) {
+            if (regs) return launch(std::true_type{}, Const<2>{}, fp);
+          }
+          launch(std::true_type{}, Const<1>{}, fp);
+        });
+        return;
+      }
+    }
+    launch(std::false_type{}, Const<0>{}, Const<0>{});
+  }); }); });
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
 }
@@ -2518,20 +2455,18 @@ int op_launch_constraint(mhip_contact_op* op, int mode, double* X0, double* X1, 
   if (op->view.C == 0) return MHIP_SUCCESS;
   const SolverState* st = op->state.as<SolverState>();
   double* parts = op->partials.as<double>();
-#define CON(M, R)                                                                                              \
-  do {                                                                                                         \
-    if (packed && M != X_APPLY)                                                                                \
-      k_constraint<M, R, true><<<grid, kBlock, MHIP_KCON_DYN_LDS, s>>>(op->view, st, X0, X1, G0, G1, q, sp, resid_kind, parts); \
-    else                                                                                                       \
-      k_constraint<M, R, false><<<grid, kBlock, 0, s>>>(op->view, st, X0, X1, G0, G1, q, sp, resid_kind, parts); \
-  } while (0)
-#define CONK(K) \
-  do { if (mode == X_APPLY) CON(X_APPLY, K); else if (mode == X_INIT) CON(X_INIT, K); else CON(X_SOLVE, K); } while (0)
-  if (op->kin == KIN_ROD) CONK(KIN_ROD);
-  else if (op->kin == KIN_RIGID) CONK(KIN_RIGID);
-  else CONK(KIN_TRANS);
-#undef CONK
-#undef CON
+  // packed INIT / SOLVE sweeps read and write the packed (x, g) pairs; APPLY has no packed form
+  pick<X_APPLY, X_INIT, X_SOLVE>(mode, [&](auto m) { with_kin(op, [&](auto kin) {
+    constexpr int M = decltype(m)::value, K = decltype(kin)::value;
+    auto launch = [&](auto pk) {
+      k_constraint<M, K, decltype(pk)::value>
+          <<<grid, kBlock, 0, s>>>(op->view, st, X0, X1, G0, G1, q, sp, resid_kind, parts);
+    };
+    if constexpr (M != X_APPLY) {
+      if (packed) return launch(std::true_type{});
+    }
+    launch(std::false_type{});
+  }); });
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
 }
@@ -2540,9 +2475,6 @@ int op_launch_constraint(mhip_contact_op* op, int mode, double* X0, double* X1, 
 // `stride` is the distance between the three planes on entry and on return
 #ifndef MHIP_FOLD_ABOVE
 #define MHIP_FOLD_ABOVE 4096
-#endif
-#ifndef MHIP_FOLD_FINALIZE
-#define MHIP_FOLD_FINALIZE 1
 #endif
 #ifndef MHIP_FOLD_BLOCK
 #define MHIP_FOLD_BLOCK 128   // threads of a folding workgroup (64 / 128 / 256: 136.9 / 136.4 / 137.0 ms per step)
@@ -2585,12 +2517,11 @@ int op_snapshot_active(mhip_contact_op* op, hipStream_t s) {
   k_active_count<<<grid_for(cnt), kBlock, 0, s>>>(v.body_first, cnt, v.inc_ptr, v.body_mask, op->acnt.as<int32_t>());
   MHIP_LAUNCH_CHECK();
   if (int e = exclusive_scan_i32(op->acnt.as<int32_t>(), local, cnt, op->scanws.ptr, s)) return e;
-#define FILL(H)                                                                                                   \
-  k_active_fill_flat<H><<<grid_exact(cnt), kBlock, 0, s>>>(v.body_first, cnt, v.inc_ptr, v.inc, v.half, v.body_mask, local, \
-                                                           op->aptr.as<int32_t>(), op->aent.as<int32_t>(),          \
-                                                           op->arec.as<double>(), op->snap_mask.as<unsigned long long>())
-  if (hw == 6) FILL(6); else if (hw == 4) FILL(4); else FILL(3);
-#undef FILL
+  pick<6, 4, 3>(hw, [&](auto h) {
+    k_active_fill_flat<decltype(h)::value><<<grid_exact(cnt), kBlock, 0, s>>>(
+        v.body_first, cnt, v.inc_ptr, v.inc, v.half, v.body_mask, local, op->aptr.as<int32_t>(), op->aent.as<int32_t>(),
+        op->arec.as<double>(), op->snap_mask.as<unsigned long long>());
+  });
   MHIP_LAUNCH_CHECK();
   // the length of the compact lists travels to the host with the next poll (it picks the flat sweep's chunk; see
   // op_launch_body): pinned spare words behind host_state, no synchronisation here
@@ -2605,10 +2536,6 @@ int op_snapshot_active(mhip_contact_op* op, hipStream_t s) {
 }
 // from this many completed iterations on the masks have settled enough for a snapshot to pay
 constexpr unsigned kSnapshotAfter = 8;
-#ifndef MHIP_SNAPSHOT_AT_INIT
-#define MHIP_SNAPSHOT_AT_INIT 1
-#endif
-
 
 // ---- Cold tier ---------------------------------------------------------------------------------------------------------
 // Two thirds of the contacts of a packing are inactive (x = 0, g > 0) and most of them stay so for the whole solve, yet
@@ -2980,15 +2907,12 @@ int tier_update(mhip_contact_op* op, TierPairs& cur, unsigned iters_done, unsign
   else
     t.saved = v;
   if (int e = mhip_fill(N, m.fire_at, __builtin_huge_val(), reinterpret_cast<mhip_stream_t>(s))) return e;
-#define PERMUTE(K)                                                                                                    \
-  k_tier_permute<K><<<grid_for(C), kBlock, 0, s>>>(C, I, H, cur_is_p1 ? 1 : 0, v.pairs, v.normal, v.arc_s, v.arc_t, v.ra, \
-                                                   v.rb, cur.q,                                                      \
-                                                   orig_src, v.pos, dst, reinterpret_cast<const double2*>(cur.P0),   \
-                                                   reinterpret_cast<const double2*>(cur.P1), P0d, P1d, m.flags,      \
-                                                   m.rank, m.new_of, wake_old, H_old, m.wake[dst_set],               \
-                                                   t.drift.as<double>(), m.fire_at)
-  if (op->kin == KIN_ROD) PERMUTE(KIN_ROD); else if (op->kin == KIN_RIGID) PERMUTE(KIN_RIGID); else PERMUTE(KIN_TRANS);
-#undef PERMUTE
+  with_kin(op, [&](auto kin) {
+    k_tier_permute<decltype(kin)::value><<<grid_for(C), kBlock, 0, s>>>(
+        C, I, H, cur_is_p1 ? 1 : 0, v.pairs, v.normal, v.arc_s, v.arc_t, v.ra, v.rb, cur.q, orig_src, v.pos, dst,
+        reinterpret_cast<const double2*>(cur.P0), reinterpret_cast<const double2*>(cur.P1), P0d, P1d, m.flags, m.rank,
+        m.new_of, wake_old, H_old, m.wake[dst_set], t.drift.as<double>(), m.fire_at);
+  });
   MHIP_LAUNCH_CHECK();
   k_tier_remap_inc<<<grid_for(2 * C), kBlock, 0, s>>>(2 * C, op->inc.as<int32_t>(), m.new_of);
   MHIP_LAUNCH_CHECK();
@@ -3081,11 +3005,10 @@ int tier_release(mhip_contact_op* op, TierPairs& cur, bool final, double* P0, do
       vprev = rows;
     }
     const unsigned grid = grid_for(t.I - t.H);
-#define REFRESH(K)                                                                                              \
-  k_tier_refresh_sleepers<K><<<grid, kBlock, 0, s>>>(v, t.H, t.I, static_cast<int>(cur1), vcur, vprev, cur.q,   \
-                                                     m.wake[t.set], T0, T1)
-    if (op->kin == KIN_ROD) REFRESH(KIN_ROD); else if (op->kin == KIN_RIGID) REFRESH(KIN_RIGID); else REFRESH(KIN_TRANS);
-#undef REFRESH
+    with_kin(op, [&](auto kin) {
+      k_tier_refresh_sleepers<decltype(kin)::value>
+          <<<grid, kBlock, 0, s>>>(v, t.H, t.I, static_cast<int>(cur1), vcur, vprev, cur.q, m.wake[t.set], T0, T1);
+    });
     MHIP_LAUNCH_CHECK();
   }
   if (final)
@@ -3132,14 +3055,13 @@ int op_launch_constraint_tiered(mhip_contact_op* op, const TierPairs& cur, Space
   OpView hot = op->view;
   hot.c_first = 0; hot.c_end = t.H; hot.part_offset = 0; hot.part_stride = kStageStride;
   const TierCheck tc{t.H, t.I, m.wake[t.set], m.list, m.counters, m.fired, m.fire_at, gcheck};
-#define TIERED(K)                                                                                                 \
-  k_constraint<X_SOLVE, K, true><<<ghot + gcheck, kBlock, MHIP_KCON_DYN_LDS, s>>>(hot, st, cur.P0, cur.P1, nullptr, nullptr,     \
-                                                                 cur.q, sp, resid_kind, parts, tc)
   if (ghot + gcheck) {
-    if (op->kin == KIN_ROD) TIERED(KIN_ROD); else if (op->kin == KIN_RIGID) TIERED(KIN_RIGID); else TIERED(KIN_TRANS);
+    with_kin(op, [&](auto kin) {
+      k_constraint<X_SOLVE, decltype(kin)::value, true><<<ghot + gcheck, kBlock, 0, s>>>(
+          hot, st, cur.P0, cur.P1, nullptr, nullptr, cur.q, sp, resid_kind, parts, tc);
+    });
     MHIP_LAUNCH_CHECK();
   }
-#undef TIERED
   *nparts = ghot + gcheck;
   return MHIP_SUCCESS;
 }
@@ -3149,6 +3071,68 @@ int check_config(const mhip_pgd_config* cfg) {
   MHIP_REQUIRE(cfg->residual_kind == MHIP_RESIDUAL_PROJECTED_DIFF ||
                    cfg->residual_kind == MHIP_RESIDUAL_PROJECTED_GRADIENT,
                MHIP_ERR_INVALID_ARGUMENT, "unknown residual kind %d", cfg->residual_kind);
+  return MHIP_SUCCESS;
+}
+
+// the partial triples of an untiered constraint sweep of cgrid workgroups -> the solver state (above MHIP_FOLD_ABOVE of
+// them: folded first)
+template <int M>
+void finalize_sweep(mhip_contact_op* op, unsigned cgrid, const mhip_pgd_config* cfg, hipStream_t s) {
+  SolverState* st = op->state.as<SolverState>();
+  unsigned np = cgrid;
+  size_t ps = cgrid;
+  double* pp = op->partials.as<double>();
+  fold_partials(np, ps, pp, st, M == X_INIT ? 0 : 1, s);
+  k_finalize<M><<<1, final_block(np), 0, s>>>((int)np, pp, 1, ps, st, cfg->residual_kind, cfg->tol, cfg->max_iters);
+}
+
+// The convergence poll of the plain drivers: the solver state is read back; unless it says done, or max_iters iterations
+// are enqueued, the next stretch -- 8 iterations, doubling to 64 -- is enqueued through iteration(k), k = the number of
+// iterations enqueued before this one, and its launches are checked.
+template <class Iteration>
+int poll_loop(mhip_contact_op* op, unsigned max_iters, hipStream_t s, const Iteration& iteration) {
+  unsigned enqueued = 0, chunk = 8;
+  for (;;) {
+    MHIP_HIP(hipMemcpyAsync(op->host_state, op->state.ptr, sizeof(SolverState), hipMemcpyDeviceToHost, s));
+    MHIP_HIP(hipStreamSynchronize(s));
+    if (op->host_state->done || enqueued >= max_iters) return MHIP_SUCCESS;
+    const unsigned todo = (max_iters - enqueued < chunk) ? max_iters - enqueued : chunk;
+    for (unsigned k = 0; k < todo; ++k)
+      if (int e = iteration(enqueued + k)) return e;
+    MHIP_LAUNCH_CHECK();
+    enqueued += todo;
+    if (chunk < 64) chunk *= 2;
+  }
+}
+
+// end of every driver: the stream drained, the result is the state of the last poll
+int solve_result(mhip_contact_op* op, hipStream_t s, mhip_solve_result* result) {
+  MHIP_HIP(hipStreamSynchronize(s));
+  result->num_iters = op->host_state->iter;
+  result->residual = op->host_state->residual;
+  result->converged = op->host_state->converged;
+  return MHIP_SUCCESS;
+}
+
+// argument checks of the two friction drivers; an empty problem gets its result here (the caller returns on C == 0)
+int check_friction_args(mhip_contact_op* op, const double* sep, double mu, const mhip_pgd_config* config, const double* p,
+                        const double* g, mhip_solve_result* result) {
+  MHIP_REQUIRE(op != nullptr && result != nullptr, MHIP_ERR_INVALID_ARGUMENT, "null handle / result");
+  if (int e = check_config(config)) return e;
+  MHIP_REQUIRE(config->residual_kind == MHIP_RESIDUAL_PROJECTED_DIFF, MHIP_ERR_INVALID_ARGUMENT,
+               "the friction extension supports the projected-difference residual only");
+  MHIP_REQUIRE(mu >= 0.0 && mu == mu, MHIP_ERR_INVALID_ARGUMENT, "friction coefficient must be >= 0, got %g", mu);
+  MHIP_REQUIRE(op->kin == KIN_RIGID, MHIP_ERR_INVALID_ARGUMENT,
+               "friction needs the vector-arm operator (mhip_contact_op_create with ra, rb, mob_rot)");
+  if (op->view.C == 0) {
+    result->num_iters = 0;
+    result->residual = kLowest / kSmallStep;
+    result->converged = 1;
+    return MHIP_SUCCESS;
+  }
+  MHIP_REQUIRE(sep && p && g, MHIP_ERR_INVALID_ARGUMENT, "solver vectors must not be null");
+  MHIP_REQUIRE(p != g, MHIP_ERR_INVALID_ARGUMENT, "solver vectors must not alias");
+  MHIP_REQUIRE((reinterpret_cast<uintptr_t>(op->view.half) & 15) == 0, MHIP_ERR_RUNTIME, "misaligned records");
   return MHIP_SUCCESS;
 }
 
@@ -3547,9 +3531,9 @@ static int refresh_contact_op(mhip_contact_op_t op, const double* normal, const 
     const size_t ne = 2 * C;
     const int32_t* inc = op->inc.as<int32_t>();
     double* half = op->half.as<double>();
-    if (op->kin == KIN_ROD) k_half_build<KIN_ROD><<<grid_for(ne), kBlock, 0, s>>>(ne, inc, normal, ra, rb, arc_s, arc_t, half);
-    else if (op->kin == KIN_RIGID) k_half_build<KIN_RIGID><<<grid_for(ne), kBlock, 0, s>>>(ne, inc, normal, ra, rb, arc_s, arc_t, half);
-    else k_half_build<KIN_TRANS><<<grid_for(ne), kBlock, 0, s>>>(ne, inc, normal, ra, rb, arc_s, arc_t, half);
+    with_kin(op, [&](auto kin) {
+      k_half_build<decltype(kin)::value><<<grid_for(ne), kBlock, 0, s>>>(ne, inc, normal, ra, rb, arc_s, arc_t, half);
+    });
   }
   MHIP_LAUNCH_CHECK();
   op->view.aptr = nullptr;
@@ -3653,12 +3637,10 @@ int mhip_contact_op_constraint_rate(mhip_contact_op_t op, const double* velocity
   const SolverState* st = op->state.as<SolverState>();
   double* parts = op->partials.as<double>();
   const unsigned grid = grid_for(op->view.C);
-  if (op->kin == KIN_ROD)
-    k_constraint<X_APPLY, KIN_ROD, false><<<grid, kBlock, 0, s>>>(v, st, x0, nullptr, nullptr, sep_dot, nullptr, none, 0, parts);
-  else if (op->kin == KIN_RIGID)
-    k_constraint<X_APPLY, KIN_RIGID, false><<<grid, kBlock, 0, s>>>(v, st, x0, nullptr, nullptr, sep_dot, nullptr, none, 0, parts);
-  else
-    k_constraint<X_APPLY, KIN_TRANS, false><<<grid, kBlock, 0, s>>>(v, st, x0, nullptr, nullptr, sep_dot, nullptr, none, 0, parts);
+  with_kin(op, [&](auto kin) {
+    k_constraint<X_APPLY, decltype(kin)::value, false>
+        <<<grid, kBlock, 0, s>>>(v, st, x0, nullptr, nullptr, sep_dot, nullptr, none, 0, parts);
+  });
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
 }
@@ -3760,13 +3742,7 @@ int mhip_bbpgd_solve_contact(mhip_contact_op_t op, const double* q, const mhip_s
   // initialize: x_tmp = x ; g_tmp = A x_tmp + q ; residual ; step = 1/res   (the pair lands packed in P0)
   if (int e = op_launch_body(op, X_INIT, x, x, nullptr, nullptr, sp, s)) return e;
   if (int e = op_launch_constraint(op, X_INIT, P0, P1, x, nullptr, q, sp, rk, cgrid, s, true)) return e;
-  {
-    unsigned np = cgrid;
-    size_t ps = cgrid;
-    double* pp = parts;
-    fold_partials(np, ps, pp, st, 0, s);
-    k_finalize<X_INIT><<<1, final_block(np), 0, s>>>((int)np, pp, 1, ps, st, rk, config->tol, config->max_iters);
-  }
+  finalize_sweep<X_INIT>(op, cgrid, config, s);
   MHIP_LAUNCH_CHECK();
   unsigned enqueued = 0, chunk = 8, last_todo = 0, iter_before = 0;
   const bool prof = op->profile;
@@ -3835,14 +3811,12 @@ int mhip_bbpgd_solve_contact(mhip_contact_op_t op, const double* q, const mhip_s
       enqueued = op->host_state->iter;
     }
     if (op->host_state->done || enqueued >= config->max_iters) break;
-#if MHIP_SNAPSHOT_AT_INIT
     // the masks of the INITIAL iterate exist (the init sweep wrote them): a first snapshot of the active lists at the
     // first poll -- unless the problem was solved already -- so that iterations 1 ... 8 stream compact lists too instead
     // of walking every body's mask (round 3: k_body at 130-196 us in those iterations against 110 with a snapshot); what
     // becomes active since takes the per-body path
     if (enqueued == 0)
       if (int e = op_snapshot_active(op, s)) return e;
-#endif
     // cold tier: the drift bookkeeping starts with the first iteration, the first classification comes with the first
     // snapshot (short solves -- a relaxed packing needs ~100 iterations -- get their tiers early)
     const bool light = plan.light_poll();
@@ -3880,7 +3854,7 @@ int mhip_bbpgd_solve_contact(mhip_contact_op_t op, const double* q, const mhip_s
       }
       if (pk) MHIP_HIP(hipEventRecord(op->events[3 * k + 2], s));
       double* pp = parts;
-      if (MHIP_FOLD_FINALIZE && np > MHIP_FOLD_ABOVE) {
+      if (np > MHIP_FOLD_ABOVE) {
         // (folded records behind the kRed planes of partials, as fold_partials places them; the ticket word lives in
         // the spare words behind the solver state and is left at zero by every launch that finalizes)
         k_fold_finalize<X_SOLVE><<<kFoldGroups, MHIP_FOLD_BLOCK, 0, s>>>(
@@ -3888,7 +3862,6 @@ int mhip_bbpgd_solve_contact(mhip_contact_op_t op, const double* q, const mhip_s
             st, rk, config->tol, config->max_iters, tier.active ? op->tiering : 0,
             tier.active ? op->view.tier_counters : nullptr);
       } else {
-        fold_partials(np, ps, pp, st, 1, s);
         k_finalize<X_SOLVE><<<1, final_block(np), 0, s>>>((int)np, pp, 1, ps, st, rk, config->tol, config->max_iters,
                                                           tier.active ? op->tiering : 0,
                                                           tier.active ? op->view.tier_counters : nullptr);
@@ -3910,21 +3883,9 @@ int mhip_bbpgd_solve_contact(mhip_contact_op_t op, const double* q, const mhip_s
   // rods: the angular velocities of the final iterate (the iterations' sweeps keep only the (U, Z) rows)
   if (op->kin == KIN_ROD)
     if (int e = op_launch_body(op, X_APPLY, x, nullptr, nullptr, nullptr, sp, s)) return e;
-  MHIP_HIP(hipStreamSynchronize(s));
-  result->num_iters = op->host_state->iter;
-  result->residual = op->host_state->residual;
-  result->converged = op->host_state->converged;
-  return MHIP_SUCCESS;
+  return solve_result(op, s, result);
 }
 
-#ifdef MHIP_EXP_COUNT_MM
-int mhip_debug_counters(unsigned long long* out4) {
-  MHIP_HIP(hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_dbg), 4 * sizeof(unsigned long long)));
-  const unsigned long long z[4] = {0, 0, 0, 0};
-  MHIP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_dbg), z, sizeof(z)));
-  return MHIP_SUCCESS;
-}
-#endif
 /* cold-tier statistics of the last mhip_bbpgd_solve_contact on this operator (all zero when the solve did not tier) */
 int mhip_contact_op_tier_stats(mhip_contact_op_t op, size_t* tiered_iterations, double* mean_hot_fraction,
                                size_t* renumberings, size_t* wakeups) {
@@ -3952,24 +3913,10 @@ int mhip_bbpgd_solve_contact_friction(mhip_contact_op_t op, const double* sep, d
                                       const mhip_pgd_config* config, double* p, double* g,
                                       mhip_solve_result* result, mhip_stream_t stream) {
   TraceRange trace_range("solve_friction_contact (extension)");
-  MHIP_REQUIRE(op != nullptr && result != nullptr, MHIP_ERR_INVALID_ARGUMENT, "null handle / result");
-  if (int e = check_config(config)) return e;
-  MHIP_REQUIRE(config->residual_kind == MHIP_RESIDUAL_PROJECTED_DIFF, MHIP_ERR_INVALID_ARGUMENT,
-               "the friction extension supports the projected-difference residual only");
-  MHIP_REQUIRE(mu >= 0.0 && mu == mu, MHIP_ERR_INVALID_ARGUMENT, "friction coefficient must be >= 0, got %g", mu);
-  MHIP_REQUIRE(op->kin == KIN_RIGID, MHIP_ERR_INVALID_ARGUMENT,
-               "friction needs the vector-arm operator (mhip_contact_op_create with ra, rb, mob_rot)");
+  if (int e = check_friction_args(op, sep, mu, config, p, g, result)) return e;
   const size_t C = op->view.C;
+  if (C == 0) return MHIP_SUCCESS;
   hipStream_t s = as_stream(stream);
-  if (C == 0) {
-    result->num_iters = 0;
-    result->residual = kLowest / kSmallStep;
-    result->converged = 1;
-    return MHIP_SUCCESS;
-  }
-  MHIP_REQUIRE(sep && p && g, MHIP_ERR_INVALID_ARGUMENT, "solver vectors must not be null");
-  MHIP_REQUIRE(p != g, MHIP_ERR_INVALID_ARGUMENT, "solver vectors must not alias");
-  MHIP_REQUIRE((reinterpret_cast<uintptr_t>(op->view.half) & 15) == 0, MHIP_ERR_RUNTIME, "misaligned records");
   if (int e = op->iterate.reserve(2 * (6 * C + 2) * sizeof(double))) return e;
   double* P0 = op->iterate.as<double>();
   double* P1 = P0 + 6 * C;
@@ -3979,45 +3926,21 @@ int mhip_bbpgd_solve_contact_friction(mhip_contact_op_t op, const double* sep, d
   const int G = 8;  // lanes per body of the body sweep, two half-edge chains each
   const unsigned bgrid = grid_exact(op->view.body_count * (size_t)G);
   op->last_stream = s;
-  auto finalize = [&](bool init) {
-    unsigned np = cgrid;
-    size_t ps = cgrid;
-    double* pp = parts;
-    fold_partials(np, ps, pp, st, init ? 0 : 1, s);
-    if (init)
-      k_finalize<X_INIT><<<1, final_block(np), 0, s>>>((int)np, pp, 1, ps, st, config->residual_kind, config->tol,
-                                                       config->max_iters);
-    else
-      k_finalize<X_SOLVE><<<1, final_block(np), 0, s>>>((int)np, pp, 1, ps, st, config->residual_kind, config->tol,
-                                                        config->max_iters);
-  };
   if (op->view.body_count > 0) k_body_friction<true, 8, 2><<<bgrid, kBlock, 0, s>>>(op->view, st, P0, P1, p, mu);
   k_constraint_friction<true><<<cgrid, kBlock, 0, s>>>(op->view, st, P0, P1, p, sep, mu, parts);
-  finalize(true);
+  finalize_sweep<X_INIT>(op, cgrid, config, s);
   MHIP_LAUNCH_CHECK();
-  unsigned enqueued = 0, chunk = 8;
-  for (;;) {
-    MHIP_HIP(hipMemcpyAsync(op->host_state, st, sizeof(SolverState), hipMemcpyDeviceToHost, s));
-    MHIP_HIP(hipStreamSynchronize(s));
-    if (op->host_state->done || enqueued >= config->max_iters) break;
-    const unsigned todo = (config->max_iters - enqueued < chunk) ? config->max_iters - enqueued : chunk;
-    for (unsigned k = 0; k < todo; ++k) {
-      if (op->view.body_count > 0)
-        k_body_friction<false, 8, 2><<<bgrid, kBlock, 0, s>>>(op->view, st, P0, P1, nullptr, mu);
-      k_constraint_friction<false><<<cgrid, kBlock, 0, s>>>(op->view, st, P0, P1, nullptr, sep, mu, parts);
-      finalize(false);
-    }
-    MHIP_LAUNCH_CHECK();
-    enqueued += todo;
-    if (chunk < 64) chunk *= 2;
-  }
+  if (int e = poll_loop(op, config->max_iters, s, [&](unsigned) -> int {
+        if (op->view.body_count > 0)
+          k_body_friction<false, 8, 2><<<bgrid, kBlock, 0, s>>>(op->view, st, P0, P1, nullptr, mu);
+        k_constraint_friction<false><<<cgrid, kBlock, 0, s>>>(op->view, st, P0, P1, nullptr, sep, mu, parts);
+        finalize_sweep<X_SOLVE>(op, cgrid, config, s);
+        return MHIP_SUCCESS;
+      }))
+    return e;
   k_finish_friction<<<grid_for(C), kBlock, 0, s>>>(C, st, P0, P1, p, g);
   MHIP_LAUNCH_CHECK();
-  MHIP_HIP(hipStreamSynchronize(s));
-  result->num_iters = op->host_state->iter;
-  result->residual = op->host_state->residual;
-  result->converged = op->host_state->converged;
-  return MHIP_SUCCESS;
+  return solve_result(op, s, result);
 }
 
 /* BUILD EXTENSION (parity unpinned): the same cone complementarity problem by APGD -- Nesterov-accelerated projected
@@ -4027,24 +3950,10 @@ int mhip_bbpgd_solve_contact_friction(mhip_contact_op_t op, const double* sep, d
 int mhip_apgd_solve_contact_friction(mhip_contact_op_t op, const double* sep, double mu, const mhip_pgd_config* config,
                                      double* p, double* g, mhip_solve_result* result, mhip_stream_t stream) {
   TraceRange trace_range("solve_friction_contact, APGD (extension)");
-  MHIP_REQUIRE(op != nullptr && result != nullptr, MHIP_ERR_INVALID_ARGUMENT, "null handle / result");
-  if (int e = check_config(config)) return e;
-  MHIP_REQUIRE(config->residual_kind == MHIP_RESIDUAL_PROJECTED_DIFF, MHIP_ERR_INVALID_ARGUMENT,
-               "the friction extension supports the projected-difference residual only");
-  MHIP_REQUIRE(mu >= 0.0 && mu == mu, MHIP_ERR_INVALID_ARGUMENT, "friction coefficient must be >= 0, got %g", mu);
-  MHIP_REQUIRE(op->kin == KIN_RIGID, MHIP_ERR_INVALID_ARGUMENT,
-               "friction needs the vector-arm operator (mhip_contact_op_create with ra, rb, mob_rot)");
+  if (int e = check_friction_args(op, sep, mu, config, p, g, result)) return e;
   const size_t C = op->view.C;
+  if (C == 0) return MHIP_SUCCESS;
   hipStream_t s = as_stream(stream);
-  if (C == 0) {
-    result->num_iters = 0;
-    result->residual = kLowest / kSmallStep;
-    result->converged = 1;
-    return MHIP_SUCCESS;
-  }
-  MHIP_REQUIRE(sep && p && g, MHIP_ERR_INVALID_ARGUMENT, "solver vectors must not be null");
-  MHIP_REQUIRE(p != g, MHIP_ERR_INVALID_ARGUMENT, "solver vectors must not alias");
-  MHIP_REQUIRE((reinterpret_cast<uintptr_t>(op->view.half) & 15) == 0, MHIP_ERR_RUNTIME, "misaligned records");
   if (int e = op->iterate.reserve((3 * (6 * C + 2) + 16) * sizeof(double))) return e;
   ApgdBufs B;
   B.P[0] = op->iterate.as<double>();
@@ -4061,38 +3970,19 @@ int mhip_apgd_solve_contact_friction(mhip_contact_op_t op, const double* sep, do
   // p_0, g_0 = N p_0 + q and the initial residual: the INIT sweeps of the BBPGD extension (buffer 0 receives them)
   if (op->view.body_count > 0) k_body_friction<true, 8, 2><<<bgrid, kBlock, 0, s>>>(op->view, st, B.P[0], B.P[1], p, mu);
   k_constraint_friction<true><<<cgrid, kBlock, 0, s>>>(op->view, st, B.P[0], B.P[1], p, sep, mu, parts);
-  {
-    unsigned np = cgrid;
-    size_t ps = cgrid;
-    double* pp = parts;
-    fold_partials(np, ps, pp, st, 0, s);
-    k_finalize<X_INIT><<<1, final_block(np), 0, s>>>((int)np, pp, 1, ps, st, config->residual_kind, config->tol,
-                                                     config->max_iters);
-  }
+  finalize_sweep<X_INIT>(op, cgrid, config, s);
   k_apgd_begin<<<1, 1, 0, s>>>(st, as);
   MHIP_LAUNCH_CHECK();
-  unsigned enqueued = 0, chunk = 8;
-  for (;;) {
-    MHIP_HIP(hipMemcpyAsync(op->host_state, st, sizeof(SolverState), hipMemcpyDeviceToHost, s));
-    MHIP_HIP(hipStreamSynchronize(s));
-    if (op->host_state->done || enqueued >= config->max_iters) break;
-    const unsigned todo = (config->max_iters - enqueued < chunk) ? config->max_iters - enqueued : chunk;
-    for (unsigned k = 0; k < todo; ++k) {
-      if (op->view.body_count > 0) k_body_friction_apgd<8, 2><<<bgrid, kBlock, 0, s>>>(op->view, st, as, B, mu);
-      k_constraint_friction_apgd<<<cgrid, kBlock, 0, s>>>(op->view, st, as, B, sep, mu, parts);
-      k_apgd_finalize<<<1, kFinalBlock, 0, s>>>((int)cgrid, parts, st, as, config->tol, config->max_iters);
-    }
-    MHIP_LAUNCH_CHECK();
-    enqueued += todo;
-    if (chunk < 64) chunk *= 2;
-  }
+  if (int e = poll_loop(op, config->max_iters, s, [&](unsigned) -> int {
+        if (op->view.body_count > 0) k_body_friction_apgd<8, 2><<<bgrid, kBlock, 0, s>>>(op->view, st, as, B, mu);
+        k_constraint_friction_apgd<<<cgrid, kBlock, 0, s>>>(op->view, st, as, B, sep, mu, parts);
+        k_apgd_finalize<<<1, kFinalBlock, 0, s>>>((int)cgrid, parts, st, as, config->tol, config->max_iters);
+        return MHIP_SUCCESS;
+      }))
+    return e;
   k_finish_friction_apgd<<<grid_for(C), kBlock, 0, s>>>(C, st, as, B, p, g);
   MHIP_LAUNCH_CHECK();
-  MHIP_HIP(hipStreamSynchronize(s));
-  result->num_iters = op->host_state->iter;
-  result->residual = op->host_state->residual;
-  result->converged = op->host_state->converged;
-  return MHIP_SUCCESS;
+  return solve_result(op, s, result);
 }
 
 int mhip_solve_small_cqpp_batch(size_t batch, int n, const double* A, const double* q, const mhip_space* space,
@@ -4134,39 +4024,31 @@ int mhip_scrap_bbpgd_solve_contact(mhip_contact_op_t op, const double* sep, doub
   if (int e = op->iterate.reserve(2 * (C + 1) * sizeof(double2))) return e;
   double* D0 = op->iterate.as<double>();  // dt * sep_dot of the two iterates (see k_scrap_constraint)
   double* D1 = D0 + C;
-  auto constraint = [&](bool init) {
-#define SCON(R, I) k_scrap_constraint<R, I><<<cgrid, kBlock, 0, s>>>(op->view, st, lam_tmp, lam, g_tmp, g, D0, D1, sep, parts)
-    if (op->kin == KIN_ROD) { if (init) SCON(KIN_ROD, true); else SCON(KIN_ROD, false); }
-    else if (op->kin == KIN_RIGID) { if (init) SCON(KIN_RIGID, true); else SCON(KIN_RIGID, false); }
-    else { if (init) SCON(KIN_TRANS, true); else SCON(KIN_TRANS, false); }
-#undef SCON
+  auto constraint = [&](auto init) {
+    with_kin(op, [&](auto kin) {
+      k_scrap_constraint<decltype(kin)::value, decltype(init)::value><<<cgrid, kBlock, 0, s>>>(
+          op->view, st, lam_tmp, lam, g_tmp, g, D0, D1, sep, parts);
+    });
   };
   // gkm1 = D^T M D xkm1 with xkm1 = the given multipliers (:576-611)
   if (int e = launch_copy(C, lam_tmp, lam, s)) return e;
   MHIP_HIP(hipMemsetAsync(st, 0, sizeof(SolverState), s));
   if (int e = op_launch_body(op, X_INIT, lam_tmp, lam, g_tmp, g, lcp, s)) return e;
-  constraint(true);
+  constraint(std::true_type{});
   MHIP_LAUNCH_CHECK();
   k_scrap_finalize<true><<<1, kBlock, 0, s>>>((int)cgrid, parts, st, max_allowable_overlap, max_iterations);
   MHIP_LAUNCH_CHECK();
-  unsigned enqueued = 0, chunk = 8;
-  for (;;) {
-    MHIP_HIP(hipMemcpyAsync(op->host_state, st, sizeof(SolverState), hipMemcpyDeviceToHost, s));
-    MHIP_HIP(hipStreamSynchronize(s));
-    if (op->host_state->done || enqueued >= max_iterations) break;
-    const unsigned todo = (max_iterations - enqueued < chunk) ? max_iterations - enqueued : chunk;
-    for (unsigned k = 0; k < todo; ++k) {
-      // first iteration: the projected step sees sep only (signed_sep_dot == 0 at :639) -> q stands in for g_tmp
-      const double* gbody = (enqueued + k == 0) ? sep : g_tmp;
-      if (int e = op_launch_body(op, X_SOLVE, lam_tmp, lam, gbody, g, lcp, s)) return e;
-      constraint(false);
-      MHIP_LAUNCH_CHECK();
-      k_scrap_finalize<false><<<1, kBlock, 0, s>>>((int)cgrid, parts, st, max_allowable_overlap, max_iterations);
-      MHIP_LAUNCH_CHECK();
-    }
-    enqueued += todo;
-    if (chunk < 64) chunk *= 2;
-  }
+  if (int e = poll_loop(op, max_iterations, s, [&](unsigned k) -> int {
+        // first iteration: the projected step sees sep only (signed_sep_dot == 0 at :639) -> q stands in for g_tmp
+        const double* gbody = (k == 0) ? sep : g_tmp;
+        if (int e = op_launch_body(op, X_SOLVE, lam_tmp, lam, gbody, g, lcp, s)) return e;
+        constraint(std::false_type{});
+        MHIP_LAUNCH_CHECK();
+        k_scrap_finalize<false><<<1, kBlock, 0, s>>>((int)cgrid, parts, st, max_allowable_overlap, max_iterations);
+        MHIP_LAUNCH_CHECK();
+        return MHIP_SUCCESS;
+      }))
+    return e;
   k_finish<<<grid_for(C), kBlock, 0, s>>>(C, st, lam_tmp, lam, g_tmp, g);
   MHIP_LAUNCH_CHECK();
   if (max_speed && op->view.N > 0) {
@@ -4182,11 +4064,7 @@ int mhip_scrap_bbpgd_solve_contact(mhip_contact_op_t op, const double* sep, doub
     MHIP_HIP(hipStreamSynchronize(s));
     *max_speed = rs.host[0] < 0.0 ? 0.0 : rs.host[0];
   }
-  MHIP_HIP(hipStreamSynchronize(s));
-  result->num_iters = op->host_state->iter;
-  result->residual = op->host_state->residual;
-  result->converged = op->host_state->converged;
-  return MHIP_SUCCESS;
+  return solve_result(op, s, result);
 }
 
 int mhip_contact_op_set_partition(mhip_contact_op_t op, size_t body_first, size_t body_count,
@@ -4312,11 +4190,10 @@ int mhip_bbpgd_stage_constraint_range(mhip_contact_op_t op, int init, size_t c_f
     }
     if (grid + extra == 0) return MHIP_SUCCESS;
     MHIP_REQUIRE(st.part_used + grid + extra <= kStageStride, MHIP_ERR_RUNTIME, "too many constraint sweeps in one iteration");
-#define STAGED(K)                                                                                                    \
-  k_constraint<X_SOLVE, K, true><<<grid + extra, kBlock, 0, s>>>(vw, sst, st.P0, st.P1, nullptr, nullptr, st.q_cur, \
-                                                                st.sp, st.cfg.residual_kind, parts, tc)
-    if (op->kin == KIN_ROD) STAGED(KIN_ROD); else if (op->kin == KIN_RIGID) STAGED(KIN_RIGID); else STAGED(KIN_TRANS);
-#undef STAGED
+    with_kin(op, [&](auto kin) {
+      k_constraint<X_SOLVE, decltype(kin)::value, true><<<grid + extra, kBlock, 0, s>>>(
+          vw, sst, st.P0, st.P1, nullptr, nullptr, st.q_cur, st.sp, st.cfg.residual_kind, parts, tc);
+    });
     MHIP_LAUNCH_CHECK();
     st.part_used += grid + extra;  // (the service workgroups' records follow the sweeping ones')
     return MHIP_SUCCESS;
