@@ -153,6 +153,47 @@ int mhip_contact_spherocylinders_periodic(size_t c, const int32_t* pairs, const 
 int mhip_hertz_contact_force(size_t c, size_t n, const int32_t* pairs, const double* sep, const double* radius,
                              const double* youngs_modulus, double youngs_modulus_scalar, const double* poisson_ratio,
                              double poisson_ratio_scalar, double* force, double* max_overlap, mhip_stream_t stream);
+/* Frictional Hertzian contact of two rods with a per-pair tangential history, per linker.  For sep > 0 the history row
+ * is reset and the force is +0.0 (both rows are written only where they are not +0.0 already); otherwise
+ *   v_cp,b = U_b + W_b x ((s_b - 1/2)(p1_b - p0_b))   from velocity_prev [n][6] (U, W), the previous step's rows, and the
+ *                                                     arm of the rod-compressed operator (arclength clamped to [0, 1])
+ *   rel = v_cp,j - v_cp,i,  rel_n = (rel . n) n,  rel_t = rel - rel_n
+ *   tang_disp += rel_t dt,  tang_disp -= (tang_disp . n) n
+ *   R* = r_i r_j / (r_i + r_j),  m* = m_i m_j / (m_i + m_j) with m = 4/3 pi r^3 density,  hp = sqrt(-R* sep)
+ *   F_n = hp (k_n sep n + m* normal_damping rel_n),  F_t = hp (k_t tang_disp + m* tangential_damping rel_t)
+ *   if |F_t| > mu |F_n|: tang_disp and F_t are rescaled onto the Coulomb bound (F_t = 0 if |tang_disp| == 0)
+ *   force[c] = F_n + F_t   on body i; body j receives its negative (mhip_contact_op_body_sweep_vector)
+ * with k_n = 4/3 E* (E* as in mhip_hertz_contact_force) and k_t = 8 G*, G* = G_i G_j / (G_j (2 - nu_i) + G_i (2 - nu_j)),
+ * G = 0.5 E / (1 + nu): for equal materials the reference's 4/3 G / (1 - nu) and 4 G / (2 - nu).  Right-fold dot and
+ * norm, the reference's association.  Materials as in mhip_hertz_contact_force.  tang_disp [c][3] is read and written,
+ * "j relative to i".  stats [device, 16 bytes]: a double max(0, -sep) over the contact branch, then a uint64 count of
+ * the contacts whose tangential force was capped; both order independent.  A pair index outside [0, n) gives NaN rows
+ * and is never dereferenced.  Refused before any HIP call: mu < 0, a negative damping, density or dt, anything not
+ * finite, a null pointer that would be dereferenced.
+ * Replaces: SpherocylinderSegmentSpherocylinderSegmentFrictionalHertzianContact.cpp:384-518 (rigid rods). */
+typedef struct {
+  double mu, normal_damping, tangential_damping, density, dt;
+} mhip_hertz_friction_params;
+int mhip_hertz_friction_force(size_t c, size_t n, const int32_t* pairs, const double* sep, const double* normal,
+                              const double* arc_s, const double* arc_t, const double* seg /*[n][8]*/,
+                              const double* radius, const double* youngs_modulus, double youngs_modulus_scalar,
+                              const double* poisson_ratio, double poisson_ratio_scalar,
+                              const double* velocity_prev /*[n][6]*/,
+                              const mhip_hertz_friction_params* params /*[host]*/, double* tang_disp /*[c][3] in/out*/,
+                              double* force /*[c][3]*/, void* stats /*[device]*/, mhip_stream_t stream);
+/* Carries a per-pair history [c][3] from one contact list to the next.  Each new pair (i, j) receives the row of the old
+ * pair whose endpoints, renumbered through new_of_old [n_old] (NULL: the numbering is unchanged; a negative image: the
+ * body is gone), are {i, j} -- negated when the orientation came out swapped, the history being "j relative to i" --
+ * and +0.0 otherwise.  64-bit pair keys, the radix sort, one binary search per new pair; with new_of_old == NULL the old
+ * list must be canonical (sorted by (i, j), i < j, as the broad phase returns it) and nothing is sorted.  An old pair with
+ * an endpoint outside [0, n_old) carries nothing.  *carried [host] or NULL = number of new pairs that found their old
+ * row.  Synchronises when carried is given or new_of_old is NULL: in the latter case an old list that does not ascend
+ * strictly is refused with MHIP_ERR_INVALID_ARGUMENT after the fact (hist_new is then not to be used).  hist_new must
+ * not be hist_old. */
+int mhip_contact_history_carry(size_t c_old, const int32_t* pairs_old, const double* hist_old,
+                               const int32_t* new_of_old /*[n_old] or NULL*/, size_t n_old, size_t c_new,
+                               const int32_t* pairs_new, double* hist_new, size_t* carried /*[host] or NULL*/,
+                               mhip_stream_t stream);
 
 /* Growth and division of spherocylinders: the body population of the colony loop changes on the device
  * (scrap/parameter_interface/alens/tests/performance_tests/Bacteria.cpp:1033-1080).  Per step, before the AABBs:
@@ -462,6 +503,12 @@ int mhip_contact_op_apply(mhip_contact_op_t handle, const double* x, double* y, 
  *           force and torque (cp - x_body) x F summed per body) followed by compute_generalized_velocity
  *           (scrap/parameter_interface/alens/tests/performance_tests/Bacteria.cpp:806-848, dry drag). */
 int mhip_contact_op_body_sweep(mhip_contact_op_t handle, const double* x, mhip_stream_t stream);
+/* The same sweep for a vector force per contact, force [C][3]: U_b = m_t sum +/-F_c, W_b = m_r sum arm x (+/-F_c) with +
+ * on side i and - on side j, over the operator's own incidence index and half-edge arms (spheres, vector arms, rod
+ * arms), fixed-order double-double sums.  body_sweep_vector(-x_c n_c) gives the rows of body_sweep(x) bit for bit.  The
+ * operator is left as mhip_contact_op_body_sweep leaves it (rod rows hold (U, W x u), omega is filled), so
+ * mhip_contact_op_body_velocity reads the result.  Refused while a staged solve is in progress. */
+int mhip_contact_op_body_sweep_vector(mhip_contact_op_t handle, const double* force, mhip_stream_t stream);
 /* The transpose sweep alone: sep_dot [C] = D^T U of a caller-given velocity [N][6] (U, W) rows,
  *   sep_dot_c = n_c . [(U_j + W_j x rb) - (U_i + W_i x ra)]
  * with the operator's own kinematics (spheres, vector arms, rod arms).  It is apply's constraint sweep (X_APPLY) on the

@@ -780,6 +780,44 @@ inline void evaluate_linker_potentials(size_t num_linkers, size_t num_bodies, co
                                  force, max_overlap, stream));
 }
 
+/// Parameters of the frictional Hertzian rod contact (the reference hard-codes mu = 0.5, no damping, density 1:
+/// ...FrictionalHertzianContact.cpp:406-417)
+struct FrictionalHertzParams {
+  double friction_coeff = 0.5;
+  double normal_damping_coeff = 0.0;
+  double tang_damping_coeff = 0.0;
+  double density = 1.0;
+};
+
+/// EvaluateLinkerPotentials with SpherocylinderSegmentSpherocylinderSegmentFrictionalHertzianContact (:384-518): the
+/// force vector [C][3] on the left rod of every linker from the previous step's body velocities [N][6] and the linker's
+/// tangential displacement [C][3] (updated in place); stats [device, 16 bytes] = (double max overlap, uint64 capped
+/// contacts) (mhip_hertz_friction_force).
+inline void evaluate_frictional_linker_potentials(size_t num_linkers, size_t num_bodies, const int32_t* pairs,
+                                                  const double* sep, const double* normal, const double* arc_s,
+                                                  const double* arc_t, const double* seg, const double* radius,
+                                                  const HertzMaterial& material, const double* velocity_prev,
+                                                  const FrictionalHertzParams& params, double dt, double* tang_disp,
+                                                  double* force, void* stats, mhip_stream_t stream = nullptr) {
+  const mhip_hertz_friction_params p{params.friction_coeff, params.normal_damping_coeff, params.tang_damping_coeff,
+                                     params.density, dt};
+  check(mhip_hertz_friction_force(num_linkers, num_bodies, pairs, sep, normal, arc_s, arc_t, seg, radius,
+                                  material.youngs_modulus_per_body, material.youngs_modulus,
+                                  material.poisson_ratio_per_body, material.poisson_ratio, velocity_prev, &p, tang_disp,
+                                  force, stats, stream));
+}
+
+/// A linker field [C][3] follows its pairs from one neighbour list to the next (the reference keeps it on the linker
+/// entity, which persists while the pair stays listed): mhip_contact_history_carry.  Returns the rows carried.
+inline size_t carry_linker_history(size_t num_old, const int32_t* pairs_old, const double* hist_old,
+                                   const int32_t* new_of_old, size_t num_bodies_old, size_t num_new,
+                                   const int32_t* pairs_new, double* hist_new, mhip_stream_t stream = nullptr) {
+  size_t carried = 0;
+  check(mhip_contact_history_carry(num_old, pairs_old, hist_old, new_of_old, num_bodies_old, num_new, pairs_new, hist_new,
+                                   &carried, stream));
+  return carried;
+}
+
 }  // namespace linkers
 
 // ---- contact operator (a LinearOp with apply(x, y)) ---------------------------------------------------------------------
@@ -818,6 +856,10 @@ class ContactOperator {
   /// U = M D f of per-linker force magnitudes f [C] (body i gets -f n, body j +f n) -- the body sweep of apply alone
   void linker_potential_force_reduction(const double* force, mhip_stream_t stream = nullptr) const {
     check(mhip_contact_op_body_sweep(h_, force, stream));
+  }
+  /// the same for a force VECTOR per linker, force [C][3] on body i (body j gets its negative)
+  void linker_potential_force_reduction_vector(const double* force, mhip_stream_t stream = nullptr) const {
+    check(mhip_contact_op_body_sweep_vector(h_, force, stream));
   }
   /// [num_bodies][6] (U, W) of the last apply / body sweep / solve (device pointer, valid in stream order)
   const double* compute_generalized_velocity() const {

@@ -5,6 +5,9 @@
 //   -> ContactOperator (rod-compressed) -> solve_lcp (fused BBPGD) -> body velocities -> Euler + quaternion update
 // Opt-in soft contact (SpherocylinderStepper::set_hertz_contact): the solve is replaced by the Hertz force per linker
 // and the operator's body sweep on it, U = M D f (Bacteria.cpp:755-848).
+// Opt-in friction on top of it (SpherocylinderStepper::set_hertz_friction): the reference's frictional Hertzian rod
+// contact with a tangential history per pair (...FrictionalHertzianContact.cpp:384-518), a force vector per linker and
+// the operator's vector body sweep; the history follows the pairs through list rebuilds and reorder_bodies.
 // Opt-in growth (SpherocylinderStepper::set_growth): the colony step of the same app (Bacteria.cpp:1033-1080) in front
 // of compute_aabb -- divide_bacteria (:926-966) -> grow_bacteria (:905-920) -- on a body population that lives in
 // grow-only device storage, with the rebuild rule of growing bodies (check_update_neighbor_list, :685-748).
@@ -13,6 +16,8 @@
 #pragma once
 #include <chrono>
 #include <cmath>
+#include <cstdint>
+#include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -37,6 +42,8 @@ struct StepStats {
   bool converged = false, rebuilt = false;
   double max_overlap = 0.0;  // Hertz mode: max(0, -sep) over the step's contacts (what dt is chosen from)
   size_t num_born = 0;       // growth mode: bodies that divided this step (children are rows n_before + k)
+  size_t num_sliding = 0;    // frictional Hertz mode: contacts whose tangential force was capped at mu |F_n|
+  size_t num_carried = 0;    // frictional Hertz mode: history rows carried to a rebuilt list this step
 };
 
 /// grow-only storage that keeps its first `live` doubles: reallocates with headroom only when `need` does not fit
@@ -77,6 +84,7 @@ class SpherocylinderStepper {
     gather(brad_, 1);
     gather(mob_t_, 1);
     gather(mob_r_, 1);
+    if (friction_) renumber_history();
     // the neighbour list and the operator's incidence index are in the old numbering
     links_.invalidate();
     op_.reset();
@@ -94,12 +102,32 @@ class SpherocylinderStepper {
     material_.poisson_ratio = poisson_ratio;
   }
 
+  /// Friction on top of the Hertz contact (opt-in, after set_hertz_contact): the reference's frictional Hertzian rod
+  /// contact, mu >= 0, damping coefficients and density >= 0 (defaults: the reference's).  The stepper then owns the
+  /// previous step's body velocities (zero before the first step) and the tangential displacement of every listed
+  /// pair, carried through list rebuilds and reorder_bodies.  Not combined with growth.
+  void set_hertz_friction(double mu, double gamma_n = 0.0, double gamma_t = 0.0, double density = 1.0) {
+    if (!hertz_) throw std::logic_error("set_hertz_friction: call set_hertz_contact first");
+    if (growth_) throw std::logic_error("set_hertz_friction: not combined with set_growth");
+    for (double v : {mu, gamma_n, gamma_t, density})
+      if (!(v >= 0.0 && v < HUGE_VAL))
+        throw std::invalid_argument("set_hertz_friction: mu, the damping coefficients and the density must be finite "
+                                    "and >= 0");
+    friction_ = true;
+    friction_params_ = linkers::FrictionalHertzParams{mu, gamma_n, gamma_t, density};
+    prev_vel_ = DeviceVector(6 * n_ + 1);
+    check(mhip_fill(6 * n_, prev_vel_.data(), 0.0, nullptr));
+    num_hist_ = 0;
+    have_hist_ = have_renumber_ = false;
+  }
+
   /// The bacterial colony step (Bacteria.cpp:1033-1080), opt-in: every step first divides the rods with length >
   /// division_length (children appended as rows n + k, parent_of()[k] their parent) and grows every length by
   /// dt * growth_rate, then rebuilds the list iff there were births, force_rebuild, or some AABB corner moved by
   /// >= search_buffer since the last build -- the centre rule is not consulted.  Mobilities are carried as given
   /// (children copy their parent's).  Buffers are sized max(capacity_hint, n + n/8 + 16) and grow with headroom.
   void set_growth(double growth_rate, double division_length, size_t capacity_hint = 0) {
+    if (friction_) throw std::logic_error("set_growth: not combined with set_hertz_friction");
     if (!(growth_rate >= 0.0 && growth_rate < HUGE_VAL))
       throw std::invalid_argument("set_growth: growth_rate must be finite and >= 0");
     if (!(division_length >= 0.0 && division_length < HUGE_VAL))
@@ -120,7 +148,12 @@ class SpherocylinderStepper {
     if (growth_) st.num_born = grow_and_divide();
     double *sep = nullptr, *normal = nullptr, *s = nullptr, *t = nullptr;
     const size_t C = contacts(st, force_rebuild, sep, normal, s, t);
-    if (hertz_) {
+    if (friction_) {
+      st.num_carried = carry_history(C);
+      linkers::evaluate_frictional_linker_potentials(C, n_, pairs_.data(), sep, normal, s, t, seg_.data(), radius_.data(),
+                                                     material_, prev_vel_.data(), friction_params_, dt_,
+                                                     tang_disp_.data(), force_.data(), workspace(w_mx_, 2));
+    } else if (hertz_) {
       double* f = workspace(lambda_, C);
       double* mx = workspace(w_mx_, 1);
       linkers::evaluate_linker_potentials(C, n_, pairs_.data(), sep, radius_.data(), material_, f, mx);
@@ -133,7 +166,16 @@ class SpherocylinderStepper {
     else
       op_->refresh(normal, ContactOperator::Rods{s, t, seg_.data()});
     ContactOperator& op = *op_;
-    if (hertz_) {
+    if (friction_) {
+      op.linker_potential_force_reduction_vector(force_.data());
+      st.converged = true;
+      double h[2];
+      check(mhip_memcpy_d2h(h, w_mx_.data(), sizeof h, nullptr));
+      st.max_overlap = h[0];
+      std::uint64_t k;
+      std::memcpy(&k, &h[1], sizeof k);
+      st.num_sliding = static_cast<size_t>(k);
+    } else if (hertz_) {
       op.linker_potential_force_reduction(lambda_.data());
       st.converged = true;
       check(mhip_memcpy_d2h(&st.max_overlap, w_mx_.data(), sizeof(double), nullptr));
@@ -141,7 +183,9 @@ class SpherocylinderStepper {
       solve(op, C, sep, st);
     }
     if (integrate) {
-      check(mhip_integrate_euler(n_, dt_, op.compute_generalized_velocity(), center_.data(), quat_.data(), nullptr));
+      const double* vel = op.compute_generalized_velocity();
+      if (friction_) check(mhip_deep_copy(6 * n_, prev_vel_.data(), vel, nullptr));  // the next step's StateN
+      check(mhip_integrate_euler(n_, dt_, vel, center_.data(), quat_.data(), nullptr));
       // wrap_rigid_inplace(Spherocylinder): the centre goes back into the box (periodicity.hpp:1094-1113)
       if (periodic_) check(mhip_wrap_rigid(n_, box_, center_.data(), nullptr));
     }
@@ -161,6 +205,10 @@ class SpherocylinderStepper {
   const DeviceVector& lambda() const { return lambda_; }
   size_t num_lambda() const { return num_lambda_; }
   const DeviceArray<int32_t>& pairs() const { return pairs_; }
+  /// frictional Hertz mode: the linker forces [C][3] (on body i) and tangential displacements [C][3] of the last step,
+  /// rows of pairs() (the first 3 * num_contacts entries)
+  const DeviceVector& contact_force() const { return force_; }
+  const DeviceVector& tang_disp() const { return tang_disp_; }
 
  private:
   /// compute_aabb -> neighbour list (rebuild rule) -> segments -> narrow phase; returns the number of contacts
@@ -181,7 +229,10 @@ class SpherocylinderStepper {
     } else {
       st.rebuilt = links_.generate(n_, aabb_.data(), center_.data(), brad_.data(), nullptr, force_rebuild);
     }
-    if (st.rebuilt) links_.links_into(pairs_);
+    if (st.rebuilt) {
+      links_.links_into(pairs_);
+      ++links_generation_;
+    }
     const size_t C = links_.num_links();
     st.num_contacts = C;
     check(mhip_spherocylinder_segments(n_, center_.data(), quat_.data(), radius_.data(), length_.data(), seg_.data(),
@@ -197,6 +248,52 @@ class SpherocylinderStepper {
       check(mhip_contact_spherocylinders(C, pairs_.data(), seg_.data(), nullptr, sep, normal, nullptr, nullptr,
                                          nullptr, nullptr, s, t, nullptr));
     return C;
+  }
+  /// frictional Hertz mode: the history follows the list.  After a rebuild (or a renumbering) every pair of the new list
+  /// receives the row of the same pair of the list the history belongs to, every other pair +0.0.
+  size_t carry_history(size_t C) {
+    const bool moved = !have_hist_ || have_renumber_ || hist_list_ != links_generation_;
+    if (!moved) return 0;
+    DeviceVector next(3 * C + 1);
+    size_t carried = 0;
+    if (have_hist_)
+      carried = linkers::carry_linker_history(num_hist_, hist_pairs_.data(), tang_disp_.data(),
+                                              have_renumber_ ? renumber_.data() : nullptr, n_, C, pairs_.data(),
+                                              next.data());
+    else
+      check(mhip_fill(3 * C, next.data(), 0.0, nullptr));
+    tang_disp_ = std::move(next);
+    force_ = DeviceVector(3 * C + 1);
+    check(mhip_fill(3 * C, force_.data(), 0.0, nullptr));
+    // a copy of the list the history now belongs to (pairs_ is overwritten by the next rebuild): 8 bytes per pair
+    if (hist_pairs_.size() < 2 * C) hist_pairs_ = DeviceArray<int32_t>(2 * C + C / 4 + 16);
+    check(mhip_deep_copy(C, reinterpret_cast<double*>(hist_pairs_.data()),
+                         reinterpret_cast<const double*>(pairs_.data()), nullptr));
+    num_hist_ = C;
+    hist_list_ = links_generation_;
+    have_hist_ = true;
+    have_renumber_ = false;
+    return carried;
+  }
+  /// reorder_bodies in frictional Hertz mode: the previous velocities move with their rows; the history keeps its old
+  /// pair list and is carried through new_of_old (the inverse permutation) at the rebuild that follows
+  void renumber_history() {
+    DeviceVector moved(6 * n_ + 1);
+    check(mhip_gather_rows(n_, 6, perm_.data(), prev_vel_.data(), moved.data(), nullptr));
+    prev_vel_ = std::move(moved);
+    if (!have_hist_) return;
+    std::vector<int32_t> perm = perm_.download();
+    perm.resize(n_);
+    std::vector<int32_t> inv(n_);
+    for (size_t k = 0; k < n_; ++k) inv[static_cast<size_t>(perm[k])] = static_cast<int32_t>(k);
+    if (have_renumber_) {  // two reorders without a step between them compose
+      const std::vector<int32_t> first = renumber_.download();
+      std::vector<int32_t> both(n_);
+      for (size_t b = 0; b < n_; ++b) both[b] = inv[static_cast<size_t>(first[b])];
+      inv.swap(both);
+    }
+    renumber_ = DeviceArray<int32_t>(inv);
+    have_renumber_ = true;
   }
   /// the LCP: fused BBPGD from lambda = 0 (NgpLcp.cpp:890-891)
   void solve(ContactOperator& op, size_t C, const double* sep, StepStats& st) {
@@ -258,6 +355,12 @@ class SpherocylinderStepper {
   size_t num_lambda_ = 0;
   bool hertz_ = false;
   linkers::HertzMaterial material_;
+  bool friction_ = false, have_hist_ = false, have_renumber_ = false;
+  linkers::FrictionalHertzParams friction_params_;
+  DeviceVector prev_vel_, tang_disp_, force_;  // [n][6] previous velocities; [C][3] history and linker forces
+  DeviceArray<int32_t> hist_pairs_, renumber_;  // the list tang_disp_ belongs to; new index of every old body
+  size_t num_hist_ = 0;
+  unsigned long long links_generation_ = 0, hist_list_ = 0;
   bool growth_ = false, have_ref_ = false;
   double rate_ = 0.0, division_ = 0.0, buffer_ = 0.0;
   DeviceVector aabb_ref_;  // growth mode: the AABBs of the last build

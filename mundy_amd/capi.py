@@ -37,6 +37,11 @@ class SolveResult(C.Structure):
     _fields_ = [("num_iters", C.c_uint), ("residual", C.c_double), ("converged", C.c_int)]
 
 
+class HertzFrictionParams(C.Structure):
+    _fields_ = [("mu", C.c_double), ("normal_damping", C.c_double), ("tangential_damping", C.c_double),
+                ("density", C.c_double), ("dt", C.c_double)]
+
+
 class VelocityHalo(C.Structure):
     """mhip_velocity_halo: the per-iteration ghost-velocity exchange of one rank (host lists + one device index list)"""
     _fields_ = [("velocity", C.c_void_p), ("num_send_peers", C.c_int), ("send_peer", C.POINTER(C.c_int)),
@@ -100,6 +105,9 @@ SIGNATURES = {
     "mhip_contact_mixed_periodic": [_sz] + [_vp] * 5 + [C.POINTER(_d)] + [_vp] * 6 + [C.POINTER(_sz), _vp],
     "mhip_contact_spherocylinders_periodic": [_sz, _vp, _vp, _vp, C.POINTER(_d)] + [_vp] * 9,
     "mhip_hertz_contact_force": [_sz, _sz, _vp, _vp, _vp, _vp, _d, _vp, _d, _vp, _vp, _vp],
+    "mhip_hertz_friction_force": [_sz, _sz] + [_vp] * 8 + [_d, _vp, _d, _vp, C.POINTER(HertzFrictionParams), _vp, _vp, _vp,
+                                  _vp],
+    "mhip_contact_history_carry": [_sz, _vp, _vp, _vp, _sz, _sz, _vp, _vp, C.POINTER(_sz), _vp],
     "mhip_select_dividing": [_sz, _vp, _d, _vp, C.POINTER(_sz), _vp],
     "mhip_divide_grow_spherocylinders": [_sz, _sz, _vp, _d, _d, C.POINTER(_d), _vp, _vp, _vp, _vp, _vp],
     "mhip_aabb_moved": [_sz, _vp, _vp, _d, C.POINTER(_i), _vp],
@@ -143,6 +151,7 @@ SIGNATURES = {
     "mhip_contact_op_destroy": [_vp],
     "mhip_contact_op_apply": [_vp, _vp, _vp, _vp],
     "mhip_contact_op_body_sweep": [_vp, _vp, _vp],
+    "mhip_contact_op_body_sweep_vector": [_vp, _vp, _vp],
     "mhip_contact_op_constraint_rate": [_vp, _vp, _vp, _vp],
     "mhip_contact_op_body_velocity": [_vp, C.POINTER(_vp)],
     "mhip_contact_op_set_profiling": [_vp, _i],

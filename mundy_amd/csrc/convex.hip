@@ -1927,6 +1927,59 @@ __global__ void __launch_bounds__(kBlock) k_assemble_velocity(size_t n, const do
   }
 }
 
+// Body sweep of a VECTOR force per contact (mhip_contact_op_body_sweep_vector): F_c acts on body i, -F_c on body j, at the
+// operator's own lever arms.  The incidence index and the half-edge records are k_body's; of a record only the arm is
+// used (rods: the arclength coefficient, vector arms: r), and it is fetched only for a contact whose force is not zero
+// (a zero row adds +/-0 to sums that start at +0.0: nothing).  G lanes per body, double-double sums in fixed order,
+// and the rows are written as k_body's X_APPLY sweep writes them: (U, W) resp. (U, W x u) and omega for rods.
+template <int KIN, int G>
+__global__ void __launch_bounds__(kBlock) k_body_vector(OpView op, const double* __restrict__ force) {
+  constexpr int HW = (KIN == KIN_RIGID) ? 6 : (KIN == KIN_ROD ? 4 : 3);
+  const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  const int sub = static_cast<int>(t % G);
+  if (t / G >= op.body_count) return;  // (whole groups of G lanes leave together: G divides the wave)
+  const size_t b = op.body_first + t / G;
+  DD3 Fdd{{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}}, Tdd{{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
+  const int32_t beg = op.inc_ptr[b], end = op.inc_ptr[b + 1];
+  for (int32_t k = beg + sub; k < end; k += G) {
+    const int32_t e = op.inc[k];
+    V3 f = load3(force, static_cast<size_t>(e >> 1));
+    if (f.x == 0.0 && f.y == 0.0 && f.z == 0.0) continue;
+    if (e & 1) f = V3{-f.x, -f.y, -f.z};  // side j receives -F_c
+    dd_add(Fdd, f);
+    const double* H = op.half + static_cast<size_t>(k) * HW;
+    if (KIN == KIN_RIGID) dd_add(Tdd, cross(V3{H[3], H[4], H[5]}, f));  // torque r x f
+    if (KIN == KIN_ROD) dd_add(Tdd, H[3] * f);  // S = sum coef f; the torque is u x S
+  }
+#pragma unroll
+  for (int off = G / 2; off > 0; off >>= 1) {
+    dd_add(Fdd.x, dd_shfl_xor(Fdd.x, off));
+    dd_add(Fdd.y, dd_shfl_xor(Fdd.y, off));
+    dd_add(Fdd.z, dd_shfl_xor(Fdd.z, off));
+    if (KIN != KIN_TRANS) {
+      dd_add(Tdd.x, dd_shfl_xor(Tdd.x, off));
+      dd_add(Tdd.y, dd_shfl_xor(Tdd.y, off));
+      dd_add(Tdd.z, dd_shfl_xor(Tdd.z, off));
+    }
+  }
+  if (sub != 0) return;
+  const V3 F = dd_value(Fdd), T = dd_value(Tdd);  // the one rounding of each sum
+  const double mt = op.mt[b], mr = (KIN != KIN_TRANS) ? op.mr[b] : 0.0;
+  V3 W{0.0, 0.0, 0.0};
+  if (KIN == KIN_RIGID) W = V3{mr * T.x, mr * T.y, mr * T.z};
+  if (KIN == KIN_ROD) {
+    const V3 axis = load3(op.axis, b);
+    const V3 tq = cross(axis, T);
+    const V3 w{mr * tq.x, mr * tq.y, mr * tq.z};
+    store3(op.omega, b, w);
+    W = cross(w, axis);  // the row carries Z = W x u
+  }
+  double2* v = reinterpret_cast<double2*>(op.vel + 6 * b);
+  v[0] = make_double2(mt * F.x, mt * F.y);
+  v[1] = make_double2(mt * F.z, W.x);
+  v[2] = make_double2(W.y, W.z);
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // BUILD EXTENSION -- Coulomb friction as a cone complementarity problem (BASELINE configs[2] says "frictional LCP"; the
 // reference has no frictional solver at all, SURVEY F2: parity unpinned, flagged wherever it is exposed).
@@ -3609,6 +3662,23 @@ int mhip_contact_op_body_sweep(mhip_contact_op_t op, const double* x, mhip_strea
   MHIP_REQUIRE(!op->stage.active, MHIP_ERR_RUNTIME, "a staged solve is in progress");
   const Space none{MHIP_SPACE_UNCONSTRAINED, 0, 0};
   return op_launch_body(op, X_APPLY, x, x, nullptr, nullptr, none, as_stream(stream));
+}
+
+// The same rows for a vector force per contact: U_b = m_t sum +/-F_c, W_b = m_r sum arm x (+/-F_c), + on side i and - on
+// side j (a frictional linker force has a tangential part, which no scalar along n carries).  The operator is left as
+// mhip_contact_op_body_sweep leaves it: body_velocity reads the rows.
+int mhip_contact_op_body_sweep_vector(mhip_contact_op_t op, const double* force, mhip_stream_t stream) {
+  MHIP_REQUIRE(op != nullptr, MHIP_ERR_INVALID_ARGUMENT, "operator handle is null");
+  MHIP_REQUIRE(op->view.C == 0 || force, MHIP_ERR_INVALID_ARGUMENT, "force must not be null");
+  MHIP_REQUIRE(!op->stage.active, MHIP_ERR_RUNTIME, "a staged solve is in progress");
+  if (op->view.N == 0 || op->view.body_count == 0) return MHIP_SUCCESS;
+  hipStream_t s = as_stream(stream);
+  op->last_stream = s;
+  constexpr int G = 4;  // lanes per body (the sums do not depend on it)
+  const unsigned grid = grid_exact(op->view.body_count * (size_t)G);
+  with_kin(op, [&](auto kin) { k_body_vector<decltype(kin)::value, G><<<grid, kBlock, 0, s>>>(op->view, force); });
+  MHIP_LAUNCH_CHECK();
+  return MHIP_SUCCESS;
 }
 
 // The constraint sweep of apply alone, on a velocity the caller gives: sep_dot = D^T U.  The operator's own view with

@@ -316,6 +316,71 @@ def hertz_contact_force(pairs, sep, radius, youngs_modulus=1000.0, poisson_ratio
     return f, mx
 
 
+def _finite_nonneg_param(value, name):
+    v = float(value)
+    if not (v >= 0.0 and v < float("inf")):
+        raise ValueError("%s must be finite and >= 0, got %r" % (name, value))
+    return v
+
+
+def hertz_friction_force(pairs, sep, normal, arc_s, arc_t, seg, radius, velocity_prev, tang_disp, mu, dt,
+                         damping=(0.0, 0.0), density=1.0, youngs_modulus=1000.0, poisson_ratio=0.3, out=None,
+                         stats=None):
+    """Frictional Hertzian rod contact per linker with a tangential history (mhip_hertz_friction_force; the reference's
+    SpherocylinderSegmentSpherocylinderSegmentFrictionalHertzianContact.cpp:384-518).  velocity_prev [n, 6] = the
+    previous step's (U, W) rows; tang_disp [C, 3] is updated in place ("j relative to i"); damping = (normal,
+    tangential).  Returns (force [C, 3] on body i -- body j receives its negative, ContactOperator.body_sweep_vector --,
+    stats [2] float64 device tensor: max(0, -sep), and the number of capped contacts as int64 bits: stats.view(int64)[1])."""
+    c, n = pairs.shape[0], radius.shape[0]
+    E, E0 = _material(youngs_modulus, n, "youngs_modulus", 0.0, float("inf"))
+    nu, nu0 = _material(poisson_ratio, n, "poisson_ratio", 0.0, 1.0)
+    prm = capi.HertzFrictionParams(_finite_nonneg_param(mu, "mu"), _finite_nonneg_param(damping[0], "normal damping"),
+                                   _finite_nonneg_param(damping[1], "tangential damping"),
+                                   _finite_nonneg_param(density, "density"), _finite_nonneg_param(dt, "dt"))
+    if tuple(tang_disp.shape) != (c, 3):
+        raise ValueError("tang_disp must have shape [%d, 3], got %s" % (c, tuple(tang_disp.shape)))
+    if tuple(velocity_prev.shape) != (n, 6):
+        raise ValueError("velocity_prev must have shape [%d, 6], got %s" % (n, tuple(velocity_prev.shape)))
+    for name, t in (("sep", sep), ("arc_s", arc_s), ("arc_t", arc_t)):
+        if tuple(t.shape) != (c,):
+            raise ValueError("%s must have shape [%d], got %s" % (name, c, tuple(t.shape)))
+    if tuple(normal.shape) != (c, 3) or tuple(seg.shape) != (n, 8):
+        raise ValueError("normal must have shape [%d, 3] and seg [%d, 8]" % (c, n))
+    f = _new(sep, c, 3) if out is None else out
+    if tuple(f.shape) != (c, 3):
+        raise ValueError("out must have shape [%d, 3], got %s" % (c, tuple(f.shape)))
+    if out is None:
+        f.zero_()  # (rows out of contact are written only where they are not +0.0 already)
+    st = _new(sep, 2) if stats is None else stats
+    capi.check(capi.load().mhip_hertz_friction_force(
+        c, n, _ptr(pairs, torch.int32, 2, name="pairs"), _ptr(sep, name="sep"), _ptr(normal, cols=3, name="normal"),
+        _ptr(arc_s, name="arc_s"), _ptr(arc_t, name="arc_t"), _ptr(seg, cols=8, name="seg"), _ptr(radius, name="radius"),
+        _ptr(E, allow_none=True, name="youngs_modulus"), E0, _ptr(nu, allow_none=True, name="poisson_ratio"), nu0,
+        _ptr(velocity_prev, cols=6, name="velocity_prev"), C.byref(prm), _ptr(tang_disp, cols=3, name="tang_disp"),
+        _ptr(f, cols=3, name="out"), _ptr(st, name="stats"), _stream()))
+    return f, st
+
+
+def carry_contact_history(pairs_old, hist_old, pairs_new, new_of_old=None, want_count=False):
+    """history rows [C_old, 3] of the pairs of one contact list -> rows [C_new, 3] of the next: a new pair (i, j) receives
+    the row of the old pair whose endpoints, renumbered through new_of_old [n_old] int32 (None: unchanged numbering, and
+    the old list must be the broad phase's canonical sorted one), are {i, j}, negated if the orientation came out
+    swapped; every other new pair +0.0 (mhip_contact_history_carry).  want_count: returns (rows, carried).  Synchronises
+    when want_count or new_of_old is None; an unrenumbered old list that does not ascend strictly raises ValueError."""
+    c_old, c_new = pairs_old.shape[0], pairs_new.shape[0]
+    if tuple(hist_old.shape) != (c_old, 3):
+        raise ValueError("hist_old must have shape [%d, 3], got %s" % (c_old, tuple(hist_old.shape)))
+    out = _new(hist_old, c_new, 3)
+    n_old = 0 if new_of_old is None else new_of_old.shape[0]
+    k = C.c_size_t(0)
+    capi.check(capi.load().mhip_contact_history_carry(
+        c_old, _ptr(pairs_old, torch.int32, 2, name="pairs_old"), _ptr(hist_old, cols=3, name="hist_old"),
+        _ptr(new_of_old, torch.int32, allow_none=True, name="new_of_old"), n_old, c_new,
+        _ptr(pairs_new, torch.int32, 2, name="pairs_new"), _ptr(out, cols=3, name="hist_new"),
+        C.byref(k) if want_count else None, _stream()))
+    return (out, int(k.value)) if want_count else out
+
+
 # ---- broad phase (GenNeighborLinks, mundy_mesh/GenNeighborLinkers.hpp:294-866) ---------------------------------------
 class GenNeighborLinks:
     """Builder-style mirror of mundy::mesh::GenNeighborLinks: set_* -> concretize() -> generate().
@@ -636,6 +701,14 @@ class ContactOperator:
         if tuple(x.shape) != (self.num_constraints,):
             raise ValueError("x must have shape [%d], got %s" % (self.num_constraints, tuple(x.shape)))
         capi.check(capi.load().mhip_contact_op_body_sweep(self._h, _ptr(x, name="x"), _stream()))
+
+    def body_sweep_vector(self, force):
+        """the velocity rows (U, W) of a vector force per contact, force [C, 3]: body i gets +F_c, body j -F_c, at the
+        operator's lever arms (mhip_contact_op_body_sweep_vector); body_velocity() reads them.
+        body_sweep_vector(-x[:, None] * n) gives the rows of body_sweep(x) bit for bit."""
+        if tuple(force.shape) != (self.num_constraints, 3):
+            raise ValueError("force must have shape [%d, 3], got %s" % (self.num_constraints, tuple(force.shape)))
+        capi.check(capi.load().mhip_contact_op_body_sweep_vector(self._h, _ptr(force, name="force"), _stream()))
 
     def constraint_rate(self, velocity, out=None):
         """sep_dot [C] = D^T U of a velocity [N, 6] (U, W): n_c . [(U_j + W_j x rb) - (U_i + W_i x ra)] with this

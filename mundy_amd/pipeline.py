@@ -27,6 +27,14 @@ springs= / brownian_kt= add the bead-spring chain step of the chromatin app (sph
         -> contacts, q = sep + dt D^T U_ext (ContactOperator.constraint_rate) -> solve (or Hertz f)
         -> U = U_ext + M D lambda -> Euler update
 
+hertz_friction= replaces the frictionless Hertz force by the reference's frictional rod contact with a per-pair
+tangential history (SpherocylinderSegmentSpherocylinderSegmentFrictionalHertzianContact.cpp:384-518, run every step by
+CollidingOverdampedFrictionalSperm.cpp:1553-1731):
+
+    ... -> broad phase (on a rebuild: the history is carried to the new list) -> contacts
+        -> frictional force per linker from the previous step's body velocities (a vector per contact)
+        -> operator build / refresh -> body_sweep_vector -> U = M D F (+ U_ext = M F_ext) -> Euler update
+
 Everything is device resident; host logic here only sequences library calls.
 """
 import math
@@ -50,6 +58,7 @@ class StepStats:
     max_overlap: float = 0.0  # contact_model="hertz": max(0, -sep) over the step's contacts (what dt is chosen from)
     num_born: int = 0  # growth mode: bodies that divided this step (their children are rows n_before + k)
     max_spring_length: float = 0.0  # springs=: the longest spring at the start of the step
+    num_sliding: int = 0  # hertz_friction=: contacts whose tangential force was capped at mu |F_n| this step
 
 
 class ContactStepper:
@@ -60,7 +69,8 @@ class ContactStepper:
                  mob_rot=None, rod_kinematics=True, kinds=None, shape=None, friction=None, contact_cutoff=None,
                  conservative_ellipsoid_box=False, friction_method="apgd", contact_model="lcp", youngs_modulus=1000.0,
                  poisson_ratio=0.3, growth_rate=None, division_length=None, capacity=None, ids=None, springs=None,
-                 brownian_kt=None, rng_keys=None, rng_counter=None):
+                 brownian_kt=None, rng_keys=None, rng_counter=None, hertz_friction=None, hertz_damping=(0.0, 0.0),
+                 hertz_density=1.0):
         """kind = "sphere" | "spherocylinder" | "mixed".  Mixed systems (BASELINE configs[4]) pass kinds [n] int32
         (0 sphere, 1 spherocylinder, 2 ellipsoid) and shape [n, 3] = (r,-,-) / (r,L,-) / (r1,r2,r3) instead of
         radius / length.
@@ -77,7 +87,13 @@ class ContactStepper:
         growth, friction or cutoff; springs take no periodic box).  r is the rest length (Hookean) or r_max (FENE); k and
         r numbers or per-spring arrays.  rng_keys (integers in [0, 2^63), default arange(n)) and rng_counter (default
         0) key the Philox stream of each body; the counters advance by one per step.  step(external_force=) adds a
-        per-step [n, 3] force to the spring force."""
+        per-step [n, 3] force to the spring force.
+        hertz_friction = mu >= 0 (None = off): the reference's frictional Hertzian rod contact with a tangential history
+        per pair; needs contact_model="hertz", kind="spherocylinder" and rod_kinematics=True (free space or an
+        orthorhombic box; no growth, springs or noise).  hertz_damping = (normal, tangential) >= 0 and hertz_density >= 0
+        (the sphere mass of the rod radius weighs the damping) default to the reference's values.  The stepper then
+        owns prev_velocity [n, 6] (zero before the first step) and tang_disp [C, 3] with the pair list it belongs to;
+        step(external_force=) adds U_ext = (m_t F, 0) to the contact velocity."""
         if kind not in ("sphere", "spherocylinder", "mixed"):
             raise ValueError("kind must be 'sphere', 'spherocylinder' or 'mixed'")
         if contact_model not in ("lcp", "hertz"):
@@ -94,6 +110,15 @@ class ContactStepper:
             ops._material(youngs_modulus, center.shape[0], "youngs_modulus", 0.0, float("inf"))
             ops._material(poisson_ratio, center.shape[0], "poisson_ratio", 0.0, 1.0)
         self.youngs_modulus, self.poisson_ratio = youngs_modulus, poisson_ratio
+        self.hertz_friction = None
+        if hertz_friction is not None:  # (checked before anything reaches the device)
+            self._check_hertz_friction(contact_model, kind, rod_kinematics, growth_rate, springs, brownian_kt,
+                                       periodic_box, hertz_friction, hertz_damping, hertz_density)
+            self.hertz_friction = float(hertz_friction)
+            self.hertz_damping = (float(hertz_damping[0]), float(hertz_damping[1]))
+            self.hertz_density = float(hertz_density)
+        elif hertz_damping not in ((0.0, 0.0), [0.0, 0.0]) or hertz_density != 1.0:
+            raise ValueError("hertz_damping and hertz_density belong to the frictional Hertz contact: pass hertz_friction")
         self.growth = growth_rate is not None
         if self.growth:  # (checked before anything reaches the device)
             self._check_growth(kind, search_kind, friction, contact_cutoff, warm_start, growth_rate, division_length,
@@ -169,6 +194,81 @@ class ContactStepper:
         self.springs = self.rng_keys = self.rng_counter = None
         if self.chain:
             self._init_chain(*chain_spec)
+        if self.hertz_friction is not None:
+            self._init_hertz_friction()
+
+    # -- frictional Hertz contact (FrictionalHertzianContact.cpp:384-518) -------------------------------------------------
+    @staticmethod
+    def _check_hertz_friction(contact_model, kind, rod_kinematics, growth_rate, springs, kt, box, mu, damping, density):
+        if contact_model != "hertz":
+            raise ValueError("hertz_friction needs contact_model='hertz'")
+        if kind != "spherocylinder":
+            raise ValueError("hertz_friction is the reference's rod-rod kernel: kind must be 'spherocylinder', not %r"
+                             % kind)
+        if not rod_kinematics:
+            raise ValueError("hertz_friction needs rod_kinematics=True (the arclength form of the contact points)")
+        if growth_rate is not None:
+            raise ValueError("hertz_friction does not run in growth mode")
+        if springs is not None or kt is not None:
+            raise ValueError("hertz_friction takes no springs or brownian_kt")
+        if box is not None:
+            import numpy as np
+            if np.asarray(box.cpu() if isinstance(box, torch.Tensor) else box).size != 3:
+                raise ValueError("hertz_friction takes an orthorhombic periodic box (3 edge lengths)")
+        if not isinstance(damping, (tuple, list)) or len(damping) != 2:
+            raise ValueError("hertz_damping must be (normal, tangential)")
+        for name, v in (("hertz_friction", mu), ("hertz_damping[0]", damping[0]), ("hertz_damping[1]", damping[1]),
+                        ("hertz_density", density)):
+            v = float(v)
+            if not (v >= 0.0 and v < math.inf):
+                raise ValueError("%s must be finite and >= 0, got %r" % (name, v))
+
+    def _init_hertz_friction(self):
+        n, dev = self.center.shape[0], self.center.device
+        self.prev_velocity = torch.zeros((n, 6), dtype=torch.float64, device=dev)  # the reference's StateN field
+        self.tang_disp = None      # [C, 3], "j relative to i", rows of hist_pairs
+        self.hist_pairs = None     # the pair list tang_disp belongs to
+        self.contact_force = None  # [C, 3], on body i
+        self._renumber = None      # reorder_bodies since the last carry: new index of every old body (int32)
+        self._fr_stats = torch.zeros(2, dtype=torch.float64, device=dev)  # (max_overlap, num_sliding as int64 bits)
+        self._fr_u_ext = None
+        self._fr_has_ext = False
+        self.last_carried = 0      # new pairs that found their old history row at the last carry
+        self.velocity = None
+
+    def _carry_history(self):
+        """tang_disp follows the neighbour list: after a rebuild, a renumbering or a restore every pair of the new list
+        receives the row of the same pair of the old one, every other pair +0.0"""
+        pairs = self.links.pairs
+        if self.hist_pairs is pairs and self._renumber is None:
+            return
+        dev = self.center.device
+        if self.tang_disp is None:
+            self.tang_disp = torch.zeros((pairs.shape[0], 3), dtype=torch.float64, device=dev)
+            self.last_carried = 0
+        else:
+            self.tang_disp, self.last_carried = ops.carry_contact_history(self.hist_pairs, self.tang_disp, pairs,
+                                                                          new_of_old=self._renumber, want_count=True)
+        self._renumber = None
+        self.hist_pairs = pairs
+        self.contact_force = torch.zeros((pairs.shape[0], 3), dtype=torch.float64, device=dev)
+
+    def _hertz_friction(self, rebuilt, mark):
+        """frictional soft contact: per-linker force vector from the previous step's velocities and the history, then the
+        operator's vector body sweep -- U = M D F (no solve)"""
+        self._carry_history()
+        mark("history_carry")
+        c, pairs = self.contacts, self.links.pairs
+        ops.hertz_friction_force(pairs, c["sep"], c["normal"], c["s"], c["t"], self.seg, self.radius, self.prev_velocity,
+                                 self.tang_disp, self.hertz_friction, self.dt, damping=self.hertz_damping,
+                                 density=self.hertz_density, youngs_modulus=self.youngs_modulus,
+                                 poisson_ratio=self.poisson_ratio, out=self.contact_force, stats=self._fr_stats)
+        mark("hertz_force")
+        self._hertz_operator(rebuilt)
+        mark("operator")
+        self.op.body_sweep_vector(self.contact_force)
+        mark("body_sweep")
+        return ops.SolveResult(num_iters=0, residual=0.0, converged=True)
 
     # -- bead-spring chains with thermal noise (NgpHP1.cpp:3802-3990) ----------------------------------------------------
     @staticmethod
@@ -370,7 +470,11 @@ class ContactStepper:
             snap = {k: getattr(self, k).clone() for k in self._per_body()}
             snap["_n"], snap["_next_id"] = self.n, self.next_id
             return snap
-        return {k: getattr(self, k).clone() for k in self._BODY_ARRAYS if getattr(self, k, None) is not None}
+        snap = {k: getattr(self, k).clone() for k in self._BODY_ARRAYS if getattr(self, k, None) is not None}
+        if self.hertz_friction is not None:  # the history, the list it belongs to and the previous velocities
+            snap["_fr"] = (self.prev_velocity.clone(), None if self.tang_disp is None else self.tang_disp.clone(),
+                           self.hist_pairs, self._renumber)
+        return snap
 
     def restore(self, snap):
         if self.growth:
@@ -382,6 +486,12 @@ class ContactStepper:
             self._forget_numbering()
             return
         for k, v in snap.items():
+            if k == "_fr":
+                self.prev_velocity.copy_(v[0])
+                # (a clone: the stepper updates its history in place, and the next step carries it to the list in use)
+                self.tang_disp = None if v[1] is None else v[1].clone()
+                self.hist_pairs, self._renumber = (None if v[1] is None else v[2].clone()), v[3]
+                continue
             getattr(self, k).copy_(v)
 
     def _forget_numbering(self):
@@ -420,6 +530,11 @@ class ContactStepper:
                 t.copy_(ops.gather_rows(perm, t) if t.dtype == torch.float64 else t[perm.long()])
         if getattr(self, "springs", None) is not None:
             self._renumber_springs(perm)
+        if self.hertz_friction is not None:  # previous velocities move with their rows, the history through the inverse
+            self.prev_velocity = ops.gather_rows(perm, self.prev_velocity)
+            inv = torch.empty_like(perm)
+            inv[perm.long()] = torch.arange(perm.shape[0], dtype=perm.dtype, device=perm.device)
+            self._renumber = inv if self._renumber is None else inv[self._renumber.long()].contiguous()
         # the neighbour list, the operator's incidence index and the multipliers are in the old numbering: a reused list
         # would pair the wrong bodies unless the displacement test happened to fire, so force the rebuild
         self._forget_numbering()
@@ -487,6 +602,8 @@ class ContactStepper:
     def resolve_collisions(self, rebuilt):
         if self.contact_model == "hertz":
             self.contact_pairs = self.links.pairs
+            if self.hertz_friction is not None:
+                return self._hertz_friction(rebuilt, lambda name: None)
             return self._hertz(rebuilt, lambda name: None)
         if self.contact_cutoff is not None and self.friction is None:
             self.full_contacts = self.contacts
@@ -557,7 +674,15 @@ class ContactStepper:
                                                              self.youngs_modulus, self.poisson_ratio,
                                                              max_overlap=self._chain_stats[0:1] if self.chain else None)
         mark("hertz_force")
-        # the operator follows the neighbour list: built on a rebuild, its geometry refreshed otherwise
+        self._hertz_operator(rebuilt)
+        mark("operator")
+        self.op.body_sweep(self.lam)
+        mark("body_sweep")
+        return ops.SolveResult(num_iters=0, residual=0.0, converged=True)
+
+    def _hertz_operator(self, rebuilt):
+        """the operator follows the neighbour list: built on a rebuild, its geometry refreshed otherwise"""
+        c, pairs = self.contacts, self.links.pairs
         reuse = not rebuilt and self.op is not None and self.op.num_constraints == pairs.shape[0]
         if self.op is not None and not reuse:
             self.op.close()
@@ -572,16 +697,17 @@ class ContactStepper:
         else:
             self.op = ops.ContactOperator(pairs, c["normal"], self.mob_trans, self.dt, ra=c.get("ra"), rb=c.get("rb"),
                                           mob_rot=self.mob_rot, priority=c["sep"])
-        mark("operator")
-        self.op.body_sweep(self.lam)
-        mark("body_sweep")
-        return ops.SolveResult(num_iters=0, residual=0.0, converged=True)
 
     def integrate(self):
         vel = self.op.body_velocity()
         if self.chain:  # U = U_ext + U_contact
             ops.axpby(1.0, self.u_ext.view(-1), 1.0, vel.view(-1))
             self.velocity = vel
+        if self.hertz_friction is not None:  # U = U_contact (+ U_ext); the next step's previous velocity
+            if self._fr_has_ext:  # the U_ext of this step(external_force=) only: consumed here
+                ops.axpby(1.0, self._fr_u_ext.view(-1), 1.0, vel.view(-1))
+                self._fr_has_ext = False
+            self.prev_velocity = self.velocity = vel
         ops.integrate_euler(self.dt, vel, self.center, self.quat)
         if self.box is not None:
             # wrap_rigid_inplace of a Sphere / Spherocylinder / Ellipsoid: the centre goes back into the box,
@@ -591,7 +717,7 @@ class ContactStepper:
     # -- one timestep -------------------------------------------------------------------------------------------------
     def step(self, integrate=True, force_rebuild=False, timed=False, external_force=None):
         if external_force is not None:
-            if not self.chain:
+            if not self.chain and self.hertz_friction is None:
                 raise ValueError("external_force belongs to the chain step: pass springs= or brownian_kt= (0.0: no noise)")
             if tuple(external_force.shape) != (self.center.shape[0], 3):
                 raise ValueError("external_force must have shape [%d, 3], got %s" % (self.center.shape[0],
@@ -620,10 +746,14 @@ class ContactStepper:
         if self.chain:
             self.external_velocity(external_force)
             mark("springs_brownian")
+        elif self.hertz_friction is not None:
+            self._fr_has_ext = external_force is not None
+            if self._fr_has_ext:  # U_ext = (m_t F, 0)
+                self._fr_u_ext = ops.drag_velocity(self.mob_trans, external_force, out=self._fr_u_ext)
         self.compute_contacts()
         mark("narrowphase")
-        if self.contact_model == "hertz":  # (stages: hertz_force, operator, body_sweep)
-            res = self._hertz(st.rebuilt, mark)
+        if self.contact_model == "hertz":  # (stages: [history_carry,] hertz_force, operator, body_sweep)
+            res = (self._hertz if self.hertz_friction is None else self._hertz_friction)(st.rebuilt, mark)
             self.contact_pairs = self.links.pairs
         else:
             res = self.resolve_collisions(st.rebuilt)
@@ -639,6 +769,9 @@ class ContactStepper:
             over = int(h.view(torch.int32)[4])
             if over:
                 raise RuntimeError("%d FENE spring(s) stretched to L >= r_max: no force (reduce dt)" % over)
+        elif self.hertz_friction is not None:  # the one read of the step: (max_overlap, num_sliding)
+            h = self._fr_stats.cpu()
+            st.max_overlap, st.num_sliding = float(h[0]), int(h.view(torch.int64)[1])
         elif self.contact_model == "hertz":
             st.max_overlap = float(self.max_overlap.item())
         if timed:
