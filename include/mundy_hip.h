@@ -272,6 +272,64 @@ int mhip_brownian_velocity(size_t n, const uint64_t* keys, uint64_t* counters /*
 int mhip_drag_velocity(size_t n, const double* mob_trans, const double* force, double* velocity /*[n][6]*/,
                        mhip_stream_t stream);
 
+/* Crosslinkers that bind and unbind: the kinetic Monte Carlo stage of the HP1 app (scrap/.../HP1.cpp:4728-4739 in the
+ * step; :3264-3438 rates, :3440-3594 sampling, :3597-3748 state changes; NgpHP1.cpp:1830-2137 the same over a
+ * per-crosslinker list of bind sites), which the reference runs serially on the host in an STK modification cycle.
+ * m crosslinkers over n bodies.  Crosslinker c has a fixed left head at body left[c] and a right head at right[c];
+ * right[c] == left[c] means singly bound (as the reference represents it).  Several crosslinkers may bind one site.
+ * While doubly bound, c is the spring (left[c], right[c]) of mhip_springs_force, type / k / r as there (the library's
+ * FENE sign).  DESIGN.md 5f states the model and its deviations.
+ *   binding rate of a singly bound c to site s, d = |x_s - x_left| (right-fold norm), inv_kt = 1 / kt:
+ *     HOOKEAN  A exp(-0.5 inv_kt k (d - r0) (d - r0))                      (HP1.cpp:3320, its association)
+ *     FENE     d < r_max: A pow(1 - (d / r_max) (d / r_max), 0.5 inv_kt k r_max r_max), else 0   (:3332-3334)
+ *     s == left[c] is skipped (:3298-3306); d > capture_radius has rate 0 exactly, whatever the candidate list holds
+ *   one uniform per crosslinker and step: u = ((w0 << 21) | (w1 >> 11)) 2^-53 from block 0 of Philox at
+ *     (keys[c], counters[c]); counters[c] += 1 whatever the state (:3487-3491, :3560-3565)
+ *   singly bound: z_tot = sum of dt rate_s over the candidate row of left[c], left to right from +0.0; binds iff
+ *     u < 1 - exp(-z_tot), to the first site whose running sum of (1 - exp(-z_tot)) dt / z_tot rate_s exceeds u
+ *     (:3504-3527); z_tot == 0 never binds
+ *   doubly bound: unbinds iff u < 1 - exp(-(dt k_off)) (what :3554-3573 reduces to); then right[c] = left[c]
+ *   both populations are sampled from the state at the start of the step (:3757-3764).
+ * create [host arrays; right NULL = all singly bound; is_site [n] bytes, NULL = every body is a bind site] refuses
+ *   (MHIP_ERR_INVALID_ARGUMENT, before any HIP call) an index outside [0, n), a right head that is neither left[c] nor a
+ *   bind site, an unknown type, k < 0, r0 < 0, r_max <= 0, bind_rate (A) < 0, unbind_rate (k_off) < 0, kt <= 0,
+ *   capture_radius <= 0 and anything not finite; it builds both body -> crosslinker incidences on the device and
+ *   synchronises `stream`.
+ * set_candidates: the bind sites each body's crosslinkers may reach, as the CSR (row_ptr [n + 1], col [num_entries]) of a
+ *   neighbour search that lists at least every site within capture_radius (mhip_broadphase_get_pairs); copied, and
+ *   every row sorted by ids[col] (int64 [n]; NULL = by col) ONCE here: the order a crosslinker walks its candidates in
+ *   (the reference walks its connected linkers, :3473, :3510).  With ids that survive a renumbering of the bodies, a
+ *   step is bit-identical after it.
+ * kmc_step: one step of the above at the positions `center`; events [device, 2 ints] = (binds, unbinds) of this step
+ *   (the perform_state_change passes :3597-3748 without a modification cycle); the incidence of the right ends is
+ *   rebuilt on the device.  z_total [m] (optional) receives z_tot of every singly bound crosslinker (0 for a doubly
+ *   bound one): what a test compares the rates through.  MHIP_ERR_RUNTIME without candidates.  No synchronisation.
+ * force: every doubly bound crosslinker as its spring; each body adds its terms in ascending crosslinker index from
+ *   +0.0 (no atomics on forces; the two ends receive exactly negated vectors) and the sum is written to force [n][3]
+ *   (accumulate = 0) or added to it (accumulate = 1).  *overstretched / *max_length [device] as mhip_springs_force.
+ *   (compute_hookean_spring_forces / compute_fene_spring_forces over the doubly bound part, :4736-4739)
+ * get_state / set_state: left and right [m] int32 device arrays out of / into the handle (get: NULL skips; set: left
+ *   NULL = unchanged; indices are not checked), the incidences rebuilt.
+ * renumber: the bodies were permuted; new_of_old [n] int32 = the new index of every old body.  Crosslinker indices do
+ *   not change.  The candidates are dropped (set_candidates again). */
+typedef struct mhip_crosslinkers* mhip_crosslinkers_t;
+int mhip_crosslinkers_create(mhip_crosslinkers_t* handle, size_t n, size_t m, const int32_t* left /*[host] m*/,
+                             const int32_t* right /*[host] m or NULL*/, const unsigned char* is_site /*[host] n or NULL*/,
+                             int type, double k, double r, double bind_rate, double unbind_rate, double kt,
+                             double capture_radius, mhip_stream_t stream);
+int mhip_crosslinkers_set_candidates(mhip_crosslinkers_t handle, const int32_t* row_ptr, const int32_t* col,
+                                     size_t num_entries, const int64_t* ids, mhip_stream_t stream);
+int mhip_crosslinkers_kmc_step(mhip_crosslinkers_t handle, const double* center, double dt, const uint64_t* keys,
+                               uint64_t* counters /*in/out*/, int* events /*[device] 2*/,
+                               double* z_total /*[device] m or NULL*/, mhip_stream_t stream);
+int mhip_crosslinkers_force(mhip_crosslinkers_t handle, const double* center, double* force, int accumulate,
+                            int* overstretched /*[device]*/, double* max_length /*[device]*/, mhip_stream_t stream);
+int mhip_crosslinkers_get_state(mhip_crosslinkers_t handle, int32_t* left, int32_t* right, mhip_stream_t stream);
+int mhip_crosslinkers_set_state(mhip_crosslinkers_t handle, const int32_t* left, const int32_t* right,
+                                mhip_stream_t stream);
+int mhip_crosslinkers_renumber(mhip_crosslinkers_t handle, const int32_t* new_of_old, mhip_stream_t stream);
+int mhip_crosslinkers_destroy(mhip_crosslinkers_t handle);
+
 /* Mixed shapes (BASELINE configs[4]): kind[n] = 0 sphere, 1 spherocylinder, 2 ellipsoid; shape[n][3] = (r,-,-) /
  * (r,L,-) / (r1,r2,r3); quat is ignored for spheres.  compute_aabb dispatches on kind (compute_aabb.hpp:72-127) and
  * also returns the bounding radii (compute_bounding_radius.hpp:61-93).  contact_mixed bins the pairs by shape class and

@@ -114,6 +114,14 @@ SIGNATURES = {
     "mhip_springs_create": [C.POINTER(_vp), _sz, _sz, _vp, _i, _vp, _d, _vp, _d, _vp],
     "mhip_springs_force": [_vp, _vp, _vp, _vp, _vp, _vp],
     "mhip_springs_destroy": [_vp],
+    "mhip_crosslinkers_create": [C.POINTER(_vp), _sz, _sz, _vp, _vp, _vp, _i, _d, _d, _d, _d, _d, _d, _vp],
+    "mhip_crosslinkers_set_candidates": [_vp, _vp, _vp, _sz, _vp, _vp],
+    "mhip_crosslinkers_kmc_step": [_vp, _vp, _d, _vp, _vp, _vp, _vp, _vp],
+    "mhip_crosslinkers_force": [_vp, _vp, _vp, _i, _vp, _vp, _vp],
+    "mhip_crosslinkers_get_state": [_vp, _vp, _vp, _vp],
+    "mhip_crosslinkers_set_state": [_vp, _vp, _vp, _vp],
+    "mhip_crosslinkers_renumber": [_vp, _vp, _vp],
+    "mhip_crosslinkers_destroy": [_vp],
     "mhip_philox4x32_10": [_sz, _vp, _vp, C.c_uint32, _vp, _vp],
     "mhip_brownian_velocity": [_sz, _vp, _vp, _d, _d, _vp, _vp, _vp],
     "mhip_drag_velocity": [_sz, _vp, _vp, _vp, _vp],

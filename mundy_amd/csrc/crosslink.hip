@@ -1,0 +1,459 @@
+// crosslink.hip -- crosslinkers that bind and unbind: the kinetic Monte Carlo stage of the reference's HP1 app
+// (scrap/.../HP1.cpp:3264-3438 rates, :3440-3594 sampling, :3597-3748 state changes, :4728-4739 place in the step;
+// NgpHP1.cpp:1830-2137 the same over a per-crosslinker list of bind sites), which the reference runs serially on the
+// host inside an STK modification cycle.  Here the spring set changes on the device:
+//   candidate rows   the CSR of a neighbour search (sources: beads with a crosslinker, targets: bind sites), each row
+//                    sorted by original body id once per list build
+//   KMC              one lane per crosslinker: one Philox uniform, two passes over the left bead's row (total rate, then
+//                    the running sum that picks the site), nothing stored per candidate
+//   incidence        body -> crosslinker lists of the left ends (static) and of the right ends of the doubly bound ones
+//                    (rebuilt after every KMC step: count, scan, fill, per-body sort)
+//   force            one lane per body, its left and right lists merged in ascending crosslinker index, no atomics
+// All of it gathers a few rows per lane: bound by the latency of those gathers.
+#include "mhip_internal.hpp"
+#include "chain_device.hpp"
+
+#include <cmath>
+
+namespace mhip {
+
+struct XlParams {
+  double k, r, A, k_off, inv_kt, cap;
+};
+
+// binding rate of a singly bound crosslinker to a site at distance d (HP1.cpp:3320, :3332-3334, their association)
+template <int TYPE>
+__device__ inline double xl_rate(double d, const XlParams& p) {
+  if (TYPE == MHIP_SPRING_HOOKEAN) return p.A * exp(-0.5 * p.inv_kt * p.k * (d - p.r) * (d - p.r));
+  return d < p.r ? p.A * pow(1.0 - (d / p.r) * (d / p.r), 0.5 * p.inv_kt * p.k * p.r * p.r) : 0.0;
+}
+
+// ---- candidate rows: sorted by original body id when the list is built ---------------------------------------------
+__global__ void __launch_bounds__(kBlock) k_xl_entry_keys(size_t entries, const int32_t* __restrict__ col,
+                                                         const int64_t* __restrict__ ids, int64_t* __restrict__ key) {
+  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < entries; e += (size_t)gridDim.x * blockDim.x)
+    key[e] = ids ? ids[col[e]] : static_cast<int64_t>(col[e]);
+}
+// one row per lane, insertion sort of (key, col): rows hold the bind sites within reach of one bead (tens)
+__global__ void __launch_bounds__(kBlock) k_xl_row_sort(size_t n, const int32_t* __restrict__ ptr,
+                                                       int64_t* __restrict__ key, int32_t* __restrict__ col) {
+  for (size_t b = blockIdx.x * (size_t)blockDim.x + threadIdx.x; b < n; b += (size_t)gridDim.x * blockDim.x) {
+    const int32_t lo = ptr[b], hi = ptr[b + 1];
+    for (int32_t a = lo + 1; a < hi; ++a) {
+      const int64_t kv = key[a];
+      const int32_t cv = col[a];
+      int32_t j = a - 1;
+      while (j >= lo && (key[j] > kv || (key[j] == kv && col[j] > cv))) {
+        key[j + 1] = key[j];
+        col[j + 1] = col[j];
+        --j;
+      }
+      key[j + 1] = kv;
+      col[j + 1] = cv;
+    }
+  }
+}
+
+// ---- KMC: one lane per crosslinker ---------------------------------------------------------------------------------
+// u = ((w0 << 21) | (w1 >> 11)) 2^-53 from block 0 at (key, counter); the counter advances whatever the state
+// (HP1.cpp:3487-3491, :3560-3565).  Every lane reads and writes the state of its own crosslinker only and the rates do
+// not depend on the other crosslinkers (no site exclusivity in the reference), so sampling from the state at the start
+// of the step and applying afterwards (:3757-3764) is what the in-place update computes.
+template <int TYPE>
+__global__ void __launch_bounds__(kBlock)
+    k_xl_kmc(size_t m, const int32_t* __restrict__ left, int32_t* __restrict__ right, const int32_t* __restrict__ ptr,
+             const int32_t* __restrict__ col, const double* __restrict__ center, const uint64_t* __restrict__ keys,
+             uint64_t* __restrict__ ctrs, XlParams p, double dt, int* __restrict__ events,
+             double* __restrict__ z_out) {
+  int binds = 0, unbinds = 0;
+  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
+    const uint64_t ctr = ctrs[c];
+    const uint4 w = philox_draw(keys[c], ctr, 0u);
+    ctrs[c] = ctr + 1;
+    const double u =
+        static_cast<double>((static_cast<uint64_t>(w.x) << 21) | static_cast<uint64_t>(w.y >> 11)) * 0x1p-53;
+    const int32_t l = left[c];
+    if (right[c] != l) {  // doubly bound: what HP1.cpp:3554-3573 reduces to
+      if (u < 1.0 - exp(-(dt * p.k_off))) {
+        right[c] = l;
+        ++unbinds;
+      }
+      if (z_out) z_out[c] = 0.0;
+      continue;
+    }
+    const V3 xl = load3(center, l);
+    const int32_t lo = ptr[l], hi = ptr[l + 1];
+    double z_tot = 0.0;
+    for (int32_t e = lo; e < hi; ++e) {
+      const int32_t s = col[e];
+      if (s == l) continue;  // the self site (HP1.cpp:3298-3306)
+      const double d = norm(load3(center, s) - xl);
+      if (!(d <= p.cap)) continue;  // beyond the capture radius: rate 0 exactly, whatever the list still holds
+      z_tot += dt * xl_rate<TYPE>(d, p);
+    }
+    if (z_out) z_out[c] = z_tot;
+    const double p_bind = 1.0 - exp(-z_tot);
+    if (!(u < p_bind)) continue;  // (z_tot = 0: p_bind = 0, never)
+    const double scale = p_bind * dt / z_tot;
+    double cumsum = 0.0;
+    for (int32_t e = lo; e < hi; ++e) {
+      const int32_t s = col[e];
+      if (s == l) continue;
+      const double d = norm(load3(center, s) - xl);
+      if (!(d <= p.cap)) continue;
+      cumsum += scale * xl_rate<TYPE>(d, p);
+      if (u < cumsum) {  // HP1.cpp:3518-3527
+        right[c] = s;
+        ++binds;
+        break;
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    binds += __shfl_xor(binds, off, 64);
+    unbinds += __shfl_xor(unbinds, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (binds) atomicAdd(&events[0], binds);
+    if (unbinds) atomicAdd(&events[1], unbinds);
+  }
+}
+
+// ---- body -> crosslinker incidence ---------------------------------------------------------------------------------
+// crosslinker c is listed at body at[c]; with `other`, only where at[c] != other[c] (the right ends of the doubly bound)
+__global__ void __launch_bounds__(kBlock) k_xl_count(size_t m, const int32_t* __restrict__ at,
+                                                    const int32_t* __restrict__ other, int32_t* __restrict__ deg) {
+  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
+    const int32_t b = at[c];
+    if (!other || other[c] != b) atomicAdd(&deg[b], 1);
+  }
+}
+__global__ void __launch_bounds__(kBlock) k_xl_fill(size_t m, const int32_t* __restrict__ at,
+                                                   const int32_t* __restrict__ other, const int32_t* __restrict__ ptr,
+                                                   int32_t* __restrict__ cursor, int32_t* __restrict__ ent) {
+  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
+    const int32_t b = at[c];
+    if (!other || other[c] != b) ent[ptr[b] + atomicAdd(&cursor[b], 1)] = static_cast<int32_t>(c);
+  }
+}
+__global__ void __launch_bounds__(kBlock) k_xl_renumber(size_t m, const int32_t* __restrict__ new_of_old,
+                                                       int32_t* __restrict__ left, int32_t* __restrict__ right) {
+  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
+    left[c] = new_of_old[left[c]];
+    right[c] = new_of_old[right[c]];
+  }
+}
+
+// ---- force: one body per lane ----------------------------------------------------------------------------------------
+// The body's left list (crosslinkers anchored here, doubly bound or not) and right list (doubly bound ones whose right
+// head sits here) are merged in ascending crosslinker index.  A doubly bound crosslinker is the spring (left, right) of
+// mhip_springs_force: d = x_right - x_left, L, fm and fm d in the same operations at both ends, + at the left end and -
+// at the right, summed from +0.0.  Its statistics are taken at the left end only.
+template <int TYPE, bool ACCUMULATE>
+__global__ void __launch_bounds__(kBlock)
+    k_xl_force(size_t n, const int32_t* __restrict__ lptr, const int32_t* __restrict__ lent,
+               const int32_t* __restrict__ rptr, const int32_t* __restrict__ rent, const int32_t* __restrict__ left,
+               const int32_t* __restrict__ right, const double* __restrict__ center, double k, double r,
+               double* __restrict__ force, int* __restrict__ overstretched,
+               unsigned long long* __restrict__ max_length_bits) {
+  double lmax = 0.0;
+  for (size_t b = blockIdx.x * (size_t)blockDim.x + threadIdx.x; b < n; b += (size_t)gridDim.x * blockDim.x) {
+    double fx = 0.0, fy = 0.0, fz = 0.0;
+    int32_t a = lptr[b], e = rptr[b];
+    const int32_t ae = lptr[b + 1], ee = rptr[b + 1];
+    while (a < ae || e < ee) {
+      const int32_t ca = a < ae ? lent[a] : 0x7fffffff;
+      const int32_t ce = e < ee ? rent[e] : 0x7fffffff;
+      const bool at_left = ca < ce;  // (never equal: a crosslinker in the right list has right != left)
+      const int32_t c = at_left ? ca : ce;
+      if (at_left) ++a;
+      else ++e;
+      const int32_t i = at_left ? static_cast<int32_t>(b) : left[c];
+      const int32_t j = at_left ? right[c] : static_cast<int32_t>(b);
+      if (i == j) continue;  // singly bound: no force
+      const V3 d = load3(center, j) - load3(center, i);
+      const double L = sqrt(dot(d, d));
+      double fm;
+      if (TYPE == MHIP_SPRING_HOOKEAN) {
+        fm = k * (L - r) * (1.0 / L);
+      } else {
+        const double q = L / r;
+        fm = (L < r) ? k / (1.0 - q * q) : __builtin_nan("");
+        if (at_left && !(L < r)) atomicAdd(overstretched, 1);
+      }
+      if (at_left) lmax = L > lmax ? L : lmax;
+      const double tx = fm * d.x, ty = fm * d.y, tz = fm * d.z;
+      if (at_left) {
+        fx = fx + tx; fy = fy + ty; fz = fz + tz;
+      } else {
+        fx = fx - tx; fy = fy - ty; fz = fz - tz;
+      }
+    }
+    if (ACCUMULATE) {
+      force[3 * b] = force[3 * b] + fx;
+      force[3 * b + 1] = force[3 * b + 1] + fy;
+      force[3 * b + 2] = force[3 * b + 2] + fz;
+    } else {
+      force[3 * b] = fx;
+      force[3 * b + 1] = fy;
+      force[3 * b + 2] = fz;
+    }
+  }
+  // non-negative doubles order like their bits: an atomic max on the bits is order independent (as chain.hip)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double o = __shfl_xor(lmax, off, 64);
+    lmax = o > lmax ? o : lmax;
+  }
+  __shared__ double wave_max[kBlock / 64];
+  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = lmax;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double mx = wave_max[0];
+#pragma unroll
+    for (int w = 1; w < kBlock / 64; ++w) mx = wave_max[w] > mx ? wave_max[w] : mx;
+    if (mx > 0.0) atomicMax(max_length_bits, static_cast<unsigned long long>(__double_as_longlong(mx)));
+  }
+}
+
+}  // namespace mhip
+
+using namespace mhip;
+
+struct mhip_crosslinkers {
+  size_t n = 0, m = 0;
+  int type = MHIP_SPRING_HOOKEAN;
+  XlParams p{};
+  DeviceBuffer left, right, lptr, lent, rptr, rent, cursor, ws, cptr, ccol, ckey;
+  size_t cand_entries = 0;
+  bool has_candidates = false;
+  void release() {
+    left.release(); right.release(); lptr.release(); lent.release(); rptr.release(); rent.release(); cursor.release();
+    ws.release(); cptr.release(); ccol.release(); ckey.release();
+  }
+};
+
+namespace {
+
+// count -> scan -> fill -> per-body sort of the crosslinkers listed at at[c] (where at[c] != other[c], if given)
+int build_incidence(mhip_crosslinkers* h, const int32_t* at, const int32_t* other, int32_t* ptr, int32_t* ent,
+                    hipStream_t s) {
+  const size_t n = h->n, m = h->m;
+  int32_t* deg = h->cursor.as<int32_t>();
+  MHIP_HIP(hipMemsetAsync(deg, 0, (n + 1) * sizeof(int32_t), s));
+  if (m > 0) k_xl_count<<<grid_for(m), kBlock, 0, s>>>(m, at, other, deg);
+  MHIP_LAUNCH_CHECK();
+  if (n > 0) {
+    if (int e = exclusive_scan_i32(deg, ptr, n, h->ws.ptr, s)) return e;
+  } else {
+    MHIP_HIP(hipMemsetAsync(ptr, 0, sizeof(int32_t), s));
+  }
+  MHIP_HIP(hipMemsetAsync(deg, 0, (n + 1) * sizeof(int32_t), s));
+  if (m > 0) {
+    k_xl_fill<<<grid_for(m), kBlock, 0, s>>>(m, at, other, ptr, deg, ent);
+    MHIP_LAUNCH_CHECK();
+    sort_incidence_lists(n, ptr, ent, s);
+    MHIP_LAUNCH_CHECK();
+  }
+  return MHIP_SUCCESS;
+}
+int build_left(mhip_crosslinkers* h, hipStream_t s) {
+  return build_incidence(h, h->left.as<int32_t>(), nullptr, h->lptr.as<int32_t>(), h->lent.as<int32_t>(), s);
+}
+int build_right(mhip_crosslinkers* h, hipStream_t s) {
+  return build_incidence(h, h->right.as<int32_t>(), h->left.as<int32_t>(), h->rptr.as<int32_t>(),
+                         h->rent.as<int32_t>(), s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mhip_crosslinkers_create(mhip_crosslinkers_t* handle, size_t n, size_t m, const int32_t* left, const int32_t* right,
+                             const unsigned char* is_site, int type, double k, double r, double bind_rate,
+                             double unbind_rate, double kt, double capture_radius, mhip_stream_t stream) {
+  MHIP_REQUIRE(handle != nullptr, MHIP_ERR_INVALID_ARGUMENT, "handle is null");
+  *handle = nullptr;
+  MHIP_REQUIRE(type == MHIP_SPRING_HOOKEAN || type == MHIP_SPRING_FENE, MHIP_ERR_INVALID_ARGUMENT,
+               "unknown spring type %d", type);
+  MHIP_REQUIRE(m == 0 || left, MHIP_ERR_INVALID_ARGUMENT, "left is null");
+  MHIP_REQUIRE(n < (1ull << 31), MHIP_ERR_INVALID_ARGUMENT, "too many bodies for 32-bit crosslinker heads");
+  MHIP_REQUIRE(m < (1ull << 31), MHIP_ERR_INVALID_ARGUMENT, "too many crosslinkers for 32-bit incidence entries");
+  const bool fene = type == MHIP_SPRING_FENE;
+  MHIP_REQUIRE(std::isfinite(k) && k >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "crosslinker spring constant k must be finite and >= 0, got %g", k);
+  MHIP_REQUIRE(std::isfinite(r) && (fene ? r > 0.0 : r >= 0.0), MHIP_ERR_INVALID_ARGUMENT,
+               "crosslinker %s must be finite and %s 0, got %g", fene ? "r_max" : "rest length", fene ? ">" : ">=", r);
+  MHIP_REQUIRE(std::isfinite(bind_rate) && bind_rate >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "bind_rate must be finite and >= 0, got %g", bind_rate);
+  MHIP_REQUIRE(std::isfinite(unbind_rate) && unbind_rate >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "unbind_rate must be finite and >= 0, got %g", unbind_rate);
+  MHIP_REQUIRE(std::isfinite(kt) && kt > 0.0, MHIP_ERR_INVALID_ARGUMENT, "kt must be finite and > 0, got %g", kt);
+  MHIP_REQUIRE(std::isfinite(capture_radius) && capture_radius > 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "capture_radius must be finite and > 0, got %g", capture_radius);
+  // host arrays: every crosslinker is checked here, before anything reaches the device
+  for (size_t c = 0; c < m; ++c) {
+    const int32_t l = left[c], rr = right ? right[c] : l;
+    MHIP_REQUIRE(l >= 0 && static_cast<size_t>(l) < n, MHIP_ERR_INVALID_ARGUMENT,
+                 "crosslinker %zu: left head at %d, an index outside [0, %zu)", c, l, n);
+    MHIP_REQUIRE(rr >= 0 && static_cast<size_t>(rr) < n, MHIP_ERR_INVALID_ARGUMENT,
+                 "crosslinker %zu: right head at %d, an index outside [0, %zu)", c, rr, n);
+    MHIP_REQUIRE(rr == l || !is_site || is_site[rr], MHIP_ERR_INVALID_ARGUMENT,
+                 "crosslinker %zu: right head at body %d, which is not a bind site", c, rr);
+  }
+  auto* h = new mhip_crosslinkers;
+  h->n = n;
+  h->m = m;
+  h->type = type;
+  h->p = XlParams{k, r, bind_rate, unbind_rate, 1.0 / kt, capture_radius};
+  hipStream_t s = as_stream(stream);
+  auto fail_free = [h](int e) {
+    h->release();
+    delete h;
+    return e;
+  };
+  int e = MHIP_SUCCESS;
+  if ((e = h->left.reserve(m * sizeof(int32_t) + 8)) || (e = h->right.reserve(m * sizeof(int32_t) + 8)) ||
+      (e = h->lent.reserve(m * sizeof(int32_t) + 8)) || (e = h->rent.reserve(m * sizeof(int32_t) + 8)) ||
+      (e = h->lptr.reserve((n + 1) * sizeof(int32_t))) || (e = h->rptr.reserve((n + 1) * sizeof(int32_t))) ||
+      (e = h->cursor.reserve((n + 1) * sizeof(int32_t))) || (e = h->ws.reserve(scan_workspace_bytes(n) + 8)))
+    return fail_free(e);
+  auto hip = [&](hipError_t err) {
+    return err == hipSuccess ? MHIP_SUCCESS
+                             : fail(MHIP_ERR_HIP, "mhip_crosslinkers_create: %s", hipGetErrorString(err));
+  };
+  if (m > 0) {
+    if ((e = hip(hipMemcpyAsync(h->left.ptr, left, m * sizeof(int32_t), hipMemcpyHostToDevice, s)))) return fail_free(e);
+    if ((e = hip(hipMemcpyAsync(h->right.ptr, right ? right : left, m * sizeof(int32_t), hipMemcpyHostToDevice, s))))
+      return fail_free(e);
+  }
+  if ((e = build_left(h, s)) || (e = build_right(h, s))) return fail_free(e);
+  // the caller's host arrays may go as soon as this returns
+  if ((e = hip(hipStreamSynchronize(s)))) return fail_free(e);
+  *handle = h;
+  return MHIP_SUCCESS;
+}
+
+int mhip_crosslinkers_destroy(mhip_crosslinkers_t h) {
+  if (!h) return MHIP_SUCCESS;
+  h->release();
+  delete h;
+  return MHIP_SUCCESS;
+}
+
+int mhip_crosslinkers_set_candidates(mhip_crosslinkers_t h, const int32_t* row_ptr, const int32_t* col,
+                                     size_t num_entries, const int64_t* ids, mhip_stream_t stream) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "crosslinkers handle is null");
+  MHIP_REQUIRE(row_ptr != nullptr, MHIP_ERR_INVALID_ARGUMENT, "row_ptr is null");
+  MHIP_REQUIRE(num_entries == 0 || col, MHIP_ERR_INVALID_ARGUMENT, "col is null");
+  MHIP_REQUIRE(num_entries < (1ull << 31), MHIP_ERR_INVALID_ARGUMENT, "too many candidates for a 32-bit row_ptr");
+  hipStream_t s = as_stream(stream);
+  h->has_candidates = false;
+  if (int e = h->cptr.reserve((h->n + 1) * sizeof(int32_t))) return e;
+  if (int e = h->ccol.reserve(num_entries * sizeof(int32_t) + 8)) return e;
+  if (int e = h->ckey.reserve(num_entries * sizeof(int64_t) + 8)) return e;
+  MHIP_HIP(hipMemcpyAsync(h->cptr.ptr, row_ptr, (h->n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  if (num_entries > 0) {
+    MHIP_HIP(hipMemcpyAsync(h->ccol.ptr, col, num_entries * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    k_xl_entry_keys<<<grid_for(num_entries), kBlock, 0, s>>>(num_entries, h->ccol.as<int32_t>(), ids,
+                                                            h->ckey.as<int64_t>());
+    MHIP_LAUNCH_CHECK();
+    k_xl_row_sort<<<grid_for(h->n), kBlock, 0, s>>>(h->n, h->cptr.as<int32_t>(), h->ckey.as<int64_t>(),
+                                                   h->ccol.as<int32_t>());
+    MHIP_LAUNCH_CHECK();
+  }
+  h->cand_entries = num_entries;
+  h->has_candidates = true;
+  return MHIP_SUCCESS;
+}
+
+int mhip_crosslinkers_kmc_step(mhip_crosslinkers_t h, const double* center, double dt, const uint64_t* keys,
+                               uint64_t* counters, int* events, double* z_total, mhip_stream_t stream) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "crosslinkers handle is null");
+  MHIP_REQUIRE(std::isfinite(dt) && dt > 0.0, MHIP_ERR_INVALID_ARGUMENT, "dt must be finite and > 0, got %g", dt);
+  MHIP_REQUIRE(events != nullptr, MHIP_ERR_INVALID_ARGUMENT, "events is null");
+  MHIP_REQUIRE(h->m == 0 || (center && keys && counters), MHIP_ERR_INVALID_ARGUMENT,
+               "center / keys / counters is null");
+  MHIP_REQUIRE(h->has_candidates, MHIP_ERR_RUNTIME,
+               "mhip_crosslinkers_set_candidates has not been called since the handle was created or renumbered");
+  hipStream_t s = as_stream(stream);
+  MHIP_HIP(hipMemsetAsync(events, 0, 2 * sizeof(int), s));
+  if (h->m == 0) return MHIP_SUCCESS;
+  const unsigned grid = grid_for(h->m);
+#define XL_KMC(T)                                                                                                     \
+  k_xl_kmc<T><<<grid, kBlock, 0, s>>>(h->m, h->left.as<int32_t>(), h->right.as<int32_t>(), h->cptr.as<int32_t>(),    \
+                                      h->ccol.as<int32_t>(), center, keys, counters, h->p, dt, events, z_total)
+  if (h->type == MHIP_SPRING_FENE) XL_KMC(MHIP_SPRING_FENE);
+  else XL_KMC(MHIP_SPRING_HOOKEAN);
+#undef XL_KMC
+  MHIP_LAUNCH_CHECK();
+  // the right ends moved (or not: the rebuild is cheaper than a host round trip to find out)
+  return build_right(h, s);
+}
+
+int mhip_crosslinkers_force(mhip_crosslinkers_t h, const double* center, double* force, int accumulate,
+                            int* overstretched, double* max_length, mhip_stream_t stream) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "crosslinkers handle is null");
+  MHIP_REQUIRE(overstretched != nullptr && max_length != nullptr, MHIP_ERR_INVALID_ARGUMENT,
+               "overstretched / max_length is null");
+  MHIP_REQUIRE(h->n == 0 || (center && force), MHIP_ERR_INVALID_ARGUMENT, "center / force is null");
+  hipStream_t s = as_stream(stream);
+  MHIP_HIP(hipMemsetAsync(overstretched, 0, sizeof(int), s));
+  MHIP_HIP(hipMemsetAsync(max_length, 0, sizeof(double), s));  // +0.0: also the answer without a doubly bound one
+  if (h->n == 0) return MHIP_SUCCESS;
+  const unsigned grid = grid_for(h->n);
+  unsigned long long* mx = reinterpret_cast<unsigned long long*>(max_length);
+#define XL_FORCE(T, ACC)                                                                                             \
+  k_xl_force<T, ACC><<<grid, kBlock, 0, s>>>(h->n, h->lptr.as<int32_t>(), h->lent.as<int32_t>(),                     \
+                                             h->rptr.as<int32_t>(), h->rent.as<int32_t>(), h->left.as<int32_t>(),    \
+                                             h->right.as<int32_t>(), center, h->p.k, h->p.r, force, overstretched, mx)
+  if (h->type == MHIP_SPRING_FENE) {
+    if (accumulate) XL_FORCE(MHIP_SPRING_FENE, true);
+    else XL_FORCE(MHIP_SPRING_FENE, false);
+  } else {
+    if (accumulate) XL_FORCE(MHIP_SPRING_HOOKEAN, true);
+    else XL_FORCE(MHIP_SPRING_HOOKEAN, false);
+  }
+#undef XL_FORCE
+  MHIP_LAUNCH_CHECK();
+  return MHIP_SUCCESS;
+}
+
+int mhip_crosslinkers_get_state(mhip_crosslinkers_t h, int32_t* left, int32_t* right, mhip_stream_t stream) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "crosslinkers handle is null");
+  hipStream_t s = as_stream(stream);
+  if (h->m == 0) return MHIP_SUCCESS;
+  if (left) MHIP_HIP(hipMemcpyAsync(left, h->left.ptr, h->m * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  if (right) MHIP_HIP(hipMemcpyAsync(right, h->right.ptr, h->m * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  return MHIP_SUCCESS;
+}
+
+int mhip_crosslinkers_set_state(mhip_crosslinkers_t h, const int32_t* left, const int32_t* right,
+                                mhip_stream_t stream) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "crosslinkers handle is null");
+  MHIP_REQUIRE(h->m == 0 || right, MHIP_ERR_INVALID_ARGUMENT, "right is null");
+  hipStream_t s = as_stream(stream);
+  if (h->m == 0) return MHIP_SUCCESS;
+  if (left) {
+    MHIP_HIP(hipMemcpyAsync(h->left.ptr, left, h->m * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (int e = build_left(h, s)) return e;
+  }
+  MHIP_HIP(hipMemcpyAsync(h->right.ptr, right, h->m * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  return build_right(h, s);
+}
+
+int mhip_crosslinkers_renumber(mhip_crosslinkers_t h, const int32_t* new_of_old, mhip_stream_t stream) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "crosslinkers handle is null");
+  MHIP_REQUIRE(h->n == 0 || new_of_old, MHIP_ERR_INVALID_ARGUMENT, "new_of_old is null");
+  hipStream_t s = as_stream(stream);
+  h->has_candidates = false;  // the candidate rows are in the old numbering
+  if (h->m > 0) {
+    k_xl_renumber<<<grid_for(h->m), kBlock, 0, s>>>(h->m, new_of_old, h->left.as<int32_t>(), h->right.as<int32_t>());
+    MHIP_LAUNCH_CHECK();
+  }
+  if (int e = build_left(h, s)) return e;
+  return build_right(h, s);
+}
+
+}  // extern "C"

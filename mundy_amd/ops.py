@@ -1182,3 +1182,151 @@ def drag_velocity(mob_trans, force=None, out=None):
                                               _ptr(force, cols=3, allow_none=True, name="force"),
                                               _ptr(v, cols=6, name="out"), _stream()))
     return v
+
+
+# ---- crosslinkers that bind and unbind (HP1.cpp:3264-3748, :4728-4739) ------------------------------------------------
+def check_crosslinkers(n, left, right, sites, kind, k, r, bind_rate, unbind_rate, kt, capture_radius):
+    """host-side validation of a crosslinker set (no library call) -> (left int32 [m], right int32 [m], sites uint8
+    [n], type, k, r, bind_rate, unbind_rate, kt, capture_radius)"""
+    import numpy as np
+
+    def host(a):
+        return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+    if kind not in SPRING_TYPES:
+        raise ValueError("crosslinker spring type must be 'hookean' or 'fene', got %r" % (kind,))
+    if left is None:
+        raise ValueError("crosslinkers need left: the body of every fixed left head")
+    le = host(left)
+    if le.ndim != 1 or not (le.dtype.kind in "iu" or le.size == 0):
+        raise ValueError("crosslinker left must be integers of shape [m], got %s %s" % (le.dtype, le.shape))
+    m = le.shape[0]
+    if le.size and (le.min() < 0 or le.max() >= n):
+        raise ValueError("crosslinker left: an index outside [0, %d)" % n)
+    if sites is None:
+        raise ValueError("crosslinkers need sites: a byte mask [n] of the bodies a right head may bind to")
+    si = host(sites)
+    if si.shape != (n,) or si.dtype.kind not in "biu":
+        raise ValueError("crosslinker sites must be a bool / integer mask of shape [%d], got %s %s" % (n, si.dtype,
+                                                                                                    si.shape))
+    if si.size and (si.min() < 0 or si.max() > 1):
+        raise ValueError("crosslinker sites must hold 0 / 1 only")
+    si = np.ascontiguousarray(si, dtype=np.uint8)
+    if right is None:
+        ri = le.copy()
+    else:
+        ri = host(right)
+        if ri.shape != (m,) or not (ri.dtype.kind in "iu" or ri.size == 0):
+            raise ValueError("crosslinker right must be integers of shape [%d], got %s %s" % (m, ri.dtype, ri.shape))
+        if ri.size and (ri.min() < 0 or ri.max() >= n):
+            raise ValueError("crosslinker right: an index outside [0, %d)" % n)
+        bad = (ri != le) & (si[ri] == 0)
+        if bad.any():
+            c = int(np.argmax(bad))
+            raise ValueError("crosslinker %d: right head at body %d, which is not a bind site" % (c, int(ri[c])))
+    fene = kind == "fene"
+    _, k0 = _spring_param(float(k), m, "crosslinker spring constant k", False)
+    _, r0 = _spring_param(float(r), m, "crosslinker r_max" if fene else "crosslinker rest length r0", fene)
+    _, a0 = _spring_param(float(bind_rate), m, "bind_rate", False)
+    _, off = _spring_param(float(unbind_rate), m, "unbind_rate", False)
+    _, kt0 = _spring_param(float(kt), m, "crosslinker kt", True)
+    _, cap = _spring_param(float(capture_radius), m, "capture_radius", True)
+    return (np.ascontiguousarray(le, dtype=np.int32), np.ascontiguousarray(ri, dtype=np.int32), si, SPRING_TYPES[kind],
+            k0, r0, a0, off, kt0, cap)
+
+
+class Crosslinkers:
+    """m crosslinkers over n bodies (mhip_crosslinkers_*): fixed left heads, right heads that bind to the bodies of the
+    `sites` mask and unbind (right == left: singly bound); a doubly bound one is a spring of `kind` / k / r.
+    set_candidates(row_ptr, col, ids) -> kmc_step(center, dt, keys, counters) -> force(center)."""
+
+    def __init__(self, n, left, right, sites, kind, k, r, bind_rate, unbind_rate, kt, capture_radius):
+        le, ri, si, t, k0, r0, a0, off, kt0, cap = check_crosslinkers(n, left, right, sites, kind, k, r, bind_rate,
+                                                                       unbind_rate, kt, capture_radius)
+        self.n, self.num_crosslinkers, self.kind = int(n), le.shape[0], kind
+        self.k, self.r, self.capture_radius = k0, r0, cap
+        h = C.c_void_p()
+        cp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        capi.check(capi.load().mhip_crosslinkers_create(C.byref(h), self.n, le.shape[0], cp(le), cp(ri), cp(si), t, k0,
+                                                        r0, a0, off, kt0, cap, _stream()))
+        self._h = h
+
+    def set_candidates(self, row_ptr, col, ids=None):
+        """the CSR of a neighbour search over the bodies; every row is sorted by ids[col] (int64 [n]) here, once"""
+        if tuple(row_ptr.shape) != (self.n + 1,):
+            raise ValueError("row_ptr must have shape [%d], got %s" % (self.n + 1, tuple(row_ptr.shape)))
+        if ids is not None and tuple(ids.shape) != (self.n,):
+            raise ValueError("ids must have shape [%d], got %s" % (self.n, tuple(ids.shape)))
+        capi.check(capi.load().mhip_crosslinkers_set_candidates(
+            self._h, _ptr(row_ptr, torch.int32, name="row_ptr"), _ptr(col, torch.int32, name="col"), col.shape[0],
+            _ptr(ids, torch.int64, allow_none=True, name="ids"), _stream()))
+
+    def kmc_step(self, center, dt, keys, counters, events=None, z_total=None):
+        """one KMC step at `center`; counters += 1; -> events int32 [2] = (binds, unbinds), left on the device;
+        z_total (optional float64 [m]) receives every singly bound crosslinker's total rate x dt"""
+        m = self.num_crosslinkers
+        if tuple(center.shape) != (self.n, 3):
+            raise ValueError("center must have shape [%d, 3], got %s" % (self.n, tuple(center.shape)))
+        if tuple(keys.shape) != (m,) or tuple(counters.shape) != (m,):
+            raise ValueError("keys and counters must have shape [%d]" % m)
+        if z_total is not None and tuple(z_total.shape) != (m,):
+            raise ValueError("z_total must have shape [%d]" % m)
+        ev = torch.empty(2, dtype=torch.int32, device=center.device) if events is None else events
+        capi.check(capi.load().mhip_crosslinkers_kmc_step(self._h, _ptr(center, cols=3, name="center"), float(dt),
+                                                          _u64(keys, "keys"), _u64(counters, "counters"),
+                                                          _ptr(ev, torch.int32, name="events"),
+                                                          _ptr(z_total, allow_none=True, name="z_total"), _stream()))
+        return ev
+
+    def force(self, center, out=None, accumulate=False, stats=None):
+        """the doubly bound crosslinkers as springs: written to (or, accumulate=True, added into) out [n, 3];
+        stats as Springs.force"""
+        if tuple(center.shape) != (self.n, 3):
+            raise ValueError("center must have shape [%d, 3], got %s" % (self.n, tuple(center.shape)))
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs out")
+            out = torch.empty((self.n, 3), dtype=torch.float64, device=center.device)
+        if stats is None:
+            stats = (torch.empty(1, dtype=torch.int32, device=center.device),
+                     torch.empty(1, dtype=torch.float64, device=center.device))
+        over, mx = stats
+        capi.check(capi.load().mhip_crosslinkers_force(self._h, _ptr(center, cols=3, name="center"),
+                                                       _ptr(out, cols=3, name="out"), 1 if accumulate else 0,
+                                                       C.c_void_p(over.data_ptr()), C.c_void_p(mx.data_ptr()),
+                                                       _stream()))
+        return out, over, mx
+
+    def state(self, device):
+        """-> (left, right) int32 [m] device tensors (copies)"""
+        le, ri = (torch.empty(self.num_crosslinkers, dtype=torch.int32, device=device) for _ in range(2))
+        capi.check(capi.load().mhip_crosslinkers_get_state(self._h, _ptr(le, torch.int32), _ptr(ri, torch.int32),
+                                                           _stream()))
+        return le, ri
+
+    def set_state(self, left, right):
+        """left (None = unchanged) and right int32 [m] device tensors into the handle; indices are not checked"""
+        m = self.num_crosslinkers
+        for name, t in (("left", left), ("right", right)):
+            if t is not None and tuple(t.shape) != (m,):
+                raise ValueError("%s must have shape [%d], got %s" % (name, m, tuple(t.shape)))
+        capi.check(capi.load().mhip_crosslinkers_set_state(self._h, _ptr(left, torch.int32, allow_none=True, name="left"),
+                                                           _ptr(right, torch.int32, name="right"), _stream()))
+
+    def renumber(self, new_of_old):
+        """the bodies were permuted: new_of_old int32 [n]; the candidates are dropped"""
+        if tuple(new_of_old.shape) != (self.n,):
+            raise ValueError("new_of_old must have shape [%d], got %s" % (self.n, tuple(new_of_old.shape)))
+        capi.check(capi.load().mhip_crosslinkers_renumber(self._h, _ptr(new_of_old, torch.int32, name="new_of_old"),
+                                                          _stream()))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            capi.load().mhip_crosslinkers_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

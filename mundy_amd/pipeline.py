@@ -27,6 +27,12 @@ springs= / brownian_kt= add the bead-spring chain step of the chromatin app (sph
         -> contacts, q = sep + dt D^T U_ext (ContactOperator.constraint_rate) -> solve (or Hertz f)
         -> U = U_ext + M D lambda -> Euler update
 
+crosslinkers= adds the kinetic Monte Carlo stage of the HP1 app to the chain step (HP1.cpp:4728-4739):
+
+    ... -> broad phase, and the candidate list of the crosslinkers (its own search and rebuild rule)
+        -> KMC at the positions of the start of the step: right heads bind and unbind
+        -> spring forces + the doubly bound crosslinkers as springs (+ external_force) -> the chain step as above
+
 hertz_friction= replaces the frictionless Hertz force by the reference's frictional rod contact with a per-pair
 tangential history (SpherocylinderSegmentSpherocylinderSegmentFrictionalHertzianContact.cpp:384-518, run every step by
 CollidingOverdampedFrictionalSperm.cpp:1553-1731):
@@ -59,6 +65,10 @@ class StepStats:
     num_born: int = 0  # growth mode: bodies that divided this step (their children are rows n_before + k)
     max_spring_length: float = 0.0  # springs=: the longest spring at the start of the step
     num_sliding: int = 0  # hertz_friction=: contacts whose tangential force was capped at mu |F_n| this step
+    crosslinker_bound: int = 0    # crosslinkers=: doubly bound crosslinkers after this step's KMC
+    crosslinker_binds: int = 0    # ... right heads that bound this step
+    crosslinker_unbinds: int = 0  # ... and that unbound
+    max_crosslinker_length: float = 0.0  # ... the longest doubly bound crosslinker at this step's force evaluation
 
 
 class ContactStepper:
@@ -70,7 +80,7 @@ class ContactStepper:
                  conservative_ellipsoid_box=False, friction_method="apgd", contact_model="lcp", youngs_modulus=1000.0,
                  poisson_ratio=0.3, growth_rate=None, division_length=None, capacity=None, ids=None, springs=None,
                  brownian_kt=None, rng_keys=None, rng_counter=None, hertz_friction=None, hertz_damping=(0.0, 0.0),
-                 hertz_density=1.0):
+                 hertz_density=1.0, crosslinkers=None):
         """kind = "sphere" | "spherocylinder" | "mixed".  Mixed systems (BASELINE configs[4]) pass kinds [n] int32
         (0 sphere, 1 spherocylinder, 2 ellipsoid) and shape [n, 3] = (r,-,-) / (r,L,-) / (r1,r2,r3) instead of
         radius / length.
@@ -93,7 +103,15 @@ class ContactStepper:
         orthorhombic box; no growth, springs or noise).  hertz_damping = (normal, tangential) >= 0 and hertz_density >= 0
         (the sphere mass of the rod radius weighs the damping) default to the reference's values.  The stepper then
         owns prev_velocity [n, 6] (zero before the first step) and tang_disp [C, 3] with the pair list it belongs to;
-        step(external_force=) adds U_ext = (m_t F, 0) to the contact velocity."""
+        step(external_force=) adds U_ext = (m_t F, 0) to the contact velocity.
+        crosslinkers = dict(left=, right=None, sites=, kind=, k=, r=, bind_rate=, unbind_rate=, kt=, capture_radius=,
+        skin=, keys=None, counter=None): m crosslinkers with fixed left heads at the bodies left [m] and right heads
+        that bind to the bodies of the byte mask sites [n] and unbind (right [m], default = left: all singly bound); the
+        chain step (spheres, free space, either contact model, with or without springs / brownian_kt).  kind / k / r:
+        the spring a doubly bound crosslinker is; bind_rate (A) and unbind_rate (k_off) >= 0, kt > 0 (the Boltzmann
+        weight of binding), capture_radius > 0 (no binding beyond it), skin >= 0 (buffer of the candidate search).  keys
+        (integers in [0, 2^63), default arange(m)) and counter (default 0) key each crosslinker's Philox stream.  The
+        stepper then owns ids [n] (int64, arange(n): the order candidates are walked in, kept by reorder_bodies)."""
         if kind not in ("sphere", "spherocylinder", "mixed"):
             raise ValueError("kind must be 'sphere', 'spherocylinder' or 'mixed'")
         if contact_model not in ("lcp", "hertz"):
@@ -110,6 +128,10 @@ class ContactStepper:
             ops._material(youngs_modulus, center.shape[0], "youngs_modulus", 0.0, float("inf"))
             ops._material(poisson_ratio, center.shape[0], "poisson_ratio", 0.0, 1.0)
         self.youngs_modulus, self.poisson_ratio = youngs_modulus, poisson_ratio
+        xl_spec = None
+        if crosslinkers is not None:  # (checked before anything reaches the device)
+            xl_spec = self._check_crosslinkers(kind, center.shape[0], periodic_box, friction, contact_cutoff, growth_rate,
+                                               hertz_friction, crosslinkers)
         self.hertz_friction = None
         if hertz_friction is not None:  # (checked before anything reaches the device)
             self._check_hertz_friction(contact_model, kind, rod_kinematics, growth_rate, springs, brownian_kt,
@@ -125,7 +147,7 @@ class ContactStepper:
                                radius, quat, length, periodic_box, capacity, ids)
         elif division_length is not None or capacity is not None or ids is not None:
             raise ValueError("division_length, capacity and ids belong to growth mode: pass growth_rate")
-        self.chain = springs is not None or brownian_kt is not None
+        self.chain = springs is not None or brownian_kt is not None or crosslinkers is not None
         if self.chain:  # (checked before anything reaches the device)
             chain_spec = self._check_chain(kind, center.shape[0], periodic_box, friction, contact_cutoff, springs,
                                            brownian_kt, rng_keys, rng_counter)
@@ -196,6 +218,9 @@ class ContactStepper:
             self._init_chain(*chain_spec)
         if self.hertz_friction is not None:
             self._init_hertz_friction()
+        self.crosslinkers = None
+        if xl_spec is not None:
+            self._init_crosslinkers(xl_spec)
 
     # -- frictional Hertz contact (FrictionalHertzianContact.cpp:384-518) -------------------------------------------------
     @staticmethod
@@ -331,13 +356,113 @@ class ContactStepper:
         self.springs.close()
         self.springs = ops.Springs(self.center.shape[0], *self._spring_spec)
 
+    # -- crosslinkers that bind and unbind (HP1.cpp:3264-3748, :4728-4739) ------------------------------------------------
+    _XL_KEYS = ("left", "right", "sites", "kind", "k", "r", "bind_rate", "unbind_rate", "kt", "capture_radius", "skin",
+                "keys", "counter")
+
+    @staticmethod
+    def _check_crosslinkers(kind, n, box, friction, contact_cutoff, growth_rate, hertz_friction, spec):
+        import numpy as np
+        if kind != "sphere":
+            raise ValueError("crosslinkers are wired for spheres only (the chain step), not %r" % kind)
+        if growth_rate is not None:
+            raise ValueError("crosslinkers do not run in growth mode")
+        if hertz_friction is not None:
+            raise ValueError("crosslinkers take no hertz_friction (the rod contact)")
+        if friction is not None or contact_cutoff is not None:
+            raise ValueError("crosslinkers take no friction or contact_cutoff")
+        if box is not None:
+            raise ValueError("crosslinkers take no periodic_box (no minimum-image crosslinkers)")
+        if not isinstance(spec, dict):
+            raise ValueError("crosslinkers must be a dict with the keys %s" % ", ".join(ContactStepper._XL_KEYS))
+        unknown = sorted(set(spec) - set(ContactStepper._XL_KEYS))
+        if unknown:
+            raise ValueError("crosslinkers: unknown key(s) %s" % ", ".join(unknown))
+        missing = [k for k in ContactStepper._XL_KEYS if k not in spec and k not in ("right", "keys", "counter")]
+        if missing:
+            raise ValueError("crosslinkers: missing key(s) %s" % ", ".join(missing))
+        checked = ops.check_crosslinkers(n, spec["left"], spec.get("right"), spec["sites"], spec["kind"], spec["k"],
+                                         spec["r"], spec["bind_rate"], spec["unbind_rate"], spec["kt"],
+                                         spec["capture_radius"])
+        skin = float(spec["skin"])
+        if not (skin >= 0.0 and skin < math.inf):
+            raise ValueError("crosslinker skin must be finite and >= 0, got %r" % (spec["skin"],))
+        m = checked[0].shape[0]
+
+        def ints(t, name):
+            if t is None:
+                return None
+            a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+            if a.dtype.kind not in "iu" or a.shape != (m,):
+                raise ValueError("crosslinker %s must be integers of shape [%d], got %s %s" % (name, m, a.dtype, a.shape))
+            if a.size and (int(a.min()) < 0 or int(a.max()) >= 2 ** 63):
+                raise ValueError("crosslinker %s must lie in [0, 2^63)" % name)
+            return np.ascontiguousarray(a, dtype=np.int64)
+        return checked, spec["kind"], skin, ints(spec.get("keys"), "keys"), ints(spec.get("counter"), "counter")
+
+    def _init_crosslinkers(self, xl_spec):
+        import numpy as np
+        (le, ri, si, _, k, r, a, off, kt, cap), skind, skin, keys, counter = xl_spec
+        n, dev = self.center.shape[0], self.center.device
+        m = le.shape[0]
+        self.crosslinkers = ops.Crosslinkers(n, le, ri, si, skind, k, r, a, off, kt, cap)
+        self.crosslinker_skin = skin
+        self.xl_keys = torch.arange(m, dtype=torch.int64, device=dev) if keys is None else torch.from_numpy(keys).to(dev)
+        self.xl_counter = (torch.zeros(m, dtype=torch.int64, device=dev) if counter is None else
+                           torch.from_numpy(counter).to(dev))
+        self.crosslinker_bound = int((ri != le).sum())
+        # per-body arrays of the candidate search: who carries a crosslinker, who is a bind site, every body's reach
+        src = np.zeros(n, dtype=np.uint8)
+        src[le] = 1
+        self.xl_sources, self.xl_sites = torch.from_numpy(src).to(dev), torch.from_numpy(si).to(dev)
+        self.xl_reach = torch.full((n,), 0.5 * cap, dtype=torch.float64, device=dev)
+        self.ids = torch.arange(n, dtype=torch.int64, device=dev)
+        self._BODY_ARRAYS = ContactStepper._BODY_ARRAYS + ("ids", "xl_sources", "xl_sites")
+        # [.., crosslinker (binds, unbinds) as two int32, longest crosslinker, overstretched crosslinkers (int32)]
+        self._chain_stats = torch.zeros(6, dtype=torch.float64, device=dev)
+        self.xl_links = None
+        self.crosslinker_rebuilds = 0  # candidate lists built so far
+        self._new_crosslinker_search()
+
+    def _new_crosslinker_search(self):
+        """the candidate search: bounding spheres of radius capture_radius / 2 (+ skin), sources the beads that carry a
+        crosslinker, targets the bind sites; a fresh builder, since the masks follow the body numbering"""
+        if self.xl_links is not None:
+            self.xl_links.close()
+        self.xl_links = (ops.GenNeighborLinks().set_search_buffer(self.crosslinker_skin)
+                         .set_search_kind(ops.SEARCH_SPHERES).set_enforce_source_target_symmetry(True)
+                         .acts_on(self.xl_sources, self.xl_sites).concretize())
+
+    def crosslinker_kmc(self):
+        """candidate list (rebuilt by the displacement rule, rows sorted by id once per build) -> one KMC step at the
+        current positions; the event counts stay on the device (self._chain_stats)"""
+        if self.xl_links.generate(None, self.center, self.xl_reach):
+            self.crosslinker_rebuilds += 1
+            self.crosslinkers.set_candidates(self.xl_links.row_ptr, self.xl_links.col, self.ids)
+        self.crosslinkers.kmc_step(self.center, self.dt, self.xl_keys, self.xl_counter,
+                                   events=self._chain_stats.view(torch.int32)[6:8])
+
+    def crosslinker_state(self):
+        """-> (left, right) int32 [m] device tensors in the current body numbering; right == left: singly bound"""
+        return self.crosslinkers.state(self.center.device)
+
     def external_velocity(self, external_force=None):
-        """U_ext = M (F_spring + F_ext) + U_brown into self.u_ext (the rng counters advance)"""
+        """U_ext = M (F_spring + F_crosslinker + F_ext) + U_brown into self.u_ext (the rng counters advance; with
+        crosslinkers, their KMC step runs first)"""
         self._chain_stats.zero_()
         force = None
+        if self.crosslinkers is not None:
+            self.crosslinker_kmc()
+            xl_stats = (self._chain_stats.view(torch.int32)[10:11], self._chain_stats[4:5])
         if self.springs is not None:
             force, _, _ = self.springs.force(self.center, out=self.spring_force,
                                              stats=(self._chain_stats.view(torch.int32)[4:5], self._chain_stats[1:2]))
+            if self.crosslinkers is not None:
+                self.crosslinkers.force(self.center, out=force, accumulate=True, stats=xl_stats)
+            if external_force is not None:
+                ops.axpby(1.0, external_force.reshape(-1), 1.0, force.view(-1))
+        elif self.crosslinkers is not None:
+            force, _, _ = self.crosslinkers.force(self.center, out=self.spring_force, stats=xl_stats)
             if external_force is not None:
                 ops.axpby(1.0, external_force.reshape(-1), 1.0, force.view(-1))
         elif external_force is not None:
@@ -474,6 +599,9 @@ class ContactStepper:
         if self.hertz_friction is not None:  # the history, the list it belongs to and the previous velocities
             snap["_fr"] = (self.prev_velocity.clone(), None if self.tang_disp is None else self.tang_disp.clone(),
                            self.hist_pairs, self._renumber)
+        if self.crosslinkers is not None:  # both heads (in the numbering of the snapshot), keys, counters, bound count
+            snap["_xl"] = self.crosslinker_state() + (self.xl_keys.clone(), self.xl_counter.clone(),
+                                                      self.crosslinker_bound)
         return snap
 
     def restore(self, snap):
@@ -491,6 +619,12 @@ class ContactStepper:
                 # (a clone: the stepper updates its history in place, and the next step carries it to the list in use)
                 self.tang_disp = None if v[1] is None else v[1].clone()
                 self.hist_pairs, self._renumber = (None if v[1] is None else v[2].clone()), v[3]
+                continue
+            if k == "_xl":
+                self.crosslinkers.set_state(v[0], v[1])
+                self.xl_keys.copy_(v[2])
+                self.xl_counter.copy_(v[3])
+                self.crosslinker_bound = v[4]
                 continue
             getattr(self, k).copy_(v)
 
@@ -530,6 +664,11 @@ class ContactStepper:
                 t.copy_(ops.gather_rows(perm, t) if t.dtype == torch.float64 else t[perm.long()])
         if getattr(self, "springs", None) is not None:
             self._renumber_springs(perm)
+        if getattr(self, "crosslinkers", None) is not None:  # heads through the inverse permutation, a new search
+            inv = torch.empty(perm.shape[0], dtype=torch.int32, device=perm.device)
+            inv[perm.long()] = torch.arange(perm.shape[0], dtype=torch.int32, device=perm.device)
+            self.crosslinkers.renumber(inv)
+            self._new_crosslinker_search()
         if self.hertz_friction is not None:  # previous velocities move with their rows, the history through the inverse
             self.prev_velocity = ops.gather_rows(perm, self.prev_velocity)
             inv = torch.empty_like(perm)
@@ -769,6 +908,15 @@ class ContactStepper:
             over = int(h.view(torch.int32)[4])
             if over:
                 raise RuntimeError("%d FENE spring(s) stretched to L >= r_max: no force (reduce dt)" % over)
+            if self.crosslinkers is not None:  # (the same read)
+                hi = h.view(torch.int32)
+                st.crosslinker_binds, st.crosslinker_unbinds = int(hi[6]), int(hi[7])
+                self.crosslinker_bound += st.crosslinker_binds - st.crosslinker_unbinds
+                st.crosslinker_bound = self.crosslinker_bound
+                st.max_crosslinker_length = float(h[4])
+                if int(hi[10]):
+                    raise RuntimeError("%d FENE crosslinker(s) stretched to L >= r_max: no force (reduce dt)"
+                                       % int(hi[10]))
         elif self.hertz_friction is not None:  # the one read of the step: (max_overlap, num_sliding)
             h = self._fr_stats.cpu()
             st.max_overlap, st.num_sliding = float(h[0]), int(h.view(torch.int64)[1])
