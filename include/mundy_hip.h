@@ -330,6 +330,88 @@ int mhip_crosslinkers_set_state(mhip_crosslinkers_t handle, const int32_t* left,
 int mhip_crosslinkers_renumber(mhip_crosslinkers_t handle, const int32_t* new_of_old, mhip_stream_t stream);
 int mhip_crosslinkers_destroy(mhip_crosslinkers_t handle);
 
+/* The nuclear periphery of the HP1 app: a wall that confines every bead in a sphere or an ellipsoid
+ * (scrap/.../HP1.cpp:4063-4284; on the device NgpHP1.cpp:2409-2527).  One linear spring of constant k per bead that
+ * touches the wall, along the wall's inward normal; in the reference's association:
+ *   MHIP_PERIPHERY_SPHERE (HP1.cpp:4208-4238), R = radii[0], x = c - center:
+ *     nrm = sqrt(x0 x0 + (x1 x1 + x2 x2)), ssd = R - nrm - r; where ssd < 0: inward = (-x) (1 / nrm) and
+ *     F_k = F_k - (k inward_k) ssd.  With center = 0 this is the reference bit for bit.
+ *   MHIP_PERIPHERY_ELLIPSOID (NgpHP1.cpp:2444-2527), semi-axes radii = (a, b, c), orientation quat (w, x, y, z):
+ *     coarse filter: the level set (b0 b0 inv_a2 + b1 b1 inv_b2 + b2 b2 inv_c2) - 1, inv_a2 = 1 / (a a), at the eight
+ *     corners c -/+ r of the bead's box in the body frame conjugate(q) (corner - center); all eight < 0: no force.
+ *     Otherwise y = conjugate(q) (c - center) and the exact signed distance sd (negative inside), closest point and
+ *     outward unit normal n of the S-E class of mhip_contact_mixed (closed form, csrc/segment_ellipsoid.hpp):
+ *     ssd = -sd - r; where ssd < 0: pn = -(q n) and F_k = F_k - (k pn_k) ssd.  The reference calls a shared-normal
+ *     distance that its tree does not define; its nearest existing routine (PointEllipsoid.hpp:94-135) is good to 1e-4.
+ *     A bead that fails the filter must not sit on the ellipsoid's medial set (the closest point is not unique there);
+ *     a bead radius below the smallest semi-axis keeps every such bead away from it.
+ *   MHIP_PERIPHERY_ELLIPSOID_FAST (HP1.cpp:4148-4206), x = c - center, no orientation (quat must be the identity):
+ *     g = (x0 x0 inv_a2 + x1 x1 inv_b2 + x2 x2 inv_c2) - 1 with inv_a2 = 1 / ((a - r) (a - r)); where g > 0:
+ *     F_k = F_k - k (2 x_k inv_k2).
+ *   The spherical "fast approximate" variant (HP1.cpp:4240-4264) moves positions and is not built.
+ * Precondition on the caller, for every shape: each bead radius r is below the smallest periphery radius.  The bead
+ * radii are device data and are not checked here (the stepper refuses them on the host).  Without it SPHERE divides by
+ * nrm = 0 for a bead with r >= R at the exact centre, and ELLIPSOID_FAST by (a - r) = 0: the force is then not finite.
+ * center [n][3], radius [n], force [n][3].  accumulate = 0: force is written, +0.0 for a body without wall contact (a
+ * body with contact gets 0.0 - term); accumulate = 1: the term is subtracted from force, which stays untouched where
+ * there is no contact.  No atomics on forces.  colliding [device, 1 int, or NULL] = number of bodies with contact;
+ * max_overlap [device, 1 double, or NULL] = the largest -ssd (ELLIPSOID_FAST: the largest g), +0.0 without contact,
+ * order independent.  Refused with MHIP_ERR_INVALID_ARGUMENT before any HIP call: an unknown shape, radii <= 0 (SPHERE:
+ * radii[0] only), k < 0, a quaternion that is not unit to 1e-12 (|q|^2 - 1), a non-identity quat with ELLIPSOID_FAST,
+ * anything not finite. */
+#define MHIP_PERIPHERY_SPHERE 0
+#define MHIP_PERIPHERY_ELLIPSOID 1
+#define MHIP_PERIPHERY_ELLIPSOID_FAST 2
+typedef struct mhip_periphery {
+  int shape;
+  double center[3];
+  double quat[4];
+  double radii[3];
+  double k;
+} mhip_periphery;
+int mhip_periphery_force(const mhip_periphery* periphery, size_t n, const double* center, const double* radius,
+                         double* force, int accumulate, int* colliding /*[device] or NULL*/,
+                         double* max_overlap /*[device] or NULL*/, mhip_stream_t stream);
+
+/* Active euchromatin force dipoles of the HP1 app (scrap/.../HP1.cpp:2796-2826, :3770-3853, :4286-4354): m springs
+ * (i, j) = pairs[s] between n bodies, each a two-state (0 inactive, 1 active) Poisson process with the rates kon
+ * (0 -> 1) and koff (1 -> 0); an active spring pushes its beads apart with a force of magnitude sigma.
+ *   uniform: u = (((w0 << 21) | (w1 >> 11)) + 1) 2^-53 in (0, 1] from block 0 of Philox at (keys[s], counter[s]): the
+ *     library's own map (openrand's stream is not reproduced), so log(u) is finite
+ *   create [host arrays; keys NULL = the spring's index, counters NULL = 0]: every spring inactive,
+ *     next_time = -log(u) (1 / kon), counter + 1, elapsed = 0 (:2796-2826); builds the body -> spring incidence on the
+ *     device and synchronises `stream`.  Refuses (MHIP_ERR_INVALID_ARGUMENT, before any HIP call) an index outside
+ *     [0, n), a spring from a body to itself, kon <= 0, koff <= 0, a key or counter outside [0, 2^63), anything not
+ *     finite.
+ *   sample: a spring with elapsed >= next_time draws u, flips its state, sets next_time = -log(u) (1 / koff) when it
+ *     switched on or -log(u) (1 / kon) when it switched off, elapsed = 0 and counter + 1 (:3798-3816).  A spring that
+ *     does not switch draws nothing.  switches [device, 2 ints] = (switched on, switched off) of this call.
+ *   force: for a spring in state 1, nvec = x_j - x_i, nsqr = n0 n0 + n1 n1 + n2 n2 (left to right),
+ *     t_k = (sigma / sqrt(nsqr)) nvec_k; body i receives -t and body j +t (:4325-4347), the same operations at both
+ *     ends, so exactly negated vectors.  Each body adds its terms in ascending spring index from +0.0 (no atomics on
+ *     forces); the sum is written to force [n][3] (accumulate = 0: +0.0 for a body without an active spring) or added to
+ *     it (accumulate = 1: untouched for such a body).
+ *     active [device, 1 int, or NULL] = number of springs in state 1.
+ *   advance: elapsed += dt for every spring (:3835-3853); dt < 0 or not finite is refused.
+ *   get_state / set_state: state [m] int32, next_time [m], elapsed [m], counters [m] device arrays out of / into the
+ *     handle; NULL skips.  Nothing is checked.
+ *   renumber: the bodies were permuted; new_of_old [n] int32 = the new index of every old body.  Spring indices, states
+ *     and timers do not change; the incidence is rebuilt. */
+typedef struct mhip_active_springs* mhip_active_springs_t;
+int mhip_active_springs_create(mhip_active_springs_t* handle, size_t n, size_t m, const int32_t* pairs /*[host] m x 2*/,
+                               double sigma, double kon, double koff, const uint64_t* keys /*[host] m or NULL*/,
+                               const uint64_t* counters /*[host] m or NULL*/, mhip_stream_t stream);
+int mhip_active_springs_sample(mhip_active_springs_t handle, int* switches /*[device] 2*/, mhip_stream_t stream);
+int mhip_active_springs_force(mhip_active_springs_t handle, const double* center, double* force, int accumulate,
+                              int* active /*[device] or NULL*/, mhip_stream_t stream);
+int mhip_active_springs_advance(mhip_active_springs_t handle, double dt, mhip_stream_t stream);
+int mhip_active_springs_get_state(mhip_active_springs_t handle, int32_t* state, double* next_time, double* elapsed,
+                                  uint64_t* counters, mhip_stream_t stream);
+int mhip_active_springs_set_state(mhip_active_springs_t handle, const int32_t* state, const double* next_time,
+                                  const double* elapsed, const uint64_t* counters, mhip_stream_t stream);
+int mhip_active_springs_renumber(mhip_active_springs_t handle, const int32_t* new_of_old, mhip_stream_t stream);
+int mhip_active_springs_destroy(mhip_active_springs_t handle);
+
 /* Mixed shapes (BASELINE configs[4]): kind[n] = 0 sphere, 1 spherocylinder, 2 ellipsoid; shape[n][3] = (r,-,-) /
  * (r,L,-) / (r1,r2,r3); quat is ignored for spheres.  compute_aabb dispatches on kind (compute_aabb.hpp:72-127) and
  * also returns the bounding radii (compute_bounding_radius.hpp:61-93).  contact_mixed bins the pairs by shape class and

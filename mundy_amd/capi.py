@@ -14,6 +14,7 @@ SEARCH_METHOD_AUTO, SEARCH_METHOD_GRID, SEARCH_METHOD_MORTON_LBVH = 0, 1, 2
 SPACE_UNCONSTRAINED, SPACE_LOWER_BOUND, SPACE_UPPER_BOUND, SPACE_BOUNDED = 0, 1, 2, 3
 RESIDUAL_PROJECTED_DIFF, RESIDUAL_PROJECTED_GRADIENT = 0, 1
 SPRING_HOOKEAN, SPRING_FENE = 0, 1
+PERIPHERY_SPHERE, PERIPHERY_ELLIPSOID, PERIPHERY_ELLIPSOID_FAST = 0, 1, 2
 
 
 class MhipError(RuntimeError):
@@ -40,6 +41,11 @@ class SolveResult(C.Structure):
 class HertzFrictionParams(C.Structure):
     _fields_ = [("mu", C.c_double), ("normal_damping", C.c_double), ("tangential_damping", C.c_double),
                 ("density", C.c_double), ("dt", C.c_double)]
+
+
+class Periphery(C.Structure):
+    _fields_ = [("shape", C.c_int), ("center", C.c_double * 3), ("quat", C.c_double * 4), ("radii", C.c_double * 3),
+                ("k", C.c_double)]
 
 
 class VelocityHalo(C.Structure):
@@ -122,6 +128,15 @@ SIGNATURES = {
     "mhip_crosslinkers_set_state": [_vp, _vp, _vp, _vp],
     "mhip_crosslinkers_renumber": [_vp, _vp, _vp],
     "mhip_crosslinkers_destroy": [_vp],
+    "mhip_periphery_force": [C.POINTER(Periphery), _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp],
+    "mhip_active_springs_create": [C.POINTER(_vp), _sz, _sz, _vp, _d, _d, _d, _vp, _vp, _vp],
+    "mhip_active_springs_sample": [_vp, _vp, _vp],
+    "mhip_active_springs_force": [_vp, _vp, _vp, _i, _vp, _vp],
+    "mhip_active_springs_advance": [_vp, _d, _vp],
+    "mhip_active_springs_get_state": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "mhip_active_springs_set_state": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "mhip_active_springs_renumber": [_vp, _vp, _vp],
+    "mhip_active_springs_destroy": [_vp],
     "mhip_philox4x32_10": [_sz, _vp, _vp, C.c_uint32, _vp, _vp],
     "mhip_brownian_velocity": [_sz, _vp, _vp, _d, _d, _vp, _vp, _vp],
     "mhip_drag_velocity": [_sz, _vp, _vp, _vp, _vp],

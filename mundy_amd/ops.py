@@ -1330,3 +1330,201 @@ class Crosslinkers:
             self.close()
         except Exception:
             pass
+
+
+# ---- the nuclear periphery (HP1.cpp:4063-4284, NgpHP1.cpp:2409-2527) ---------------------------------------------------
+PERIPHERY_SHAPES = {"sphere": capi.PERIPHERY_SPHERE, "ellipsoid": capi.PERIPHERY_ELLIPSOID,
+                    "ellipsoid_fast": capi.PERIPHERY_ELLIPSOID_FAST}
+_PERIPHERY_KEYS = ("shape", "radius", "radii", "k", "center", "quat")
+
+
+def check_periphery(spec):
+    """host-side validation of a periphery dict(shape=, radius= or radii=, k=, center=(0, 0, 0), quat=(1, 0, 0, 0)) (no
+    library call) -> (shape name, radii (3 floats; a sphere's radius three times), k, center, quat)"""
+    import math
+    if not isinstance(spec, dict):
+        raise ValueError("periphery must be a dict with the keys %s" % ", ".join(_PERIPHERY_KEYS))
+    unknown = sorted(set(spec) - set(_PERIPHERY_KEYS))
+    if unknown:
+        raise ValueError("periphery: unknown key(s) %s" % ", ".join(unknown))
+    missing = [k for k in ("shape", "k") if k not in spec]
+    if missing:
+        raise ValueError("periphery: missing key(s) %s" % ", ".join(missing))
+    shape = spec["shape"]
+    if shape not in PERIPHERY_SHAPES:
+        raise ValueError("periphery shape must be 'sphere', 'ellipsoid' or 'ellipsoid_fast', got %r" % (shape,))
+    want, other = ("radius", "radii") if shape == "sphere" else ("radii", "radius")
+    if want not in spec:
+        raise ValueError("periphery: missing key(s) %s" % want)
+    if other in spec:
+        raise ValueError("periphery: shape %r takes %s, not %s" % (shape, want, other))
+
+    def floats(v, count, name):
+        try:
+            a = [float(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
+        except TypeError:
+            a = None
+        if a is None or len(a) != count:
+            raise ValueError("periphery %s must be %d numbers, got %r" % (name, count, v))
+        if not all(math.isfinite(x) for x in a):
+            raise ValueError("periphery %s must be finite, got %r" % (name, a))
+        return a
+    radii = floats([spec["radius"]] * 3, 3, "radius") if shape == "sphere" else floats(spec["radii"], 3, "radii")
+    if not all(x > 0.0 for x in radii):
+        raise ValueError("periphery %s must be finite and > 0, got %r" % (want, radii if want == "radii" else radii[0]))
+    k = floats([spec["k"]], 1, "k")[0]
+    if not k >= 0.0:
+        raise ValueError("periphery k must be finite and >= 0, got %r" % k)
+    center = floats(spec.get("center", (0.0, 0.0, 0.0)), 3, "center")
+    quat = floats(spec.get("quat", (1.0, 0.0, 0.0, 0.0)), 4, "quat")
+    q2 = quat[0] * quat[0] + quat[1] * quat[1] + quat[2] * quat[2] + quat[3] * quat[3]
+    if not abs(q2 - 1.0) <= 1e-12:
+        raise ValueError("periphery quat must be a unit quaternion to 1e-12, |q|^2 - 1 = %g" % (q2 - 1.0))
+    if shape == "ellipsoid_fast" and quat != [1.0, 0.0, 0.0, 0.0]:
+        raise ValueError("periphery shape 'ellipsoid_fast' has no orientation (HP1.cpp:4155-4159): quat must be "
+                         "(1, 0, 0, 0)")
+    return shape, radii, k, center, quat
+
+
+def periphery_force(periphery, center, radius, out=None, accumulate=False, stats=None):
+    """the wall force of a periphery dict (check_periphery) on every bead (mhip_periphery_force): written to (or,
+    accumulate=True, added into) out [n, 3] -> (out, colliding [1] int32, max_overlap [1] float64), the two statistics
+    left on the device; stats: an optional (int32 [1], float64 [1]) pair to write them into"""
+    shape, radii, k, c, q = periphery if isinstance(periphery, tuple) else check_periphery(periphery)
+    n = center.shape[0]
+    if tuple(center.shape) != (n, 3) or tuple(radius.shape) != (n,):
+        raise ValueError("center must have shape [n, 3] and radius [n], got %s and %s" % (tuple(center.shape),
+                                                                                          tuple(radius.shape)))
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs out")
+        out = torch.empty((n, 3), dtype=torch.float64, device=center.device)
+    if stats is None:
+        stats = (torch.empty(1, dtype=torch.int32, device=center.device),
+                 torch.empty(1, dtype=torch.float64, device=center.device))
+    col, mx = stats
+    cfg = capi.Periphery(PERIPHERY_SHAPES[shape], (C.c_double * 3)(*c), (C.c_double * 4)(*q), (C.c_double * 3)(*radii), k)
+    capi.check(capi.load().mhip_periphery_force(C.byref(cfg), n, _ptr(center, cols=3, name="center"),
+                                                _ptr(radius, name="radius"), _ptr(out, cols=3, name="out"),
+                                                1 if accumulate else 0, C.c_void_p(col.data_ptr()),
+                                                C.c_void_p(mx.data_ptr()), _stream()))
+    return out, col, mx
+
+
+# ---- active euchromatin force dipoles (HP1.cpp:2796-2826, :3770-3853, :4286-4354) --------------------------------------
+def check_active_springs(n, pairs, sigma, kon, koff, keys=None, counter=None):
+    """host-side validation of an active spring set (no library call) -> (pairs int32 [m, 2] host, sigma, kon, koff, keys
+    uint64 [m] / None, counter uint64 [m] / None)"""
+    import math
+    import numpy as np
+    p = pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
+    if p.size == 0:
+        p = p.reshape(0, 2)
+    if p.ndim != 2 or p.shape[1] != 2 or not (p.dtype.kind in "iu" or p.size == 0):
+        raise ValueError("active spring pairs must be integers of shape [m, 2], got %s %s" % (p.dtype, p.shape))
+    if p.size and (p.min() < 0 or p.max() >= n):
+        raise ValueError("active spring pairs: an index outside [0, %d)" % n)
+    if p.size and (p[:, 0] == p[:, 1]).any():
+        raise ValueError("active spring pairs: a spring from a body to itself (spring %d)"
+                         % int(np.argmax(p[:, 0] == p[:, 1])))
+    m = p.shape[0]
+    sigma, kon, koff = float(sigma), float(kon), float(koff)
+    if not math.isfinite(sigma):
+        raise ValueError("active sigma must be finite, got %r" % sigma)
+    for name, v in (("kon", kon), ("koff", koff)):
+        if not (v > 0.0 and math.isfinite(v)):
+            raise ValueError("active %s must be finite and > 0, got %r" % (name, v))
+
+    def ints(t, name):
+        if t is None:
+            return None
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        if a.dtype.kind not in "iu" or a.shape != (m,):
+            raise ValueError("active %s must be integers of shape [%d], got %s %s" % (name, m, a.dtype, a.shape))
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= 2 ** 63):
+            raise ValueError("active %s must lie in [0, 2^63)" % name)
+        return np.ascontiguousarray(a, dtype=np.uint64)
+    return np.ascontiguousarray(p, dtype=np.int32), sigma, kon, koff, ints(keys, "keys"), ints(counter, "counter")
+
+
+class ActiveSprings:
+    """m springs over n bodies that switch on and off as two-state Poisson processes and push their beads apart while on
+    (mhip_active_springs_*): sample() -> force(center) -> ... -> advance(dt).  keys (default: the spring's index) and
+    counter (default 0) key each spring's Philox stream."""
+
+    def __init__(self, n, pairs, sigma, kon, koff, keys=None, counter=None):
+        p, sigma, kon, koff, ks, cs = check_active_springs(n, pairs, sigma, kon, koff, keys, counter)
+        self.n, self.num_springs = int(n), p.shape[0]
+        self.pairs, self.sigma, self.kon, self.koff = p, sigma, kon, koff
+        h = C.c_void_p()
+        cp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        capi.check(capi.load().mhip_active_springs_create(C.byref(h), self.n, p.shape[0], cp(p), sigma, kon, koff,
+                                                          cp(ks), cp(cs), _stream()))
+        self._h = h
+
+    def sample(self, switches=None):
+        """springs whose time has come switch; -> switches int32 [2] = (on, off) of this call, left on the device"""
+        sw = torch.empty(2, dtype=torch.int32, device="cuda") if switches is None else switches
+        capi.check(capi.load().mhip_active_springs_sample(self._h, _ptr(sw, torch.int32, name="switches"), _stream()))
+        return sw
+
+    def force(self, center, out=None, accumulate=False, active=None):
+        """the force dipoles of the springs in state 1: written to (or, accumulate=True, added into) out [n, 3]
+        -> (out, active int32 [1] = their number, left on the device)"""
+        if tuple(center.shape) != (self.n, 3):
+            raise ValueError("center must have shape [%d, 3], got %s" % (self.n, tuple(center.shape)))
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs out")
+            out = torch.empty((self.n, 3), dtype=torch.float64, device=center.device)
+        if active is None:
+            active = torch.empty(1, dtype=torch.int32, device=center.device)
+        capi.check(capi.load().mhip_active_springs_force(self._h, _ptr(center, cols=3, name="center"),
+                                                         _ptr(out, cols=3, name="out"), 1 if accumulate else 0,
+                                                         _ptr(active, torch.int32, name="active"), _stream()))
+        return out, active
+
+    def advance(self, dt):
+        dt = float(dt)
+        if not (dt >= 0.0 and dt < float("inf")):
+            raise ValueError("dt must be finite and >= 0, got %r" % dt)
+        capi.check(capi.load().mhip_active_springs_advance(self._h, dt, _stream()))
+
+    def state(self, device="cuda"):
+        """-> (state int32 [m], next_time [m], elapsed [m], counter int64 [m]) device tensors (copies)"""
+        m = self.num_springs
+        st = torch.empty(m, dtype=torch.int32, device=device)
+        nt, el = (torch.empty(m, dtype=torch.float64, device=device) for _ in range(2))
+        ct = torch.empty(m, dtype=torch.int64, device=device)
+        capi.check(capi.load().mhip_active_springs_get_state(self._h, _ptr(st, torch.int32), _ptr(nt), _ptr(el),
+                                                             _u64(ct, "counter"), _stream()))
+        return st, nt, el, ct
+
+    def set_state(self, state=None, next_time=None, elapsed=None, counter=None):
+        """device tensors of the shapes state() returns into the handle; None = unchanged; values are not checked"""
+        m = self.num_springs
+        for name, t in (("state", state), ("next_time", next_time), ("elapsed", elapsed), ("counter", counter)):
+            if t is not None and tuple(t.shape) != (m,):
+                raise ValueError("%s must have shape [%d], got %s" % (name, m, tuple(t.shape)))
+        capi.check(capi.load().mhip_active_springs_set_state(
+            self._h, _ptr(state, torch.int32, allow_none=True, name="state"),
+            _ptr(next_time, allow_none=True, name="next_time"), _ptr(elapsed, allow_none=True, name="elapsed"),
+            _ptr(counter, torch.int64, allow_none=True, name="counter"), _stream()))
+
+    def renumber(self, new_of_old):
+        """the bodies were permuted: new_of_old int32 [n]"""
+        if tuple(new_of_old.shape) != (self.n,):
+            raise ValueError("new_of_old must have shape [%d], got %s" % (self.n, tuple(new_of_old.shape)))
+        capi.check(capi.load().mhip_active_springs_renumber(self._h, _ptr(new_of_old, torch.int32, name="new_of_old"),
+                                                            _stream()))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            capi.load().mhip_active_springs_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

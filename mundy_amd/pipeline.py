@@ -33,6 +33,13 @@ crosslinkers= adds the kinetic Monte Carlo stage of the HP1 app to the chain ste
         -> KMC at the positions of the start of the step: right heads bind and unbind
         -> spring forces + the doubly bound crosslinkers as springs (+ external_force) -> the chain step as above
 
+periphery= / active_forces= add the last two force terms of that app's step (HP1.cpp:4733-4741, :4839-4842): the wall
+of the nucleus and the active euchromatin force dipoles, in the reference's order:
+
+    ... -> crosslinker KMC -> active sampling (springs whose time has come switch on or off)
+        -> spring forces -> crosslinker springs -> periphery force -> active force dipoles (+ external_force)
+        -> the chain step as above -> Euler update -> the active springs' timers advance by dt
+
 hertz_friction= replaces the frictionless Hertz force by the reference's frictional rod contact with a per-pair
 tangential history (SpherocylinderSegmentSpherocylinderSegmentFrictionalHertzianContact.cpp:384-518, run every step by
 CollidingOverdampedFrictionalSperm.cpp:1553-1731):
@@ -69,6 +76,10 @@ class StepStats:
     crosslinker_binds: int = 0    # ... right heads that bound this step
     crosslinker_unbinds: int = 0  # ... and that unbound
     max_crosslinker_length: float = 0.0  # ... the longest doubly bound crosslinker at this step's force evaluation
+    periphery_colliding: int = 0         # periphery=: beads in contact with the wall at this step's force evaluation
+    max_periphery_overlap: float = 0.0   # ... the deepest of them (ellipsoid_fast: the largest level-set value)
+    active_springs: int = 0              # active_forces=: springs in the active state at this step's force evaluation
+    active_switches: tuple = (0, 0)      # ... springs that switched (on, off) this step
 
 
 class ContactStepper:
@@ -80,7 +91,7 @@ class ContactStepper:
                  conservative_ellipsoid_box=False, friction_method="apgd", contact_model="lcp", youngs_modulus=1000.0,
                  poisson_ratio=0.3, growth_rate=None, division_length=None, capacity=None, ids=None, springs=None,
                  brownian_kt=None, rng_keys=None, rng_counter=None, hertz_friction=None, hertz_damping=(0.0, 0.0),
-                 hertz_density=1.0, crosslinkers=None):
+                 hertz_density=1.0, crosslinkers=None, periphery=None, active_forces=None):
         """kind = "sphere" | "spherocylinder" | "mixed".  Mixed systems (BASELINE configs[4]) pass kinds [n] int32
         (0 sphere, 1 spherocylinder, 2 ellipsoid) and shape [n, 3] = (r,-,-) / (r,L,-) / (r1,r2,r3) instead of
         radius / length.
@@ -111,7 +122,17 @@ class ContactStepper:
         the spring a doubly bound crosslinker is; bind_rate (A) and unbind_rate (k_off) >= 0, kt > 0 (the Boltzmann
         weight of binding), capture_radius > 0 (no binding beyond it), skin >= 0 (buffer of the candidate search).  keys
         (integers in [0, 2^63), default arange(m)) and counter (default 0) key each crosslinker's Philox stream.  The
-        stepper then owns ids [n] (int64, arange(n): the order candidates are walked in, kept by reorder_bodies)."""
+        stepper then owns ids [n] (int64, arange(n): the order candidates are walked in, kept by reorder_bodies).
+        periphery = dict(shape="sphere" | "ellipsoid" | "ellipsoid_fast", radius= (sphere) or radii= (3 semi-axes), k=,
+        center=(0, 0, 0), quat=(1, 0, 0, 0)): the wall of the nucleus, a linear spring of constant k >= 0 on every bead
+        that touches it ("ellipsoid": exact distance; "ellipsoid_fast": the reference's level-set force, no quat); the
+        chain step (spheres, free space, either contact model).  Every bead radius must be below the smallest periphery
+        radius.  scale_periphery(factor) shrinks or grows it between steps.
+        active_forces = dict(springs=, sigma=, kon=, koff=, keys=None, counter=None): the springs= pairs listed in
+        springs [ma] (indices, no repeats) switch on at the rate kon and off at the rate koff (> 0) and push their
+        beads apart with a force of magnitude sigma while on; keys (integers in [0, 2^63), default arange(ma)) and
+        counter (default 0) key each one's Philox stream.  Needs springs=.  The timers advance by dt at the end of every
+        step that integrates."""
         if kind not in ("sphere", "spherocylinder", "mixed"):
             raise ValueError("kind must be 'sphere', 'spherocylinder' or 'mixed'")
         if contact_model not in ("lcp", "hertz"):
@@ -132,6 +153,10 @@ class ContactStepper:
         if crosslinkers is not None:  # (checked before anything reaches the device)
             xl_spec = self._check_crosslinkers(kind, center.shape[0], periodic_box, friction, contact_cutoff, growth_rate,
                                                hertz_friction, crosslinkers)
+        nucleus_spec = None
+        if periphery is not None or active_forces is not None:  # (checked before anything reaches the device)
+            nucleus_spec = self._check_nucleus(kind, center.shape[0], radius, periodic_box, friction, contact_cutoff,
+                                               growth_rate, hertz_friction, springs, periphery, active_forces)
         self.hertz_friction = None
         if hertz_friction is not None:  # (checked before anything reaches the device)
             self._check_hertz_friction(contact_model, kind, rod_kinematics, growth_rate, springs, brownian_kt,
@@ -147,7 +172,8 @@ class ContactStepper:
                                radius, quat, length, periodic_box, capacity, ids)
         elif division_length is not None or capacity is not None or ids is not None:
             raise ValueError("division_length, capacity and ids belong to growth mode: pass growth_rate")
-        self.chain = springs is not None or brownian_kt is not None or crosslinkers is not None
+        self.chain = (springs is not None or brownian_kt is not None or crosslinkers is not None or
+                      nucleus_spec is not None)
         if self.chain:  # (checked before anything reaches the device)
             chain_spec = self._check_chain(kind, center.shape[0], periodic_box, friction, contact_cutoff, springs,
                                            brownian_kt, rng_keys, rng_counter)
@@ -221,6 +247,9 @@ class ContactStepper:
         self.crosslinkers = None
         if xl_spec is not None:
             self._init_crosslinkers(xl_spec)
+        self.periphery = self.active = None
+        if nucleus_spec is not None:
+            self._init_nucleus(*nucleus_spec)
 
     # -- frictional Hertz contact (FrictionalHertzianContact.cpp:384-518) -------------------------------------------------
     @staticmethod
@@ -446,10 +475,119 @@ class ContactStepper:
         """-> (left, right) int32 [m] device tensors in the current body numbering; right == left: singly bound"""
         return self.crosslinkers.state(self.center.device)
 
-    def external_velocity(self, external_force=None):
-        """U_ext = M (F_spring + F_crosslinker + F_ext) + U_brown into self.u_ext (the rng counters advance; with
-        crosslinkers, their KMC step runs first)"""
-        self._chain_stats.zero_()
+    # -- the nuclear periphery and the active force dipoles (HP1.cpp:4063-4354) -------------------------------------------
+    _ACTIVE_KEYS = ("springs", "sigma", "kon", "koff", "keys", "counter")
+
+    @staticmethod
+    def _check_nucleus(kind, n, radius, box, friction, contact_cutoff, growth_rate, hertz_friction, springs, periphery,
+                       active):
+        import numpy as np
+        what = "periphery / active_forces"
+        if kind != "sphere":
+            raise ValueError("%s are wired for spheres only (the chain step), not %r" % (what, kind))
+        if growth_rate is not None:
+            raise ValueError("%s do not run in growth mode" % what)
+        if hertz_friction is not None:
+            raise ValueError("%s take no hertz_friction (the rod contact)" % what)
+        if friction is not None or contact_cutoff is not None:
+            raise ValueError("%s take no friction or contact_cutoff" % what)
+        if box is not None:
+            raise ValueError("%s take no periodic_box (the nucleus is a closed wall)" % what)
+        per = act = None
+        if periphery is not None:
+            per = ops.check_periphery(periphery)
+        if active is not None:
+            if not isinstance(active, dict):
+                raise ValueError("active_forces must be a dict with the keys %s" % ", ".join(ContactStepper._ACTIVE_KEYS))
+            unknown = sorted(set(active) - set(ContactStepper._ACTIVE_KEYS))
+            if unknown:
+                raise ValueError("active_forces: unknown key(s) %s" % ", ".join(unknown))
+            missing = [k for k in ContactStepper._ACTIVE_KEYS if k not in active and k not in ("keys", "counter")]
+            if missing:
+                raise ValueError("active_forces: missing key(s) %s" % ", ".join(missing))
+            if springs is None:
+                raise ValueError("active_forces needs springs=: its springs are indices into those pairs")
+            if not isinstance(springs, (tuple, list)) or len(springs) != 4:
+                raise ValueError("springs must be (pairs, 'hookean' | 'fene', k, r)")
+            pairs = springs[0]
+            p = pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
+            p = p.reshape(-1, 2)
+            idx = active["springs"]
+            idx = idx.detach().cpu().numpy() if isinstance(idx, torch.Tensor) else np.asarray(idx)
+            if idx.ndim != 1 or not (idx.dtype.kind in "iu" or idx.size == 0):
+                raise ValueError("active_forces springs must be integers of shape [ma], got %s %s" % (idx.dtype, idx.shape))
+            idx = idx.astype(np.int64)
+            if idx.size and (idx.min() < 0 or idx.max() >= p.shape[0]):
+                raise ValueError("active_forces springs: an index outside [0, %d)" % p.shape[0])
+            if np.unique(idx).size != idx.size:
+                raise ValueError("active_forces springs: a spring is listed more than once")
+            act = ops.check_active_springs(n, p[idx], active["sigma"], active["kon"], active["koff"],
+                                           active.get("keys"), active.get("counter"))
+        # the one read of the beads (a reduction and a readback for a device tensor): after both dicts have passed
+        rmax = float(radius.max()) if radius.shape[0] else 0.0
+        if per is not None and rmax >= min(per[1]):
+            raise ValueError("periphery: a bead radius %g >= the smallest periphery radius %g" % (rmax, min(per[1])))
+        return per, act, rmax
+
+    def _init_nucleus(self, per, act, rmax):
+        dev = self.center.device
+        self._max_bead_radius = rmax
+        if per is not None:
+            self.periphery = dict(shape=per[0], radii=list(per[1]), k=per[2], center=list(per[3]), quat=list(per[4]))
+        if act is not None:
+            self.active = ops.ActiveSprings(self.center.shape[0], *act)
+        # [.., deepest wall overlap, (beads at the wall, active springs) as two int32, active switches (on, off) as two]
+        self._chain_stats = torch.zeros(9, dtype=torch.float64, device=dev)
+
+    def _periphery_spec(self):
+        p = self.periphery
+        return p["shape"], p["radii"], p["k"], p["center"], p["quat"]
+
+    def scale_periphery(self, factor):
+        """the compression run (HP1.cpp:4715-4726): every periphery radius *= factor, between steps"""
+        if self.periphery is None:
+            raise ValueError("scale_periphery needs periphery=")
+        factor = float(factor)
+        if not (factor > 0.0 and factor < math.inf):
+            raise ValueError("scale_periphery: factor must be finite and > 0, got %r" % factor)
+        radii = [r * factor for r in self.periphery["radii"]]
+        if not all(r < math.inf for r in radii) or self._max_bead_radius >= min(radii):
+            raise ValueError("scale_periphery: a bead radius %g >= the smallest periphery radius %g"
+                             % (self._max_bead_radius, min(radii)))
+        self.periphery["radii"] = radii
+
+    def active_state(self):
+        """-> (state int32, next_time, elapsed, counter int64) [ma] device tensors of the active springs (copies)"""
+        return self.active.state(self.center.device)
+
+    def _nucleus_force(self, external_force):
+        """the force stage in the reference's order (HP1.cpp:4733-4741): crosslinker KMC, active sampling, springs,
+        crosslinker springs, periphery, active force dipoles, external force; every term after the first is added into
+        self.spring_force"""
+        st, si = self._chain_stats, self._chain_stats.view(torch.int32)
+        force, written = self.spring_force, False
+        if self.crosslinkers is not None:
+            self.crosslinker_kmc()
+        if self.active is not None:
+            self.active.sample(switches=si[16:18])
+        if self.springs is not None:
+            self.springs.force(self.center, out=force, stats=(si[4:5], st[1:2]))
+            written = True
+        if self.crosslinkers is not None:
+            self.crosslinkers.force(self.center, out=force, accumulate=written, stats=(si[10:11], st[4:5]))
+            written = True
+        if self.periphery is not None:
+            ops.periphery_force(self._periphery_spec(), self.center, self.radius, out=force, accumulate=written,
+                                stats=(si[14:15], st[6:7]))
+            written = True
+        if self.active is not None:
+            self.active.force(self.center, out=force, accumulate=written, active=si[15:16])
+        if external_force is not None:
+            ops.axpby(1.0, external_force.reshape(-1), 1.0, force.view(-1))
+        return force
+
+    def _chain_force(self, external_force):
+        """F_spring + F_crosslinker + F_ext (None: no force at all); with crosslinkers, their KMC step runs first"""
         force = None
         if self.crosslinkers is not None:
             self.crosslinker_kmc()
@@ -467,6 +605,16 @@ class ContactStepper:
                 ops.axpby(1.0, external_force.reshape(-1), 1.0, force.view(-1))
         elif external_force is not None:
             force = external_force
+        return force
+
+    def external_velocity(self, external_force=None):
+        """U_ext = M (F_spring + F_crosslinker + F_periphery + F_active + F_ext) + U_brown into self.u_ext (the rng
+        counters advance; with crosslinkers, their KMC step runs first, then the active springs' sampling)"""
+        self._chain_stats.zero_()
+        if self.periphery is not None or self.active is not None:
+            force = self._nucleus_force(external_force)
+        else:
+            force = self._chain_force(external_force)
         ops.drag_velocity(self.mob_trans, force, out=self.u_ext)
         if self.brownian_kt is not None:
             ops.brownian_velocity(self.rng_keys, self.rng_counter, self.brownian_kt, self.dt, self.mob_trans,
@@ -602,6 +750,10 @@ class ContactStepper:
         if self.crosslinkers is not None:  # both heads (in the numbering of the snapshot), keys, counters, bound count
             snap["_xl"] = self.crosslinker_state() + (self.xl_keys.clone(), self.xl_counter.clone(),
                                                       self.crosslinker_bound)
+        if self.periphery is not None:  # its size (scale_periphery)
+            snap["_periphery"] = list(self.periphery["radii"])
+        if self.active is not None:  # states, timers and counters
+            snap["_active"] = self.active_state()
         return snap
 
     def restore(self, snap):
@@ -625,6 +777,12 @@ class ContactStepper:
                 self.xl_keys.copy_(v[2])
                 self.xl_counter.copy_(v[3])
                 self.crosslinker_bound = v[4]
+                continue
+            if k == "_periphery":
+                self.periphery["radii"] = list(v)
+                continue
+            if k == "_active":
+                self.active.set_state(*v)
                 continue
             getattr(self, k).copy_(v)
 
@@ -664,11 +822,15 @@ class ContactStepper:
                 t.copy_(ops.gather_rows(perm, t) if t.dtype == torch.float64 else t[perm.long()])
         if getattr(self, "springs", None) is not None:
             self._renumber_springs(perm)
-        if getattr(self, "crosslinkers", None) is not None:  # heads through the inverse permutation, a new search
+        crosslinkers, active = getattr(self, "crosslinkers", None), getattr(self, "active", None)
+        if crosslinkers is not None or active is not None:  # both are renumbered through the inverse permutation
             inv = torch.empty(perm.shape[0], dtype=torch.int32, device=perm.device)
             inv[perm.long()] = torch.arange(perm.shape[0], dtype=torch.int32, device=perm.device)
-            self.crosslinkers.renumber(inv)
+        if crosslinkers is not None:  # heads, and a new search
+            crosslinkers.renumber(inv)
             self._new_crosslinker_search()
+        if active is not None:  # endpoints; states and timers stay
+            active.renumber(inv)
         if self.hertz_friction is not None:  # previous velocities move with their rows, the history through the inverse
             self.prev_velocity = ops.gather_rows(perm, self.prev_velocity)
             inv = torch.empty_like(perm)
@@ -899,6 +1061,8 @@ class ContactStepper:
             mark("solve")
         if integrate:
             self.integrate()
+            if self.chain and self.active is not None:  # update_euchromatin_state_time (HP1.cpp:4839-4842)
+                self.active.advance(self.dt)
         mark("integrate")
         st.num_contacts = self.contact_pairs.shape[0]
         st.num_iters, st.residual, st.converged = res.num_iters, res.residual, res.converged
@@ -917,6 +1081,10 @@ class ContactStepper:
                 if int(hi[10]):
                     raise RuntimeError("%d FENE crosslinker(s) stretched to L >= r_max: no force (reduce dt)"
                                        % int(hi[10]))
+            if self.periphery is not None or self.active is not None:  # (the same read)
+                hi = h.view(torch.int32)
+                st.periphery_colliding, st.max_periphery_overlap = int(hi[14]), float(h[6])
+                st.active_springs, st.active_switches = int(hi[15]), (int(hi[16]), int(hi[17]))
         elif self.hertz_friction is not None:  # the one read of the step: (max_overlap, num_sliding)
             h = self._fr_stats.cpu()
             st.max_overlap, st.num_sliding = float(h[0]), int(h.view(torch.int64)[1])
