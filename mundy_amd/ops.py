@@ -5,8 +5,10 @@ solve_cqpp, solve_lcp, PGDConfig, SolveResult (mundy_math/convex.hpp).  torch is
 current stream); all arithmetic runs in the HIP library.  float64 everywhere; pairs are int32 [C, 2].
 """
 import ctypes as C
+import math
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from . import capi
@@ -36,6 +38,56 @@ def _ptr(t, dtype=torch.float64, cols=None, name="tensor", allow_none=False):
 
 def _new(ref, *shape, dtype=torch.float64):
     return torch.empty(shape, dtype=dtype, device=ref.device)
+
+
+class _Handle:
+    """owner of one library handle self._h; _destroy names the C function that frees it.  close() is idempotent and safe
+    on an object whose constructor raised before the handle existed"""
+    _h = None
+    _destroy = None
+
+    def close(self):
+        if self._h:
+            getattr(capi.load(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- host-side validation shared by the wrappers and the stepper (no library call) -----------------------------------
+def _finite_nonneg(value, name):
+    v = float(value)
+    if not (v >= 0.0 and v < float("inf")):
+        raise ValueError("%s must be finite and >= 0, got %r" % (name, value))
+    return v
+
+
+def check_dict_spec(spec, what, keys, optional=()):
+    """a keyword given as a dict: it is one, holds no key outside `keys`, and every key not in `optional`"""
+    if not isinstance(spec, dict):
+        raise ValueError("%s must be a dict with the keys %s" % (what, ", ".join(keys)))
+    unknown = sorted(set(spec) - set(keys))
+    if unknown:
+        raise ValueError("%s: unknown key(s) %s" % (what, ", ".join(unknown)))
+    missing = [k for k in keys if k not in spec and k not in optional]
+    if missing:
+        raise ValueError("%s: missing key(s) %s" % (what, ", ".join(missing)))
+
+
+def check_philox_ints(t, count, name, dtype=np.int64):
+    """Philox keys / counters: integers of shape [count] in [0, 2^63) -> contiguous host array of dtype (None stays None)"""
+    if t is None:
+        return None
+    a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    if a.dtype.kind not in "iu" or a.shape != (count,):
+        raise ValueError("%s must be integers of shape [%d], got %s %s" % (name, count, a.dtype, a.shape))
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= 2 ** 63):
+        raise ValueError("%s must lie in [0, 2^63)" % name)
+    return np.ascontiguousarray(a, dtype=dtype)
 
 
 def device_info():
@@ -316,13 +368,6 @@ def hertz_contact_force(pairs, sep, radius, youngs_modulus=1000.0, poisson_ratio
     return f, mx
 
 
-def _finite_nonneg_param(value, name):
-    v = float(value)
-    if not (v >= 0.0 and v < float("inf")):
-        raise ValueError("%s must be finite and >= 0, got %r" % (name, value))
-    return v
-
-
 def hertz_friction_force(pairs, sep, normal, arc_s, arc_t, seg, radius, velocity_prev, tang_disp, mu, dt,
                          damping=(0.0, 0.0), density=1.0, youngs_modulus=1000.0, poisson_ratio=0.3, out=None,
                          stats=None):
@@ -334,9 +379,9 @@ def hertz_friction_force(pairs, sep, normal, arc_s, arc_t, seg, radius, velocity
     c, n = pairs.shape[0], radius.shape[0]
     E, E0 = _material(youngs_modulus, n, "youngs_modulus", 0.0, float("inf"))
     nu, nu0 = _material(poisson_ratio, n, "poisson_ratio", 0.0, 1.0)
-    prm = capi.HertzFrictionParams(_finite_nonneg_param(mu, "mu"), _finite_nonneg_param(damping[0], "normal damping"),
-                                   _finite_nonneg_param(damping[1], "tangential damping"),
-                                   _finite_nonneg_param(density, "density"), _finite_nonneg_param(dt, "dt"))
+    prm = capi.HertzFrictionParams(_finite_nonneg(mu, "mu"), _finite_nonneg(damping[0], "normal damping"),
+                                   _finite_nonneg(damping[1], "tangential damping"),
+                                   _finite_nonneg(density, "density"), _finite_nonneg(dt, "dt"))
     if tuple(tang_disp.shape) != (c, 3):
         raise ValueError("tang_disp must have shape [%d, 3], got %s" % (c, tuple(tang_disp.shape)))
     if tuple(velocity_prev.shape) != (n, 6):
@@ -382,13 +427,14 @@ def carry_contact_history(pairs_old, hist_old, pairs_new, new_of_old=None, want_
 
 
 # ---- broad phase (GenNeighborLinks, mundy_mesh/GenNeighborLinkers.hpp:294-866) ---------------------------------------
-class GenNeighborLinks:
+class GenNeighborLinks(_Handle):
     """Builder-style mirror of mundy::mesh::GenNeighborLinks: set_* -> concretize() -> generate().
 
     generate(aabb, center, bounding_radius) returns True when a search was performed (first call, or some centre moved
     more than half the search buffer, :510-543, :603-615); the links are then available as .pairs ([P, 2] int32,
     sorted by (source, target)), .row_ptr / .col (CSR).
     """
+    _destroy = "mhip_broadphase_destroy"
 
     def __init__(self):
         h = C.c_void_p()
@@ -424,7 +470,6 @@ class GenNeighborLinks:
         if box is None:
             self._cfg.periodic = 0
         else:
-            import numpy as np
             a = np.asarray(box, dtype=np.float64)
             if a.shape == (3,):
                 self._cfg.periodic = 1
@@ -571,17 +616,6 @@ class GenNeighborLinks:
         self._generated = True
         return True
 
-    def close(self):
-        if self._h:
-            capi.load().mhip_broadphase_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---- convex (mundy_math/convex.hpp) ----------------------------------------------------------------------------------
 @dataclass
@@ -648,8 +682,9 @@ def gemv(A, x):
     return y
 
 
-class ContactOperator:
+class ContactOperator(_Handle):
     """Matrix-free A = dt D^T M D over a neighbour list (the LinearOp of seam S2; apply(x, y) as convex.hpp:133-136)."""
+    _destroy = "mhip_contact_op_destroy"
 
     def __init__(self, pairs, normal, mob_trans, dt, ra=None, rb=None, mob_rot=None, rod=None, priority=None):
         """rod = (arc_s, arc_t, seg): spherocylinders with rod-compressed lever arms (mhip_contact_op_create_rods).
@@ -769,17 +804,6 @@ class ContactOperator:
         a, b, n = C.c_double(), C.c_double(), C.c_size_t()
         capi.check(capi.load().mhip_contact_op_get_profile(self._h, C.byref(a), C.byref(b), C.byref(n)))
         return a.value, b.value, int(n.value)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            capi.load().mhip_contact_op_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _state(x0, state):
@@ -913,7 +937,6 @@ def curve_keys(center, lo, hi, level, key_table):
 def hilbert_key_table(level):
     """table[ix, iy, iz] = position of the lattice cell along mundy::math::hilbert_3d (Hilbert.hpp:48-83): the library's
     own generator (host code, needs no GPU); numpy int32 array of shape (2^level,) * 3"""
-    import numpy as np
     n = 1 << int(level)
     table = np.empty((n, n, n), dtype=np.int32)
     capi.check(capi.load().mhip_hilbert_key_table(int(level), C.c_void_p(table.ctypes.data)))
@@ -939,13 +962,6 @@ def select_contacts(sep, cutoff):
 
 
 # ---- growth and division of spherocylinders (Bacteria.cpp:905-966, :685-748) -------------------------------------------
-def _finite_nonneg(value, name):
-    v = float(value)
-    if not (v >= 0.0 and v < float("inf")):
-        raise ValueError("%s must be finite and >= 0, got %r" % (name, value))
-    return v
-
-
 def select_dividing(length, division_length):
     """divide_bacteria's mark + partial_sum (mhip_select_dividing): (parent_of, num_born) -- int32 ascending indices of
     the bodies with length > division_length (strict; NaN never divides); birth k becomes row n + k"""
@@ -1060,7 +1076,6 @@ SPRING_TYPES = {"hookean": capi.SPRING_HOOKEAN, "fene": capi.SPRING_FENE}
 def _spring_param(value, m, name, positive):
     """a per-spring parameter: a number -> (None, value); an array / tensor [m] -> (host float64 array, 0.0); checked
     here on the host, as the library checks it again before any HIP call"""
-    import numpy as np
     if isinstance(value, (torch.Tensor, np.ndarray, list, tuple)):
         a = np.ascontiguousarray((value.detach().cpu().numpy() if isinstance(value, torch.Tensor) else
                                   np.asarray(value)), dtype=np.float64)
@@ -1078,7 +1093,6 @@ def _spring_param(value, m, name, positive):
 
 def check_springs(pairs, kind, k, r, n):
     """host-side validation of a spring set -> (pairs int32 [m, 2] host, type, k array / None, k0, r array / None, r0)"""
-    import numpy as np
     if kind not in SPRING_TYPES:
         raise ValueError("spring type must be 'hookean' or 'fene', got %r" % (kind,))
     p = pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
@@ -1097,10 +1111,11 @@ def check_springs(pairs, kind, k, r, n):
     return np.ascontiguousarray(p, dtype=np.int32), SPRING_TYPES[kind], ka, k0, ra, r0
 
 
-class Springs:
+class Springs(_Handle):
     """A spring set between n bodies (mhip_springs_*): kind "hookean" (r = rest length) or "fene" (r = r_max); k and r
     numbers or per-spring arrays.  force(center) -> (force [n, 3], overstretched [1] int32, max_length [1] float64), the
     two statistics left on the device.  Every body sums its terms in ascending spring index from +0.0."""
+    _destroy = "mhip_springs_destroy"
 
     def __init__(self, n, pairs, kind, k, r):
         p, t, ka, k0, ra, r0 = check_springs(pairs, kind, k, r, n)
@@ -1124,17 +1139,6 @@ class Springs:
         capi.check(capi.load().mhip_springs_force(self._h, _ptr(center, cols=3, name="center"), _ptr(f, name="out"),
                                                   C.c_void_p(over.data_ptr()), C.c_void_p(mx.data_ptr()), _stream()))
         return f, over, mx
-
-    def close(self):
-        if getattr(self, "_h", None):
-            capi.load().mhip_springs_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _u64(t, name):
@@ -1188,7 +1192,6 @@ def drag_velocity(mob_trans, force=None, out=None):
 def check_crosslinkers(n, left, right, sites, kind, k, r, bind_rate, unbind_rate, kt, capture_radius):
     """host-side validation of a crosslinker set (no library call) -> (left int32 [m], right int32 [m], sites uint8
     [n], type, k, r, bind_rate, unbind_rate, kt, capture_radius)"""
-    import numpy as np
 
     def host(a):
         return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
@@ -1235,10 +1238,11 @@ def check_crosslinkers(n, left, right, sites, kind, k, r, bind_rate, unbind_rate
             k0, r0, a0, off, kt0, cap)
 
 
-class Crosslinkers:
+class Crosslinkers(_Handle):
     """m crosslinkers over n bodies (mhip_crosslinkers_*): fixed left heads, right heads that bind to the bodies of the
     `sites` mask and unbind (right == left: singly bound); a doubly bound one is a spring of `kind` / k / r.
     set_candidates(row_ptr, col, ids) -> kmc_step(center, dt, keys, counters) -> force(center)."""
+    _destroy = "mhip_crosslinkers_destroy"
 
     def __init__(self, n, left, right, sites, kind, k, r, bind_rate, unbind_rate, kt, capture_radius):
         le, ri, si, t, k0, r0, a0, off, kt0, cap = check_crosslinkers(n, left, right, sites, kind, k, r, bind_rate,
@@ -1320,17 +1324,6 @@ class Crosslinkers:
         capi.check(capi.load().mhip_crosslinkers_renumber(self._h, _ptr(new_of_old, torch.int32, name="new_of_old"),
                                                           _stream()))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            capi.load().mhip_crosslinkers_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---- the nuclear periphery (HP1.cpp:4063-4284, NgpHP1.cpp:2409-2527) ---------------------------------------------------
 PERIPHERY_SHAPES = {"sphere": capi.PERIPHERY_SPHERE, "ellipsoid": capi.PERIPHERY_ELLIPSOID,
@@ -1341,15 +1334,7 @@ _PERIPHERY_KEYS = ("shape", "radius", "radii", "k", "center", "quat")
 def check_periphery(spec):
     """host-side validation of a periphery dict(shape=, radius= or radii=, k=, center=(0, 0, 0), quat=(1, 0, 0, 0)) (no
     library call) -> (shape name, radii (3 floats; a sphere's radius three times), k, center, quat)"""
-    import math
-    if not isinstance(spec, dict):
-        raise ValueError("periphery must be a dict with the keys %s" % ", ".join(_PERIPHERY_KEYS))
-    unknown = sorted(set(spec) - set(_PERIPHERY_KEYS))
-    if unknown:
-        raise ValueError("periphery: unknown key(s) %s" % ", ".join(unknown))
-    missing = [k for k in ("shape", "k") if k not in spec]
-    if missing:
-        raise ValueError("periphery: missing key(s) %s" % ", ".join(missing))
+    check_dict_spec(spec, "periphery", _PERIPHERY_KEYS, optional=("radius", "radii", "center", "quat"))
     shape = spec["shape"]
     if shape not in PERIPHERY_SHAPES:
         raise ValueError("periphery shape must be 'sphere', 'ellipsoid' or 'ellipsoid_fast', got %r" % (shape,))
@@ -1415,8 +1400,6 @@ def periphery_force(periphery, center, radius, out=None, accumulate=False, stats
 def check_active_springs(n, pairs, sigma, kon, koff, keys=None, counter=None):
     """host-side validation of an active spring set (no library call) -> (pairs int32 [m, 2] host, sigma, kon, koff, keys
     uint64 [m] / None, counter uint64 [m] / None)"""
-    import math
-    import numpy as np
     p = pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
     if p.size == 0:
         p = p.reshape(0, 2)
@@ -1434,23 +1417,15 @@ def check_active_springs(n, pairs, sigma, kon, koff, keys=None, counter=None):
     for name, v in (("kon", kon), ("koff", koff)):
         if not (v > 0.0 and math.isfinite(v)):
             raise ValueError("active %s must be finite and > 0, got %r" % (name, v))
-
-    def ints(t, name):
-        if t is None:
-            return None
-        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-        if a.dtype.kind not in "iu" or a.shape != (m,):
-            raise ValueError("active %s must be integers of shape [%d], got %s %s" % (name, m, a.dtype, a.shape))
-        if a.size and (int(a.min()) < 0 or int(a.max()) >= 2 ** 63):
-            raise ValueError("active %s must lie in [0, 2^63)" % name)
-        return np.ascontiguousarray(a, dtype=np.uint64)
-    return np.ascontiguousarray(p, dtype=np.int32), sigma, kon, koff, ints(keys, "keys"), ints(counter, "counter")
+    return (np.ascontiguousarray(p, dtype=np.int32), sigma, kon, koff, check_philox_ints(keys, m, "active keys", np.uint64),
+            check_philox_ints(counter, m, "active counter", np.uint64))
 
 
-class ActiveSprings:
+class ActiveSprings(_Handle):
     """m springs over n bodies that switch on and off as two-state Poisson processes and push their beads apart while on
     (mhip_active_springs_*): sample() -> force(center) -> ... -> advance(dt).  keys (default: the spring's index) and
     counter (default 0) key each spring's Philox stream."""
+    _destroy = "mhip_active_springs_destroy"
 
     def __init__(self, n, pairs, sigma, kon, koff, keys=None, counter=None):
         p, sigma, kon, koff, ks, cs = check_active_springs(n, pairs, sigma, kon, koff, keys, counter)
@@ -1517,14 +1492,3 @@ class ActiveSprings:
             raise ValueError("new_of_old must have shape [%d], got %s" % (self.n, tuple(new_of_old.shape)))
         capi.check(capi.load().mhip_active_springs_renumber(self._h, _ptr(new_of_old, torch.int32, name="new_of_old"),
                                                             _stream()))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            capi.load().mhip_active_springs_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

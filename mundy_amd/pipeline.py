@@ -54,9 +54,43 @@ import math
 
 from dataclasses import dataclass, field
 
+import numpy as np
 import torch
 
 from . import ops, synth
+
+# The chain step's statistics array, read once per step (layout: DESIGN.md 5h, shared with the C++ step apps):
+# name -> (first mode that writes it, float64 slot, int32 lane of that slot or None for the float64 itself)
+STATS = {
+    "max_overlap": ("chain", 0, None), "max_spring_length": ("chain", 1, None),
+    "springs_overstretched": ("chain", 2, 0),
+    "crosslinker_binds": ("crosslinkers", 3, 0), "crosslinker_unbinds": ("crosslinkers", 3, 1),
+    "max_crosslinker_length": ("crosslinkers", 4, None), "crosslinkers_overstretched": ("crosslinkers", 5, 0),
+    "max_periphery_overlap": ("nucleus", 6, None), "periphery_colliding": ("nucleus", 7, 0),
+    "active_springs": ("nucleus", 7, 1), "active_switches_on": ("nucleus", 8, 0),
+    "active_switches_off": ("nucleus", 8, 1)}
+STATS_LENGTH = {"chain": 3, "crosslinkers": 6, "nucleus": 9}  # float64 slots of the array, by the last mode switched on
+# two-int records that one kernel writes at once: name -> its entries, lanes 0 and 1 of one slot
+STAT_PAIRS = {"crosslinker_events": ("crosslinker_binds", "crosslinker_unbinds"),
+              "active_switches": ("active_switches_on", "active_switches_off")}
+
+
+def stat(buf, name):
+    """the entry `name` of a statistics array, for a kernel to write: a float64 [1] view, an int32 [1] view, or the
+    int32 [2] view of a pair of STAT_PAIRS"""
+    first, second = STAT_PAIRS.get(name, (name, None))
+    _, slot, lane = STATS[first]
+    if lane is None:
+        return buf[slot:slot + 1]
+    return buf.view(torch.int32)[2 * slot + lane:2 * slot + lane + (1 if second is None else 2)]
+
+
+def read_stats(buf):
+    """one copy of a statistics array to the host -> {name: value} of the entries the array is long enough to hold"""
+    h = buf.cpu()
+    f, i = h.tolist(), h.view(torch.int32).tolist()
+    return {name: f[slot] if lane is None else i[2 * slot + lane]
+            for name, (_, slot, lane) in STATS.items() if slot < len(f)}
 
 
 @dataclass
@@ -149,14 +183,13 @@ class ContactStepper:
             ops._material(youngs_modulus, center.shape[0], "youngs_modulus", 0.0, float("inf"))
             ops._material(poisson_ratio, center.shape[0], "poisson_ratio", 0.0, 1.0)
         self.youngs_modulus, self.poisson_ratio = youngs_modulus, poisson_ratio
+        chain_only = (kind, growth_rate, hertz_friction, friction, contact_cutoff, periodic_box)
         xl_spec = None
         if crosslinkers is not None:  # (checked before anything reaches the device)
-            xl_spec = self._check_crosslinkers(kind, center.shape[0], periodic_box, friction, contact_cutoff, growth_rate,
-                                               hertz_friction, crosslinkers)
+            xl_spec = self._check_crosslinkers(chain_only, center.shape[0], crosslinkers)
         nucleus_spec = None
         if periphery is not None or active_forces is not None:  # (checked before anything reaches the device)
-            nucleus_spec = self._check_nucleus(kind, center.shape[0], radius, periodic_box, friction, contact_cutoff,
-                                               growth_rate, hertz_friction, springs, periphery, active_forces)
+            nucleus_spec = self._check_nucleus(chain_only, center.shape[0], radius, springs, periphery, active_forces)
         self.hertz_friction = None
         if hertz_friction is not None:  # (checked before anything reaches the device)
             self._check_hertz_friction(contact_model, kind, rod_kinematics, growth_rate, springs, brownian_kt,
@@ -230,26 +263,50 @@ class ContactStepper:
         self.contacts = None
         self.work_mapping = None  # (xcd_tile, lanes_per_body) for ContactOperator.set_work_mapping: time only
         self.tiering = None       # ContactOperator.set_tiering mode (None: the library default): time only
+        self.profile_next = False  # per-kernel timing of the next solve (ContactOperator.set_profiling): time only
         # BUILD OPTION (None = off, the reference's behaviour: every neighbour pair is a constraint, NgpLcp.cpp:346-373):
         # only pairs within contact_cutoff of touching become constraints of this step (ballot compaction of the
         # candidate list); the dropped pairs are checked afterwards (they must satisfy g >= 0, i.e. stay inactive) and
         # the step is redone on the full list if one does not.
         self.contact_cutoff = None if contact_cutoff is None else float(contact_cutoff)
         self.cutoff_fallbacks = 0
-        self.ids = None
+        self.ids = self.springs = self.rng_keys = self.rng_counter = self.crosslinkers = None
+        self.xl_sources = self.xl_sites = self.periphery = self.active = None
         if self.growth:
             self._init_growth(growth_rate, division_length, capacity, ids, search_buffer)
-        self.springs = self.rng_keys = self.rng_counter = None
         if self.chain:
             self._init_chain(*chain_spec)
         if self.hertz_friction is not None:
             self._init_hertz_friction()
-        self.crosslinkers = None
         if xl_spec is not None:
             self._init_crosslinkers(xl_spec)
-        self.periphery = self.active = None
         if nucleus_spec is not None:
             self._init_nucleus(*nucleus_spec)
+        # the optional modes that carry state of their own: snapshot, restore and reorder_bodies call their
+        # _snapshot_<mode>() / _restore_<mode>(saved) / _renumber_<mode>(perm, inv) hooks in this order
+        on = dict(growth=self.growth, friction=self.hertz_friction is not None, springs=self.springs is not None,
+                  crosslinkers=self.crosslinkers is not None, periphery=self.periphery is not None,
+                  active=self.active is not None)
+        self._modes = [m for m, v in on.items() if v]
+
+    @staticmethod
+    def _check_chain_only(what, why_no_box, kind, growth_rate, hertz_friction, friction, contact_cutoff, box):
+        """`what` (a plural) belongs to the chain step: spheres in free space, no growth, no friction of either kind"""
+        if kind != "sphere":
+            raise ValueError("%s are wired for spheres only (the chain step), not %r" % (what, kind))
+        if growth_rate is not None:
+            raise ValueError("%s do not run in growth mode" % what)
+        if hertz_friction is not None:
+            raise ValueError("%s take no hertz_friction (the rod contact)" % what)
+        if friction is not None or contact_cutoff is not None:
+            raise ValueError("%s take no friction or contact_cutoff" % what)
+        if box is not None:
+            raise ValueError("%s take no periodic_box (%s)" % (what, why_no_box))
+
+    @staticmethod
+    def _check_orthorhombic(what, box):
+        if box is not None and np.asarray(box.cpu() if isinstance(box, torch.Tensor) else box).size != 3:
+            raise ValueError("%s takes an orthorhombic periodic box (3 edge lengths)" % what)
 
     # -- frictional Hertz contact (FrictionalHertzianContact.cpp:384-518) -------------------------------------------------
     @staticmethod
@@ -265,17 +322,12 @@ class ContactStepper:
             raise ValueError("hertz_friction does not run in growth mode")
         if springs is not None or kt is not None:
             raise ValueError("hertz_friction takes no springs or brownian_kt")
-        if box is not None:
-            import numpy as np
-            if np.asarray(box.cpu() if isinstance(box, torch.Tensor) else box).size != 3:
-                raise ValueError("hertz_friction takes an orthorhombic periodic box (3 edge lengths)")
+        ContactStepper._check_orthorhombic("hertz_friction", box)
         if not isinstance(damping, (tuple, list)) or len(damping) != 2:
             raise ValueError("hertz_damping must be (normal, tangential)")
         for name, v in (("hertz_friction", mu), ("hertz_damping[0]", damping[0]), ("hertz_damping[1]", damping[1]),
                         ("hertz_density", density)):
-            v = float(v)
-            if not (v >= 0.0 and v < math.inf):
-                raise ValueError("%s must be finite and >= 0, got %r" % (name, v))
+            ops._finite_nonneg(float(v), name)
 
     def _init_hertz_friction(self):
         n, dev = self.center.shape[0], self.center.device
@@ -289,6 +341,23 @@ class ContactStepper:
         self._fr_has_ext = False
         self.last_carried = 0      # new pairs that found their old history row at the last carry
         self.velocity = None
+
+    def _snapshot_friction(self):
+        """the history, the list it belongs to and the previous velocities"""
+        return (self.prev_velocity.clone(), None if self.tang_disp is None else self.tang_disp.clone(),
+                self.hist_pairs, self._renumber)
+
+    def _restore_friction(self, saved):
+        prev, disp, pairs, renumber = saved
+        self.prev_velocity.copy_(prev)
+        # (a clone: the stepper updates its history in place, and the next step carries it to the list in use)
+        self.tang_disp = None if disp is None else disp.clone()
+        self.hist_pairs, self._renumber = (None if disp is None else pairs.clone()), renumber
+
+    def _renumber_friction(self, perm, inv):
+        """previous velocities move with their rows, the history through the inverse at the next carry"""
+        self.prev_velocity = ops.gather_rows(perm, self.prev_velocity)
+        self._renumber = inv if self._renumber is None else inv[self._renumber.long()].contiguous()
 
     def _carry_history(self):
         """tang_disp follows the neighbour list: after a rebuild, a renumbering or a restore every pair of the new list
@@ -318,7 +387,7 @@ class ContactStepper:
                                  density=self.hertz_density, youngs_modulus=self.youngs_modulus,
                                  poisson_ratio=self.poisson_ratio, out=self.contact_force, stats=self._fr_stats)
         mark("hertz_force")
-        self._hertz_operator(rebuilt)
+        self._operator(rebuilt, pairs)
         mark("operator")
         self.op.body_sweep_vector(self.contact_force)
         mark("body_sweep")
@@ -327,7 +396,6 @@ class ContactStepper:
     # -- bead-spring chains with thermal noise (NgpHP1.cpp:3802-3990) ----------------------------------------------------
     @staticmethod
     def _check_chain(kind, n, box, friction, contact_cutoff, springs, kt, keys, counter):
-        import numpy as np
         if kind != "sphere":
             raise ValueError("springs and Brownian noise are wired for spheres only, not %r" % kind)
         if friction is not None or contact_cutoff is not None:
@@ -342,22 +410,11 @@ class ContactStepper:
             p, _, ka, k0, ra, r0 = ops.check_springs(pairs, skind, k, r, n)
             spec = (p, skind, ka if ka is not None else k0, ra if ra is not None else r0)
         if kt is not None:
-            kt = float(kt)
-            if not (kt >= 0.0 and kt < math.inf):
-                raise ValueError("brownian_kt must be finite and >= 0, got %r" % (kt,))
+            kt = ops._finite_nonneg(float(kt), "brownian_kt")
         elif keys is not None or counter is not None:
             raise ValueError("rng_keys and rng_counter key the Brownian noise: pass brownian_kt")
-
-        def ints(t, name, hi):
-            if t is None:
-                return None
-            a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-            if a.dtype.kind not in "iu" or a.shape != (n,):
-                raise ValueError("%s must be integers of shape [%d], got %s %s" % (name, n, a.dtype, a.shape))
-            if a.size and (int(a.min()) < 0 or int(a.max()) >= hi):
-                raise ValueError("%s must lie in [0, 2^63)" % name)
-            return np.ascontiguousarray(a, dtype=np.int64)
-        return spec, kt, ints(keys, "rng_keys", 2 ** 63), ints(counter, "rng_counter", 2 ** 63)
+        return (spec, kt, ops.check_philox_ints(keys, n, "rng_keys"),
+                ops.check_philox_ints(counter, n, "rng_counter"))
 
     def _init_chain(self, spec, kt, keys, counter):
         n, dev = self.center.shape[0], self.center.device
@@ -368,20 +425,22 @@ class ContactStepper:
                          torch.from_numpy(keys).to(dev))
         self.rng_counter = (torch.zeros(n, dtype=torch.int64, device=dev) if counter is None else
                             torch.from_numpy(counter).to(dev))
-        # [max_overlap, max_spring_length, overstretched (int32 in the low word)]: one read per step
-        self._chain_stats = torch.zeros(3, dtype=torch.float64, device=dev)
+        self._chain_stats = torch.zeros(STATS_LENGTH["chain"], dtype=torch.float64, device=dev)  # one read per step
         self.spring_force = torch.zeros((n, 3), dtype=torch.float64, device=dev)
         self.u_ext = torch.zeros((n, 6), dtype=torch.float64, device=dev)
         self.velocity = None
 
-    def _renumber_springs(self, perm):
-        """reorder_bodies: spring endpoints through the inverse permutation (spring order kept), new handle"""
-        import numpy as np
+    def _snapshot_springs(self):
+        return None  # (the set is fixed: nothing to save)
+
+    def _restore_springs(self, saved):
+        pass
+
+    def _renumber_springs(self, perm, inv):
+        """spring endpoints through the inverse permutation (spring order kept): a new handle from the host copy of
+        the pairs, the library has no renumbering of a spring set"""
         p, skind, k, r = self._spring_spec
-        pm = perm.cpu().numpy().astype(np.int64)
-        inv = np.empty(pm.shape[0], dtype=np.int64)
-        inv[pm] = np.arange(pm.shape[0])
-        self._spring_spec = (np.ascontiguousarray(inv[p], dtype=np.int32), skind, k, r)
+        self._spring_spec = (np.ascontiguousarray(inv.cpu().numpy()[p], dtype=np.int32), skind, k, r)
         self.springs.close()
         self.springs = ops.Springs(self.center.shape[0], *self._spring_spec)
 
@@ -390,47 +449,18 @@ class ContactStepper:
                 "keys", "counter")
 
     @staticmethod
-    def _check_crosslinkers(kind, n, box, friction, contact_cutoff, growth_rate, hertz_friction, spec):
-        import numpy as np
-        if kind != "sphere":
-            raise ValueError("crosslinkers are wired for spheres only (the chain step), not %r" % kind)
-        if growth_rate is not None:
-            raise ValueError("crosslinkers do not run in growth mode")
-        if hertz_friction is not None:
-            raise ValueError("crosslinkers take no hertz_friction (the rod contact)")
-        if friction is not None or contact_cutoff is not None:
-            raise ValueError("crosslinkers take no friction or contact_cutoff")
-        if box is not None:
-            raise ValueError("crosslinkers take no periodic_box (no minimum-image crosslinkers)")
-        if not isinstance(spec, dict):
-            raise ValueError("crosslinkers must be a dict with the keys %s" % ", ".join(ContactStepper._XL_KEYS))
-        unknown = sorted(set(spec) - set(ContactStepper._XL_KEYS))
-        if unknown:
-            raise ValueError("crosslinkers: unknown key(s) %s" % ", ".join(unknown))
-        missing = [k for k in ContactStepper._XL_KEYS if k not in spec and k not in ("right", "keys", "counter")]
-        if missing:
-            raise ValueError("crosslinkers: missing key(s) %s" % ", ".join(missing))
+    def _check_crosslinkers(chain_only, n, spec):
+        ContactStepper._check_chain_only("crosslinkers", "no minimum-image crosslinkers", *chain_only)
+        ops.check_dict_spec(spec, "crosslinkers", ContactStepper._XL_KEYS, optional=("right", "keys", "counter"))
         checked = ops.check_crosslinkers(n, spec["left"], spec.get("right"), spec["sites"], spec["kind"], spec["k"],
                                          spec["r"], spec["bind_rate"], spec["unbind_rate"], spec["kt"],
                                          spec["capture_radius"])
-        skin = float(spec["skin"])
-        if not (skin >= 0.0 and skin < math.inf):
-            raise ValueError("crosslinker skin must be finite and >= 0, got %r" % (spec["skin"],))
+        skin = ops._finite_nonneg(spec["skin"], "crosslinker skin")
         m = checked[0].shape[0]
-
-        def ints(t, name):
-            if t is None:
-                return None
-            a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-            if a.dtype.kind not in "iu" or a.shape != (m,):
-                raise ValueError("crosslinker %s must be integers of shape [%d], got %s %s" % (name, m, a.dtype, a.shape))
-            if a.size and (int(a.min()) < 0 or int(a.max()) >= 2 ** 63):
-                raise ValueError("crosslinker %s must lie in [0, 2^63)" % name)
-            return np.ascontiguousarray(a, dtype=np.int64)
-        return checked, spec["kind"], skin, ints(spec.get("keys"), "keys"), ints(spec.get("counter"), "counter")
+        return (checked, spec["kind"], skin, ops.check_philox_ints(spec.get("keys"), m, "crosslinker keys"),
+                ops.check_philox_ints(spec.get("counter"), m, "crosslinker counter"))
 
     def _init_crosslinkers(self, xl_spec):
-        import numpy as np
         (le, ri, si, _, k, r, a, off, kt, cap), skind, skin, keys, counter = xl_spec
         n, dev = self.center.shape[0], self.center.device
         m = le.shape[0]
@@ -446,9 +476,7 @@ class ContactStepper:
         self.xl_sources, self.xl_sites = torch.from_numpy(src).to(dev), torch.from_numpy(si).to(dev)
         self.xl_reach = torch.full((n,), 0.5 * cap, dtype=torch.float64, device=dev)
         self.ids = torch.arange(n, dtype=torch.int64, device=dev)
-        self._BODY_ARRAYS = ContactStepper._BODY_ARRAYS + ("ids", "xl_sources", "xl_sites")
-        # [.., crosslinker (binds, unbinds) as two int32, longest crosslinker, overstretched crosslinkers (int32)]
-        self._chain_stats = torch.zeros(6, dtype=torch.float64, device=dev)
+        self._chain_stats = torch.zeros(STATS_LENGTH["crosslinkers"], dtype=torch.float64, device=dev)
         self.xl_links = None
         self.crosslinker_rebuilds = 0  # candidate lists built so far
         self._new_crosslinker_search()
@@ -469,42 +497,38 @@ class ContactStepper:
             self.crosslinker_rebuilds += 1
             self.crosslinkers.set_candidates(self.xl_links.row_ptr, self.xl_links.col, self.ids)
         self.crosslinkers.kmc_step(self.center, self.dt, self.xl_keys, self.xl_counter,
-                                   events=self._chain_stats.view(torch.int32)[6:8])
+                                   events=stat(self._chain_stats, "crosslinker_events"))
 
     def crosslinker_state(self):
         """-> (left, right) int32 [m] device tensors in the current body numbering; right == left: singly bound"""
         return self.crosslinkers.state(self.center.device)
 
+    def _snapshot_crosslinkers(self):
+        """both heads (in the numbering of the snapshot), keys, counters, bound count"""
+        return self.crosslinker_state() + (self.xl_keys.clone(), self.xl_counter.clone(), self.crosslinker_bound)
+
+    def _restore_crosslinkers(self, saved):
+        left, right, keys, counter, self.crosslinker_bound = saved
+        self.crosslinkers.set_state(left, right)
+        self.xl_keys.copy_(keys)
+        self.xl_counter.copy_(counter)
+
+    def _renumber_crosslinkers(self, perm, inv):
+        """heads through the inverse permutation, and a new search"""
+        self.crosslinkers.renumber(inv)
+        self._new_crosslinker_search()
+
     # -- the nuclear periphery and the active force dipoles (HP1.cpp:4063-4354) -------------------------------------------
     _ACTIVE_KEYS = ("springs", "sigma", "kon", "koff", "keys", "counter")
 
     @staticmethod
-    def _check_nucleus(kind, n, radius, box, friction, contact_cutoff, growth_rate, hertz_friction, springs, periphery,
-                       active):
-        import numpy as np
-        what = "periphery / active_forces"
-        if kind != "sphere":
-            raise ValueError("%s are wired for spheres only (the chain step), not %r" % (what, kind))
-        if growth_rate is not None:
-            raise ValueError("%s do not run in growth mode" % what)
-        if hertz_friction is not None:
-            raise ValueError("%s take no hertz_friction (the rod contact)" % what)
-        if friction is not None or contact_cutoff is not None:
-            raise ValueError("%s take no friction or contact_cutoff" % what)
-        if box is not None:
-            raise ValueError("%s take no periodic_box (the nucleus is a closed wall)" % what)
+    def _check_nucleus(chain_only, n, radius, springs, periphery, active):
+        ContactStepper._check_chain_only("periphery / active_forces", "the nucleus is a closed wall", *chain_only)
         per = act = None
         if periphery is not None:
             per = ops.check_periphery(periphery)
         if active is not None:
-            if not isinstance(active, dict):
-                raise ValueError("active_forces must be a dict with the keys %s" % ", ".join(ContactStepper._ACTIVE_KEYS))
-            unknown = sorted(set(active) - set(ContactStepper._ACTIVE_KEYS))
-            if unknown:
-                raise ValueError("active_forces: unknown key(s) %s" % ", ".join(unknown))
-            missing = [k for k in ContactStepper._ACTIVE_KEYS if k not in active and k not in ("keys", "counter")]
-            if missing:
-                raise ValueError("active_forces: missing key(s) %s" % ", ".join(missing))
+            ops.check_dict_spec(active, "active_forces", ContactStepper._ACTIVE_KEYS, optional=("keys", "counter"))
             if springs is None:
                 raise ValueError("active_forces needs springs=: its springs are indices into those pairs")
             if not isinstance(springs, (tuple, list)) or len(springs) != 4:
@@ -536,8 +560,7 @@ class ContactStepper:
             self.periphery = dict(shape=per[0], radii=list(per[1]), k=per[2], center=list(per[3]), quat=list(per[4]))
         if act is not None:
             self.active = ops.ActiveSprings(self.center.shape[0], *act)
-        # [.., deepest wall overlap, (beads at the wall, active springs) as two int32, active switches (on, off) as two]
-        self._chain_stats = torch.zeros(9, dtype=torch.float64, device=dev)
+        self._chain_stats = torch.zeros(STATS_LENGTH["nucleus"], dtype=torch.float64, device=dev)
 
     def _periphery_spec(self):
         p = self.periphery
@@ -556,66 +579,64 @@ class ContactStepper:
                              % (self._max_bead_radius, min(radii)))
         self.periphery["radii"] = radii
 
+    def _snapshot_periphery(self):
+        return list(self.periphery["radii"])  # its size (scale_periphery)
+
+    def _restore_periphery(self, saved):
+        self.periphery["radii"] = list(saved)
+
+    def _renumber_periphery(self, perm, inv):
+        pass
+
     def active_state(self):
         """-> (state int32, next_time, elapsed, counter int64) [ma] device tensors of the active springs (copies)"""
         return self.active.state(self.center.device)
 
-    def _nucleus_force(self, external_force):
+    def _snapshot_active(self):
+        return self.active_state()  # states, timers and counters
+
+    def _restore_active(self, saved):
+        self.active.set_state(*saved)
+
+    def _renumber_active(self, perm, inv):
+        self.active.renumber(inv)  # endpoints; states and timers stay
+
+    def _force_stage(self, external_force):
         """the force stage in the reference's order (HP1.cpp:4733-4741): crosslinker KMC, active sampling, springs,
-        crosslinker springs, periphery, active force dipoles, external force; every term after the first is added into
-        self.spring_force"""
-        st, si = self._chain_stats, self._chain_stats.view(torch.int32)
-        force, written = self.spring_force, False
+        crosslinker springs, periphery, active force dipoles, external force; every term after the first that writes is
+        added into self.spring_force.  With no such term the caller's external_force (or None: no force at all) is
+        returned as it is, not copied."""
+        st, force, written = self._chain_stats, self.spring_force, False
         if self.crosslinkers is not None:
             self.crosslinker_kmc()
         if self.active is not None:
-            self.active.sample(switches=si[16:18])
+            self.active.sample(switches=stat(st, "active_switches"))
         if self.springs is not None:
-            self.springs.force(self.center, out=force, stats=(si[4:5], st[1:2]))
+            self.springs.force(self.center, out=force,
+                               stats=(stat(st, "springs_overstretched"), stat(st, "max_spring_length")))
             written = True
         if self.crosslinkers is not None:
-            self.crosslinkers.force(self.center, out=force, accumulate=written, stats=(si[10:11], st[4:5]))
+            self.crosslinkers.force(self.center, out=force, accumulate=written,
+                                    stats=(stat(st, "crosslinkers_overstretched"), stat(st, "max_crosslinker_length")))
             written = True
         if self.periphery is not None:
             ops.periphery_force(self._periphery_spec(), self.center, self.radius, out=force, accumulate=written,
-                                stats=(si[14:15], st[6:7]))
+                                stats=(stat(st, "periphery_colliding"), stat(st, "max_periphery_overlap")))
             written = True
         if self.active is not None:
-            self.active.force(self.center, out=force, accumulate=written, active=si[15:16])
+            self.active.force(self.center, out=force, accumulate=written, active=stat(st, "active_springs"))
+            written = True
+        if not written:
+            return external_force
         if external_force is not None:
             ops.axpby(1.0, external_force.reshape(-1), 1.0, force.view(-1))
-        return force
-
-    def _chain_force(self, external_force):
-        """F_spring + F_crosslinker + F_ext (None: no force at all); with crosslinkers, their KMC step runs first"""
-        force = None
-        if self.crosslinkers is not None:
-            self.crosslinker_kmc()
-            xl_stats = (self._chain_stats.view(torch.int32)[10:11], self._chain_stats[4:5])
-        if self.springs is not None:
-            force, _, _ = self.springs.force(self.center, out=self.spring_force,
-                                             stats=(self._chain_stats.view(torch.int32)[4:5], self._chain_stats[1:2]))
-            if self.crosslinkers is not None:
-                self.crosslinkers.force(self.center, out=force, accumulate=True, stats=xl_stats)
-            if external_force is not None:
-                ops.axpby(1.0, external_force.reshape(-1), 1.0, force.view(-1))
-        elif self.crosslinkers is not None:
-            force, _, _ = self.crosslinkers.force(self.center, out=self.spring_force, stats=xl_stats)
-            if external_force is not None:
-                ops.axpby(1.0, external_force.reshape(-1), 1.0, force.view(-1))
-        elif external_force is not None:
-            force = external_force
         return force
 
     def external_velocity(self, external_force=None):
         """U_ext = M (F_spring + F_crosslinker + F_periphery + F_active + F_ext) + U_brown into self.u_ext (the rng
         counters advance; with crosslinkers, their KMC step runs first, then the active springs' sampling)"""
         self._chain_stats.zero_()
-        if self.periphery is not None or self.active is not None:
-            force = self._nucleus_force(external_force)
-        else:
-            force = self._chain_force(external_force)
-        ops.drag_velocity(self.mob_trans, force, out=self.u_ext)
+        ops.drag_velocity(self.mob_trans, self._force_stage(external_force), out=self.u_ext)
         if self.brownian_kt is not None:
             ops.brownian_velocity(self.rng_keys, self.rng_counter, self.brownian_kt, self.dt, self.mob_trans,
                                   self.u_ext)
@@ -635,32 +656,19 @@ class ContactStepper:
             raise ValueError("growth mode has no warm start: the constraint set changes with every birth")
         if quat is None or length is None:
             raise ValueError("spherocylinders need quat and length")
-        g = float(growth_rate)
-        if not (g >= 0.0 and g < math.inf):
-            raise ValueError("growth_rate must be finite and >= 0, got %r" % (growth_rate,))
+        ops._finite_nonneg(growth_rate, "growth_rate")
         if division_length is None:
             raise ValueError("growth mode needs division_length")
-        D = float(division_length)
-        if not (D >= 0.0 and D < math.inf):
-            raise ValueError("division_length must be finite and >= 0, got %r" % (division_length,))
+        D = ops._finite_nonneg(division_length, "division_length")
         rmax = float(radius.max()) if radius.shape[0] else 0.0
         if D < 2.0 * rmax:
             raise ValueError("division_length %g < 2 * max(radius) = %g: a child's length 0.5 L - r would not be "
                              "positive" % (D, 2.0 * rmax))
-        if box is not None:
-            import numpy as np
-            if np.asarray(box.cpu() if isinstance(box, torch.Tensor) else box).size != 3:
-                raise ValueError("growth mode takes an orthorhombic periodic box (3 edge lengths)")
+        ContactStepper._check_orthorhombic("growth mode", box)
         if capacity is not None and int(capacity) < 0:
             raise ValueError("capacity must be >= 0")
         if ids is not None and (ids.dtype != torch.int64 or tuple(ids.shape) != (radius.shape[0],)):
             raise ValueError("ids must be int64 of shape [n]")
-
-    def _per_body(self):
-        """the per-body arrays a body carries (and a child copies from its parent) in growth mode"""
-        names = ["center", "quat", "radius", "length", "bounding_radius", "mob_trans", "mob_rot", "ids"]
-        names += [k for k in ("youngs_modulus", "poisson_ratio") if isinstance(getattr(self, k), torch.Tensor)]
-        return names
 
     def _init_growth(self, growth_rate, division_length, capacity, ids, search_buffer):
         self.growth_rate, self.division_length = float(growth_rate), float(division_length)
@@ -685,7 +693,7 @@ class ContactStepper:
             return
         cap = need if fresh else need + need // 8 + 16
         n = self.n
-        for name in self._per_body() + ["seg"]:
+        for name in self._body_arrays() + ["seg"]:
             old = getattr(self, name)
             buf = torch.empty((cap,) + tuple(old.shape[1:]), dtype=old.dtype, device=self.center.device)
             if name != "seg":
@@ -698,6 +706,20 @@ class ContactStepper:
         for name, buf in self._store.items():
             setattr(self, name, buf[:self.n])
 
+    def _snapshot_growth(self):
+        return self.n, self.next_id
+
+    def _restore_growth(self, saved):
+        """the views take the saved body count (restore then fills them); every list is in another numbering"""
+        self._ensure_capacity(saved[0])
+        self.n, self.next_id = saved
+        self._view()
+        self._aabb_ref = None
+        self._forget_numbering()
+
+    def _renumber_growth(self, perm, inv):
+        self._aabb_ref = None  # the corner rebuild rule starts over
+
     def grow_and_divide(self):
         """divide_bacteria -> grow_bacteria (Bacteria.cpp:926-966, :905-920) on the device: returns the birth count.
         Children are rows n + k with parent last_parent_of[k] and id next_id + k; the new bounding radii follow."""
@@ -709,7 +731,7 @@ class ContactStepper:
         ops.divide_grow_spherocylinders(n, parent_of, self.dt, self.growth_rate, s["center"], s["quat"], s["radius"],
                                         s["length"], box=self.box)
         if nb:
-            for name in self._per_body():
+            for name in self._body_arrays():
                 if name not in ("center", "quat", "radius", "length", "bounding_radius", "ids"):
                     ops.copy_parent_rows(parent_of, n, s[name])
             s["ids"][n:n + nb] = torch.arange(self.next_id, self.next_id + nb, dtype=torch.int64,
@@ -733,58 +755,28 @@ class ContactStepper:
         return rebuild
 
     # -- stages -----------------------------------------------------------------------------------------------------
-    _BODY_ARRAYS = ("center", "radius", "quat", "length", "bounding_radius", "mob_trans", "mob_rot", "shape", "kinds",
-                    "rng_keys", "rng_counter")
+    def _body_arrays(self):
+        """the names of the tensors this stepper carries per body, in any mode: what snapshot / restore save, what
+        reorder_bodies permutes, what growth mode stores with headroom and a child copies from its parent"""
+        names = ("center", "radius", "quat", "length", "bounding_radius", "mob_trans", "mob_rot", "shape", "kinds", "ids",
+                 "rng_keys", "rng_counter", "xl_sources", "xl_sites")
+        if self.contact_model == "hertz":  # (the LCP ignores the materials, and does not check them)
+            names += ("youngs_modulus", "poisson_ratio")
+        return [k for k in names if isinstance(getattr(self, k), torch.Tensor)]
 
     def snapshot(self):
-        """device copies of every per-body array (to restart a step from the same input); growth mode: and the body
-        count"""
-        if self.growth:
-            snap = {k: getattr(self, k).clone() for k in self._per_body()}
-            snap["_n"], snap["_next_id"] = self.n, self.next_id
-            return snap
-        snap = {k: getattr(self, k).clone() for k in self._BODY_ARRAYS if getattr(self, k, None) is not None}
-        if self.hertz_friction is not None:  # the history, the list it belongs to and the previous velocities
-            snap["_fr"] = (self.prev_velocity.clone(), None if self.tang_disp is None else self.tang_disp.clone(),
-                           self.hist_pairs, self._renumber)
-        if self.crosslinkers is not None:  # both heads (in the numbering of the snapshot), keys, counters, bound count
-            snap["_xl"] = self.crosslinker_state() + (self.xl_keys.clone(), self.xl_counter.clone(),
-                                                      self.crosslinker_bound)
-        if self.periphery is not None:  # its size (scale_periphery)
-            snap["_periphery"] = list(self.periphery["radii"])
-        if self.active is not None:  # states, timers and counters
-            snap["_active"] = self.active_state()
+        """device copies of every per-body array (to restart a step from the same input) under its name, and what each
+        mode saves of its own under "_<mode>" (growth mode: the body count)"""
+        snap = {k: getattr(self, k).clone() for k in self._body_arrays()}
+        for m in self._modes:
+            snap["_" + m] = getattr(self, "_snapshot_" + m)()
         return snap
 
     def restore(self, snap):
-        if self.growth:
-            self._ensure_capacity(snap["_n"])
-            self.n, self.next_id = snap["_n"], snap["_next_id"]
-            for k in self._per_body():
-                self._store[k][:self.n].copy_(snap[k])
-            self._view()
-            self._forget_numbering()
-            return
-        for k, v in snap.items():
-            if k == "_fr":
-                self.prev_velocity.copy_(v[0])
-                # (a clone: the stepper updates its history in place, and the next step carries it to the list in use)
-                self.tang_disp = None if v[1] is None else v[1].clone()
-                self.hist_pairs, self._renumber = (None if v[1] is None else v[2].clone()), v[3]
-                continue
-            if k == "_xl":
-                self.crosslinkers.set_state(v[0], v[1])
-                self.xl_keys.copy_(v[2])
-                self.xl_counter.copy_(v[3])
-                self.crosslinker_bound = v[4]
-                continue
-            if k == "_periphery":
-                self.periphery["radii"] = list(v)
-                continue
-            if k == "_active":
-                self.active.set_state(*v)
-                continue
-            getattr(self, k).copy_(v)
+        for m in self._modes:
+            getattr(self, "_restore_" + m)(snap["_" + m])
+        for k in self._body_arrays():
+            getattr(self, k).copy_(snap[k])
 
     def _forget_numbering(self):
         """the neighbour list, the operator's incidence index and the multipliers are in an old numbering"""
@@ -793,15 +785,14 @@ class ContactStepper:
             self.op.close()
             self.op = None
         self.lam = None
-        if self.growth:
-            self._aabb_ref = None
 
     def reorder_bodies(self, cell_size=None, lo=None, curve="morton", hi=None, level=7):
         """Space-filling-curve permutation of all per-body arrays by centre (what the reference's zmorton /
         Hilbert helpers are advertised for): neighbours in space become neighbours in memory, so every gather of the
         contact sweeps hits nearby lines.  curve = "morton" (lattice of edge cell_size anchored at lo) or "hilbert"
-        (the hilbert_3d order of a (2^level)^3 lattice over [lo, hi]; both give the same sweep times).  Returns the
-        permutation (new position k holds old body perm[k])."""
+        (the hilbert_3d order of a (2^level)^3 lattice over [lo, hi]; both give the same sweep times).  Every per-body
+        tensor is permuted in place, the caller's center and radius and, in the Hertz model where they are tensors, its
+        youngs_modulus and poisson_ratio among them.  Returns the permutation (new position k holds old body perm[k])."""
         if lo is None:
             lo = self.center.min(dim=0).values.tolist() if self.box is None else [0.0, 0.0, 0.0]
         if curve == "hilbert":
@@ -816,26 +807,14 @@ class ContactStepper:
             perm = ops.morton_order(self.center, lo, cell_size)
         else:
             raise ValueError("curve must be 'morton' or 'hilbert'")
-        for name in (self._per_body() if self.growth else self._BODY_ARRAYS):
-            t = getattr(self, name, None)
-            if t is not None:
-                t.copy_(ops.gather_rows(perm, t) if t.dtype == torch.float64 else t[perm.long()])
-        if getattr(self, "springs", None) is not None:
-            self._renumber_springs(perm)
-        crosslinkers, active = getattr(self, "crosslinkers", None), getattr(self, "active", None)
-        if crosslinkers is not None or active is not None:  # both are renumbered through the inverse permutation
-            inv = torch.empty(perm.shape[0], dtype=torch.int32, device=perm.device)
-            inv[perm.long()] = torch.arange(perm.shape[0], dtype=torch.int32, device=perm.device)
-        if crosslinkers is not None:  # heads, and a new search
-            crosslinkers.renumber(inv)
-            self._new_crosslinker_search()
-        if active is not None:  # endpoints; states and timers stay
-            active.renumber(inv)
-        if self.hertz_friction is not None:  # previous velocities move with their rows, the history through the inverse
-            self.prev_velocity = ops.gather_rows(perm, self.prev_velocity)
+        for name in self._body_arrays():
+            t = getattr(self, name)
+            t.copy_(ops.gather_rows(perm, t) if t.dtype == torch.float64 else t[perm.long()])
+        if self._modes:  # every mode renumbers its own state through the one inverse: the new index of every old body
             inv = torch.empty_like(perm)
             inv[perm.long()] = torch.arange(perm.shape[0], dtype=perm.dtype, device=perm.device)
-            self._renumber = inv if self._renumber is None else inv[self._renumber.long()].contiguous()
+            for m in self._modes:
+                getattr(self, "_renumber_" + m)(perm, inv)
         # the neighbour list, the operator's incidence index and the multipliers are in the old numbering: a reused list
         # would pair the wrong bodies unless the displacement test happened to fire, so force the rebuild
         self._forget_numbering()
@@ -900,12 +879,12 @@ class ContactStepper:
         g = c["sep"][dropped] - self.dt * ((vi - vj) * n).sum(dim=1)
         return bool((g >= -self.cfg.tol).all())
 
-    def resolve_collisions(self, rebuilt):
+    def resolve_collisions(self, rebuilt, mark=lambda name: None):
+        """the contact stage of either model; mark(name) is told the Hertz stages ([history_carry,] hertz_force,
+        operator, body_sweep) as they are issued"""
         if self.contact_model == "hertz":
             self.contact_pairs = self.links.pairs
-            if self.hertz_friction is not None:
-                return self._hertz_friction(rebuilt, lambda name: None)
-            return self._hertz(rebuilt, lambda name: None)
+            return (self._hertz if self.hertz_friction is None else self._hertz_friction)(rebuilt, mark)
         if self.contact_cutoff is not None and self.friction is None:
             self.full_contacts = self.contacts
             pairs, self.contacts, dropped = self._compact_contacts()
@@ -920,14 +899,32 @@ class ContactStepper:
         self.contact_pairs = self.links.pairs
         return self._resolve(rebuilt, self.links.pairs)
 
-    def _resolve(self, rebuilt, pairs):
+    def _operator(self, rebuilt, pairs, lcp=False):
+        """the operator follows the constraint list: built when the list is new, its geometry refreshed (the incidence
+        index kept) on a step that reuses it; the LCP path reuses only a live handle"""
         c = self.contacts
-        # a step that reuses the neighbour list keeps the operator's incidence index and only refreshes its geometry
-        reuse = (not rebuilt and self.op is not None and self.friction is None and
-                 self.op.num_constraints == pairs.shape[0] and getattr(self.op, "_h", None))
+        reuse = not rebuilt and self.op is not None and self.op.num_constraints == pairs.shape[0]
+        if lcp:
+            reuse = reuse and bool(self.op._h)
         if self.op is not None and not reuse:
             self.op.close()
-        if self.friction is not None:
+        if self.kind == "spherocylinder" and self.rod_kinematics:
+            if reuse:
+                self.op.refresh(c["normal"], rod=(c["s"], c["t"], self.seg))
+            else:
+                self.op = ops.ContactOperator(pairs, c["normal"], self.mob_trans, self.dt, mob_rot=self.mob_rot,
+                                              rod=(c["s"], c["t"], self.seg), priority=c["sep"])
+        elif reuse:
+            self.op.refresh(c["normal"], ra=c.get("ra"), rb=c.get("rb"))
+        else:
+            self.op = ops.ContactOperator(pairs, c["normal"], self.mob_trans, self.dt, ra=c.get("ra"), rb=c.get("rb"),
+                                          mob_rot=self.mob_rot, priority=c["sep"])
+
+    def _resolve(self, rebuilt, pairs):
+        c = self.contacts
+        if self.friction is not None:  # a new operator at the surface lever arms, every step
+            if self.op is not None:
+                self.op.close()
             ra, rb = ops.surface_lever_arms(pairs, c["normal"], c["ra"], c["rb"], self.radius)
             self.op = ops.ContactOperator(pairs, c["normal"], self.mob_trans, self.dt, ra=ra, rb=rb,
                                           mob_rot=self.mob_rot)
@@ -935,22 +932,12 @@ class ContactStepper:
                                                    method=self.friction_method)
             self.impulse, self.lam = p, (p * c["normal"]).sum(dim=1)
             return res
-        if self.kind == "spherocylinder" and self.rod_kinematics:
-            if reuse:
-                self.op.refresh(c["normal"], rod=(c["s"], c["t"], self.seg))
-            else:
-                self.op = ops.ContactOperator(pairs, c["normal"], self.mob_trans, self.dt,
-                                              mob_rot=self.mob_rot, rod=(c["s"], c["t"], self.seg), priority=c["sep"])
-        elif reuse:
-            self.op.refresh(c["normal"], ra=c.get("ra"), rb=c.get("rb"))
-        else:
-            self.op = ops.ContactOperator(pairs, c["normal"], self.mob_trans, self.dt, ra=c.get("ra"),
-                                          rb=c.get("rb"), mob_rot=self.mob_rot, priority=c["sep"])
+        self._operator(rebuilt, pairs, lcp=True)
         if self.work_mapping is not None:
             self.op.set_work_mapping(*self.work_mapping)
         if self.tiering is not None:
             self.op.set_tiering(self.tiering)
-        if getattr(self, "profile_next", False):
+        if self.profile_next:
             self.op.set_profiling(True)  # per-kernel HIP-event timing of the fused iteration (bench.py roofline)
         nc = pairs.shape[0]
         if rebuilt or self.lam is None or not self.warm_start or self.lam.shape[0] != nc:
@@ -973,31 +960,14 @@ class ContactStepper:
         c, pairs = self.contacts, self.links.pairs
         self.lam, self.max_overlap = ops.hertz_contact_force(pairs, c["sep"], self._contact_radius(),
                                                              self.youngs_modulus, self.poisson_ratio,
-                                                             max_overlap=self._chain_stats[0:1] if self.chain else None)
+                                                             max_overlap=(stat(self._chain_stats, "max_overlap")
+                                                                          if self.chain else None))
         mark("hertz_force")
-        self._hertz_operator(rebuilt)
+        self._operator(rebuilt, pairs)
         mark("operator")
         self.op.body_sweep(self.lam)
         mark("body_sweep")
         return ops.SolveResult(num_iters=0, residual=0.0, converged=True)
-
-    def _hertz_operator(self, rebuilt):
-        """the operator follows the neighbour list: built on a rebuild, its geometry refreshed otherwise"""
-        c, pairs = self.contacts, self.links.pairs
-        reuse = not rebuilt and self.op is not None and self.op.num_constraints == pairs.shape[0]
-        if self.op is not None and not reuse:
-            self.op.close()
-        if self.kind == "spherocylinder" and self.rod_kinematics:
-            if reuse:
-                self.op.refresh(c["normal"], rod=(c["s"], c["t"], self.seg))
-            else:
-                self.op = ops.ContactOperator(pairs, c["normal"], self.mob_trans, self.dt, mob_rot=self.mob_rot,
-                                              rod=(c["s"], c["t"], self.seg), priority=c["sep"])
-        elif reuse:
-            self.op.refresh(c["normal"], ra=c.get("ra"), rb=c.get("rb"))
-        else:
-            self.op = ops.ContactOperator(pairs, c["normal"], self.mob_trans, self.dt, ra=c.get("ra"), rb=c.get("rb"),
-                                          mob_rot=self.mob_rot, priority=c["sep"])
 
     def integrate(self):
         vel = self.op.body_velocity()
@@ -1053,11 +1023,8 @@ class ContactStepper:
                 self._fr_u_ext = ops.drag_velocity(self.mob_trans, external_force, out=self._fr_u_ext)
         self.compute_contacts()
         mark("narrowphase")
-        if self.contact_model == "hertz":  # (stages: [history_carry,] hertz_force, operator, body_sweep)
-            res = (self._hertz if self.hertz_friction is None else self._hertz_friction)(st.rebuilt, mark)
-            self.contact_pairs = self.links.pairs
-        else:
-            res = self.resolve_collisions(st.rebuilt)
+        res = self.resolve_collisions(st.rebuilt, mark)
+        if self.contact_model == "lcp":
             mark("solve")
         if integrate:
             self.integrate()
@@ -1066,25 +1033,24 @@ class ContactStepper:
         mark("integrate")
         st.num_contacts = self.contact_pairs.shape[0]
         st.num_iters, st.residual, st.converged = res.num_iters, res.residual, res.converged
-        if self.chain:  # the one read of the step: (max_overlap, max_spring_length, overstretched)
-            h = self._chain_stats.cpu()
-            st.max_overlap, st.max_spring_length = float(h[0]), float(h[1])
-            over = int(h.view(torch.int32)[4])
-            if over:
-                raise RuntimeError("%d FENE spring(s) stretched to L >= r_max: no force (reduce dt)" % over)
-            if self.crosslinkers is not None:  # (the same read)
-                hi = h.view(torch.int32)
-                st.crosslinker_binds, st.crosslinker_unbinds = int(hi[6]), int(hi[7])
+        if self.chain:
+            got = read_stats(self._chain_stats)  # the one read of the step
+            st.max_overlap, st.max_spring_length = got["max_overlap"], got["max_spring_length"]
+            if got["springs_overstretched"]:
+                raise RuntimeError("%d FENE spring(s) stretched to L >= r_max: no force (reduce dt)"
+                                   % got["springs_overstretched"])
+            if self.crosslinkers is not None:
+                st.crosslinker_binds, st.crosslinker_unbinds = got["crosslinker_binds"], got["crosslinker_unbinds"]
                 self.crosslinker_bound += st.crosslinker_binds - st.crosslinker_unbinds
                 st.crosslinker_bound = self.crosslinker_bound
-                st.max_crosslinker_length = float(h[4])
-                if int(hi[10]):
+                st.max_crosslinker_length = got["max_crosslinker_length"]
+                if got["crosslinkers_overstretched"]:
                     raise RuntimeError("%d FENE crosslinker(s) stretched to L >= r_max: no force (reduce dt)"
-                                       % int(hi[10]))
-            if self.periphery is not None or self.active is not None:  # (the same read)
-                hi = h.view(torch.int32)
-                st.periphery_colliding, st.max_periphery_overlap = int(hi[14]), float(h[6])
-                st.active_springs, st.active_switches = int(hi[15]), (int(hi[16]), int(hi[17]))
+                                       % got["crosslinkers_overstretched"])
+            if self.periphery is not None or self.active is not None:
+                st.periphery_colliding, st.max_periphery_overlap = got["periphery_colliding"], got["max_periphery_overlap"]
+                st.active_springs = got["active_springs"]
+                st.active_switches = (got["active_switches_on"], got["active_switches_off"])
         elif self.hertz_friction is not None:  # the one read of the step: (max_overlap, num_sliding)
             h = self._fr_stats.cpu()
             st.max_overlap, st.num_sliding = float(h[0]), int(h.view(torch.int64)[1])

@@ -229,3 +229,39 @@ def test_chain_step_app_compiles_and_links():
                            "-Wl,-rpath-link,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib",
                            "-o", exe])
     assert os.path.exists(exe)
+
+
+def test_statistics_table_is_sound():
+    """every entry of the chain step's statistics array has a place of its own, and lies inside the array of the first
+    mode that writes it (no library, no device: the layout is DESIGN.md 5h)"""
+    from mundy_amd import pipeline
+    table, length = pipeline.STATS, pipeline.STATS_LENGTH
+    assert length == dict(chain=3, crosslinkers=6, nucleus=9)
+    places = [(slot, lane) for _, slot, lane in table.values()]
+    assert len(set(places)) == len(places)
+    float_slots = {slot for slot, lane in places if lane is None}
+    int_slots = {slot for slot, lane in places if lane is not None}
+    assert not float_slots & int_slots
+    assert all(lane in (None, 0, 1) for _, lane in places)
+    for name, (mode, slot, lane) in table.items():
+        assert 0 <= slot < length[mode], name
+    assert float_slots | int_slots == set(range(9))
+    # the accessor returns views of the buffer at those places, for the device array and its host copy alike
+    buf = torch.zeros(9, dtype=torch.float64)
+    for k, name in enumerate(table):
+        pipeline.stat(buf, name)[0] = k + 1
+    assert buf.tolist()[:2] == [1.0, 2.0] and buf.view(torch.int32).tolist()[4:6] == [3, 0]
+    for k, (name, (_, slot, lane)) in enumerate(table.items()):
+        got = buf[slot] if lane is None else buf.view(torch.int32)[2 * slot + lane]
+        assert got == k + 1, name
+    # a pair is two entries in lanes 0 and 1 of one slot, and its view holds both
+    for pair, (first, second) in pipeline.STAT_PAIRS.items():
+        assert pair not in table and table[first][1:] == (table[second][1], 0) and table[second][2] == 1
+        assert table[first][0] == table[second][0]
+    assert pipeline.stat(buf, "crosslinker_events").tolist() == [4, 5]
+    assert pipeline.stat(buf, "active_switches").tolist() == [11, 12]
+    # and the decode of the step's one readback gives every name its value, or leaves out what a shorter array lacks
+    assert pipeline.read_stats(buf) == {name: k + 1 for k, name in enumerate(table)}
+    for mode, count in length.items():
+        assert set(pipeline.read_stats(buf[:count])) == {name for name, (m, slot, _) in table.items() if slot < count}
+        assert {name for name, (m, _, _) in table.items() if m == mode} <= set(pipeline.read_stats(buf[:count]))

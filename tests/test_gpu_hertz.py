@@ -98,6 +98,32 @@ def test_per_linker_force_matches_the_model(kind, per_body):
     assert mx == mx_ref
 
 
+def test_per_body_materials_follow_their_bodies():
+    """reorder_bodies, snapshot and restore carry per-body youngs_modulus / poisson_ratio tensors like every other
+    per-body array (outside growth mode they used to stay behind: the bodies moved, their materials did not)"""
+    from gpu_util import assert_bits_equal, host
+    rng = np.random.default_rng(11)
+    n = 3000
+    b = _spheres(rng, n, 18.0)
+    E, nu = _materials(rng, n, True)
+    st = _stepper(b, E, nu)
+    snap = st.snapshot()
+    perm = host(st.reorder_bodies()).astype(np.int64)
+    assert (perm != np.arange(n)).any() and (np.sort(perm) == np.arange(n)).all()
+    assert_bits_equal(host(st.youngs_modulus), E[perm], "youngs_modulus after reorder_bodies")
+    assert_bits_equal(host(st.poisson_ratio), nu[perm], "poisson_ratio after reorder_bodies")
+    assert_bits_equal(host(st.center), b["center"][perm], "center after reorder_bodies")
+    st.step()
+    pairs, sep = host(st.links.pairs), host(st.contacts["sep"])
+    over = sep < 0
+    assert over.sum() > 100
+    f, f_ref = host(st.lam), hertz_force(pairs, sep, b["radius"][perm], E[perm], nu[perm])[0]
+    assert np.all(np.abs(f[over] - f_ref[over]) <= 1e-14 * np.abs(f_ref[over]))
+    st.restore(snap)
+    for name, want in (("youngs_modulus", E), ("poisson_ratio", nu), ("center", b["center"]), ("radius", b["radius"])):
+        assert_bits_equal(host(getattr(st, name)), want, name + " after restore")
+
+
 def _check_rows(vel, F, T, scale, mt, mr, arm_max):
     U_ref, W_ref = mt[:, None] * F, (mr[:, None] * T if mr is not None else np.zeros_like(T))
     tol_u = 1e-12 * mt * scale

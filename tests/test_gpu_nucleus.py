@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import chain_model as cm
+import crosslinker_model as xm
 import periphery_model as pm
 from gpu_util import assert_bits_equal, dev, host
 
@@ -461,6 +462,75 @@ def test_step_force_is_the_models_sum_in_the_reference_order(oracle):
         assert_bits_equal(host(st.spring_force), F + ext, "springs, periphery, active dipoles, external force")
         x0 = host(st.center).copy()
     assert col > 0
+
+
+# every valid choice of force terms: the active dipoles act on springs, so they need them (8 + 16 = 24 cases)
+TERM_SUBSETS = [t for t in ((s, x, p, a, e) for s in (0, 1) for x in (0, 1) for p in (0, 1) for a in (0, 1)
+                            for e in (0, 1)) if t[0] or not t[3]]
+ROUND_WALL = dict(shape="sphere", radius=39.0, k=10.0, center=(39.5, 2.4, 2.4))   # the chains' end beads reach 39.5
+
+
+@pytest.mark.parametrize("terms", TERM_SUBSETS, ids=lambda t: "".join(c for c, on in zip("SXPAE", t) if on) or "none")
+def test_force_stage_is_the_models_sum_for_every_choice_of_terms(terms):
+    """springs, crosslinker springs, periphery, active dipoles, external force: whichever of them are switched on, the
+    stepper's force is the numpy models summed in the reference's order, bit for bit, over three steps, from the
+    stepper's own crosslinker heads (after its KMC) and active states (after its sampling); every term that is on
+    acts on some bead in at least one of the steps"""
+    from mundy_amd import pipeline
+    has_s, has_x, has_p, has_a, has_e = terms
+    assert len(TERM_SUBSETS) == 24
+    c0, pairs, left, keys = _chains()
+    n, radius = c0.shape[0], np.full(c0.shape[0], 0.3)
+    idx = np.arange(0, pairs.shape[0], 3)
+    kw = dict(dt=1e-3, viscosity=1.0, search_buffer=0.4)
+    if has_s:
+        kw["springs"] = (pairs, "hookean", 3.0, 1.0)
+    if has_x:  # every fourth crosslinker doubly bound from the start, to the next bead of its chain (left is even)
+        right = left.copy()
+        right[::4] += 1
+        kw["crosslinkers"] = dict(left=left, right=right, sites=np.ones(n, np.uint8), kind="hookean", k=3.0, r=1.0,
+                                  bind_rate=300.0, unbind_rate=150.0, kt=0.1, capture_radius=1.5, skin=0.3,
+                                  keys=keys[:left.shape[0]])
+    if has_p:
+        kw["periphery"] = ROUND_WALL
+    if has_a:
+        kw["active_forces"] = dict(springs=idx, sigma=2.0, kon=300.0, koff=200.0, keys=keys[:idx.shape[0]] + 7)
+    if not (has_s or has_x or has_p):
+        kw["brownian_kt"] = 0.0   # no noise: the keyword switches the chain step on
+    st = pipeline.ContactStepper("sphere", dev(c0), dev(radius), **kw)
+    ext = np.random.default_rng(31).normal(size=(n, 3)) if has_e else None
+    x0 = c0.copy()
+    acted = dict(x=0, p=0, a=0)
+    for _ in range(3):
+        s = st.step(external_force=None if ext is None else dev(ext))
+        F = None
+        if has_s:
+            F = cm.spring_force(n, pairs, "hookean", 3.0, 1.0, x0)[0]
+        if has_x:
+            le, ri = (host(t).astype(np.int64) for t in st.crosslinker_state())
+            X = xm.crosslinker_force(n, le, ri, "hookean", 3.0, 1.0, x0)[0]
+            F = X if F is None else F + X
+            acted["x"] += int((ri != le).sum() > 0 and np.abs(X).max() > 0.0)
+            assert s.crosslinker_bound == int((ri != le).sum())
+        if has_p:
+            F, col, mx = pm.sphere_force(x0, radius, ROUND_WALL["radius"], ROUND_WALL["k"], ROUND_WALL["center"], force=F)
+            acted["p"] += int(col > 0)
+            assert (s.periphery_colliding, s.max_periphery_overlap) == (col, mx)
+        if has_a:
+            state = host(st.active_state()[0])
+            F, count = pm.active_force(n, pairs[idx], state, 2.0, x0, force=F)
+            acted["a"] += int(count > 0)
+            assert s.active_springs == count
+        if F is not None:
+            assert_bits_equal(host(st.spring_force), F if ext is None else F + ext, "the force stage's sum")
+        elif has_e:   # the caller's force goes to the drag as it is
+            assert_bits_equal(host(st.u_ext), cm.drag_velocity(host(st.mob_trans), ext), "U_ext of the external force")
+            assert not host(st.spring_force).any()
+        else:
+            assert not host(st.u_ext).any() and not host(st.spring_force).any()
+        x0 = host(st.center).copy()
+    # a bound crosslinker under tension, a bead at the wall, an active spring: in some step, for every term that is on
+    assert all(acted[k] > 0 for k, on in (("x", has_x), ("p", has_p), ("a", has_a)) if on), acted
 
 
 # ---- 5. the C++ driver ----------------------------------------------------------------------------------------------------
