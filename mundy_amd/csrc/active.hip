@@ -8,18 +8,16 @@
 //   advance   elapsed += dt
 // All elementwise or per-body gathers of a few rows: HBM bound.
 #include "mhip_internal.hpp"
-#include "chain_device.hpp"
+#include "force_device.hpp"
 
 #include <cmath>
 #include <vector>
 
 namespace mhip {
 
-// u = (((w0 << 21) | (w1 >> 11)) + 1) 2^-53 in (0, 1] from block 0 at (key, counter): log(u) is finite
+// u = (philox_u53 + 1) 2^-53 in (0, 1] from block 0 at (key, counter): log(u) is finite
 __device__ inline double active_uniform(uint64_t key, uint64_t ctr) {
-  const uint4 w = philox_draw(key, ctr, 0u);
-  const uint64_t m = (static_cast<uint64_t>(w.x) << 21) | static_cast<uint64_t>(w.y >> 11);
-  return static_cast<double>(m + 1) * 0x1p-53;
+  return static_cast<double>(philox_u53(philox_draw(key, ctr, 0u)) + 1) * 0x1p-53;
 }
 
 // every spring inactive, its first switching time drawn at the rate kon (HP1.cpp:2796-2826)
@@ -56,15 +54,8 @@ __global__ void __launch_bounds__(kBlock)
     }
     elapsed[s] = 0.0;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    on += __shfl_xor(on, o, 64);
-    off += __shfl_xor(off, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    if (on) atomicAdd(&switches[0], on);
-    if (off) atomicAdd(&switches[1], off);
-  }
+  wave_stat_add(on, &switches[0]);
+  wave_stat_add(off, &switches[1]);
 }
 
 __global__ void __launch_bounds__(kBlock) k_active_advance(size_t m, double dt, double* __restrict__ elapsed) {
@@ -72,24 +63,6 @@ __global__ void __launch_bounds__(kBlock) k_active_advance(size_t m, double dt, 
     elapsed[s] = elapsed[s] + dt;
 }
 
-// incidence: entry (s << 1) | side of spring s at body pairs[s][side] (the layout of chain.hip's springs)
-__global__ void __launch_bounds__(kBlock) k_active_count(size_t m, const int2* __restrict__ pairs,
-                                                        int32_t* __restrict__ deg) {
-  for (size_t s = blockIdx.x * (size_t)blockDim.x + threadIdx.x; s < m; s += (size_t)gridDim.x * blockDim.x) {
-    const int2 p = pairs[s];
-    atomicAdd(&deg[p.x], 1);
-    atomicAdd(&deg[p.y], 1);
-  }
-}
-__global__ void __launch_bounds__(kBlock) k_active_fill(size_t m, const int2* __restrict__ pairs,
-                                                       const int32_t* __restrict__ ptr, int32_t* __restrict__ cursor,
-                                                       int32_t* __restrict__ ent) {
-  for (size_t s = blockIdx.x * (size_t)blockDim.x + threadIdx.x; s < m; s += (size_t)gridDim.x * blockDim.x) {
-    const int2 p = pairs[s];
-    ent[ptr[p.x] + atomicAdd(&cursor[p.x], 1)] = static_cast<int32_t>(s << 1);
-    ent[ptr[p.y] + atomicAdd(&cursor[p.y], 1)] = static_cast<int32_t>((s << 1) | 1);
-  }
-}
 __global__ void __launch_bounds__(kBlock) k_active_renumber(size_t m, const int32_t* __restrict__ new_of_old,
                                                            int2* __restrict__ pairs) {
   for (size_t s = blockIdx.x * (size_t)blockDim.x + threadIdx.x; s < m; s += (size_t)gridDim.x * blockDim.x) {
@@ -108,7 +81,7 @@ __global__ void __launch_bounds__(kBlock)
                    int* __restrict__ active) {
   int count = 0;
   for (size_t b = blockIdx.x * (size_t)blockDim.x + threadIdx.x; b < n; b += (size_t)gridDim.x * blockDim.x) {
-    double fx = 0.0, fy = 0.0, fz = 0.0;
+    V3 f{0.0, 0.0, 0.0};
     bool any = false;
     const int32_t lo = ptr[b], hi = ptr[b + 1];
     for (int32_t e = lo; e < hi; ++e) {
@@ -119,29 +92,18 @@ __global__ void __launch_bounds__(kBlock)
       const int2 p = pairs[s];
       const V3 nv = load3(center, p.y) - load3(center, p.x);
       const double nsqr = nv.x * nv.x + nv.y * nv.y + nv.z * nv.z;
-      const double c = sigma / sqrt(nsqr);
-      const double tx = c * nv.x, ty = c * nv.y, tz = c * nv.z;
+      const V3 t = (sigma / sqrt(nsqr)) * nv;
       if (en & 1) {
-        fx = fx + tx; fy = fy + ty; fz = fz + tz;
+        f = f + t;
       } else {
-        fx = fx - tx; fy = fy - ty; fz = fz - tz;
+        f = f - t;
         ++count;  // a spring is counted at its first end
       }
     }
-    if (ACCUMULATE) {
-      if (!any) continue;  // untouched without an active spring
-      force[3 * b] = force[3 * b] + fx;
-      force[3 * b + 1] = force[3 * b + 1] + fy;
-      force[3 * b + 2] = force[3 * b + 2] + fz;
-    } else {
-      force[3 * b] = fx;
-      force[3 * b + 1] = fy;
-      force[3 * b + 2] = fz;
-    }
+    if (ACCUMULATE && !any) continue;  // untouched without an active spring
+    write_force<ACCUMULATE>(force, b, f);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) count += __shfl_xor(count, o, 64);
-  if ((threadIdx.x & 63) == 0 && count && active) atomicAdd(active, count);
+  wave_stat_add(count, active);
 }
 
 }  // namespace mhip
@@ -151,37 +113,14 @@ using namespace mhip;
 struct mhip_active_springs {
   size_t n = 0, m = 0;
   double sigma = 0.0, inv_kon = 0.0, inv_koff = 0.0;
-  DeviceBuffer pairs, keys, ctrs, state, next_time, elapsed, ptr, ent, cursor, ws;
-  void release() {
-    pairs.release(); keys.release(); ctrs.release(); state.release(); next_time.release(); elapsed.release();
-    ptr.release(); ent.release(); cursor.release(); ws.release();
-  }
+  HandleBuffer pairs, keys, ctrs, state, next_time, elapsed, ptr, ent, cursor, ws;
 };
 
 namespace {
 
-// count -> scan -> fill -> per-body sort
-int build_incidence(mhip_active_springs* h, hipStream_t s) {
-  const size_t n = h->n, m = h->m;
-  int32_t* deg = h->cursor.as<int32_t>();
-  int32_t* ptr = h->ptr.as<int32_t>();
-  const int2* p2 = h->pairs.as<int2>();
-  MHIP_HIP(hipMemsetAsync(deg, 0, (n + 1) * sizeof(int32_t), s));
-  if (m > 0) k_active_count<<<grid_for(m), kBlock, 0, s>>>(m, p2, deg);
-  MHIP_LAUNCH_CHECK();
-  if (n > 0) {
-    if (int e = exclusive_scan_i32(deg, ptr, n, h->ws.ptr, s)) return e;
-  } else {
-    MHIP_HIP(hipMemsetAsync(ptr, 0, sizeof(int32_t), s));
-  }
-  MHIP_HIP(hipMemsetAsync(deg, 0, (n + 1) * sizeof(int32_t), s));
-  if (m > 0) {
-    k_active_fill<<<grid_for(m), kBlock, 0, s>>>(m, p2, ptr, deg, h->ent.as<int32_t>());
-    MHIP_LAUNCH_CHECK();
-    sort_incidence_lists(n, ptr, h->ent.as<int32_t>(), s);
-    MHIP_LAUNCH_CHECK();
-  }
-  return MHIP_SUCCESS;
+int build_lists(mhip_active_springs* h, hipStream_t s) {
+  return build_incidence(h->n, h->m, PairEnds{h->pairs.as<int2>()}, h->cursor.as<int32_t>(), h->ptr.as<int32_t>(),
+                         h->ent.as<int32_t>(), h->ws.ptr, s);
 }
 
 }  // namespace
@@ -212,56 +151,45 @@ int mhip_active_springs_create(mhip_active_springs_t* handle, size_t n, size_t m
       MHIP_REQUIRE(counters[s] < (1ull << 63), MHIP_ERR_INVALID_ARGUMENT, "active spring %zu: counter outside [0, 2^63)",
                    s);
   }
-  auto* h = new mhip_active_springs;
+  auto h = std::make_unique<mhip_active_springs>();
   h->n = n;
   h->m = m;
   h->sigma = sigma;
   h->inv_kon = 1.0 / kon;
   h->inv_koff = 1.0 / koff;
   hipStream_t s = as_stream(stream);
-  auto fail_free = [h](int e) {
-    h->release();
-    delete h;
-    return e;
-  };
   int e = MHIP_SUCCESS;
   if ((e = h->ptr.reserve((n + 1) * sizeof(int32_t))) || (e = h->cursor.reserve((n + 1) * sizeof(int32_t))) ||
       (e = h->pairs.reserve(2 * m * sizeof(int32_t) + 8)) || (e = h->ent.reserve(2 * m * sizeof(int32_t) + 8)) ||
       (e = h->ws.reserve(scan_workspace_bytes(n) + 8)) || (e = h->keys.reserve(m * sizeof(uint64_t) + 8)) ||
       (e = h->ctrs.reserve(m * sizeof(uint64_t) + 8)) || (e = h->state.reserve(m * sizeof(int32_t) + 8)) ||
       (e = h->next_time.reserve(m * sizeof(double) + 8)) || (e = h->elapsed.reserve(m * sizeof(double) + 8)))
-    return fail_free(e);
-  auto hip = [&](hipError_t err) {
-    return err == hipSuccess ? MHIP_SUCCESS
-                             : fail(MHIP_ERR_HIP, "mhip_active_springs_create: %s", hipGetErrorString(err));
-  };
+    return e;
   std::vector<uint64_t> seq;
   if (m > 0) {
     if (!keys) {  // the spring's index keys its stream
       seq.resize(m);
       for (size_t i = 0; i < m; ++i) seq[i] = i;
     }
-    if ((e = hip(hipMemcpyAsync(h->pairs.ptr, pairs, 2 * m * sizeof(int32_t), hipMemcpyHostToDevice, s))) ||
-        (e = hip(hipMemcpyAsync(h->keys.ptr, keys ? keys : seq.data(), m * sizeof(uint64_t), hipMemcpyHostToDevice, s))))
-      return fail_free(e);
-    if (counters) e = hip(hipMemcpyAsync(h->ctrs.ptr, counters, m * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    else e = hip(hipMemsetAsync(h->ctrs.ptr, 0, m * sizeof(uint64_t), s));
-    if (e) return fail_free(e);
+    if ((e = upload(__func__, h->pairs, pairs, 2 * m * sizeof(int32_t), s)) ||
+        (e = upload(__func__, h->keys, keys ? keys : seq.data(), m * sizeof(uint64_t), s)))
+      return e;
+    if (counters) e = upload(__func__, h->ctrs, counters, m * sizeof(uint64_t), s);
+    else e = hip_status(__func__, hipMemsetAsync(h->ctrs.ptr, 0, m * sizeof(uint64_t), s));
+    if (e) return e;
     k_active_init<<<grid_for(m), kBlock, 0, s>>>(m, h->keys.as<uint64_t>(), h->ctrs.as<uint64_t>(), h->inv_kon,
                                                 h->state.as<int32_t>(), h->next_time.as<double>(),
                                                 h->elapsed.as<double>());
-    if ((e = hip(hipGetLastError()))) return fail_free(e);
+    if ((e = hip_status(__func__, hipGetLastError()))) return e;
   }
-  if ((e = build_incidence(h, s))) return fail_free(e);
+  if ((e = build_lists(h.get(), s))) return e;
   // the caller's host arrays (and seq) may go as soon as this returns
-  if ((e = hip(hipStreamSynchronize(s)))) return fail_free(e);
-  *handle = h;
+  if ((e = hip_status(__func__, hipStreamSynchronize(s)))) return e;
+  *handle = h.release();
   return MHIP_SUCCESS;
 }
 
 int mhip_active_springs_destroy(mhip_active_springs_t h) {
-  if (!h) return MHIP_SUCCESS;
-  h->release();
   delete h;
   return MHIP_SUCCESS;
 }
@@ -287,12 +215,11 @@ int mhip_active_springs_force(mhip_active_springs_t h, const double* center, dou
   if (active) MHIP_HIP(hipMemsetAsync(active, 0, sizeof(int), s));
   if (h->n == 0) return MHIP_SUCCESS;
   const unsigned grid = grid_for(h->n);
-  if (accumulate)
-    k_active_force<true><<<grid, kBlock, 0, s>>>(h->n, h->ptr.as<int32_t>(), h->ent.as<int32_t>(), h->pairs.as<int2>(),
-                                                 h->state.as<int32_t>(), center, h->sigma, force, active);
-  else
-    k_active_force<false><<<grid, kBlock, 0, s>>>(h->n, h->ptr.as<int32_t>(), h->ent.as<int32_t>(), h->pairs.as<int2>(),
-                                                  h->state.as<int32_t>(), center, h->sigma, force, active);
+  dispatch<true, false>(accumulate != 0, [&](auto acc) {
+    k_active_force<decltype(acc)::value><<<grid, kBlock, 0, s>>>(h->n, h->ptr.as<int32_t>(), h->ent.as<int32_t>(),
+                                                                 h->pairs.as<int2>(), h->state.as<int32_t>(), center,
+                                                                 h->sigma, force, active);
+  });
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
 }
@@ -340,7 +267,7 @@ int mhip_active_springs_renumber(mhip_active_springs_t h, const int32_t* new_of_
     k_active_renumber<<<grid_for(h->m), kBlock, 0, s>>>(h->m, new_of_old, h->pairs.as<int2>());
     MHIP_LAUNCH_CHECK();
   }
-  return build_incidence(h, s);
+  return build_lists(h, s);
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 //   drag velocity   U = M F of a per-body force (the U_ext = M F_ext of resolve_collisions, NgpHP1.cpp:1488-1531)
 // All elementwise or per-body gathers of a few rows: HBM bound.
 #include "mhip_internal.hpp"
-#include "chain_device.hpp"
+#include "force_device.hpp"
 
 namespace mhip {
 
@@ -17,13 +17,11 @@ __global__ void __launch_bounds__(kBlock) k_philox(size_t count, const uint64_t*
     out[i] = philox_draw(keys[i], ctrs[i], block);
 }
 
-// uniform -> normal (documented in mundy_hip.h): two words give a 53-bit integer m = (w0 << 21) | (w1 >> 11);
-// u1 = (m + 1) 2^-53 in (0, 1], u2 = m' 2^-53 in [0, 1) from the other two words; Box-Muller
+// uniform -> normal (documented in mundy_hip.h): u1 = (m + 1) 2^-53 in (0, 1] from the 53-bit integer m of the first two
+// words, u2 = m' 2^-53 in [0, 1) from the other two words; Box-Muller
 __device__ inline void box_muller(uint4 w, double& z0, double& z1) {
-  const uint64_t m = (static_cast<uint64_t>(w.x) << 21) | static_cast<uint64_t>(w.y >> 11);
-  const uint64_t mp = (static_cast<uint64_t>(w.z) << 21) | static_cast<uint64_t>(w.w >> 11);
-  const double u1 = static_cast<double>(m + 1) * 0x1p-53;
-  const double u2 = static_cast<double>(mp) * 0x1p-53;
+  const double u1 = static_cast<double>(philox_u53(w) + 1) * 0x1p-53;
+  const double u2 = static_cast<double>(philox_u53(make_uint4(w.z, w.w, 0u, 0u))) * 0x1p-53;
   const double rad = sqrt(-2.0 * log(u1));
   const double th = 6.283185307179586 * u2;
   z0 = rad * cos(th);
@@ -66,28 +64,21 @@ __global__ void __launch_bounds__(kBlock) k_drag_velocity(size_t n, const double
   }
 }
 
-// ---- springs -----------------------------------------------------------------------------------------------------
-// incidence: entry (s << 1) | side of spring s at body pairs[s][side], each body's list ascending in s
-__global__ void __launch_bounds__(kBlock) k_spring_count(size_t m, const int2* __restrict__ pairs,
-                                                        int32_t* __restrict__ deg) {
-  for (size_t s = blockIdx.x * (size_t)blockDim.x + threadIdx.x; s < m; s += (size_t)gridDim.x * blockDim.x) {
-    const int2 p = pairs[s];
-    atomicAdd(&deg[p.x], 1);
-    atomicAdd(&deg[p.y], 1);
-  }
+// ---- body -> entry incidence (force_device.hpp) ------------------------------------------------------------------
+template <class SRC>
+__global__ void __launch_bounds__(kBlock) k_incidence_count(size_t m, SRC src, int32_t* __restrict__ deg) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < m; i += (size_t)gridDim.x * blockDim.x)
+    src(i, [&](int32_t b, int32_t) { atomicAdd(&deg[b], 1); });
 }
-__global__ void __launch_bounds__(kBlock) k_spring_fill(size_t m, const int2* __restrict__ pairs,
-                                                       const int32_t* __restrict__ ptr, int32_t* __restrict__ cursor,
-                                                       int32_t* __restrict__ ent) {
-  for (size_t s = blockIdx.x * (size_t)blockDim.x + threadIdx.x; s < m; s += (size_t)gridDim.x * blockDim.x) {
-    const int2 p = pairs[s];
-    ent[ptr[p.x] + atomicAdd(&cursor[p.x], 1)] = static_cast<int32_t>(s << 1);
-    ent[ptr[p.y] + atomicAdd(&cursor[p.y], 1)] = static_cast<int32_t>((s << 1) | 1);
-  }
+template <class SRC>
+__global__ void __launch_bounds__(kBlock) k_incidence_fill(size_t m, SRC src, const int32_t* __restrict__ ptr,
+                                                          int32_t* __restrict__ cursor, int32_t* __restrict__ ent) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < m; i += (size_t)gridDim.x * blockDim.x)
+    src(i, [&](int32_t b, int32_t e) { ent[ptr[b] + atomicAdd(&cursor[b], 1)] = e; });
 }
 // the fill order depends on atomic arrival: each body sorts its own short list (chains: 2 entries)
-__global__ void __launch_bounds__(kBlock) k_spring_sort(size_t n, const int32_t* __restrict__ ptr,
-                                                       int32_t* __restrict__ ent) {
+__global__ void __launch_bounds__(kBlock) k_incidence_sort(size_t n, const int32_t* __restrict__ ptr,
+                                                          int32_t* __restrict__ ent) {
   for (size_t b = blockIdx.x * (size_t)blockDim.x + threadIdx.x; b < n; b += (size_t)gridDim.x * blockDim.x) {
     const int32_t lo = ptr[b], hi = ptr[b + 1];
     for (int32_t a = lo + 1; a < hi; ++a) {
@@ -102,11 +93,29 @@ __global__ void __launch_bounds__(kBlock) k_spring_sort(size_t n, const int32_t*
   }
 }
 
-// the same per-body sort for any body -> entry incidence in CSR form (crosslink.hip: the crosslinker ends)
-void sort_incidence_lists(size_t n, const int32_t* ptr, int32_t* ent, hipStream_t s) {
-  k_spring_sort<<<grid_for(n), kBlock, 0, s>>>(n, ptr, ent);
+template <class SRC>
+int build_incidence(size_t n, size_t m, SRC src, int32_t* deg, int32_t* ptr, int32_t* ent, void* ws, hipStream_t s) {
+  MHIP_HIP(hipMemsetAsync(deg, 0, (n + 1) * sizeof(int32_t), s));
+  if (m > 0) k_incidence_count<<<grid_for(m), kBlock, 0, s>>>(m, src, deg);
+  MHIP_LAUNCH_CHECK();
+  if (n > 0) {
+    if (int e = exclusive_scan_i32(deg, ptr, n, ws, s)) return e;
+  } else {
+    MHIP_HIP(hipMemsetAsync(ptr, 0, sizeof(int32_t), s));
+  }
+  MHIP_HIP(hipMemsetAsync(deg, 0, (n + 1) * sizeof(int32_t), s));
+  if (m > 0) {
+    k_incidence_fill<<<grid_for(m), kBlock, 0, s>>>(m, src, ptr, deg, ent);
+    MHIP_LAUNCH_CHECK();
+    k_incidence_sort<<<grid_for(n), kBlock, 0, s>>>(n, ptr, ent);
+    MHIP_LAUNCH_CHECK();
+  }
+  return MHIP_SUCCESS;
 }
+template int build_incidence(size_t, size_t, PairEnds, int32_t*, int32_t*, int32_t*, void*, hipStream_t);
+template int build_incidence(size_t, size_t, ListedAt, int32_t*, int32_t*, int32_t*, void*, hipStream_t);
 
+// ---- springs -----------------------------------------------------------------------------------------------------
 // One body per lane: walk its springs in ascending index, recompute each spring's d = x_j - x_i, L = |d| and term
 // fm d in the same operations at both ends (so the two ends receive exactly negated vectors), sum from +0.0.
 // The spring's own statistics (longest L, overstretched FENE) are taken at its first end only.
@@ -118,54 +127,23 @@ __global__ void __launch_bounds__(kBlock)
                    int* __restrict__ overstretched, unsigned long long* __restrict__ max_length_bits) {
   double lmax = 0.0;
   for (size_t b = blockIdx.x * (size_t)blockDim.x + threadIdx.x; b < n; b += (size_t)gridDim.x * blockDim.x) {
-    double fx = 0.0, fy = 0.0, fz = 0.0;
+    V3 f{0.0, 0.0, 0.0};
     const int32_t lo = ptr[b], hi = ptr[b + 1];
     for (int32_t e = lo; e < hi; ++e) {
       const int32_t en = ent[e];
       const int32_t s = en >> 1;
+      const bool first = (en & 1) == 0;
       const int2 p = pairs[s];
-      const V3 xi{center[3 * (size_t)p.x], center[3 * (size_t)p.x + 1], center[3 * (size_t)p.x + 2]};
-      const V3 xj{center[3 * (size_t)p.y], center[3 * (size_t)p.y + 1], center[3 * (size_t)p.y + 2]};
-      const V3 d = xj - xi;
-      const double L = sqrt(dot(d, d));
-      const double k = K_ARRAY ? kk[s] : k0;
+      const V3 d = load3(center, p.y) - load3(center, p.x);
       const double r = R_ARRAY ? rr[s] : r0;
-      double fm;
-      if (TYPE == MHIP_SPRING_HOOKEAN) {
-        fm = k * (L - r) * (1.0 / L);  // NgpHP1.cpp:1054-1069
-      } else {
-        // FENE, -grad of U = -1/2 k r_max^2 ln(1 - (L / r_max)^2): attractive, no force at L >= r_max
-        const double q = L / r;
-        fm = (L < r) ? k / (1.0 - q * q) : __builtin_nan("");
-        if ((en & 1) == 0 && !(L < r)) atomicAdd(overstretched, 1);
-      }
-      if ((en & 1) == 0) lmax = L > lmax ? L : lmax;
-      const double tx = fm * d.x, ty = fm * d.y, tz = fm * d.z;
-      if (en & 1) {
-        fx = fx - tx; fy = fy - ty; fz = fz - tz;
-      } else {
-        fx = fx + tx; fy = fy + ty; fz = fz + tz;
-      }
+      const SpringTerm t = spring_term<TYPE>(d, K_ARRAY ? kk[s] : k0, r);
+      if (TYPE == MHIP_SPRING_FENE && first && !(t.L < r)) atomicAdd(overstretched, 1);
+      if (first) lmax = t.L > lmax ? t.L : lmax;
+      add_term(f, !first, t.fm, d);
     }
-    force[3 * b] = fx;
-    force[3 * b + 1] = fy;
-    force[3 * b + 2] = fz;
+    store3(force, b, f);
   }
-  // non-negative doubles order like their bits: an atomic max on the bits is order independent (as hertz.hip)
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double o = __shfl_xor(lmax, off, 64);
-    lmax = o > lmax ? o : lmax;
-  }
-  __shared__ double wave_max[kBlock / 64];
-  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = lmax;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double mx = wave_max[0];
-#pragma unroll
-    for (int w = 1; w < kBlock / 64; ++w) mx = wave_max[w] > mx ? wave_max[w] : mx;
-    if (mx > 0.0) atomicMax(max_length_bits, static_cast<unsigned long long>(__double_as_longlong(mx)));
-  }
+  block_stat_max(lmax, max_length_bits);
 }
 
 }  // namespace mhip
@@ -177,7 +155,7 @@ struct mhip_springs {
   int type = MHIP_SPRING_HOOKEAN;
   double k0 = 0.0, r0 = 0.0;
   bool k_array = false, r_array = false;
-  DeviceBuffer pairs, k, r, ptr, ent, cursor, ws;
+  HandleBuffer pairs, k, r, ptr, ent, cursor, ws;
 };
 
 extern "C" {
@@ -208,7 +186,7 @@ int mhip_springs_create(mhip_springs_t* handle, size_t n, size_t m, const int32_
     if (r) MHIP_REQUIRE(r_ok(r[s]), MHIP_ERR_INVALID_ARGUMENT, "spring %zu: %s must be finite and %s 0, got %g", s, rname,
                         type == MHIP_SPRING_FENE ? ">" : ">=", r[s]);
   }
-  auto* h = new mhip_springs;
+  auto h = std::make_unique<mhip_springs>();
   h->n = n;
   h->m = m;
   h->type = type;
@@ -217,51 +195,28 @@ int mhip_springs_create(mhip_springs_t* handle, size_t n, size_t m, const int32_
   h->k_array = k != nullptr;
   h->r_array = r != nullptr;
   hipStream_t s = as_stream(stream);
-  auto fail_free = [h](int e) {
-    h->pairs.release(); h->k.release(); h->r.release(); h->ptr.release(); h->ent.release(); h->cursor.release();
-    h->ws.release();
-    delete h;
-    return e;
-  };
   int e = MHIP_SUCCESS;
   if ((e = h->ptr.reserve((n + 1) * sizeof(int32_t))) || (e = h->cursor.reserve((n + 1) * sizeof(int32_t))) ||
       (e = h->pairs.reserve(2 * m * sizeof(int32_t) + 8)) || (e = h->ent.reserve(2 * m * sizeof(int32_t) + 8)) ||
       (e = h->ws.reserve(scan_workspace_bytes(n) + 8)))
-    return fail_free(e);
-  if (k && (e = h->k.reserve(m * sizeof(double) + 8))) return fail_free(e);
-  if (r && (e = h->r.reserve(m * sizeof(double) + 8))) return fail_free(e);
-  auto hip = [&](hipError_t err) {
-    return err == hipSuccess ? MHIP_SUCCESS
-                             : fail(MHIP_ERR_HIP, "mhip_springs_create: %s", hipGetErrorString(err));
-  };
+    return e;
+  if (k && (e = h->k.reserve(m * sizeof(double) + 8))) return e;
+  if (r && (e = h->r.reserve(m * sizeof(double) + 8))) return e;
   if (m > 0) {
-    if ((e = hip(hipMemcpyAsync(h->pairs.ptr, pairs, 2 * m * sizeof(int32_t), hipMemcpyHostToDevice, s)))) return fail_free(e);
-    if (k && (e = hip(hipMemcpyAsync(h->k.ptr, k, m * sizeof(double), hipMemcpyHostToDevice, s)))) return fail_free(e);
-    if (r && (e = hip(hipMemcpyAsync(h->r.ptr, r, m * sizeof(double), hipMemcpyHostToDevice, s)))) return fail_free(e);
+    if ((e = upload(__func__, h->pairs, pairs, 2 * m * sizeof(int32_t), s))) return e;
+    if (k && (e = upload(__func__, h->k, k, m * sizeof(double), s))) return e;
+    if (r && (e = upload(__func__, h->r, r, m * sizeof(double), s))) return e;
   }
-  if ((e = hip(hipMemsetAsync(h->cursor.ptr, 0, (n + 1) * sizeof(int32_t), s)))) return fail_free(e);
-  const int2* p2 = h->pairs.as<int2>();
-  int32_t* deg = h->cursor.as<int32_t>();
-  if (m > 0) k_spring_count<<<grid_for(m), kBlock, 0, s>>>(m, p2, deg);
-  if ((e = hip(hipGetLastError()))) return fail_free(e);
-  if (n > 0 && (e = exclusive_scan_i32(deg, h->ptr.as<int32_t>(), n, h->ws.ptr, s))) return fail_free(e);
-  if (n == 0 && (e = hip(hipMemsetAsync(h->ptr.ptr, 0, sizeof(int32_t), s)))) return fail_free(e);
-  if ((e = hip(hipMemsetAsync(h->cursor.ptr, 0, (n + 1) * sizeof(int32_t), s)))) return fail_free(e);
-  if (m > 0) {
-    k_spring_fill<<<grid_for(m), kBlock, 0, s>>>(m, p2, h->ptr.as<int32_t>(), deg, h->ent.as<int32_t>());
-    k_spring_sort<<<grid_for(n), kBlock, 0, s>>>(n, h->ptr.as<int32_t>(), h->ent.as<int32_t>());
-  }
-  if ((e = hip(hipGetLastError()))) return fail_free(e);
+  if ((e = build_incidence(n, m, PairEnds{h->pairs.as<int2>()}, h->cursor.as<int32_t>(), h->ptr.as<int32_t>(),
+                           h->ent.as<int32_t>(), h->ws.ptr, s)))
+    return e;
   // the caller's host arrays may go as soon as this returns
-  if ((e = hip(hipStreamSynchronize(s)))) return fail_free(e);
-  *handle = h;
+  if ((e = hip_status(__func__, hipStreamSynchronize(s)))) return e;
+  *handle = h.release();
   return MHIP_SUCCESS;
 }
 
 int mhip_springs_destroy(mhip_springs_t h) {
-  if (!h) return MHIP_SUCCESS;
-  h->pairs.release(); h->k.release(); h->r.release(); h->ptr.release(); h->ent.release(); h->cursor.release();
-  h->ws.release();
   delete h;
   return MHIP_SUCCESS;
 }
@@ -283,19 +238,12 @@ int mhip_springs_force(mhip_springs_t h, const double* center, double* force, in
   const int2* p2 = h->pairs.as<int2>();
   const double* kk = h->k_array ? h->k.as<double>() : nullptr;
   const double* rr = h->r_array ? h->r.as<double>() : nullptr;
-#define SPRING(T, KA, RA) \
-  k_spring_force<T, KA, RA><<<grid, kBlock, 0, s>>>(h->n, ptr, ent, p2, center, kk, h->k0, rr, h->r0, force, overstretched, mx)
-#define SPRING_T(T)                                      \
-  do {                                                   \
-    if (kk && rr) SPRING(T, true, true);                 \
-    else if (kk) SPRING(T, true, false);                 \
-    else if (rr) SPRING(T, false, true);                 \
-    else SPRING(T, false, false);                        \
-  } while (0)
-  if (h->type == MHIP_SPRING_FENE) SPRING_T(MHIP_SPRING_FENE);
-  else SPRING_T(MHIP_SPRING_HOOKEAN);
-#undef SPRING_T
-#undef SPRING
+  dispatch<MHIP_SPRING_FENE, MHIP_SPRING_HOOKEAN>(h->type, [&](auto type) {
+    dispatch_bools(kk != nullptr, rr != nullptr, [&](auto ka, auto ra) {
+      k_spring_force<decltype(type)::value, decltype(ka)::value, decltype(ra)::value><<<grid, kBlock, 0, s>>>(
+          h->n, ptr, ent, p2, center, kk, h->k0, rr, h->r0, force, overstretched, mx);
+    });
+  });
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
 }

@@ -11,7 +11,7 @@
 //   force            one lane per body, its left and right lists merged in ascending crosslinker index, no atomics
 // All of it gathers a few rows per lane: bound by the latency of those gathers.
 #include "mhip_internal.hpp"
-#include "chain_device.hpp"
+#include "force_device.hpp"
 
 #include <cmath>
 
@@ -55,7 +55,7 @@ __global__ void __launch_bounds__(kBlock) k_xl_row_sort(size_t n, const int32_t*
 }
 
 // ---- KMC: one lane per crosslinker ---------------------------------------------------------------------------------
-// u = ((w0 << 21) | (w1 >> 11)) 2^-53 from block 0 at (key, counter); the counter advances whatever the state
+// u = philox_u53 2^-53 in [0, 1) from block 0 at (key, counter); the counter advances whatever the state
 // (HP1.cpp:3487-3491, :3560-3565).  Every lane reads and writes the state of its own crosslinker only and the rates do
 // not depend on the other crosslinkers (no site exclusivity in the reference), so sampling from the state at the start
 // of the step and applying afterwards (:3757-3764) is what the in-place update computes.
@@ -70,8 +70,7 @@ __global__ void __launch_bounds__(kBlock)
     const uint64_t ctr = ctrs[c];
     const uint4 w = philox_draw(keys[c], ctr, 0u);
     ctrs[c] = ctr + 1;
-    const double u =
-        static_cast<double>((static_cast<uint64_t>(w.x) << 21) | static_cast<uint64_t>(w.y >> 11)) * 0x1p-53;
+    const double u = static_cast<double>(philox_u53(w)) * 0x1p-53;
     const int32_t l = left[c];
     if (right[c] != l) {  // doubly bound: what HP1.cpp:3554-3573 reduces to
       if (u < 1.0 - exp(-(dt * p.k_off))) {
@@ -109,34 +108,10 @@ __global__ void __launch_bounds__(kBlock)
       }
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    binds += __shfl_xor(binds, off, 64);
-    unbinds += __shfl_xor(unbinds, off, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    if (binds) atomicAdd(&events[0], binds);
-    if (unbinds) atomicAdd(&events[1], unbinds);
-  }
+  wave_stat_add(binds, &events[0]);
+  wave_stat_add(unbinds, &events[1]);
 }
 
-// ---- body -> crosslinker incidence ---------------------------------------------------------------------------------
-// crosslinker c is listed at body at[c]; with `other`, only where at[c] != other[c] (the right ends of the doubly bound)
-__global__ void __launch_bounds__(kBlock) k_xl_count(size_t m, const int32_t* __restrict__ at,
-                                                    const int32_t* __restrict__ other, int32_t* __restrict__ deg) {
-  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
-    const int32_t b = at[c];
-    if (!other || other[c] != b) atomicAdd(&deg[b], 1);
-  }
-}
-__global__ void __launch_bounds__(kBlock) k_xl_fill(size_t m, const int32_t* __restrict__ at,
-                                                   const int32_t* __restrict__ other, const int32_t* __restrict__ ptr,
-                                                   int32_t* __restrict__ cursor, int32_t* __restrict__ ent) {
-  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
-    const int32_t b = at[c];
-    if (!other || other[c] != b) ent[ptr[b] + atomicAdd(&cursor[b], 1)] = static_cast<int32_t>(c);
-  }
-}
 __global__ void __launch_bounds__(kBlock) k_xl_renumber(size_t m, const int32_t* __restrict__ new_of_old,
                                                        int32_t* __restrict__ left, int32_t* __restrict__ right) {
   for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
@@ -159,7 +134,7 @@ __global__ void __launch_bounds__(kBlock)
                unsigned long long* __restrict__ max_length_bits) {
   double lmax = 0.0;
   for (size_t b = blockIdx.x * (size_t)blockDim.x + threadIdx.x; b < n; b += (size_t)gridDim.x * blockDim.x) {
-    double fx = 0.0, fy = 0.0, fz = 0.0;
+    V3 f{0.0, 0.0, 0.0};
     int32_t a = lptr[b], e = rptr[b];
     const int32_t ae = lptr[b + 1], ee = rptr[b + 1];
     while (a < ae || e < ee) {
@@ -173,48 +148,14 @@ __global__ void __launch_bounds__(kBlock)
       const int32_t j = at_left ? right[c] : static_cast<int32_t>(b);
       if (i == j) continue;  // singly bound: no force
       const V3 d = load3(center, j) - load3(center, i);
-      const double L = sqrt(dot(d, d));
-      double fm;
-      if (TYPE == MHIP_SPRING_HOOKEAN) {
-        fm = k * (L - r) * (1.0 / L);
-      } else {
-        const double q = L / r;
-        fm = (L < r) ? k / (1.0 - q * q) : __builtin_nan("");
-        if (at_left && !(L < r)) atomicAdd(overstretched, 1);
-      }
-      if (at_left) lmax = L > lmax ? L : lmax;
-      const double tx = fm * d.x, ty = fm * d.y, tz = fm * d.z;
-      if (at_left) {
-        fx = fx + tx; fy = fy + ty; fz = fz + tz;
-      } else {
-        fx = fx - tx; fy = fy - ty; fz = fz - tz;
-      }
+      const SpringTerm t = spring_term<TYPE>(d, k, r);
+      if (TYPE == MHIP_SPRING_FENE && at_left && !(t.L < r)) atomicAdd(overstretched, 1);
+      if (at_left) lmax = t.L > lmax ? t.L : lmax;
+      add_term(f, !at_left, t.fm, d);
     }
-    if (ACCUMULATE) {
-      force[3 * b] = force[3 * b] + fx;
-      force[3 * b + 1] = force[3 * b + 1] + fy;
-      force[3 * b + 2] = force[3 * b + 2] + fz;
-    } else {
-      force[3 * b] = fx;
-      force[3 * b + 1] = fy;
-      force[3 * b + 2] = fz;
-    }
+    write_force<ACCUMULATE>(force, b, f);
   }
-  // non-negative doubles order like their bits: an atomic max on the bits is order independent (as chain.hip)
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double o = __shfl_xor(lmax, off, 64);
-    lmax = o > lmax ? o : lmax;
-  }
-  __shared__ double wave_max[kBlock / 64];
-  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = lmax;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double mx = wave_max[0];
-#pragma unroll
-    for (int w = 1; w < kBlock / 64; ++w) mx = wave_max[w] > mx ? wave_max[w] : mx;
-    if (mx > 0.0) atomicMax(max_length_bits, static_cast<unsigned long long>(__double_as_longlong(mx)));
-  }
+  block_stat_max(lmax, max_length_bits);
 }
 
 }  // namespace mhip
@@ -225,45 +166,21 @@ struct mhip_crosslinkers {
   size_t n = 0, m = 0;
   int type = MHIP_SPRING_HOOKEAN;
   XlParams p{};
-  DeviceBuffer left, right, lptr, lent, rptr, rent, cursor, ws, cptr, ccol, ckey;
+  HandleBuffer left, right, lptr, lent, rptr, rent, cursor, ws, cptr, ccol, ckey;
   size_t cand_entries = 0;
   bool has_candidates = false;
-  void release() {
-    left.release(); right.release(); lptr.release(); lent.release(); rptr.release(); rent.release(); cursor.release();
-    ws.release(); cptr.release(); ccol.release(); ckey.release();
-  }
 };
 
 namespace {
 
-// count -> scan -> fill -> per-body sort of the crosslinkers listed at at[c] (where at[c] != other[c], if given)
-int build_incidence(mhip_crosslinkers* h, const int32_t* at, const int32_t* other, int32_t* ptr, int32_t* ent,
-                    hipStream_t s) {
-  const size_t n = h->n, m = h->m;
-  int32_t* deg = h->cursor.as<int32_t>();
-  MHIP_HIP(hipMemsetAsync(deg, 0, (n + 1) * sizeof(int32_t), s));
-  if (m > 0) k_xl_count<<<grid_for(m), kBlock, 0, s>>>(m, at, other, deg);
-  MHIP_LAUNCH_CHECK();
-  if (n > 0) {
-    if (int e = exclusive_scan_i32(deg, ptr, n, h->ws.ptr, s)) return e;
-  } else {
-    MHIP_HIP(hipMemsetAsync(ptr, 0, sizeof(int32_t), s));
-  }
-  MHIP_HIP(hipMemsetAsync(deg, 0, (n + 1) * sizeof(int32_t), s));
-  if (m > 0) {
-    k_xl_fill<<<grid_for(m), kBlock, 0, s>>>(m, at, other, ptr, deg, ent);
-    MHIP_LAUNCH_CHECK();
-    sort_incidence_lists(n, ptr, ent, s);
-    MHIP_LAUNCH_CHECK();
-  }
-  return MHIP_SUCCESS;
-}
+// the crosslinkers listed at their left ends, and at their right ends where doubly bound
 int build_left(mhip_crosslinkers* h, hipStream_t s) {
-  return build_incidence(h, h->left.as<int32_t>(), nullptr, h->lptr.as<int32_t>(), h->lent.as<int32_t>(), s);
+  return build_incidence(h->n, h->m, ListedAt{h->left.as<int32_t>(), nullptr}, h->cursor.as<int32_t>(),
+                         h->lptr.as<int32_t>(), h->lent.as<int32_t>(), h->ws.ptr, s);
 }
 int build_right(mhip_crosslinkers* h, hipStream_t s) {
-  return build_incidence(h, h->right.as<int32_t>(), h->left.as<int32_t>(), h->rptr.as<int32_t>(),
-                         h->rent.as<int32_t>(), s);
+  return build_incidence(h->n, h->m, ListedAt{h->right.as<int32_t>(), h->left.as<int32_t>()}, h->cursor.as<int32_t>(),
+                         h->rptr.as<int32_t>(), h->rent.as<int32_t>(), h->ws.ptr, s);
 }
 
 }  // namespace
@@ -302,42 +219,30 @@ int mhip_crosslinkers_create(mhip_crosslinkers_t* handle, size_t n, size_t m, co
     MHIP_REQUIRE(rr == l || !is_site || is_site[rr], MHIP_ERR_INVALID_ARGUMENT,
                  "crosslinker %zu: right head at body %d, which is not a bind site", c, rr);
   }
-  auto* h = new mhip_crosslinkers;
+  auto h = std::make_unique<mhip_crosslinkers>();
   h->n = n;
   h->m = m;
   h->type = type;
   h->p = XlParams{k, r, bind_rate, unbind_rate, 1.0 / kt, capture_radius};
   hipStream_t s = as_stream(stream);
-  auto fail_free = [h](int e) {
-    h->release();
-    delete h;
-    return e;
-  };
   int e = MHIP_SUCCESS;
   if ((e = h->left.reserve(m * sizeof(int32_t) + 8)) || (e = h->right.reserve(m * sizeof(int32_t) + 8)) ||
       (e = h->lent.reserve(m * sizeof(int32_t) + 8)) || (e = h->rent.reserve(m * sizeof(int32_t) + 8)) ||
       (e = h->lptr.reserve((n + 1) * sizeof(int32_t))) || (e = h->rptr.reserve((n + 1) * sizeof(int32_t))) ||
       (e = h->cursor.reserve((n + 1) * sizeof(int32_t))) || (e = h->ws.reserve(scan_workspace_bytes(n) + 8)))
-    return fail_free(e);
-  auto hip = [&](hipError_t err) {
-    return err == hipSuccess ? MHIP_SUCCESS
-                             : fail(MHIP_ERR_HIP, "mhip_crosslinkers_create: %s", hipGetErrorString(err));
-  };
+    return e;
   if (m > 0) {
-    if ((e = hip(hipMemcpyAsync(h->left.ptr, left, m * sizeof(int32_t), hipMemcpyHostToDevice, s)))) return fail_free(e);
-    if ((e = hip(hipMemcpyAsync(h->right.ptr, right ? right : left, m * sizeof(int32_t), hipMemcpyHostToDevice, s))))
-      return fail_free(e);
+    if ((e = upload(__func__, h->left, left, m * sizeof(int32_t), s))) return e;
+    if ((e = upload(__func__, h->right, right ? right : left, m * sizeof(int32_t), s))) return e;
   }
-  if ((e = build_left(h, s)) || (e = build_right(h, s))) return fail_free(e);
+  if ((e = build_left(h.get(), s)) || (e = build_right(h.get(), s))) return e;
   // the caller's host arrays may go as soon as this returns
-  if ((e = hip(hipStreamSynchronize(s)))) return fail_free(e);
-  *handle = h;
+  if ((e = hip_status(__func__, hipStreamSynchronize(s)))) return e;
+  *handle = h.release();
   return MHIP_SUCCESS;
 }
 
 int mhip_crosslinkers_destroy(mhip_crosslinkers_t h) {
-  if (!h) return MHIP_SUCCESS;
-  h->release();
   delete h;
   return MHIP_SUCCESS;
 }
@@ -381,12 +286,11 @@ int mhip_crosslinkers_kmc_step(mhip_crosslinkers_t h, const double* center, doub
   MHIP_HIP(hipMemsetAsync(events, 0, 2 * sizeof(int), s));
   if (h->m == 0) return MHIP_SUCCESS;
   const unsigned grid = grid_for(h->m);
-#define XL_KMC(T)                                                                                                     \
-  k_xl_kmc<T><<<grid, kBlock, 0, s>>>(h->m, h->left.as<int32_t>(), h->right.as<int32_t>(), h->cptr.as<int32_t>(),    \
-                                      h->ccol.as<int32_t>(), center, keys, counters, h->p, dt, events, z_total)
-  if (h->type == MHIP_SPRING_FENE) XL_KMC(MHIP_SPRING_FENE);
-  else XL_KMC(MHIP_SPRING_HOOKEAN);
-#undef XL_KMC
+  dispatch<MHIP_SPRING_FENE, MHIP_SPRING_HOOKEAN>(h->type, [&](auto type) {
+    k_xl_kmc<decltype(type)::value><<<grid, kBlock, 0, s>>>(
+        h->m, h->left.as<int32_t>(), h->right.as<int32_t>(), h->cptr.as<int32_t>(), h->ccol.as<int32_t>(), center, keys,
+        counters, h->p, dt, events, z_total);
+  });
   MHIP_LAUNCH_CHECK();
   // the right ends moved (or not: the rebuild is cheaper than a host round trip to find out)
   return build_right(h, s);
@@ -404,18 +308,13 @@ int mhip_crosslinkers_force(mhip_crosslinkers_t h, const double* center, double*
   if (h->n == 0) return MHIP_SUCCESS;
   const unsigned grid = grid_for(h->n);
   unsigned long long* mx = reinterpret_cast<unsigned long long*>(max_length);
-#define XL_FORCE(T, ACC)                                                                                             \
-  k_xl_force<T, ACC><<<grid, kBlock, 0, s>>>(h->n, h->lptr.as<int32_t>(), h->lent.as<int32_t>(),                     \
-                                             h->rptr.as<int32_t>(), h->rent.as<int32_t>(), h->left.as<int32_t>(),    \
-                                             h->right.as<int32_t>(), center, h->p.k, h->p.r, force, overstretched, mx)
-  if (h->type == MHIP_SPRING_FENE) {
-    if (accumulate) XL_FORCE(MHIP_SPRING_FENE, true);
-    else XL_FORCE(MHIP_SPRING_FENE, false);
-  } else {
-    if (accumulate) XL_FORCE(MHIP_SPRING_HOOKEAN, true);
-    else XL_FORCE(MHIP_SPRING_HOOKEAN, false);
-  }
-#undef XL_FORCE
+  dispatch<MHIP_SPRING_FENE, MHIP_SPRING_HOOKEAN>(h->type, [&](auto type) {
+    dispatch<true, false>(accumulate != 0, [&](auto acc) {
+      k_xl_force<decltype(type)::value, decltype(acc)::value><<<grid, kBlock, 0, s>>>(
+          h->n, h->lptr.as<int32_t>(), h->lent.as<int32_t>(), h->rptr.as<int32_t>(), h->rent.as<int32_t>(),
+          h->left.as<int32_t>(), h->right.as<int32_t>(), center, h->p.k, h->p.r, force, overstretched, mx);
+    });
+  });
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
 }

@@ -1,0 +1,189 @@
+// force_device.hpp -- what the soft-force sources (hertz.hip, hertz_friction.hip, chain.hip, crosslink.hip, periphery.hip,
+// active.hip) share: the statistic epilogues, the spring and Hertz pair terms, the counter-based generator every
+// reference app draws from, the per-body force write, the body -> entry incidence build, the run-time flag -> template
+// argument dispatch and the lifetime of a handle's buffers.  (Not in mhip_internal.hpp: that header is part of the stamp
+// the measured solver traffic carries, build.py::sweep_kernels_stamp.)
+#pragma once
+#include "mhip_internal.hpp"
+
+#include <memory>
+#include <type_traits>
+
+namespace mhip {
+
+// ---- host: handle buffers, HIP status, flag dispatch -------------------------------------------------------------
+// A buffer owned by a heap-allocated handle: released with it.  (DeviceBuffer itself has no destructor: static and
+// thread_local buffers would call hipFree during process teardown.)
+struct HandleBuffer : DeviceBuffer {
+  HandleBuffer() = default;
+  HandleBuffer(const HandleBuffer&) = delete;
+  HandleBuffer& operator=(const HandleBuffer&) = delete;
+  ~HandleBuffer() { release(); }
+};
+
+// a HIP error as the status of the function `fn`: hip_status(__func__, hipMemcpyAsync(...))
+inline int hip_status(const char* fn, hipError_t err) {
+  return err == hipSuccess ? MHIP_SUCCESS : fail(MHIP_ERR_HIP, "%s: %s", fn, hipGetErrorString(err));
+}
+// a caller's host array into a handle's buffer
+inline int upload(const char* fn, HandleBuffer& dst, const void* src, size_t bytes, hipStream_t s) {
+  return hip_status(fn, hipMemcpyAsync(dst.ptr, src, bytes, hipMemcpyHostToDevice, s));
+}
+
+// A run-time flag (a bool or a small enum) becomes a template argument: f(std::integral_constant<T, V>{}) for the first V
+// of the list equal to v, for the last one when none is; inside f, decltype(arg)::value.  (convex.hip keeps its own
+// pick<> of the same shape: that file is part of the solver stamp and is not edited for this.)
+template <auto V, auto... Rest, class F>
+void dispatch(decltype(V) v, F&& f) {
+  if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<decltype(V), V>{});
+  else if (v == V) f(std::integral_constant<decltype(V), V>{});
+  else dispatch<Rest...>(v, f);
+}
+template <class F>
+void dispatch_bools(bool a, bool b, F&& f) {  // f(std::bool_constant<a>{}, std::bool_constant<b>{})
+  dispatch<true, false>(a, [&](auto ca) { dispatch<true, false>(b, [&](auto cb) { f(ca, cb); }); });
+}
+
+// ---- body -> entry incidence (chain.hip) -------------------------------------------------------------------------
+// A source lists item i of m at bodies: src(i, f) calls f(body, entry) for each.  build_incidence: count -> exclusive
+// scan -> fill -> per-body sort into ptr[0 .. n], ent, every body's list ascending (the fill order depends on atomic
+// arrival).  deg: n + 1 ints of scratch; ws: scan_workspace_bytes(n).  m == 0: ptr all zero, no launches.
+struct PairEnds {  // entry (s << 1) | side of pair s at body pairs[s][side]
+  const int2* pairs;
+  template <class F>
+  __device__ void operator()(size_t s, F&& f) const {
+    const int2 p = pairs[s];
+    f(p.x, static_cast<int32_t>(s << 1));
+    f(p.y, static_cast<int32_t>((s << 1) | 1));
+  }
+};
+struct ListedAt {  // entry c at body at[c]; with `other`, only where at[c] != other[c]
+  const int32_t* at;
+  const int32_t* other;
+  template <class F>
+  __device__ void operator()(size_t c, F&& f) const {
+    const int32_t b = at[c];
+    if (!other || other[c] != b) f(b, static_cast<int32_t>(c));
+  }
+};
+template <class SRC>
+int build_incidence(size_t n, size_t m, SRC src, int32_t* deg, int32_t* ptr, int32_t* ent, void* ws, hipStream_t s);
+
+// ---- Philox4x32-10 -----------------------------------------------------------------------------------------------
+// counter (c0, c1, c2, c3), key (k0, k1): ten rounds, the key bumped by the Weyl increments between rounds
+constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
+constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
+
+__device__ inline uint4 philox4x32_10(uint4 c, uint2 k) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    if (r > 0) {
+      k.x += kPhiloxW0;
+      k.y += kPhiloxW1;
+    }
+    const uint64_t p0 = static_cast<uint64_t>(kPhiloxM0) * c.x;
+    const uint64_t p1 = static_cast<uint64_t>(kPhiloxM1) * c.z;
+    c = make_uint4(static_cast<uint32_t>(p1 >> 32) ^ c.y ^ k.x, static_cast<uint32_t>(p1),
+                   static_cast<uint32_t>(p0 >> 32) ^ c.w ^ k.y, static_cast<uint32_t>(p0));
+  }
+  return c;
+}
+// key = (lo32, hi32) of the 64-bit key; counter = (lo32, hi32) of the 64-bit counter, then the block index, then 0
+__device__ inline uint4 philox_draw(uint64_t key, uint64_t ctr, uint32_t block) {
+  return philox4x32_10(make_uint4(static_cast<uint32_t>(ctr), static_cast<uint32_t>(ctr >> 32), block, 0u),
+                       make_uint2(static_cast<uint32_t>(key), static_cast<uint32_t>(key >> 32)));
+}
+// the 53-bit integer m = (w0 << 21) | (w1 >> 11) of the first two words: m 2^-53 in [0, 1), (m + 1) 2^-53 in (0, 1]
+__device__ inline uint64_t philox_u53(uint4 w) {
+  return (static_cast<uint64_t>(w.x) << 21) | static_cast<uint64_t>(w.y >> 11);
+}
+
+// ---- statistic epilogues: every lane of the workgroup calls them, after its grid-stride loop ---------------------
+// The largest v of the launch goes to one device double through an atomic max on its bit pattern: every candidate is a
+// non-negative double, whose bits order like the value, so the result does not depend on the order in which workgroups
+// arrive.  Wave max, then across the workgroup's waves, then one atomic per workgroup (the grid is capped at kMaxGrid),
+// none for +0.0 or a null `bits`.  Once per kernel: the LDS slots are not fenced for a second use.
+__device__ inline void block_stat_max(double v, unsigned long long* bits) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double o = __shfl_xor(v, off, 64);
+    v = o > v ? o : v;
+  }
+  __shared__ double wave_max[kBlock / 64];
+  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0 && bits) {
+    double m = wave_max[0];
+#pragma unroll
+    for (int w = 1; w < kBlock / 64; ++w) m = wave_max[w] > m ? wave_max[w] : m;
+    if (m > 0.0) atomicMax(bits, static_cast<unsigned long long>(__double_as_longlong(m)));
+  }
+}
+// a counter summed over the workgroup: one atomic per workgroup, none for 0 (once per kernel, as block_stat_max)
+__device__ inline void block_stat_add(unsigned v, unsigned long long* dst) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  __shared__ unsigned wave_count[kBlock / 64];
+  if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned k = 0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) k += wave_count[w];
+    if (k > 0) atomicAdd(dst, static_cast<unsigned long long>(k));
+  }
+}
+// a counter summed over the wave: one atomic per wave, none for 0 or a null dst
+__device__ inline void wave_stat_add(int v, int* dst) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((threadIdx.x & 63) == 0 && v && dst) atomicAdd(dst, v);
+}
+
+// ---- force laws ---------------------------------------------------------------------------------------------------
+// A spring of length L = |d| pulls with fm d.  Hookean (r = rest length): fm = k (L - r) (1 / L) (NgpHP1.cpp:1054-1069,
+// its association).  FENE (r = r_max), -grad of U = -1/2 k r_max^2 ln(1 - (L / r_max)^2): attractive, and no force (NaN)
+// at L >= r_max -- the caller counts that spring as overstretched where !(L < r).
+struct SpringTerm {
+  double L, fm;
+};
+template <int TYPE>
+__device__ inline SpringTerm spring_term(V3 d, double k, double r) {
+  const double L = sqrt(dot(d, d));
+  if (TYPE == MHIP_SPRING_HOOKEAN) return {L, k * (L - r) * (1.0 / L)};
+  const double q = L / r;
+  return {L, (L < r) ? k / (1.0 - q * q) : __builtin_nan("")};
+}
+// f -= fm d or f += fm d: the term is formed in the same operations at both ends of a spring, so the two ends receive
+// exactly negated vectors
+__device__ inline void add_term(V3& f, bool minus, double fm, V3 d) {
+  const V3 t = fm * d;
+  f = minus ? f - t : f + t;
+}
+
+// The (r, E, nu) of a pair's two bodies (scalar materials are kernel arguments: no per-body gather), its reduced radius
+// and effective modulus E* in the reference's expressions and association
+// (SpherocylinderSpherocylinderHertzianContact.cpp:205-219).
+struct HertzPair {
+  double ri, rj, Ei, Ej, vi, vj, Rs, Es;
+};
+template <bool E_ARRAY, bool NU_ARRAY>
+__device__ inline HertzPair hertz_pair(int2 p, const double* __restrict__ radius, const double* __restrict__ E, double E0,
+                                       const double* __restrict__ nu, double nu0) {
+  HertzPair h;
+  h.ri = radius[p.x], h.rj = radius[p.y];
+  h.Ei = E_ARRAY ? E[p.x] : E0, h.Ej = E_ARRAY ? E[p.y] : E0;
+  h.vi = NU_ARRAY ? nu[p.x] : nu0, h.vj = NU_ARRAY ? nu[p.y] : nu0;
+  h.Rs = (h.ri * h.rj) / (h.ri + h.rj);
+  h.Es = (h.Ei * h.Ej) / (h.Ej - h.Ej * h.vi * h.vi + h.Ei - h.Ei * h.vj * h.vj);
+  return h;
+}
+
+// The row of body b: force + f or f.  A kernel that leaves the rows of untouched bodies alone in accumulate mode skips
+// the call (force + 0.0 would turn a -0.0 into +0.0, and cost the traffic).
+template <bool ACCUMULATE>
+__device__ inline void write_force(double* __restrict__ force, size_t b, V3 f) {
+  store3(force, b, ACCUMULATE ? load3(force, b) + f : f);
+}
+
+}  // namespace mhip

@@ -4,12 +4,11 @@
 // HertzianContact.cpp).  Per contact: a pair and its signed separation are read, for overlapping pairs only the two
 // bodies' (r, E, nu) are gathered, and one force magnitude is written.  Elementwise and HBM bound.
 #include "mhip_internal.hpp"
+#include "force_device.hpp"
 
 namespace mhip {
 
-// The largest overlap max(0, -sep) of the launch goes to one device double through an atomic max on its bit pattern:
-// every candidate is a non-negative double, whose bits order like the value, so the result does not depend on the
-// order in which workgroups arrive.  One atomic per workgroup (the grid is capped at kMaxGrid workgroups).
+// The largest overlap max(0, -sep) of the launch goes to *max_overlap_bits (block_stat_max).
 // One contact per lane and pass.  (Four contacts a grid stride apart per lane, all their loads issued before the first is
 // used: 0.0692 against 0.0705 ms per launch at 10^6 rods, profiles/hertz_ab_unroll.txt -- not kept.)
 template <bool E_ARRAY, bool NU_ARRAY>
@@ -26,33 +25,13 @@ __global__ void __launch_bounds__(kBlock)
     if (static_cast<unsigned>(p.x) >= N || static_cast<unsigned>(p.y) >= N) {
       f = __builtin_nan("");  // a pair outside [0, N) is never dereferenced
     } else if (s < 0.0) {
-      const double ri = radius[p.x], rj = radius[p.y];
-      // scalar materials are kernel arguments: no per-body gather
-      const double Ei = E_ARRAY ? E[p.x] : E0, Ej = E_ARRAY ? E[p.y] : E0;
-      const double vi = NU_ARRAY ? nu[p.x] : nu0, vj = NU_ARRAY ? nu[p.y] : nu0;
-      // the reference's expressions and association (SpherocylinderSpherocylinderHertzianContact.cpp:205-219)
-      const double Rs = (ri * rj) / (ri + rj);
-      const double Es = (Ei * Ej) / (Ej - Ej * vi * vi + Ei - Ei * vj * vj);
-      f = (4.0 / 3.0) * Es * sqrt(Rs) * pow(-s, 1.5);
+      const HertzPair h = hertz_pair<E_ARRAY, NU_ARRAY>(p, radius, E, E0, nu, nu0);
+      f = (4.0 / 3.0) * h.Es * sqrt(h.Rs) * pow(-s, 1.5);
       dmax = -s > dmax ? -s : dmax;
     }
     force[c] = f;
   }
-  // wave max, then across the workgroup's four waves, then one atomic
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double o = __shfl_xor(dmax, off, 64);
-    dmax = o > dmax ? o : dmax;
-  }
-  __shared__ double wave_max[kBlock / 64];
-  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = dmax;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double m = wave_max[0];
-#pragma unroll
-    for (int w = 1; w < kBlock / 64; ++w) m = wave_max[w] > m ? wave_max[w] : m;
-    if (m > 0.0) atomicMax(max_overlap_bits, static_cast<unsigned long long>(__double_as_longlong(m)));
-  }
+  block_stat_max(dmax, max_overlap_bits);
 }
 
 }  // namespace mhip
@@ -80,14 +59,10 @@ int mhip_hertz_contact_force(size_t c, size_t n, const int32_t* pairs, const dou
   unsigned long long* mx = reinterpret_cast<unsigned long long*>(max_overlap);
   const double E0 = youngs_modulus_scalar, nu0 = poisson_ratio_scalar;
   const unsigned grid = grid_for(c);
-  if (youngs_modulus && poisson_ratio)
-    k_hertz_force<true, true><<<grid, kBlock, 0, s>>>(c, n, p2, sep, radius, youngs_modulus, E0, poisson_ratio, nu0, force, mx);
-  else if (youngs_modulus)
-    k_hertz_force<true, false><<<grid, kBlock, 0, s>>>(c, n, p2, sep, radius, youngs_modulus, E0, nullptr, nu0, force, mx);
-  else if (poisson_ratio)
-    k_hertz_force<false, true><<<grid, kBlock, 0, s>>>(c, n, p2, sep, radius, nullptr, E0, poisson_ratio, nu0, force, mx);
-  else
-    k_hertz_force<false, false><<<grid, kBlock, 0, s>>>(c, n, p2, sep, radius, nullptr, E0, nullptr, nu0, force, mx);
+  dispatch_bools(youngs_modulus != nullptr, poisson_ratio != nullptr, [&](auto ea, auto na) {
+    k_hertz_force<decltype(ea)::value, decltype(na)::value><<<grid, kBlock, 0, s>>>(
+        c, n, p2, sep, radius, youngs_modulus, E0, poisson_ratio, nu0, force, mx);
+  });
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
 }

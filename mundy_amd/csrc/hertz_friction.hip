@@ -8,6 +8,7 @@
 // its history row.  A pair out of contact owns two +0.0 rows (history, force); they are read and only written where
 // they are not +0.0 already, so a list whose separated pairs stay separated is never written there.
 #include "mhip_internal.hpp"
+#include "force_device.hpp"
 
 #include <cmath>
 
@@ -66,20 +67,16 @@ __global__ void __launch_bounds__(kBlock)
     td = td + rel_t * prm.dt;                                                         // :474
     td = td - dot(td, n) * n;                                                         // :475
     const double td_mag = norm(td);
-    const double ri = radius[p.x], rj = radius[p.y];
-    const double Ei = E_ARRAY ? E[p.x] : E0, Ej = E_ARRAY ? E[p.y] : E0;
-    const double ni = NU_ARRAY ? nu[p.x] : nu0, nj = NU_ARRAY ? nu[p.y] : nu0;
+    const HertzPair h = hertz_pair<E_ARRAY, NU_ARRAY>(p, radius, E, E0, nu, nu0);
     // the sphere mass of the rod radius, as written (:484-485)
-    const double mi = 4.0 / 3.0 * M_PI * ri * ri * ri * prm.density;
-    const double mj = 4.0 / 3.0 * M_PI * rj * rj * rj * prm.density;
-    const double Rs = (ri * rj) / (ri + rj);
+    const double mi = 4.0 / 3.0 * M_PI * h.ri * h.ri * h.ri * prm.density;
+    const double mj = 4.0 / 3.0 * M_PI * h.rj * h.rj * h.rj * prm.density;
     const double ms = (mi * mj) / (mi + mj);
     // k_n = 4/3 E* (hertz.hip's E*), k_t = 8 G*: for equal materials 4/3 G / (1 - nu) and 4 G / (2 - nu) (:409-411)
-    const double Es = (Ei * Ej) / (Ej - Ej * ni * ni + Ei - Ei * nj * nj);
-    const double Gi = 0.5 * Ei / (1.0 + ni), Gj = 0.5 * Ej / (1.0 + nj);
-    const double Gs = (Gi * Gj) / (Gj * (2.0 - ni) + Gi * (2.0 - nj));
-    const double kn = (4.0 / 3.0) * Es, kt = 8.0 * Gs;
-    const double hp = sqrt(-Rs * s);                                                  // :490
+    const double Gi = 0.5 * h.Ei / (1.0 + h.vi), Gj = 0.5 * h.Ej / (1.0 + h.vj);
+    const double Gs = (Gi * Gj) / (Gj * (2.0 - h.vi) + Gi * (2.0 - h.vj));
+    const double kn = (4.0 / 3.0) * h.Es, kt = 8.0 * Gs;
+    const double hp = sqrt(-h.Rs * s);                                                // :490
     const V3 damp_t = (ms * prm.tangential_damping) * rel_t;
     const V3 Fn = hp * ((kn * s) * n + (ms * prm.normal_damping) * rel_n);            // :491-493
     V3 Ft = hp * (kt * td + damp_t);                                                  // :494-495
@@ -100,30 +97,8 @@ __global__ void __launch_bounds__(kBlock)
     store3(force, c, Fn + Ft);  // on body i; body j receives the negative
     dmax = -s > dmax ? -s : dmax;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double o = __shfl_xor(dmax, off, 64);
-    dmax = o > dmax ? o : dmax;
-    capped += __shfl_xor(capped, off, 64);
-  }
-  __shared__ double wave_max[kBlock / 64];
-  __shared__ unsigned wave_capped[kBlock / 64];
-  if ((threadIdx.x & 63) == 0) {
-    wave_max[threadIdx.x >> 6] = dmax;
-    wave_capped[threadIdx.x >> 6] = capped;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double m = wave_max[0];
-    unsigned k = wave_capped[0];
-#pragma unroll
-    for (int w = 1; w < kBlock / 64; ++w) {
-      m = wave_max[w] > m ? wave_max[w] : m;
-      k += wave_capped[w];
-    }
-    if (m > 0.0) atomicMax(stats, static_cast<unsigned long long>(__double_as_longlong(m)));
-    if (k > 0) atomicAdd(stats + 1, static_cast<unsigned long long>(k));
-  }
+  block_stat_max(dmax, stats);
+  block_stat_add(capped, stats + 1);
 }
 
 // ---- history carry ---------------------------------------------------------------------------------------------------
@@ -192,17 +167,7 @@ __global__ void __launch_bounds__(kBlock)
     }
     store3(hist_new, c, h);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) found += __shfl_xor(found, off, 64);
-  __shared__ unsigned wave_found[kBlock / 64];
-  if ((threadIdx.x & 63) == 0) wave_found[threadIdx.x >> 6] = found;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned k = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) k += wave_found[w];
-    if (k > 0) atomicAdd(carried, static_cast<unsigned long long>(k));
-  }
+  block_stat_add(found, carried);
 }
 
 struct CarryScratch {
@@ -253,15 +218,11 @@ int mhip_hertz_friction_force(size_t c, size_t n, const int32_t* pairs, const do
   unsigned long long* st = static_cast<unsigned long long*>(stats);
   const double E0 = youngs_modulus_scalar, nu0 = poisson_ratio_scalar;
   const unsigned grid = grid_for(c);
-  auto launch = [&](auto ea, auto na) {
+  dispatch_bools(youngs_modulus != nullptr, poisson_ratio != nullptr, [&](auto ea, auto na) {
     k_hertz_friction_force<decltype(ea)::value, decltype(na)::value><<<grid, kBlock, 0, s>>>(
         c, n, p2, sep, normal, arc_s, arc_t, seg, radius, youngs_modulus, E0, poisson_ratio, nu0, velocity_prev, *params,
         tang_disp, force, st);
-  };
-  if (youngs_modulus && poisson_ratio) launch(std::true_type{}, std::true_type{});
-  else if (youngs_modulus) launch(std::true_type{}, std::false_type{});
-  else if (poisson_ratio) launch(std::false_type{}, std::true_type{});
-  else launch(std::false_type{}, std::false_type{});
+  });
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
 }

@@ -9,6 +9,7 @@
 // The sphere and fast kernels stream 32 B per body (+ 48 B read-modify-write for a colliding one): HBM bound.  The exact
 // kernel runs its Newton iteration on the minority of lanes next to the wall.
 #include "mhip_internal.hpp"
+#include "force_device.hpp"
 #include "segment_ellipsoid.hpp"
 
 #include <cmath>
@@ -89,38 +90,14 @@ __global__ void __launch_bounds__(kBlock)
     if (hit) {
       ++hits;
       omax = over > omax ? over : omax;
-      if (ACCUMULATE) {
-        force[3 * b] = force[3 * b] - fx;
-        force[3 * b + 1] = force[3 * b + 1] - fy;
-        force[3 * b + 2] = force[3 * b + 2] - fz;
-      } else {
-        force[3 * b] = 0.0 - fx;
-        force[3 * b + 1] = 0.0 - fy;
-        force[3 * b + 2] = 0.0 - fz;
-      }
-    } else if (!ACCUMULATE) {
-      force[3 * b] = 0.0;
-      force[3 * b + 1] = 0.0;
-      force[3 * b + 2] = 0.0;
+      // the wall force is taken off the row, or off +0.0: x - f is x + (-f) exactly, but 0.0 - f is not -f for f = +0.0
+      write_force<ACCUMULATE>(force, b, ACCUMULATE ? V3{-fx, -fy, -fz} : V3{0.0 - fx, 0.0 - fy, 0.0 - fz});
+    } else if (!ACCUMULATE) {  // accumulate: untouched without contact
+      write_force<false>(force, b, V3{0.0, 0.0, 0.0});
     }
   }
-  // one atomic per wave for the count; non-negative doubles order like their bits (as chain.hip's k_spring_force)
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double o = __shfl_xor(omax, off, 64);
-    omax = o > omax ? o : omax;
-    hits += __shfl_xor(hits, off, 64);
-  }
-  if ((threadIdx.x & 63) == 0 && hits && colliding) atomicAdd(colliding, hits);
-  __shared__ double wave_max[kBlock / 64];
-  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = omax;
-  __syncthreads();
-  if (threadIdx.x == 0 && max_overlap_bits) {
-    double mx = wave_max[0];
-#pragma unroll
-    for (int w = 1; w < kBlock / 64; ++w) mx = wave_max[w] > mx ? wave_max[w] : mx;
-    if (mx > 0.0) atomicMax(max_overlap_bits, static_cast<unsigned long long>(__double_as_longlong(mx)));
-  }
+  wave_stat_add(hits, colliding);
+  block_stat_max(omax, max_overlap_bits);
 }
 
 }  // namespace mhip
@@ -165,15 +142,12 @@ int mhip_periphery_force(const mhip_periphery* cfg, size_t n, const double* cent
                      Quat{cfg->quat[0], cfg->quat[1], cfg->quat[2], cfg->quat[3]}, V3{cfg->radii[0], r1, r2}, cfg->k};
   const unsigned grid = grid_for(n);
   unsigned long long* mx = reinterpret_cast<unsigned long long*>(max_overlap);
-#define PERIPHERY(S)                                                                                            \
-  do {                                                                                                          \
-    if (accumulate) k_periphery_force<S, true><<<grid, kBlock, 0, s>>>(n, P, center, radius, force, colliding, mx); \
-    else k_periphery_force<S, false><<<grid, kBlock, 0, s>>>(n, P, center, radius, force, colliding, mx);       \
-  } while (0)
-  if (shape == MHIP_PERIPHERY_SPHERE) PERIPHERY(MHIP_PERIPHERY_SPHERE);
-  else if (shape == MHIP_PERIPHERY_ELLIPSOID) PERIPHERY(MHIP_PERIPHERY_ELLIPSOID);
-  else PERIPHERY(MHIP_PERIPHERY_ELLIPSOID_FAST);
-#undef PERIPHERY
+  dispatch<MHIP_PERIPHERY_SPHERE, MHIP_PERIPHERY_ELLIPSOID, MHIP_PERIPHERY_ELLIPSOID_FAST>(shape, [&](auto sh) {
+    dispatch<true, false>(accumulate != 0, [&](auto acc) {
+      k_periphery_force<decltype(sh)::value, decltype(acc)::value><<<grid, kBlock, 0, s>>>(n, P, center, radius, force,
+                                                                                          colliding, mx);
+    });
+  });
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
 }

@@ -11,7 +11,10 @@ import pytest
 import torch
 
 import chain_model as cm
-from gpu_util import assert_bits_equal, dev, host
+import friction_hertz_model as fm
+import hertz_model as hm
+from gpu_util import (PAST_FULL_GRID, STAT_POSITIONS, all_pos_zero, assert_bits_equal, dev, host, line_with_one_long_bond,
+                      star_graph)
 
 pytestmark = pytest.mark.gpu
 
@@ -90,6 +93,89 @@ def test_fene_overstretched_counted_and_stepper_raises():
     st = pipeline.ContactStepper("sphere", dev(c), dev(np.full(4, 0.3)), springs=(pairs, "fene", 3.0, 1.5))
     with pytest.raises(RuntimeError, match="FENE"):
         st.step()
+
+
+# ---- the statistic epilogue the force kernels share: the maximum is found wherever it sits ------------------------------
+@pytest.mark.parametrize("pos", STAT_POSITIONS)
+def test_spring_max_length_is_found_wherever_it_sits(pos):
+    from mundy_amd import ops
+    n = PAST_FULL_GRID
+    c, pairs = line_with_one_long_bond(pos)
+    s = ops.Springs(n, pairs, "hookean", 3.0, 0.75)
+    f, over, mx = s.force(dev(c))
+    want, wover, wmx = cm.spring_force(n, pairs, "hookean", 3.0, 0.75, c)
+    assert wmx == 1.5 and float(mx.item()) == wmx and int(over.item()) == wover == 0
+    assert_bits_equal(host(f), want, "line, long bond at %d" % pos)
+    s.close()
+
+
+def _contacts_with_one_deep_overlap(pos, bodies):
+    """PAST_FULL_GRID contacts dealt round robin to `bodies` disjoint body pairs (2 k, 2 k + 1): overlap 0.25, every
+    third one apart, contact pos overlapping by 0.5"""
+    c = PAST_FULL_GRID
+    k = np.arange(c) % bodies
+    pairs = np.stack([2 * k, 2 * k + 1], axis=1).astype(np.int32)
+    sep = np.full(c, -0.25)
+    sep[1::3] = 0.125
+    sep[pos] = -0.5
+    return pairs, sep
+
+
+@pytest.mark.parametrize("pos", STAT_POSITIONS)
+def test_hertz_max_overlap_is_found_wherever_it_sits(pos):
+    from mundy_amd import ops
+    pairs, sep = _contacts_with_one_deep_overlap(pos, 1024)
+    radius = np.full(2048, 0.5)
+    _, mx = ops.hertz_contact_force(dev(pairs), dev(sep), dev(radius))
+    _, wmx = hm.hertz_force(pairs, sep, radius)
+    assert wmx == 0.5 and float(mx.item()) == wmx
+
+
+@pytest.mark.parametrize("pos", STAT_POSITIONS)
+def test_friction_hertz_statistics_are_found_wherever_they_sit(pos):
+    """every odd body pair slides sideways at speed 1 with mu = 1e-4: F_t = h k_t dt = 0.23 against mu F_n = 0.005, capped
+    by a wide margin; the even pairs are at rest, F_t = 0: not capped whatever the rounding"""
+    from mundy_amd import ops
+    nb = 1024
+    pairs, sep = _contacts_with_one_deep_overlap(pos, nb)
+    c = pairs.shape[0]
+    seg = np.tile([-1.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0], (2 * nb, 1))
+    radius = np.full(2 * nb, 0.5)
+    vel = np.zeros((2 * nb, 6))
+    vel[3::4, 0] = 1.0
+    normal, arc, td0 = np.tile([0.0, 0.0, 1.0], (c, 1)), np.full(c, 0.5), np.zeros((c, 3))
+    mu, dt = 1e-4, 1e-3
+    td = dev(td0)
+    f, stats = ops.hertz_friction_force(dev(pairs), dev(sep), dev(normal), dev(arc), dev(arc), dev(seg), dev(radius),
+                                        dev(vel), td, mu, dt)
+    wf, wtd, wmx, wcapped = fm.friction_force(pairs, sep, normal, arc, arc, seg, radius, 1000.0, 0.3, vel, mu, 0.0, 0.0,
+                                              1.0, dt, td0)
+    h = stats.cpu()
+    assert wmx == 0.5 and float(h[0]) == wmx
+    assert int(h.view(torch.int64)[1]) == wcapped == int(((pairs[:, 0] % 4 == 2) & (sep < 0)).sum())
+    assert_bits_equal(host(f), wf, "force")
+    assert_bits_equal(host(td), wtd, "history")
+
+
+# ---- the incidence build the handles share: empty and degenerate lists ---------------------------------------------
+@pytest.mark.parametrize("case", ["no springs", "one body", "star"])
+def test_spring_incidence_empty_and_star(case):
+    from mundy_amd import ops
+    rng = np.random.default_rng(31)
+    n, pairs = {"no springs": (5, np.zeros((0, 2), np.int32)), "one body": (1, np.zeros((0, 2), np.int32)),
+                "star": star_graph()}[case]
+    c = rng.normal(size=(n, 3))
+    s = ops.Springs(n, pairs, "hookean", 3.0, 0.5)
+    f, over, mx = s.force(dev(c))
+    want, wover, wmx = cm.spring_force(n, pairs, "hookean", 3.0, 0.5, c)
+    assert_bits_equal(host(f), want, case)
+    assert int(over.item()) == wover == 0
+    assert np.float64(mx.item()).view(np.uint64) == np.float64(wmx).view(np.uint64)
+    if case == "star":
+        assert np.bincount(pairs.ravel())[0] == 100 and all_pos_zero(host(f)[101:]) and wmx > 0
+    else:
+        assert all_pos_zero(host(f)) and all_pos_zero(host(mx))
+    s.close()
 
 
 # ---- generator -------------------------------------------------------------------------------------------------------

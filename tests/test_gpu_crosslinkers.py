@@ -10,7 +10,8 @@ import torch
 
 import chain_model as cm
 import crosslinker_model as xm
-from gpu_util import assert_bits_equal, dev, host
+from gpu_util import (PAST_FULL_GRID, STAT_POSITIONS, all_pos_zero, assert_bits_equal, dev, host, line_with_one_long_bond,
+                      renumberings, star_and_random_graph, star_graph)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -165,6 +166,102 @@ def test_force_after_events_equals_a_fresh_handle():
         assert_bits_equal(f, xm.crosslinker_force(n, le, ri, "hookean", p["k"], p["r"], d["center"])[0], "model")
         fresh.close()
     assert int((ri != le).sum()) == int((d["right"] != d["left"]).sum()) + total[0] - total[1]
+
+
+# ---- 3b. the helpers shared with the other force kernels: statistic epilogue, incidence build ------------------------
+PAR = dict(kind="hookean", k=5.0, r=0.5, bind_rate=2.0, unbind_rate=6.0, kt=1.0, capture_radius=1.0)
+
+
+@pytest.mark.parametrize("pos", STAT_POSITIONS)
+def test_crosslinker_max_length_is_found_wherever_it_sits(pos):
+    n = PAST_FULL_GRID
+    c, pairs = line_with_one_long_bond(pos)   # the left ends take the statistics
+    xl = _handle(n, pairs[:, 0], pairs[:, 1], np.ones(n, np.uint8), PAR)
+    f, over, mx = xl.force(dev(c))
+    want, wover, wmx = xm.crosslinker_force(n, pairs[:, 0], pairs[:, 1], "hookean", PAR["k"], PAR["r"], c)
+    assert wmx == 1.5 and float(mx.item()) == wmx and int(over.item()) == wover == 0
+    assert_bits_equal(host(f), want, "line, long crosslinker at %d" % pos)
+    xl.close()
+
+
+@pytest.mark.parametrize("case", ["no crosslinkers", "one body", "star", "all singly bound"])
+def test_crosslinker_incidence_empty_and_star(case):
+    rng = np.random.default_rng(32)
+    none = np.zeros(0, np.int64)
+    if case == "star":
+        n, pairs = star_graph()
+        left, right = pairs[:, 0], pairs[:, 1]
+    elif case == "all singly bound":   # the right incidence is empty, the left one is not
+        n = 121
+        left = rng.integers(0, 100, 300)
+        right = left.copy()
+    else:
+        n, left, right = (5 if case == "no crosslinkers" else 1), none, none
+    c = rng.normal(size=(n, 3))
+    xl = _handle(n, left, right, np.ones(n, np.uint8), PAR)
+    f, over, mx = xl.force(dev(c))
+    want, wover, wmx = xm.crosslinker_force(n, left, right, "hookean", PAR["k"], PAR["r"], c)
+    assert_bits_equal(host(f), want, case)
+    assert int(over.item()) == wover == 0
+    assert np.float64(mx.item()).view(np.uint64) == np.float64(wmx).view(np.uint64)
+    if case == "star":
+        assert all_pos_zero(host(f)[101:]) and wmx > 0
+        base = -np.zeros((n, 3))
+        base[:101] = rng.normal(size=(101, 3))
+        acc = dev(base)
+        xl.force(dev(c), out=acc, accumulate=True)
+        assert_bits_equal(host(acc)[:101], (base + want)[:101], "accumulate")
+    else:
+        assert all_pos_zero(host(f)) and all_pos_zero(host(mx))
+    xl.close()
+
+
+@pytest.fixture(scope="module")
+def renumber_case():
+    """the star and a random graph of 3000 bodies as doubly bound crosslinkers, 2000 singly bound ones, in a box dense
+    enough for tens of candidates per row"""
+    rng = np.random.default_rng(33)
+    n, pairs = star_and_random_graph(rng)
+    single = rng.integers(0, n, 2000)
+    left = np.concatenate([pairs[:, 0], single]).astype(np.int64)
+    right = np.concatenate([pairs[:, 1], single]).astype(np.int64)
+    m = left.shape[0]
+    return dict(n=n, left=left, right=right, center=rng.uniform(0.0, 8.0, (n, 3)), perms=renumberings(rng, n),
+                ids=rng.permutation(n).astype(np.int64), keys=rng.integers(0, 2 ** 63, m, dtype=np.int64),
+                counter=rng.integers(0, 2 ** 40, m, dtype=np.int64))
+
+
+@pytest.mark.parametrize("which", ["reversed", "random"])
+def test_renumbered_crosslinkers_equal_a_fresh_handle(renumber_case, which):
+    d = renumber_case
+    n, new_of_old = d["n"], d["perms"][which]
+    sites = np.ones(n, np.uint8)
+    xl = _handle(n, d["left"], d["right"], sites, PAR)
+    xl.renumber(dev(new_of_old))
+    left, right = new_of_old[d["left"]].astype(np.int64), new_of_old[d["right"]].astype(np.int64)
+    le, ri = (host(t).astype(np.int64) for t in xl.state("cuda"))
+    assert (le == left).all() and (ri == right).all()
+    fresh = _handle(n, left, right, sites, PAR)
+    c = np.empty_like(d["center"])
+    c[new_of_old] = d["center"]
+    center = dev(c)
+    f = host(xl.force(center)[0])
+    assert_bits_equal(f, host(fresh.force(center)[0]), "fresh handle")
+    want = xm.crosslinker_force(n, d["left"], d["right"], "hookean", PAR["k"], PAR["r"], d["center"])[0]
+    assert_bits_equal(f[new_of_old], want, "model in the old numbering")
+    # one KMC step on the same candidates and streams: the same events, the same state, the same force afterwards
+    links, _ = _search(center, left, sites, PAR["capture_radius"], 0.1)
+    out = []
+    for h in (xl, fresh):
+        h.set_candidates(links.row_ptr, links.col, dev(d["ids"]))
+        keys, ctr = _i64(d["keys"]), _i64(d["counter"])
+        ev = host(h.kmc_step(center, 0.05, keys, ctr))
+        out.append((ev, host(h.state("cuda")[1]), host(h.force(center)[0])))
+    assert out[0][0][0] > 0 and out[0][0][1] > 0
+    assert (out[0][0] == out[1][0]).all() and (out[0][1] == out[1][1]).all()
+    assert_bits_equal(out[0][2], out[1][2], "force after the step")
+    xl.close()
+    fresh.close()
 
 
 # ---- 4. statistics -----------------------------------------------------------------------------------------------------

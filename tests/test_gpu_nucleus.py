@@ -13,7 +13,8 @@ import torch
 import chain_model as cm
 import crosslinker_model as xm
 import periphery_model as pm
-from gpu_util import assert_bits_equal, dev, host
+from gpu_util import (PAST_FULL_GRID, STAT_POSITIONS, all_pos_zero, assert_bits_equal, dev, host, line_with_one_long_bond,
+                      renumberings, star_and_random_graph, star_graph)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -145,6 +146,44 @@ def test_fast_ellipsoid_periphery_bit_for_bit():
                  "fast, added, n = %d" % n)
         if n >= 257:
             assert 0.1 * n < want[1] < 0.7 * n
+
+
+def _beads_on_the_axes(pos, n=PAST_FULL_GRID, R=2.0):
+    """beads of radius 0.5 on the coordinate axes of a sphere of radius R: at distance 1.75 (overlap 0.25), every third
+    one at 1.0 (inside, untouched), bead pos at 2.0 (overlap 0.5); all exact"""
+    dist = np.full(n, R - 0.25)
+    dist[1::3] = 1.0
+    dist[pos] = R
+    c = np.zeros((n, 3))
+    c[np.arange(n), (np.arange(n) // 3) % 3] = dist
+    return c, np.full(n, 0.5)
+
+
+@pytest.mark.parametrize("pos", STAT_POSITIONS)
+def test_periphery_statistics_are_found_wherever_they_sit(pos):
+    c, r = _beads_on_the_axes(pos)
+    want = pm.sphere_force(c, r, 2.0, 7.0)
+    assert want[2] == 0.5 and want[1] == len(c) - len(c[1::3]) + (pos % 3 == 1)
+    _compare(_device(dict(shape="sphere", radius=2.0, k=7.0), c, r, None), want, "axes, deep bead at %d" % pos)
+
+
+def test_periphery_accumulate_leaves_untouched_rows_untouched():
+    """a bead the wall does not touch keeps its row, -0.0 included (force + 0.0 would make it +0.0)"""
+    rng = np.random.default_rng(15)
+    c, r = _beads_on_the_axes(0, n=20001)
+    inside = np.zeros(len(c), bool)
+    inside[1::3] = True
+    base = rng.normal(size=c.shape)
+    base[inside] = -0.0
+    for spec, model in ((dict(shape="sphere", radius=2.0, k=7.0), lambda: pm.sphere_force(c, r, 2.0, 7.0, force=base)),
+                        (dict(shape="ellipsoid_fast", radii=(2.0, 2.0, 2.0), k=7.0),
+                         lambda: pm.ellipsoid_fast_force(c, r, (2.0, 2.0, 2.0), 7.0, force=base)),
+                        (dict(shape="ellipsoid", radii=(2.0, 2.0, 2.0), k=7.0), None)):
+        got = _device(spec, c, r, base)
+        assert got[1] == int((~inside).sum()) and (got[0][inside].view(np.uint64) == 1 << 63).all(), spec["shape"]
+        assert (got[0][~inside] != base[~inside]).any(axis=1).all()
+        if model is not None:
+            _compare(got, model(), spec["shape"] + ", added into -0.0 rows")
 
 
 def test_ellipsoid_periphery_against_the_reference_routine(oracle):
@@ -323,6 +362,89 @@ def test_active_forces_bit_for_bit(which):
     f3, _ = act.force(dev(center[perm]))
     assert_bits_equal(host(f3), want[perm], which + ", renumbered")
     act.close()
+
+
+def test_active_count_past_a_full_grid():
+    from mundy_amd import ops
+    n = PAST_FULL_GRID
+    center, pairs = line_with_one_long_bond(0)
+    state = (np.random.default_rng(24).random(n - 1) < 0.4).astype(np.int32)
+    act = ops.ActiveSprings(n, pairs, 2.5, 1.0, 1.0)
+    act.set_state(state=dev(state))
+    f, na = act.force(dev(center))
+    want, count = pm.active_force(n, pairs, state, 2.5, center)
+    assert int(host(na)[0]) == count == int(state.sum()) > 0
+    assert_bits_equal(host(f), want, "line")
+    act.close()
+
+
+@pytest.mark.parametrize("case", ["no springs", "one body", "star"])
+def test_active_incidence_empty_and_star(case):
+    from mundy_amd import ops
+    rng = np.random.default_rng(25)
+    n, pairs = {"no springs": (5, np.zeros((0, 2), np.int32)), "one body": (1, np.zeros((0, 2), np.int32)),
+                "star": star_graph()}[case]
+    m = pairs.shape[0]
+    center = rng.normal(size=(n, 3))
+    state = (rng.random(m) < 0.7).astype(np.int32)
+    act = ops.ActiveSprings(n, pairs, 2.5, 1.0, 1.0)
+    if m:
+        act.set_state(state=dev(state))
+    assert not host(act.sample()).any()   # (nothing has elapsed: no spring switches, whatever m)
+    f, na = act.force(dev(center))
+    want, count = pm.active_force(n, pairs, state, 2.5, center)
+    assert_bits_equal(host(f), want, case)
+    assert int(host(na)[0]) == count == int(state.sum())
+    if case == "star":
+        assert count > 50 and all_pos_zero(host(f)[101:])
+    else:
+        assert all_pos_zero(host(f))
+    act.close()
+
+
+def test_active_accumulate_leaves_untouched_rows_untouched():
+    """a body without an active spring keeps its row, -0.0 included"""
+    from mundy_amd import ops
+    rng = np.random.default_rng(26)
+    n, pairs = star_and_random_graph(rng)
+    state = (rng.random(pairs.shape[0]) < 0.2).astype(np.int32)
+    state[:100] = 0                                # the hub's springs are all off: listed, yet untouched
+    center = rng.normal(size=(n, 3)) * 3.0
+    idle = np.ones(n, bool)
+    idle[pairs[state == 1].ravel()] = False
+    base = rng.normal(size=(n, 3))
+    base[idle] = -0.0
+    act = ops.ActiveSprings(n, pairs, 2.5, 1.0, 1.0)
+    act.set_state(state=dev(state))
+    f, _ = act.force(dev(center), out=dev(base.copy()), accumulate=True)
+    got = host(f)
+    assert idle[:121].all() and idle.sum() > 200 and (got[idle].view(np.uint64) == 1 << 63).all()
+    assert_bits_equal(got, pm.active_force(n, pairs, state, 2.5, center, force=base)[0], "added into -0.0 rows")
+    act.close()
+
+
+@pytest.mark.parametrize("which", ["reversed", "random"])
+def test_renumbered_active_springs_equal_a_fresh_handle(which):
+    from mundy_amd import ops
+    rng = np.random.default_rng(27)
+    n, pairs = star_and_random_graph(rng)
+    new_of_old = renumberings(rng, n)[which]
+    state = (rng.random(pairs.shape[0]) < 0.5).astype(np.int32)
+    center_old = rng.normal(size=(n, 3)) * 3.0
+    center = np.empty_like(center_old)
+    center[new_of_old] = center_old
+    act = ops.ActiveSprings(n, pairs, 2.5, 1.0, 1.0)
+    act.set_state(state=dev(state))
+    act.renumber(dev(new_of_old))
+    fresh = ops.ActiveSprings(n, new_of_old[pairs], 2.5, 1.0, 1.0)
+    fresh.set_state(state=dev(state))
+    (f, na), (g, nb) = act.force(dev(center)), fresh.force(dev(center))
+    assert_bits_equal(host(f), host(g), "fresh handle")
+    assert int(host(na)[0]) == int(host(nb)[0]) == int(state.sum())
+    assert_bits_equal(host(f)[new_of_old], pm.active_force(n, pairs, state, 2.5, center_old)[0],
+                      "model in the old numbering")
+    act.close()
+    fresh.close()
 
 
 def test_active_fraction_reaches_the_stationary_value():
