@@ -412,6 +412,96 @@ int mhip_active_springs_set_state(mhip_active_springs_t handle, const int32_t* s
 int mhip_active_springs_renumber(mhip_active_springs_t handle, const int32_t* new_of_old, mhip_stream_t stream);
 int mhip_active_springs_destroy(mhip_active_springs_t handle);
 
+/* Centerline-twist (discrete Kirchhoff rod) elastic filaments: the rod forces of the reference's sperm apps
+ * (scrap/parameter_interface/alens/tests/performance_tests/CollidingOverdampedFrictionalSperm.cpp; the same text in
+ * CollidingFrictionalSperm.cpp, CollidingSperm.cpp, NonInteractingSperm.cpp and scrap/Sperm.cpp).  DESIGN.md 5j.
+ * F filaments; filament f owns the contiguous nodes node_ptr[f] .. node_ptr[f + 1] - 1 (at least 2), N nodes in all.
+ * Edge e joins the nodes e and e + 1 of one filament and is indexed by its left node (the slot of a filament's last node
+ * is unused and stays +0.0); element i is (i - 1, i, i + 1) around an interior node i.  All state lives in the handle:
+ *   per node   center [N][3], twist [N], velocity [N][3], twist_velocity [N], force [N][3], twist_torque [N],
+ *              radius [N], rest_curvature [N][3], arclength [N], curvature [N][3] (interior nodes; +0.0 elsewhere)
+ *   per edge   tangent [N][3], orientation [N][4] (w, x, y, z), length [N], binormal [N][3], each kept twice: new and old
+ *              (the reference's StateNP1 / StateN)
+ *   per filament  phase [F] of the rest-curvature wave; the caller supplies it (the reference draws it from OpenRAND,
+ *              :1132-1133, whose stream this library does not reproduce); NULL = 0
+ * Arithmetic: dot(a, b) = a0 b0 + (a1 b1 + a2 b2), |a| = sqrt(dot(a, a)); v /= s divides componentwise and v / s
+ * multiplies by 1 / s (mundy_math/impl/VectorImpl.hpp:240-267); quaternion product and q * v as everywhere in this
+ * library (q (0, v) conjugate(q) / |q|^2); products and sums left to right as written; sin and cos are the library's
+ * fixed IEEE sequence (the oracle's shared_sincos).
+ *
+ * create  [host arrays node_ptr [F + 1] int32, radius [N], rest_curvature [N][3], arclength [N], phase [F] or NULL]
+ *   copies them and synchronises `stream`; every later call of the handle runs on that stream.  Refused with
+ *   MHIP_ERR_INVALID_ARGUMENT before any HIP call: a null handle / params / node_ptr, node_ptr[0] != 0, a node_ptr that
+ *   is not monotone, a filament of fewer than 2 nodes, rest_length <= 0, viscosity <= 0, poisson_ratio <= -1,
+ *   youngs_modulus < 0, a radius <= 0, anything not finite.
+ * set_state  [device arrays center [N][3], twist [N], edge_orientation [N][4]] copies them, computes every edge's
+ *   tangent and length from the centres (t = (x[e+1] - x[e]) /= l, :1053-1055) and zeroes velocity, twist_velocity,
+ *   force, twist_torque, curvature and binormal; old = new.  The initial triad of :1057-1068 is the caller's (the
+ *   reference builds it on the host as well).
+ * advance  the head of the time loop, :1999-2010, one kernel, per node in this order:
+ *     disable_twist (:1832-1838): twist = twist_velocity = 0;  monolayer (:1840-1862): center[0] = velocity[0] = 0
+ *     rotate_field_states (:1080-1083): the edge state's new and old copies change places (pointers)
+ *     update_generalized_position (:1779-1811): center = center + dt velocity, twist = twist + dt twist_velocity
+ *     zero_out_transient_node_fields (:1085-1093): velocity, force, twist_velocity, twist_torque = +0.0
+ * force  at the reference's `time` = timestep_index * timestep_size; two kernels, edge_pass then node_pass, which are
+ *   entry points of their own as well (the reference's compute_edge_information and its two node functions).
+ *   edge pass, compute_edge_information (:1223-1240), per edge e with t_old, q_old its old tangent and orientation:
+ *     d = x[e+1] - x[e], l = |d|, t = d /= l;  c = t_old x t, tt = dot(t_old, t)
+ *     b = (2 c) / (1 + tt): the binormal of ONE edge at two times, as the reference has it
+ *     r = [cos(twist[e] / 2), sin(twist[e] / 2) t_old];  p = [w, (0.5 c) / w], w = sqrt(0.5 (1 + tt))
+ *       (quat_from_parallel_transport, mundy_math/Quaternion.hpp:1489-1506)
+ *     q = (p r) q_old: the twist rotation is applied again every step and q is not renormalised, as in the reference
+ *   node pass, per element i (:1315-1316, :1411-1423; :1166-1167 for the wave), r = radius[i]:
+ *     g = conjugate(q[i-1]) q[i], kappa = 2 vec(g), curvature[i] = kappa
+ *     rest = rest_curvature[i], with wave != 0 its component 0 replaced by
+ *       wave_amplitude sin((wave_number arclength[i] + wave_frequency time) + phase[f])   (not written back)
+ *     dk = kappa - rest, I = 0.25 pi r r r r, G = 0.5 E / (1 + nu), il = 1 / l0
+ *     m = (-il E I dk0, -il E I dk1, -il 2 G I dk2);  m = q[i-1] * (g.w m + vec(g) x m)
+ *     with (t, b, l) of edge i:      fr = (1 / l) ((m x t + (0.5 dot(t, m)) (dot(t, b) t)) - b)    (:1426-1430; the
+ *       `- b` sits outside the 0.5 dot(t, m) factor in every one of these apps and is kept: DESIGN.md 5j)
+ *     with (t, b, l) of edge i - 1:  fl = (1 / l) (m x t + (0.5 dot(t, m)) (dot(t, b) t - b))      (:1431-1435)
+ *     node i + 1 receives +fr, node i -(fr + fl), node i - 1 +fl; twist_torque[i] += dot(t_i, m),
+ *     twist_torque[i-1] -= dot(t_{i-1}, m)   (:1437-1458)
+ *   per edge e (:1490-1504), r = radius[e+1]: k = E pi r r / l0, fs = (-k (l - l0)) t; node e + 1 receives +fs, node e -fs
+ *   Every node gathers its terms, no atomics, from external_force[i] (or +0.0 for NULL) in this order: element i - 1
+ *   (+fr), element i (-(fr + fl)), element i + 1 (+fl), edge i - 1 (+fs), edge i (-fs); the twist torque from +0.0:
+ *   element i, then element i + 1.  The result does not depend on how nodes map to workgroups.
+ *   external_force [device, N x 3, or NULL] is the seam for contact forces reduced to the nodes.
+ *   stats [device, 2 doubles]: the largest |l - l0| / l0 over the edges and the largest component of |kappa - rest| over
+ *   the elements (+0.0 without any), order independent: what a host chooses dt from.
+ * velocity  compute_generalized_velocity (:1772-1775): velocity = ((1 / (6 pi eta)) (1 / r)) force,
+ *   twist_velocity = ((1 / (8 pi eta)) ir ir ir) twist_torque, ir = 1 / r.
+ * get  device pointers to every field; those of the edge state change places at every advance, so ask again after it.
+ * force / edge_pass / node_pass / velocity / advance before set_state: MHIP_ERR_RUNTIME.  Not built: contacts between filament segments, the
+ * inertial variants (CollidingFrictionalSperm.cpp:1571-1675), clamp_edge1 (:1813-1830), several GPUs. */
+typedef struct mhip_filament_params {
+  double youngs_modulus, poisson_ratio, rest_length, viscosity;
+  double wave_amplitude, wave_number, wave_frequency; /* A, k = 2 pi / wavelength, omega = 2 pi / period (:1110-1111) */
+  int wave, disable_twist, monolayer;
+} mhip_filament_params;
+typedef struct mhip_filament_fields {
+  size_t num_nodes, num_filaments;
+  double *center, *twist, *velocity, *twist_velocity, *force, *twist_torque;
+  double *radius, *rest_curvature, *arclength, *curvature, *phase;
+  double *edge_tangent, *edge_orientation, *edge_length, *edge_binormal;
+  double *edge_tangent_old, *edge_orientation_old, *edge_length_old, *edge_binormal_old;
+} mhip_filament_fields;
+typedef struct mhip_filaments* mhip_filaments_t;
+int mhip_filaments_create(mhip_filaments_t* handle, size_t num_filaments, const int32_t* node_ptr /*[host] F + 1*/,
+                          const double* radius /*[host] N*/, const double* rest_curvature /*[host] N x 3*/,
+                          const double* arclength /*[host] N*/, const double* phase /*[host] F or NULL*/,
+                          const mhip_filament_params* params, mhip_stream_t stream);
+int mhip_filaments_set_state(mhip_filaments_t handle, const double* center, const double* twist,
+                             const double* edge_orientation);
+int mhip_filaments_advance(mhip_filaments_t handle, double dt);
+int mhip_filaments_force(mhip_filaments_t handle, double time, const double* external_force /*[device] N x 3 or NULL*/,
+                         double* stats /*[device] 2*/);
+int mhip_filaments_edge_pass(mhip_filaments_t handle);
+int mhip_filaments_node_pass(mhip_filaments_t handle, double time, const double* external_force, double* stats);
+int mhip_filaments_velocity(mhip_filaments_t handle);
+int mhip_filaments_get(mhip_filaments_t handle, mhip_filament_fields* fields /*[host]*/);
+int mhip_filaments_destroy(mhip_filaments_t handle);
+
 /* Mixed shapes (BASELINE configs[4]): kind[n] = 0 sphere, 1 spherocylinder, 2 ellipsoid; shape[n][3] = (r,-,-) /
  * (r,L,-) / (r1,r2,r3); quat is ignored for spheres.  compute_aabb dispatches on kind (compute_aabb.hpp:72-127) and
  * also returns the bounding radii (compute_bounding_radius.hpp:61-93).  contact_mixed bins the pairs by shape class and

@@ -13,6 +13,8 @@
 // grow-only device storage, with the rebuild rule of growing bodies (check_update_neighbor_list, :685-748).
 // All arrays stay on the device; the only host reads are the pair count and the solver's convergence polls (Hertz
 // mode: the largest overlap; growth mode: the birth count and the corner-test flag).
+// FilamentStepper is the elastic half of the sperm apps' step (CollidingOverdampedFrictionalSperm.cpp:1999-2027):
+//   advance -> edge pass + node pass (centerline-twist forces and twist torques at x(t + dt)) -> node drag
 #pragma once
 #include <chrono>
 #include <cmath>
@@ -44,6 +46,8 @@ struct StepStats {
   size_t num_born = 0;       // growth mode: bodies that divided this step (children are rows n_before + k)
   size_t num_sliding = 0;    // frictional Hertz mode: contacts whose tangential force was capped at mu |F_n|
   size_t num_carried = 0;    // frictional Hertz mode: history rows carried to a rebuilt list this step
+  double max_stretch = 0.0;              // FilamentStepper: the largest |l - l0| / l0 over the edges
+  double max_curvature_deviation = 0.0;  // FilamentStepper: the largest component of |kappa - kappa_rest|
 };
 
 /// grow-only storage that keeps its first `live` doubles: reallocates with headroom only when `need` does not fit
@@ -661,6 +665,64 @@ class DistributedSpherocylinderStepper {
   mhip_ghost_layout lay_{};  // of the last rebuild; its lists live in the communicator until the next plan
   mesh::GenNeighborLinks links_;
   std::unique_ptr<ContactOperator> op_;
+};
+
+/// Centerline-twist elastic filaments (mhip_filaments_*), stepped in the reference's order: the state lives in the
+/// library handle, fields() hands out its device pointers (those of the edge state change places at every step).
+class FilamentStepper {
+ public:
+  /// host arrays: node_ptr [F + 1]; center [N][3], twist [N], edge_orientation [N][4] (w, x, y, z; by left node: the
+  /// initial triad of :1057-1068 is the caller's), radius [N], rest_curvature [N][3], arclength [N]; phase [F] or empty
+  FilamentStepper(const std::vector<int32_t>& node_ptr, const std::vector<double>& center,
+                  const std::vector<double>& twist, const std::vector<double>& edge_orientation,
+                  const std::vector<double>& radius, const std::vector<double>& rest_curvature,
+                  const std::vector<double>& arclength, const std::vector<double>& phase,
+                  const mhip_filament_params& params)
+      : stats_(2) {
+    if (node_ptr.empty()) throw std::invalid_argument("FilamentStepper: node_ptr is empty");
+    const size_t f = node_ptr.size() - 1, n = static_cast<size_t>(node_ptr.back() < 0 ? 0 : node_ptr.back());
+    if (center.size() != 3 * n || twist.size() != n || edge_orientation.size() != 4 * n || radius.size() != n ||
+        rest_curvature.size() != 3 * n || arclength.size() != n || !(phase.empty() || phase.size() == f))
+      throw std::invalid_argument("FilamentStepper: array sizes do not match node_ptr");
+    check(mhip_filaments_create(&h_, f, node_ptr.data(), radius.data(), rest_curvature.data(), arclength.data(),
+                                phase.empty() ? nullptr : phase.data(), &params, nullptr));
+    try {
+      DeviceVector c(center), t(twist), q(edge_orientation);
+      check(mhip_filaments_set_state(h_, c.data(), t.data(), q.data()));
+      check(mhip_stream_synchronize(nullptr));  // the three uploads go out of scope here
+    } catch (...) {
+      mhip_filaments_destroy(h_);
+      throw;
+    }
+  }
+  FilamentStepper(const FilamentStepper&) = delete;
+  FilamentStepper& operator=(const FilamentStepper&) = delete;
+  ~FilamentStepper() { mhip_filaments_destroy(h_); }
+
+  /// advance -> forces at x(t + dt), time = step index * dt as the reference counts it (:1115) -> velocities;
+  /// external_force [device, N x 3, or null] is added first (contact forces reduced to the nodes)
+  StepStats step(double dt, const double* external_force = nullptr) {
+    check(mhip_filaments_advance(h_, dt));
+    check(mhip_filaments_force(h_, static_cast<double>(step_index_) * dt, external_force, stats_.data()));
+    check(mhip_filaments_velocity(h_));
+    ++step_index_;
+    const auto s = stats_.download();
+    StepStats st;
+    st.max_stretch = s[0];
+    st.max_curvature_deviation = s[1];
+    return st;
+  }
+  mhip_filament_fields fields() const {
+    mhip_filament_fields f{};
+    check(mhip_filaments_get(h_, &f));
+    return f;
+  }
+  size_t step_index() const { return step_index_; }
+
+ private:
+  mhip_filaments_t h_ = nullptr;
+  DeviceVector stats_;
+  size_t step_index_ = 0;
 };
 
 }  // namespace mech

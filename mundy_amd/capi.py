@@ -48,6 +48,21 @@ class Periphery(C.Structure):
                 ("k", C.c_double)]
 
 
+class FilamentParams(C.Structure):
+    _fields_ = [("youngs_modulus", C.c_double), ("poisson_ratio", C.c_double), ("rest_length", C.c_double),
+                ("viscosity", C.c_double), ("wave_amplitude", C.c_double), ("wave_number", C.c_double),
+                ("wave_frequency", C.c_double), ("wave", C.c_int), ("disable_twist", C.c_int), ("monolayer", C.c_int)]
+
+
+FILAMENT_FIELDS = ("center", "twist", "velocity", "twist_velocity", "force", "twist_torque", "radius", "rest_curvature",
+                   "arclength", "curvature", "phase", "edge_tangent", "edge_orientation", "edge_length", "edge_binormal",
+                   "edge_tangent_old", "edge_orientation_old", "edge_length_old", "edge_binormal_old")
+
+
+class FilamentFields(C.Structure):
+    _fields_ = [("num_nodes", C.c_size_t), ("num_filaments", C.c_size_t)] + [(f, C.c_void_p) for f in FILAMENT_FIELDS]
+
+
 class VelocityHalo(C.Structure):
     """mhip_velocity_halo: the per-iteration ghost-velocity exchange of one rank (host lists + one device index list)"""
     _fields_ = [("velocity", C.c_void_p), ("num_send_peers", C.c_int), ("send_peer", C.POINTER(C.c_int)),
@@ -137,6 +152,15 @@ SIGNATURES = {
     "mhip_active_springs_set_state": [_vp, _vp, _vp, _vp, _vp, _vp],
     "mhip_active_springs_renumber": [_vp, _vp, _vp],
     "mhip_active_springs_destroy": [_vp],
+    "mhip_filaments_create": [C.POINTER(_vp), _sz, _vp, _vp, _vp, _vp, _vp, C.POINTER(FilamentParams), _vp],
+    "mhip_filaments_set_state": [_vp, _vp, _vp, _vp],
+    "mhip_filaments_advance": [_vp, _d],
+    "mhip_filaments_force": [_vp, _d, _vp, _vp],
+    "mhip_filaments_edge_pass": [_vp],
+    "mhip_filaments_node_pass": [_vp, _d, _vp, _vp],
+    "mhip_filaments_velocity": [_vp],
+    "mhip_filaments_get": [_vp, C.POINTER(FilamentFields)],
+    "mhip_filaments_destroy": [_vp],
     "mhip_philox4x32_10": [_sz, _vp, _vp, C.c_uint32, _vp, _vp],
     "mhip_brownian_velocity": [_sz, _vp, _vp, _d, _d, _vp, _vp, _vp],
     "mhip_drag_velocity": [_sz, _vp, _vp, _vp, _vp],

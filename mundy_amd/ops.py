@@ -1492,3 +1492,134 @@ class ActiveSprings(_Handle):
             raise ValueError("new_of_old must have shape [%d], got %s" % (self.n, tuple(new_of_old.shape)))
         capi.check(capi.load().mhip_active_springs_renumber(self._h, _ptr(new_of_old, torch.int32, name="new_of_old"),
                                                             _stream()))
+
+
+# ---- centerline-twist elastic filaments (mhip_filaments_*) ------------------------------------------------------------
+def check_filaments(node_ptr, radius, rest_curvature, arclength, phase, youngs_modulus, poisson_ratio, rest_length,
+                    viscosity, wave):
+    """host-side validation of a filament set (no library call) -> (node_ptr int32 [F + 1], radius [N],
+    rest_curvature [N, 3], arclength [N], phase [F] / None, capi.FilamentParams without the two constraint flags)"""
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)  # noqa: E731
+    ptr = host(node_ptr)
+    if ptr.ndim != 1 or ptr.size < 1 or ptr.dtype.kind not in "iu":
+        raise ValueError("node_ptr must be integers of shape [F + 1], got %s %s" % (ptr.dtype, ptr.shape))
+    if int(ptr[0]) != 0:
+        raise ValueError("node_ptr[0] must be 0, got %d" % int(ptr[0]))
+    count = np.diff(ptr.astype(np.int64))
+    if (count < 0).any():
+        raise ValueError("node_ptr is not monotone at filament %d" % int(np.argmax(count < 0)))
+    if (count < 2).any():
+        f = int(np.argmax(count < 2))
+        raise ValueError("filament %d has %d node(s): a filament has at least 2" % (f, int(count[f])))
+    n, F = int(ptr[-1]), ptr.size - 1
+    if n >= 2 ** 31:
+        raise ValueError("too many nodes for 32-bit indices")
+    r = np.ascontiguousarray(host(radius), dtype=np.float64)
+    kr = np.ascontiguousarray(host(rest_curvature), dtype=np.float64)
+    s = np.ascontiguousarray(host(arclength), dtype=np.float64)
+    if r.shape != (n,) or kr.shape != (n, 3) or s.shape != (n,):
+        raise ValueError("radius / rest_curvature / arclength must have the shapes [%d], [%d, 3], [%d], got %s, %s, %s"
+                         % (n, n, n, r.shape, kr.shape, s.shape))
+    if not (np.isfinite(r) & (r > 0.0)).all():
+        raise ValueError("node %d: radius must be finite and > 0" % int(np.argmin(np.isfinite(r) & (r > 0.0))))
+    if not (np.isfinite(kr).all() and np.isfinite(s).all()):
+        raise ValueError("rest_curvature / arclength must be finite")
+    ph = None
+    if phase is not None:
+        ph = np.ascontiguousarray(host(phase), dtype=np.float64)
+        if ph.shape != (F,) or not np.isfinite(ph).all():
+            raise ValueError("phase must be finite and of shape [%d], got %s" % (F, ph.shape))
+    E, nu, l0, eta = float(youngs_modulus), float(poisson_ratio), float(rest_length), float(viscosity)
+    if not (E >= 0.0 and math.isfinite(E)):
+        raise ValueError("youngs_modulus must be finite and >= 0, got %r" % E)
+    if not (nu > -1.0 and math.isfinite(nu)):
+        raise ValueError("poisson_ratio must be finite and > -1, got %r" % nu)
+    if not (l0 > 0.0 and math.isfinite(l0)):
+        raise ValueError("rest_length must be finite and > 0, got %r" % l0)
+    if not (eta > 0.0 and math.isfinite(eta)):
+        raise ValueError("viscosity must be finite and > 0, got %r" % eta)
+    A = k = w = 0.0
+    if wave is not None:
+        check_dict_spec(wave, "wave", ("amplitude", "wave_number", "frequency"))
+        A, k, w = float(wave["amplitude"]), float(wave["wave_number"]), float(wave["frequency"])
+        if not (math.isfinite(A) and math.isfinite(k) and math.isfinite(w)):
+            raise ValueError("wave: amplitude, wave_number and frequency must be finite")
+    prm = capi.FilamentParams(E, nu, l0, eta, A, k, w, 1 if wave is not None else 0, 0, 0)
+    return np.ascontiguousarray(ptr, dtype=np.int32), r, kr, s, ph, prm
+
+
+class Filaments(_Handle):
+    """F centerline-twist filaments over N nodes (mhip_filaments_*): the state lives in the handle.  wave: None, or
+    dict(amplitude, wave_number, frequency) of the travelling rest-curvature wave (phase [F] keys it per filament).
+    set_state -> [advance -> force -> velocity] per step; field(name) copies a field of capi.FILAMENT_FIELDS out."""
+    _destroy = "mhip_filaments_destroy"
+    _WIDTH = {"center": 3, "velocity": 3, "force": 3, "rest_curvature": 3, "curvature": 3, "edge_tangent": 3,
+              "edge_binormal": 3, "edge_tangent_old": 3, "edge_binormal_old": 3, "edge_orientation": 4,
+              "edge_orientation_old": 4}
+
+    def __init__(self, node_ptr, radius, rest_curvature, arclength, phase=None, *, youngs_modulus, poisson_ratio,
+                 rest_length, viscosity, wave=None, disable_twist=False, monolayer=False):
+        ptr, r, kr, s, ph, prm = check_filaments(node_ptr, radius, rest_curvature, arclength, phase, youngs_modulus,
+                                                 poisson_ratio, rest_length, viscosity, wave)
+        prm.disable_twist, prm.monolayer = int(bool(disable_twist)), int(bool(monolayer))
+        self.node_ptr, self.params = ptr, prm
+        self.n, self.num_filaments = int(ptr[-1]), ptr.size - 1
+        h = C.c_void_p()
+        cp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        capi.check(capi.load().mhip_filaments_create(C.byref(h), self.num_filaments, cp(ptr), cp(r), cp(kr), cp(s), cp(ph),
+                                                     C.byref(prm), _stream()))
+        self._h = h
+
+    def set_state(self, center, twist, edge_orientation):
+        """device tensors center [N, 3], twist [N], edge_orientation [N, 4] (w, x, y, z; indexed by the left node)"""
+        n = self.n
+        for name, t, shape in (("center", center, (n, 3)), ("twist", twist, (n,)),
+                               ("edge_orientation", edge_orientation, (n, 4))):
+            if tuple(t.shape) != shape:
+                raise ValueError("%s must have shape %s, got %s" % (name, list(shape), tuple(t.shape)))
+        capi.check(capi.load().mhip_filaments_set_state(self._h, _ptr(center, name="center"), _ptr(twist, name="twist"),
+                                                        _ptr(edge_orientation, name="edge_orientation")))
+
+    def advance(self, dt):
+        capi.check(capi.load().mhip_filaments_advance(self._h, float(dt)))
+
+    def force(self, time, external_force=None, stats=None):
+        """edge pass + node pass at `time`; -> stats float64 [2] = (largest |l - l0| / l0, largest |kappa - rest|
+        component), left on the device"""
+        if external_force is not None and tuple(external_force.shape) != (self.n, 3):
+            raise ValueError("external_force must have shape [%d, 3], got %s" % (self.n, tuple(external_force.shape)))
+        if stats is None:
+            stats = torch.empty(2, dtype=torch.float64, device="cuda")
+        capi.check(capi.load().mhip_filaments_force(self._h, float(time),
+                                                    _ptr(external_force, allow_none=True, name="external_force"),
+                                                    _ptr(stats, name="stats")))
+        return stats
+
+    def edge_pass(self):
+        """the first half of force(): every edge's tangent, length, binormal and orientation"""
+        capi.check(capi.load().mhip_filaments_edge_pass(self._h))
+
+    def node_pass(self, time, external_force=None, stats=None):
+        """the second half of force(): curvature, forces and twist torques from the edge state as it stands"""
+        if stats is None:
+            stats = torch.empty(2, dtype=torch.float64, device="cuda")
+        capi.check(capi.load().mhip_filaments_node_pass(self._h, float(time),
+                                                        _ptr(external_force, allow_none=True, name="external_force"),
+                                                        _ptr(stats, name="stats")))
+        return stats
+
+    def velocity(self):
+        capi.check(capi.load().mhip_filaments_velocity(self._h))
+
+    def field(self, name):
+        """a copy of one field (capi.FILAMENT_FIELDS) as a device tensor"""
+        if name not in capi.FILAMENT_FIELDS:
+            raise ValueError("unknown filament field %r" % (name,))
+        fields = capi.FilamentFields()
+        capi.check(capi.load().mhip_filaments_get(self._h, C.byref(fields)))
+        rows = self.num_filaments if name == "phase" else self.n
+        w = self._WIDTH.get(name, 1)
+        out = torch.empty((rows, w) if w > 1 else (rows,), dtype=torch.float64, device="cuda")
+        if rows:
+            capi.check(capi.load().mhip_deep_copy(rows * w, _ptr(out), C.c_void_p(getattr(fields, name)), _stream()))
+        return out

@@ -48,6 +48,13 @@ CollidingOverdampedFrictionalSperm.cpp:1553-1731):
         -> frictional force per linker from the previous step's body velocities (a vector per contact)
         -> operator build / refresh -> body_sweep_vector -> U = M D F (+ U_ext = M F_ext) -> Euler update
 
+FilamentStepper is the other half of that app's step, the centerline-twist rod forces that make chained nodes a filament
+(CollidingOverdampedFrictionalSperm.cpp:1999-2027):
+
+    advance (disable_twist, monolayer, old <-> new edge state, x += dt v, transient fields zeroed)
+        -> edge pass + node pass: elastic forces and twist torques at x(t + dt) (+ external_force)
+        -> node drag: the velocities the next advance uses
+
 Everything is device resident; host logic here only sequences library calls.
 """
 import math
@@ -114,6 +121,8 @@ class StepStats:
     max_periphery_overlap: float = 0.0   # ... the deepest of them (ellipsoid_fast: the largest level-set value)
     active_springs: int = 0              # active_forces=: springs in the active state at this step's force evaluation
     active_switches: tuple = (0, 0)      # ... springs that switched (on, off) this step
+    max_stretch: float = 0.0               # FilamentStepper: the largest |l - l0| / l0 over the edges at the force evaluation
+    max_curvature_deviation: float = 0.0   # ... the largest component of |kappa - kappa_rest| over the elements
 
 
 class ContactStepper:
@@ -1060,4 +1069,47 @@ class ContactStepper:
             torch.cuda.synchronize()
             for (_, a), (name, b) in zip(ev[:-1], ev[1:]):
                 st.timings_ms[name] = a.elapsed_time(b)
+        return st
+
+
+class FilamentStepper:
+    """Centerline-twist elastic filaments (ops.Filaments) stepped as the reference's sperm apps step them
+    (CollidingOverdampedFrictionalSperm.cpp:1999-2027).  node_ptr [F + 1], center [N, 3], radius [N], edge_orientation
+    [N, 4] (w, x, y, z; by left node: synth.filaments builds the reference's initial triad), arclength [N]; twist and
+    rest_curvature default to 0; wave = dict(amplitude, wave_number, frequency) with phase [F].  Host arrays or tensors.
+    Contacts between filament segments are not part of it: external_force is where their node forces enter."""
+
+    def __init__(self, node_ptr, center, radius, edge_orientation, arclength, *, twist=None, rest_curvature=None,
+                 phase=None, youngs_modulus, poisson_ratio=0.3, rest_length, viscosity, wave=None, disable_twist=False,
+                 monolayer=False):
+        n = int(np.asarray(node_ptr.cpu() if isinstance(node_ptr, torch.Tensor) else node_ptr)[-1])
+        if rest_curvature is None:
+            rest_curvature = np.zeros((n, 3))
+        self.filaments = ops.Filaments(node_ptr, radius, rest_curvature, arclength, phase, youngs_modulus=youngs_modulus,
+                                       poisson_ratio=poisson_ratio, rest_length=rest_length, viscosity=viscosity,
+                                       wave=wave, disable_twist=disable_twist, monolayer=monolayer)
+        dev = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(  # noqa: E731
+            a, dtype=np.float64))).to(device="cuda", dtype=torch.float64).contiguous()
+        self.n = n
+        self.filaments.set_state(dev(center), dev(np.zeros(n) if twist is None else twist), dev(edge_orientation))
+        self.step_index = 0
+        self._stats = torch.zeros(2, dtype=torch.float64, device="cuda")
+
+    def close(self):
+        self.filaments.close()
+
+    def field(self, name):
+        return self.filaments.field(name)
+
+    def step(self, dt, external_force=None, read_stats=True):
+        """advance -> forces at x(t + dt), time = step_index * dt as the reference counts it -> velocities.
+        read_stats=False skips the one host read of the step (the statistics then stay at their defaults)."""
+        f = self.filaments
+        f.advance(dt)
+        f.force(self.step_index * float(dt), external_force, self._stats)
+        f.velocity()
+        self.step_index += 1
+        st = StepStats(num_bodies=self.n)
+        if read_stats:
+            st.max_stretch, st.max_curvature_deviation = self._stats.tolist()
         return st

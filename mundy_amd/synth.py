@@ -154,3 +154,50 @@ def chains(num_chains, beads_per_chain, r0=1.0, radius=0.5, seed=1234, cell=None
     return dict(center=center, radius=np.full(M * B, float(radius)), pairs=pairs,
                 chain=np.repeat(np.arange(M, dtype=np.int32), B), k=3.0, kt=0.1, viscosity=1.0, dt=1e-3, skin=1.0,
                 r0=float(r0))
+
+
+def triad_quaternion(d1, d2, d3):
+    """rotation_matrix_to_quaternion (mundy_math/Quaternion.hpp:1410-1427) of the matrix with the columns d1, d2, d3
+    [m, 3] each -> (w, x, y, z) [m, 4]"""
+    D00, D11, D22 = d1[:, 0], d2[:, 1], d3[:, 2]
+    half = lambda v: np.sqrt(np.maximum(0.0, v)) / 2.0  # noqa: E731
+    w = half(1.0 + D00 + D11 + D22)
+    x = np.copysign(half(1.0 + D00 - D11 - D22), d2[:, 2] - d3[:, 1])   # D21 - D12
+    y = np.copysign(half(1.0 - D00 + D11 - D22), d3[:, 0] - d1[:, 2])   # D02 - D20
+    z = np.copysign(half(1.0 - D00 - D11 + D22), d1[:, 1] - d2[:, 0])   # D10 - D01
+    return np.stack([w, x, y, z], axis=1)
+
+
+def filaments(num_filaments, nodes, radius=0.5, segment_length=1.0, rest_curvature=(0.0, 0.0, 0.0), seed=None):
+    """Straight filaments laid out as the sperm apps' declare_and_initialize_sperm does
+    (CollidingOverdampedFrictionalSperm.cpp:688-1072): filament j in the plane x = 0 at y = 2 j (2 radius), along +z from
+    z = 0, the even-numbered ones flipped (from z = segment_length (nodes - 1) along -z); node i at tail + axis i
+    segment_length with arclength i segment_length; every edge's orientation from the triad d1 = (+-1, 0, 0) (-1 for a
+    flipped filament), d3 = the tangent, d2 = d3 x d1 / |d3 x d1| (:1057-1068).  seed: the phase of filament j is
+    2 pi uniform01(seed, j, 0) (the reference draws 2 pi rng.rand() from OpenRAND); None = no phases.
+    Returns dict(node_ptr int32 [F + 1], center [N, 3], twist [N], radius [N], rest_curvature [N, 3], arclength [N],
+    edge_orientation [N, 4] (w, x, y, z; the slot of a filament's last node holds the identity), phase [F] or None)."""
+    F, B = int(num_filaments), int(nodes)
+    if B < 2:
+        raise ValueError("a filament has at least 2 nodes, got %d" % B)
+    j = np.arange(F, dtype=np.float64)
+    flip = (np.arange(F) % 2 == 0)
+    i = np.arange(B, dtype=np.float64)
+    tail = np.stack([np.zeros(F), 2.0 * j * (2.0 * radius), np.where(flip, segment_length * (B - 1), 0.0)], axis=1)
+    axis = np.stack([np.zeros(F), np.zeros(F), np.where(flip, -1.0, 1.0)], axis=1)
+    center = tail[:, None, :] + axis[:, None, :] * i[None, :, None] * segment_length
+    d = center[:, 1:] - center[:, :-1]
+    t = d / np.sqrt(d[..., 0] * d[..., 0] + (d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]))[..., None]
+    d1 = np.broadcast_to(np.stack([np.where(flip, -1.0, 1.0), np.zeros(F), np.zeros(F)], axis=1)[:, None, :], t.shape)
+    d2 = np.cross(t, d1)
+    d2 = d2 / np.sqrt(d2[..., 0] * d2[..., 0] + (d2[..., 1] * d2[..., 1] + d2[..., 2] * d2[..., 2]))[..., None]
+    quat = np.zeros((F, B, 4))
+    quat[..., 0] = 1.0
+    quat[:, :-1] = triad_quaternion(d1.reshape(-1, 3), d2.reshape(-1, 3), t.reshape(-1, 3)).reshape(F, B - 1, 4)
+    N = F * B
+    phase = None if seed is None else 2.0 * np.pi * uniform01(seed, np.arange(F), 0)
+    return dict(node_ptr=(np.arange(F + 1) * B).astype(np.int32), center=np.ascontiguousarray(center.reshape(N, 3)),
+                twist=np.zeros(N), radius=np.full(N, float(radius)),
+                rest_curvature=np.ascontiguousarray(np.broadcast_to(np.asarray(rest_curvature, dtype=np.float64), (N, 3))),
+                arclength=np.tile(i * segment_length, F), edge_orientation=np.ascontiguousarray(quat.reshape(N, 4)),
+                phase=phase)
