@@ -467,7 +467,11 @@ struct OpView {
   // rounded once: the iterates do not notice.  null = no snapshot yet (the first iterations walk the masks).
   const int32_t* aptr;                  // [N + 1] body -> its compact range
   const int32_t* aent;                  // entries (c << 1 | side), snapshot order
-  const double* arec;                   // their records, same layout as `half`
+  // their records, the words of `half` as PLANES of 16 bytes per entry, arec_stride entries apart: (n.x, n.y) |
+  // (n.z, coef) (spheres: (n.z, 0); vector arms: (n.z, r.x)) | vector arms: (r.y, r.z) -- a wave's record load covers
+  // 1 KB contiguous instead of 16 bytes out of every 32 (48) of a 2 KB (3 KB) stretch
+  const double* arec;
+  size_t arec_stride;
   const unsigned long long* snap_mask;  // [N] the masks the snapshot was taken from
   // Tiered solves (see "Cold tier" below): the body rows ping-pong between vel (even parity) and vel_alt like the
   // iterate does, so that the rows of the last TWO iterates exist when the solve ends; drift [N] accumulates, per body,
@@ -683,14 +687,22 @@ __global__ void __launch_bounds__(kBlock, MHIP_KBODY_WAVES)
   // ent / rec: the arrays kk indexes (the full lists, or the compact active lists).  EAGER: the records are fetched
   // together with the entries instead of after the iterate is known -- one dependent level less; used where nearly
   // every entry walked carries an impulse (flagged entries), not where two thirds do not (unmasked walks).
+  // planes: distance of the record planes of the compact lists (OpView::arec), 0 = the records of the full lists.
+  // (The compact lists reach this lambda only in a build with -DMHIP_KBODY_FLAT=0: with the flat stream compiled in,
+  // FLATP = 0 is launched only while there is no snapshot.  That build is an A/B option and no test makes it.)
   auto process = [&](const int32_t* __restrict__ ent, const double* __restrict__ rec, const int32_t* kk,
-                     const bool eager) {
+                     const bool eager, const size_t planes = 0) {
     int32_t e[U];
     double lam[U], xo[U];
     double2 h0[U], h1[U], h2[U];
     auto fetch = [&](int u) {
       const size_t k = static_cast<size_t>(kk[u]);
-      if (KIN == KIN_TRANS) {
+      if (planes != 0) {
+        const double2* H2 = reinterpret_cast<const double2*>(rec) + k;
+        h0[u] = H2[0];
+        h1[u] = H2[planes];
+        if (KIN == KIN_RIGID) h2[u] = H2[2 * planes];
+      } else if (KIN == KIN_TRANS) {
         const double* H = rec + k * HW;
         h0[u] = make_double2(H[0], H[1]);
         h1[u] = make_double2(H[2], 0.0);
@@ -778,16 +790,10 @@ __global__ void __launch_bounds__(kBlock, MHIP_KBODY_WAVES)
             const int32_t k0 = base + p * kBlock + static_cast<int32_t>(threadIdx.x);
             const size_t k = static_cast<size_t>(live[p] ? k0 : E1 - 1);
             r2[p] = make_double2(0.0, 0.0);
-            if (KIN == KIN_TRANS) {
-              const double* H = op.arec + k * HW;
-              r0[p] = make_double2(ld_s<NTS>(H), ld_s<NTS>(H + 1));
-              r1[p] = make_double2(ld_s<NTS>(H + 2), 0.0);
-            } else {
-              const double2* H2 = reinterpret_cast<const double2*>(op.arec + k * HW);
-              r0[p] = ld_s<NTS>(H2);
-              r1[p] = ld_s<NTS>(H2 + 1);
-              if (KIN == KIN_RIGID) r2[p] = ld_s<NTS>(H2 + 2);
-            }
+            const double2* H2 = reinterpret_cast<const double2*>(op.arec) + k;  // (planes: 1 KB contiguous per wave)
+            r0[p] = ld_s<NTS>(H2);
+            r1[p] = ld_s<NTS>(H2 + op.arec_stride);
+            if (KIN == KIN_RIGID) r2[p] = ld_s<NTS>(H2 + 2 * op.arec_stride);
           }
 #pragma unroll
           for (int p = 0; p < FLATP; ++p)
@@ -870,7 +876,7 @@ __global__ void __launch_bounds__(kBlock, MHIP_KBODY_WAVES)
           int32_t kc[U];
 #pragma unroll
           for (int u = 0; u < U; ++u) kc[u] = (k0 + u * G < ae) ? k0 + u * G : -1;
-          process(op.aent, op.arec, kc, true);
+          process(op.aent, op.arec, kc, true, op.arec_stride);
         }
       }
     }
@@ -1843,18 +1849,19 @@ __global__ void __launch_bounds__(kBlock)
     cnt[t] = __popcll(m);
   }
 }
-// The flagged entries and their records (HW doubles each), body by body in slot order, with the OUTPUT slots dealt to
-// the lanes (one lane per body walked its flagged entries one after the
-// other, 8 bytes at a time: 1.4 TB/s): a workgroup takes 256 bodies, keeps their masks, list starts and output offsets
-// in LDS, and every lane then fills output slots o, o + 256, ... of the tile -- it finds the body by bisection of the
-// offsets and the entry as the (o - offset)-th set bit of its mask.  Stores are contiguous, loads come from the tile's
-// own stretch of the incidence lists.  Same arrays, same order.
+// The flagged entries and their records, body by body in slot order: the entries as they are, the records' HW doubles
+// as planes of 16 bytes per entry, `stride` entries apart (see OpView::arec).  The OUTPUT slots are dealt to the lanes
+// (one lane per body walking its flagged entries one after the other, 8 bytes at a time, ran at 1.4 TB/s): a workgroup
+// takes 256 bodies, keeps their masks, list starts and output offsets in LDS, and every lane then fills output slots
+// o, o + 256, ... of the tile -- it finds the body by bisection of the offsets and the entry as the (o - offset)-th set
+// bit of its mask.  Stores are contiguous within every plane, loads come from the tile's own stretch of the incidence
+// lists.
 template <int HW>
 __global__ void __launch_bounds__(kBlock)
     k_active_fill_flat(size_t first, size_t count, const int32_t* __restrict__ inc_ptr, const int32_t* __restrict__ inc,
                        const double* __restrict__ half, const unsigned long long* __restrict__ body_mask,
                        const int32_t* __restrict__ aptr_local, int32_t* __restrict__ aptr, int32_t* __restrict__ aent,
-                       double* __restrict__ arec, unsigned long long* __restrict__ snap_mask) {
+                       double* __restrict__ arec, size_t stride, unsigned long long* __restrict__ snap_mask) {
   __shared__ unsigned long long tmask[kBlock];
   __shared__ int32_t tbeg[kBlock];
   __shared__ int32_t tptr[kBlock + 1];
@@ -1888,14 +1895,15 @@ __global__ void __launch_bounds__(kBlock)
     for (int r = o - tptr[lo]; r > 0; --r) m &= m - 1ull;
     const size_t k = static_cast<size_t>(tbeg[lo] + (__ffsll(static_cast<long long>(m)) - 1));
     aent[o] = inc[k];
+    double2* dst = reinterpret_cast<double2*>(arec) + o;
     if (HW % 2 == 0) {
       const double2* src = reinterpret_cast<const double2*>(half + k * HW);
-      double2* dst = reinterpret_cast<double2*>(arec + static_cast<size_t>(o) * HW);
 #pragma unroll
-      for (int w = 0; w < HW / 2; ++w) dst[w] = src[w];
-    } else {
-#pragma unroll
-      for (int w = 0; w < HW; ++w) arec[static_cast<size_t>(o) * HW + w] = half[k * HW + w];
+      for (int w = 0; w < HW / 2; ++w) dst[w * stride] = src[w];
+    } else {  // spheres: (n.x, n.y) | (n.z, 0)
+      const double* src = half + k * HW;
+      dst[0] = make_double2(src[0], src[1]);
+      dst[stride] = make_double2(src[2], 0.0);
     }
   }
 }
@@ -2564,7 +2572,8 @@ int op_snapshot_active(mhip_contact_op* op, hipStream_t s) {
   if (int e = op->aptr.reserve((N + 2) * sizeof(int32_t))) return e;
   if (int e = op->acnt.reserve((N + 2) * sizeof(int32_t))) return e;
   if (int e = op->aent.reserve((2 * C + 2) * sizeof(int32_t))) return e;
-  if (int e = op->arec.reserve((2 * C + 2) * hw * sizeof(double))) return e;
+  const size_t stride = 2 * C + 2;  // entries between two planes of the records
+  if (int e = op->arec.reserve(stride * ((hw + 1) / 2) * sizeof(double2))) return e;
   if (int e = op->snap_mask.reserve((N + 2) * sizeof(unsigned long long))) return e;
   int32_t* local = op->cursor.as<int32_t>();  // free since the incidence build
   k_active_count<<<grid_for(cnt), kBlock, 0, s>>>(v.body_first, cnt, v.inc_ptr, v.body_mask, op->acnt.as<int32_t>());
@@ -2573,7 +2582,7 @@ int op_snapshot_active(mhip_contact_op* op, hipStream_t s) {
   pick<6, 4, 3>(hw, [&](auto h) {
     k_active_fill_flat<decltype(h)::value><<<grid_exact(cnt), kBlock, 0, s>>>(
         v.body_first, cnt, v.inc_ptr, v.inc, v.half, v.body_mask, local, op->aptr.as<int32_t>(), op->aent.as<int32_t>(),
-        op->arec.as<double>(), op->snap_mask.as<unsigned long long>());
+        op->arec.as<double>(), stride, op->snap_mask.as<unsigned long long>());
   });
   MHIP_LAUNCH_CHECK();
   // the length of the compact lists travels to the host with the next poll (it picks the flat sweep's chunk; see
@@ -2584,6 +2593,7 @@ int op_snapshot_active(mhip_contact_op* op, hipStream_t s) {
   v.aptr = op->aptr.as<int32_t>();
   v.aent = op->aent.as<int32_t>();
   v.arec = op->arec.as<double>();
+  v.arec_stride = stride;
   v.snap_mask = op->snap_mask.as<unsigned long long>();
   return MHIP_SUCCESS;
 }
@@ -3522,7 +3532,7 @@ static int create_contact_op(mhip_contact_op_t* handle, int kin, size_t num_cons
   op->view = OpView{C, N, p2, normal, ra, rb, mob_trans, mob_rot, op->inc_ptr.as<int32_t>(), op->inc.as<int32_t>(),
                     op->half.as<double>(), op->vel.as<double>(), dt, 0, N, nullptr, arc_s, arc_t,
                     op->axis.as<double>(), op->omega.as<double>(), 0, 0, C, 0, 0, nullptr, nullptr,
-                    nullptr, nullptr, nullptr, nullptr};
+                    nullptr, nullptr, nullptr, 0, nullptr};
   if (N > 0 && C > 0 && !pos_built) {
     k_pos_build<<<grid_for(N), kBlock, 0, s>>>(N, op->inc_ptr.as<int32_t>(), op->inc.as<int32_t>(),
                                               op->pos.as<unsigned char>());
