@@ -472,7 +472,8 @@ int mhip_active_springs_destroy(mhip_active_springs_t handle);
  * velocity  compute_generalized_velocity (:1772-1775): velocity = ((1 / (6 pi eta)) (1 / r)) force,
  *   twist_velocity = ((1 / (8 pi eta)) ir ir ir) twist_torque, ir = 1 / r.
  * get  device pointers to every field; those of the edge state change places at every advance, so ask again after it.
- * force / edge_pass / node_pass / velocity / advance before set_state: MHIP_ERR_RUNTIME.  Not built: contacts between filament segments, the
+ * force / edge_pass / node_pass / velocity / advance before set_state: MHIP_ERR_RUNTIME.  Contacts between filament segments:
+ * mhip_filament_contacts_* below, whose node forces enter through external_force.  Not built: the
  * inertial variants (CollidingFrictionalSperm.cpp:1571-1675), clamp_edge1 (:1813-1830), several GPUs. */
 typedef struct mhip_filament_params {
   double youngs_modulus, poisson_ratio, rest_length, viscosity;
@@ -501,6 +502,86 @@ int mhip_filaments_node_pass(mhip_filaments_t handle, double time, const double*
 int mhip_filaments_velocity(mhip_filaments_t handle);
 int mhip_filaments_get(mhip_filaments_t handle, mhip_filament_fields* fields /*[host]*/);
 int mhip_filaments_destroy(mhip_filaments_t handle);
+
+/* Frictional Hertzian contacts between the segments of the filaments above: the contact half of the sperm apps' force
+ * stage (compute_hertzian_contact_force_and_torque, CollidingOverdampedFrictionalSperm.cpp:1553-1731, run at :2013-2021
+ * after the nodes have moved and before the centerline-twist forces).  DESIGN.md 5k.  FHC = .../evaluate_linker_potentials/
+ * kernels/SpherocylinderSegmentSpherocylinderSegmentFrictionalHertzianContact.cpp, RED = .../linker_potential_force_reduction/
+ * kernels/SpherocylinderSegment.cpp.  Segment i joins the nodes i and i + 1 and is indexed by its left node: every segment
+ * array has N rows, the row of a filament's last node is the degenerate record (x_i, x_i, r_i, 0) with a finite box, kept out
+ * of the search by its source / target sets.  Arithmetic as for the filaments (right-fold dot and norm).
+ *
+ * create  filaments: the handle whose nodes collide; it must outlive this one, and every call of this handle runs on
+ *   `stream`, which must be the filaments' stream.  node_ptr [host, F + 1]: the filaments' own node_ptr once more (their
+ *   handle does not give it back).  segment_radius [host, N] or NULL = the left node's radius.  Builds the source / target
+ *   mask and the exclusion lists on the host (segments at most bonded_exclusion apart along one filament never pair:
+ *   DestroyBoundNeighbors.cpp:150-170 with the reference's value 1), owns a mhip_broadphase_t, synchronises `stream`.
+ *   The reference hard-codes E = 5e5, nu = 0.3, mu = 0.5, density 1, no damping and a history step of 1e-5 whatever dt is
+ *   (FHC :406-417); here they are parameters, history_dt < 0 = the dt of the force call.  params->monolayer must be the
+ *   filaments' flag.  Refused with MHIP_ERR_INVALID_ARGUMENT before any HIP call: a null handle / filaments / params /
+ *   node_ptr, a node_ptr that is not the filaments', mu, a damping, density or skin < 0, youngs_modulus <= 0,
+ *   poisson_ratio outside (0, 1), bonded_exclusion < 1, a radius <= 0, anything not finite.
+ * save_velocity  velocity_prev [N][3] = the filaments' velocity, with monolayer its component 0 = +0.0: the StateN
+ *   velocities the force reads (FHC :388; apply_monolayer runs before rotate_field_states, :1999-2003).  To be called
+ *   before mhip_filaments_advance, which zeroes the field.
+ * update  the segment view: seg [N][8] = (x_i, x_{i+1}, r_i, 0) and the buffered boxes aabb [N][6] = (min - r - skin,
+ *   max + r + skin) (.../compute_aabb/kernels/SpherocylinderSegment.cpp:156-161).  On the first call, or when a box corner
+ *   has moved since the last build by d with |d|^2 >= skin^2 / 4 (:1565-1607; mhip_aabb_moved against the snapshot of the
+ *   last build, threshold 0.5 skin), the list is rebuilt (:1612-1717): MHIP_SEARCH_AABB on these boxes, buffer 0,
+ *   symmetric = 0, the exclusions above; tang_disp is carried (mhip_contact_history_carry), the segment -> linker
+ *   incidence is built, sep / force / share become +0.0.  *rebuilt [host] tells.  Synchronises.
+ * force  per linker (i, j), one kernel: the centreline closest points cp_i, cp_j and their distance
+ *   (distance_sq_between_line_segments, ...SpherocylinderSegmentSpherocylinderSegmentLinker.cpp:204-237), sep = distance -
+ *   (r_i + r_j), n = (cp_j - cp_i) (1 / distance).  sep > 0: tang_disp, force and share rows are +0.0 (written only where
+ *   they are not +0.0 already).  Otherwise, for each side with end nodes 0, 1 (FHC :357-380):
+ *     rv = v1 - v0, lc = cp - x0, L = |x1 - x0|, iL = 1 / L, t = (x1 - x0) iL, v from velocity_prev
+ *     v_cp = (v0 + (dot(lc, rv) t) iL) + (dot(lc, t) (rv - dot(t, rv) t)) iL
+ *   rel = v_cp,j - v_cp,i and the law of mhip_hertz_friction_force (one device function) give tang_disp[c] and force[c],
+ *   the force F on segment i.  share[c][side] (RED :206-212), with Fs = +F for side 0 (segment i) and -F for side 1:
+ *     share = (dot(lc, t) (Fs + dot(t, Fs) t)) iL - (dot(t, Fs) lc) iL      (the `+` is the reference's and is kept)
+ *   Reduction to the nodes (RED :213-221), a gather without atomics: for segment e, a0[e] = +0.0 + sum of (Fs - share) and
+ *   a1[e] = +0.0 + sum of share over its linkers in ascending list order; node_force[i] = ((external_force[i] or +0.0) +
+ *   a0[i]) + a1[i - 1], a term whose segment does not exist left out.  The twist torque of a contact is ignored, as in the
+ *   reference (RED :199).  stats [device, 16 bytes] as for mhip_hertz_friction_force: a double max(0, -sep) over the
+ *   contact branch, a uint64 count of capped contacts.  A pair index outside the segments gives NaN rows and is never
+ *   dereferenced.  node_force is what mhip_filaments_force takes as external_force.
+ *   segment_view (the first half of update), linker_pass and reduce (the two halves of force) are entry points of their
+ *   own as well, as the filaments' edge_pass and node_pass are.
+ * set_history  plants tang_disp rows: the given canonical list (pairs [c][2], tang_disp [c][3], device) is carried into the
+ *   current list; before the first update it is kept and carried into the first list (a restart).
+ * get  device pointers (they move at a rebuild: ask again after an update that rebuilt) and counts.
+ * force before save_velocity or update: MHIP_ERR_RUNTIME, the message names the missing call.
+ * Not built: periodic cells, several GPUs, a renumbering of nodes, the frictionless ...HertzianContact and WCA kernels. */
+typedef struct mhip_filament_contact_params {
+  double skin, youngs_modulus, poisson_ratio;
+  double mu, normal_damping, tangential_damping, density;
+  double history_dt;    /* < 0: the dt of the force call */
+  int bonded_exclusion; /* >= 1; the reference's value is 1 */
+  int monolayer;        /* the filaments' flag */
+} mhip_filament_contact_params;
+typedef struct mhip_filament_contact_fields {
+  size_t num_nodes, num_pairs;
+  int32_t* pairs;                       /* [num_pairs][2] */
+  double *sep, *tang_disp, *force;      /* [num_pairs], [num_pairs][3], [num_pairs][3] */
+  double* share;                        /* [num_pairs][2][3] */
+  double *node_force, *seg, *aabb, *velocity_prev; /* [N][3], [N][8], [N][6], [N][3] */
+} mhip_filament_contact_fields;
+typedef struct mhip_filament_contacts* mhip_filament_contacts_t;
+int mhip_filament_contacts_create(mhip_filament_contacts_t* handle, mhip_filaments_t filaments,
+                                  const int32_t* node_ptr /*[host] F + 1*/,
+                                  const double* segment_radius /*[host] N or NULL*/,
+                                  const mhip_filament_contact_params* params, mhip_stream_t stream);
+int mhip_filament_contacts_save_velocity(mhip_filament_contacts_t handle);
+int mhip_filament_contacts_update(mhip_filament_contacts_t handle, int* rebuilt /*[host]*/);
+int mhip_filament_contacts_force(mhip_filament_contacts_t handle, double dt,
+                                 const double* external_force /*[device] N x 3 or NULL*/, void* stats /*[device]*/);
+int mhip_filament_contacts_segment_view(mhip_filament_contacts_t handle);
+int mhip_filament_contacts_linker_pass(mhip_filament_contacts_t handle, double dt, void* stats /*[device]*/);
+int mhip_filament_contacts_reduce(mhip_filament_contacts_t handle, const double* external_force);
+int mhip_filament_contacts_set_history(mhip_filament_contacts_t handle, size_t c, const int32_t* pairs,
+                                       const double* tang_disp);
+int mhip_filament_contacts_get(mhip_filament_contacts_t handle, mhip_filament_contact_fields* fields /*[host]*/);
+int mhip_filament_contacts_destroy(mhip_filament_contacts_t handle);
 
 /* Mixed shapes (BASELINE configs[4]): kind[n] = 0 sphere, 1 spherocylinder, 2 ellipsoid; shape[n][3] = (r,-,-) /
  * (r,L,-) / (r1,r2,r3); quat is ignored for spheres.  compute_aabb dispatches on kind (compute_aabb.hpp:72-127) and

@@ -669,6 +669,7 @@ class DistributedSpherocylinderStepper {
 
 /// Centerline-twist elastic filaments (mhip_filaments_*), stepped in the reference's order: the state lives in the
 /// library handle, fields() hands out its device pointers (those of the edge state change places at every step).
+/// set_contacts adds the frictional Hertzian contacts between their segments (mhip_filament_contacts_*).
 class FilamentStepper {
  public:
   /// host arrays: node_ptr [F + 1]; center [N][3], twist [N], edge_orientation [N][4] (w, x, y, z; by left node: the
@@ -678,7 +679,7 @@ class FilamentStepper {
                   const std::vector<double>& radius, const std::vector<double>& rest_curvature,
                   const std::vector<double>& arclength, const std::vector<double>& phase,
                   const mhip_filament_params& params)
-      : stats_(2) {
+      : node_ptr_(node_ptr), monolayer_(params.monolayer), stats_(4) {
     if (node_ptr.empty()) throw std::invalid_argument("FilamentStepper: node_ptr is empty");
     const size_t f = node_ptr.size() - 1, n = static_cast<size_t>(node_ptr.back() < 0 ? 0 : node_ptr.back());
     if (center.size() != 3 * n || twist.size() != n || edge_orientation.size() != 4 * n || radius.size() != n ||
@@ -697,20 +698,58 @@ class FilamentStepper {
   }
   FilamentStepper(const FilamentStepper&) = delete;
   FilamentStepper& operator=(const FilamentStepper&) = delete;
-  ~FilamentStepper() { mhip_filaments_destroy(h_); }
+  ~FilamentStepper() {
+    mhip_filament_contacts_destroy(contacts_);
+    mhip_filaments_destroy(h_);
+  }
+
+  /// contacts between the segments from the next step on; segment_radius [N] or empty = the left node's radius;
+  /// params.monolayer is set to the filaments' flag
+  void set_contacts(mhip_filament_contact_params params, const std::vector<double>& segment_radius = {}) {
+    if (!segment_radius.empty() && segment_radius.size() != static_cast<size_t>(node_ptr_.back()))
+      throw std::invalid_argument("FilamentStepper: segment_radius does not have one entry per node");
+    params.monolayer = monolayer_;
+    mhip_filament_contacts_t c = nullptr;
+    check(mhip_filament_contacts_create(&c, h_, node_ptr_.data(), segment_radius.empty() ? nullptr : segment_radius.data(),
+                                        &params, nullptr));
+    mhip_filament_contacts_destroy(contacts_);
+    contacts_ = c;
+  }
 
   /// advance -> forces at x(t + dt), time = step index * dt as the reference counts it (:1115) -> velocities;
-  /// external_force [device, N x 3, or null] is added first (contact forces reduced to the nodes)
+  /// external_force [device, N x 3, or null] is added first.  With contacts (:2013-2021): save_velocity -> advance ->
+  /// update -> contact force with external_force -> forces with the contacts' node forces -> velocities.
   StepStats step(double dt, const double* external_force = nullptr) {
+    StepStats st;
+    if (contacts_) check(mhip_filament_contacts_save_velocity(contacts_));
     check(mhip_filaments_advance(h_, dt));
+    if (contacts_) {
+      int rebuilt = 0;
+      check(mhip_filament_contacts_update(contacts_, &rebuilt));
+      check(mhip_filament_contacts_force(contacts_, dt, external_force, stats_.data() + 2));
+      const mhip_filament_contact_fields cf = contact_fields();
+      external_force = cf.node_force;
+      st.rebuilt = rebuilt != 0;
+      st.num_contacts = cf.num_pairs;
+    }
     check(mhip_filaments_force(h_, static_cast<double>(step_index_) * dt, external_force, stats_.data()));
     check(mhip_filaments_velocity(h_));
     ++step_index_;
-    const auto s = stats_.download();
-    StepStats st;
+    const auto s = stats_.download();  // the one host read of the step
     st.max_stretch = s[0];
     st.max_curvature_deviation = s[1];
+    if (contacts_) {
+      st.max_overlap = s[2];
+      unsigned long long sliding = 0;
+      std::memcpy(&sliding, &s[3], sizeof sliding);
+      st.num_sliding = static_cast<size_t>(sliding);
+    }
     return st;
+  }
+  mhip_filament_contact_fields contact_fields() const {
+    mhip_filament_contact_fields f{};
+    if (contacts_) check(mhip_filament_contacts_get(contacts_, &f));
+    return f;
   }
   mhip_filament_fields fields() const {
     mhip_filament_fields f{};
@@ -721,7 +760,10 @@ class FilamentStepper {
 
  private:
   mhip_filaments_t h_ = nullptr;
-  DeviceVector stats_;
+  mhip_filament_contacts_t contacts_ = nullptr;
+  std::vector<int32_t> node_ptr_;
+  int monolayer_ = 0;
+  DeviceVector stats_;  // (max_stretch, max_curvature_deviation, max_overlap, the bits of num_sliding)
   size_t step_index_ = 0;
 };
 

@@ -63,6 +63,22 @@ class FilamentFields(C.Structure):
     _fields_ = [("num_nodes", C.c_size_t), ("num_filaments", C.c_size_t)] + [(f, C.c_void_p) for f in FILAMENT_FIELDS]
 
 
+class FilamentContactParams(C.Structure):
+    _fields_ = [("skin", C.c_double), ("youngs_modulus", C.c_double), ("poisson_ratio", C.c_double), ("mu", C.c_double),
+                ("normal_damping", C.c_double), ("tangential_damping", C.c_double), ("density", C.c_double),
+                ("history_dt", C.c_double), ("bonded_exclusion", C.c_int), ("monolayer", C.c_int)]
+
+
+# mhip_filament_contact_fields: name -> columns; pairs (int32) .. share have num_pairs rows, the rest num_nodes
+FILAMENT_CONTACT_FIELDS = {"pairs": 2, "sep": 1, "tang_disp": 3, "force": 3, "share": 6, "node_force": 3, "seg": 8,
+                           "aabb": 6, "velocity_prev": 3}
+
+
+class FilamentContactFields(C.Structure):
+    _fields_ = [("num_nodes", C.c_size_t), ("num_pairs", C.c_size_t)] + [(f, C.c_void_p)
+                                                                         for f in FILAMENT_CONTACT_FIELDS]
+
+
 class VelocityHalo(C.Structure):
     """mhip_velocity_halo: the per-iteration ghost-velocity exchange of one rank (host lists + one device index list)"""
     _fields_ = [("velocity", C.c_void_p), ("num_send_peers", C.c_int), ("send_peer", C.POINTER(C.c_int)),
@@ -161,6 +177,16 @@ SIGNATURES = {
     "mhip_filaments_velocity": [_vp],
     "mhip_filaments_get": [_vp, C.POINTER(FilamentFields)],
     "mhip_filaments_destroy": [_vp],
+    "mhip_filament_contacts_create": [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(FilamentContactParams), _vp],
+    "mhip_filament_contacts_save_velocity": [_vp],
+    "mhip_filament_contacts_update": [_vp, C.POINTER(_i)],
+    "mhip_filament_contacts_force": [_vp, _d, _vp, _vp],
+    "mhip_filament_contacts_segment_view": [_vp],
+    "mhip_filament_contacts_linker_pass": [_vp, _d, _vp],
+    "mhip_filament_contacts_reduce": [_vp, _vp],
+    "mhip_filament_contacts_set_history": [_vp, _sz, _vp, _vp],
+    "mhip_filament_contacts_get": [_vp, C.POINTER(FilamentContactFields)],
+    "mhip_filament_contacts_destroy": [_vp],
     "mhip_philox4x32_10": [_sz, _vp, _vp, C.c_uint32, _vp, _vp],
     "mhip_brownian_velocity": [_sz, _vp, _vp, _d, _d, _vp, _vp, _vp],
     "mhip_drag_velocity": [_sz, _vp, _vp, _vp, _vp],

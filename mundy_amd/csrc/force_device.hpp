@@ -179,6 +179,53 @@ __device__ inline HertzPair hertz_pair(int2 p, const double* __restrict__ radius
   return h;
 }
 
+// The frictional Hertzian law of one contact (sep <= 0, or NaN), after the contact-point velocities
+// (SpherocylinderSegmentSpherocylinderSegmentFrictionalHertzianContact.cpp:468-511): rel = v_cp,j - v_cp,i, n the
+// normal from i to j, td the pair's history row.  force is the one on body i; td the new history row.
+// hertz_friction.hip (rigid rods) and filament_contact.hip (flexible segments) call this one text.
+__device__ inline bool row_is_pos_zero(const double* p, size_t c) {  // the three words of row c are all +0.0
+  return (__double_as_longlong(p[3 * c]) | __double_as_longlong(p[3 * c + 1]) | __double_as_longlong(p[3 * c + 2])) == 0;
+}
+struct FrictionContact {
+  V3 force, td;
+  bool capped;
+};
+__device__ inline V3 vdiv(V3 a, double s) { return {a.x / s, a.y / s, a.z / s}; }
+__device__ inline FrictionContact hertz_friction_law(V3 rel, V3 n, double s, const HertzPair& h,
+                                                     const mhip_hertz_friction_params& prm, V3 td) {
+  const V3 rel_n = dot(rel, n) * n;
+  const V3 rel_t = rel - rel_n;
+  td = td + rel_t * prm.dt;                                                         // :474
+  td = td - dot(td, n) * n;                                                         // :475
+  const double td_mag = norm(td);
+  // the sphere mass of the rod radius, as written (:484-485)
+  const double mi = 4.0 / 3.0 * M_PI * h.ri * h.ri * h.ri * prm.density;
+  const double mj = 4.0 / 3.0 * M_PI * h.rj * h.rj * h.rj * prm.density;
+  const double ms = (mi * mj) / (mi + mj);
+  // k_n = 4/3 E* (hertz.hip's E*), k_t = 8 G*: for equal materials 4/3 G / (1 - nu) and 4 G / (2 - nu) (:409-411)
+  const double Gi = 0.5 * h.Ei / (1.0 + h.vi), Gj = 0.5 * h.Ej / (1.0 + h.vj);
+  const double Gs = (Gi * Gj) / (Gj * (2.0 - h.vi) + Gi * (2.0 - h.vj));
+  const double kn = (4.0 / 3.0) * h.Es, kt = 8.0 * Gs;
+  const double hp = sqrt(-h.Rs * s);                                                // :490
+  const V3 damp_t = (ms * prm.tangential_damping) * rel_t;
+  const V3 Fn = hp * ((kn * s) * n + (ms * prm.normal_damping) * rel_n);            // :491-493
+  V3 Ft = hp * (kt * td + damp_t);                                                  // :494-495
+  const double ft_mag = norm(Ft);
+  const double cap = prm.mu * norm(Fn);
+  const bool capped = ft_mag > cap;
+  if (capped) {  // Coulomb: rescale history and force (:497-511)
+    if (td_mag != 0.0) {
+      const double ratio = cap / ft_mag;
+      const V3 shift = vdiv(damp_t, kt);
+      td = ratio * (td + shift) - shift;
+      Ft = Ft * ratio;
+    } else {
+      Ft = V3{0.0, 0.0, 0.0};
+    }
+  }
+  return {Fn + Ft, td, capped};  // on body i; body j receives the negative
+}
+
 // The row of body b: force + f or f.  A kernel that leaves the rows of untouched bodies alone in accumulate mode skips
 // the call (force + 0.0 would turn a -0.0 into +0.0, and cost the traffic).
 template <bool ACCUMULATE>

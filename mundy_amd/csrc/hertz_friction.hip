@@ -14,10 +14,6 @@
 
 namespace mhip {
 
-__device__ inline bool row_is_pos_zero(const double* p, size_t c) {
-  return (__double_as_longlong(p[3 * c]) | __double_as_longlong(p[3 * c + 1]) | __double_as_longlong(p[3 * c + 2])) == 0;
-}
-__device__ inline V3 vdiv(V3 a, double s) { return {a.x / s, a.y / s, a.z / s}; }
 
 // velocity of the contact point of a rigid rod: U + W x ((s - 1/2)(p1 - p0)) -- the arm of the rod-compressed operator
 // (get_contact_point_velocity, :357-380, for a rod whose nodes move rigidly; the twist is dropped there too)
@@ -61,40 +57,11 @@ __global__ void __launch_bounds__(kBlock)
     const V3 vi = contact_point_velocity(vel_prev, seg, p.x, arc_s[c]);
     const V3 vj = contact_point_velocity(vel_prev, seg, p.y, arc_t[c]);
     const V3 rel = vj - vi;                                                           // :468
-    const V3 rel_n = dot(rel, n) * n;
-    const V3 rel_t = rel - rel_n;
-    V3 td = load3(tang_disp, c);
-    td = td + rel_t * prm.dt;                                                         // :474
-    td = td - dot(td, n) * n;                                                         // :475
-    const double td_mag = norm(td);
     const HertzPair h = hertz_pair<E_ARRAY, NU_ARRAY>(p, radius, E, E0, nu, nu0);
-    // the sphere mass of the rod radius, as written (:484-485)
-    const double mi = 4.0 / 3.0 * M_PI * h.ri * h.ri * h.ri * prm.density;
-    const double mj = 4.0 / 3.0 * M_PI * h.rj * h.rj * h.rj * prm.density;
-    const double ms = (mi * mj) / (mi + mj);
-    // k_n = 4/3 E* (hertz.hip's E*), k_t = 8 G*: for equal materials 4/3 G / (1 - nu) and 4 G / (2 - nu) (:409-411)
-    const double Gi = 0.5 * h.Ei / (1.0 + h.vi), Gj = 0.5 * h.Ej / (1.0 + h.vj);
-    const double Gs = (Gi * Gj) / (Gj * (2.0 - h.vi) + Gi * (2.0 - h.vj));
-    const double kn = (4.0 / 3.0) * h.Es, kt = 8.0 * Gs;
-    const double hp = sqrt(-h.Rs * s);                                                // :490
-    const V3 damp_t = (ms * prm.tangential_damping) * rel_t;
-    const V3 Fn = hp * ((kn * s) * n + (ms * prm.normal_damping) * rel_n);            // :491-493
-    V3 Ft = hp * (kt * td + damp_t);                                                  // :494-495
-    const double ft_mag = norm(Ft);
-    const double cap = prm.mu * norm(Fn);
-    if (ft_mag > cap) {  // Coulomb: rescale history and force (:497-511)
-      ++capped;
-      if (td_mag != 0.0) {
-        const double ratio = cap / ft_mag;
-        const V3 shift = vdiv(damp_t, kt);
-        td = ratio * (td + shift) - shift;
-        Ft = Ft * ratio;
-      } else {
-        Ft = V3{0.0, 0.0, 0.0};
-      }
-    }
-    store3(tang_disp, c, td);
-    store3(force, c, Fn + Ft);  // on body i; body j receives the negative
+    const FrictionContact r = hertz_friction_law(rel, n, s, h, prm, load3(tang_disp, c));
+    capped += r.capped ? 1u : 0u;
+    store3(tang_disp, c, r.td);
+    store3(force, c, r.force);  // on body i; body j receives the negative
     dmax = -s > dmax ? -s : dmax;
   }
   block_stat_max(dmax, stats);

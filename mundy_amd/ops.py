@@ -1586,14 +1586,19 @@ class Filaments(_Handle):
     def force(self, time, external_force=None, stats=None):
         """edge pass + node pass at `time`; -> stats float64 [2] = (largest |l - l0| / l0, largest |kappa - rest|
         component), left on the device"""
-        if external_force is not None and tuple(external_force.shape) != (self.n, 3):
-            raise ValueError("external_force must have shape [%d, 3], got %s" % (self.n, tuple(external_force.shape)))
+        ext = self._external(external_force)
         if stats is None:
             stats = torch.empty(2, dtype=torch.float64, device="cuda")
-        capi.check(capi.load().mhip_filaments_force(self._h, float(time),
-                                                    _ptr(external_force, allow_none=True, name="external_force"),
-                                                    _ptr(stats, name="stats")))
+        capi.check(capi.load().mhip_filaments_force(self._h, float(time), ext, _ptr(stats, name="stats")))
         return stats
+
+    def _external(self, external_force):
+        """a tensor [N, 3], None, or the pointer of a [N, 3] buffer the library owns (FilamentContacts.node_force_ptr)"""
+        if isinstance(external_force, C.c_void_p):
+            return external_force
+        if external_force is not None and tuple(external_force.shape) != (self.n, 3):
+            raise ValueError("external_force must have shape [%d, 3], got %s" % (self.n, tuple(external_force.shape)))
+        return _ptr(external_force, allow_none=True, name="external_force")
 
     def edge_pass(self):
         """the first half of force(): every edge's tangent, length, binormal and orientation"""
@@ -1603,8 +1608,7 @@ class Filaments(_Handle):
         """the second half of force(): curvature, forces and twist torques from the edge state as it stands"""
         if stats is None:
             stats = torch.empty(2, dtype=torch.float64, device="cuda")
-        capi.check(capi.load().mhip_filaments_node_pass(self._h, float(time),
-                                                        _ptr(external_force, allow_none=True, name="external_force"),
+        capi.check(capi.load().mhip_filaments_node_pass(self._h, float(time), self._external(external_force),
                                                         _ptr(stats, name="stats")))
         return stats
 
@@ -1623,3 +1627,139 @@ class Filaments(_Handle):
         if rows:
             capi.check(capi.load().mhip_deep_copy(rows * w, _ptr(out), C.c_void_p(getattr(fields, name)), _stream()))
         return out
+
+
+# ---- frictional Hertzian contacts between filament segments (mhip_filament_contacts_*) ---------------------------------
+def check_filament_contacts(n, skin, youngs_modulus, poisson_ratio, mu, damping=(0.0, 0.0), density=1.0,
+                            segment_radius=None, history_dt=None, bonded_exclusion=1):
+    """host-side validation of a contact stage over n nodes (no library call) -> (capi.FilamentContactParams without the
+    monolayer flag, segment_radius [n] / None)"""
+    def number(v, name, ok, what):
+        v = float(v)
+        if not (math.isfinite(v) and ok(v)):
+            raise ValueError("%s must be finite and %s, got %r" % (name, what, v))
+        return v
+    skin = number(skin, "skin", lambda v: v >= 0.0, ">= 0")
+    E = number(youngs_modulus, "youngs_modulus", lambda v: v > 0.0, "> 0")
+    nu = number(poisson_ratio, "poisson_ratio", lambda v: 0.0 < v < 1.0, "in (0, 1)")
+    mu = number(mu, "mu", lambda v: v >= 0.0, ">= 0")
+    if not (isinstance(damping, (tuple, list)) and len(damping) == 2):
+        raise ValueError("damping must be (normal, tangential), got %r" % (damping,))
+    gn = number(damping[0], "damping[0]", lambda v: v >= 0.0, ">= 0")
+    gt = number(damping[1], "damping[1]", lambda v: v >= 0.0, ">= 0")
+    rho = number(density, "density", lambda v: v >= 0.0, ">= 0")
+    hdt = -1.0 if history_dt is None else number(history_dt, "history_dt", lambda v: v >= 0.0, ">= 0")
+    if isinstance(bonded_exclusion, bool) or not isinstance(bonded_exclusion, (int, np.integer)) or bonded_exclusion < 1:
+        raise ValueError("bonded_exclusion must be an integer >= 1, got %r" % (bonded_exclusion,))
+    r = None
+    if segment_radius is not None:
+        r = segment_radius.detach().cpu().numpy() if isinstance(segment_radius, torch.Tensor) else segment_radius
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if r.shape != (n,):
+            raise ValueError("segment_radius must have shape [%d], got %s" % (n, r.shape))
+        if not (np.isfinite(r) & (r > 0.0)).all():
+            raise ValueError("segment %d: radius must be finite and > 0" % int(np.argmin(np.isfinite(r) & (r > 0.0))))
+    return capi.FilamentContactParams(skin, E, nu, mu, gn, gt, rho, hdt, int(bonded_exclusion), 0), r
+
+
+class FilamentContacts(_Handle):
+    """Frictional Hertzian contacts between the segments of an ops.Filaments (mhip_filament_contacts_*); segment i joins
+    the nodes i and i + 1.  Per step: save_velocity -> filaments.advance -> update -> force -> filaments.force(time,
+    node_force).  The filaments must outlive this object; all calls run on the stream current at construction."""
+    _destroy = "mhip_filament_contacts_destroy"
+
+    def __init__(self, filaments, **params):
+        prm, r = check_filament_contacts(filaments.n, **params)
+        prm.monolayer = int(filaments.params.monolayer)
+        self.filaments, self.params, self.n = filaments, prm, filaments.n
+        h = C.c_void_p()
+        capi.check(capi.load().mhip_filament_contacts_create(
+            C.byref(h), filaments._h, filaments.node_ptr.ctypes.data_as(C.c_void_p),
+            None if r is None else r.ctypes.data_as(C.c_void_p), C.byref(prm), _stream()))
+        self._h = h
+        self.stats = torch.zeros(2, dtype=torch.float64, device="cuda")
+
+    def save_velocity(self):
+        capi.check(capi.load().mhip_filament_contacts_save_velocity(self._h))
+
+    def update(self):
+        """the segment view and, when a box corner has moved by skin / 2 (or on the first call), the list -> rebuilt"""
+        rebuilt = C.c_int(0)
+        capi.check(capi.load().mhip_filament_contacts_update(self._h, C.byref(rebuilt)))
+        return bool(rebuilt.value)
+
+    def force(self, dt, external_force=None, stats=None):
+        """linker pass + reduction -> stats [2] float64 on the device: (max overlap, the bits of the int64 count of
+        capped contacts); the node forces are field("node_force") / node_force_ptr()"""
+        if external_force is not None and tuple(external_force.shape) != (self.n, 3):
+            raise ValueError("external_force must have shape [%d, 3], got %s" % (self.n, tuple(external_force.shape)))
+        stats = self.stats if stats is None else stats
+        capi.check(capi.load().mhip_filament_contacts_force(self._h, float(dt),
+                                                            _ptr(external_force, allow_none=True, name="external_force"),
+                                                            _ptr(stats, name="stats")))
+        return stats
+
+    def segment_view(self):
+        """the first half of update(): seg and aabb from the nodes as they stand"""
+        capi.check(capi.load().mhip_filament_contacts_segment_view(self._h))
+
+    def linker_pass(self, dt, stats=None):
+        """the first half of force(): sep, tang_disp, force and share of every linker, and the statistics"""
+        stats = self.stats if stats is None else stats
+        capi.check(capi.load().mhip_filament_contacts_linker_pass(self._h, float(dt), _ptr(stats, name="stats")))
+        return stats
+
+    def reduce(self, external_force=None):
+        """the second half of force(): node_force from the linker rows as they stand"""
+        capi.check(capi.load().mhip_filament_contacts_reduce(self._h, _ptr(external_force, allow_none=True,
+                                                                           name="external_force")))
+
+    def set_history(self, pairs, tang_disp):
+        """plants tang_disp [c, 3] for the canonical list pairs int32 [c, 2] (device tensors)"""
+        c = int(pairs.shape[0])
+        if tuple(tang_disp.shape) != (c, 3):
+            raise ValueError("tang_disp must have shape [%d, 3], got %s" % (c, tuple(tang_disp.shape)))
+        capi.check(capi.load().mhip_filament_contacts_set_history(
+            self._h, c, _ptr(pairs, dtype=torch.int32, cols=2, name="pairs") if c else None,
+            _ptr(tang_disp, name="tang_disp") if c else None))
+
+    def fields(self):
+        f = capi.FilamentContactFields()
+        capi.check(capi.load().mhip_filament_contacts_get(self._h, C.byref(f)))
+        return f
+
+    @property
+    def num_pairs(self):
+        return int(self.fields().num_pairs)
+
+    def node_force_ptr(self):
+        """the device pointer of node_force [N, 3]: what Filaments.force takes as external_force without a copy"""
+        return C.c_void_p(self.fields().node_force)
+
+    def _span(self, name):
+        if name not in capi.FILAMENT_CONTACT_FIELDS:
+            raise ValueError("unknown filament contact field %r" % (name,))
+        f = self.fields()
+        rows = int(f.num_pairs) if name in ("pairs", "sep", "tang_disp", "force", "share") else self.n
+        return getattr(f, name), rows, capi.FILAMENT_CONTACT_FIELDS[name]
+
+    def field(self, name):
+        """a copy of one field (capi.FILAMENT_CONTACT_FIELDS) as a device tensor; pairs int32 [c, 2], share [c, 2, 3]"""
+        ptr, rows, w = self._span(name)
+        if name == "pairs":
+            out = torch.empty((rows, 2), dtype=torch.int32, device="cuda")
+            words = rows  # one 8-byte word per pair
+        else:
+            out = torch.empty((rows, w) if w > 1 else (rows,), dtype=torch.float64, device="cuda")
+            words = rows * w
+        if words:
+            capi.check(capi.load().mhip_deep_copy(words, C.c_void_p(out.data_ptr()), C.c_void_p(ptr), _stream()))
+        return out.view(rows, 2, 3) if name == "share" else out
+
+    def set_field(self, name, value):
+        """overwrites one float64 field of the handle with `value` (a device tensor of the field's size): a restart"""
+        ptr, rows, w = self._span(name)
+        if name == "pairs" or value.numel() != rows * w:
+            raise ValueError("%s: expected %d float64 values" % (name, rows * w))
+        if rows:
+            capi.check(capi.load().mhip_deep_copy(rows * w, C.c_void_p(ptr), _ptr(value, name=name), _stream()))

@@ -123,6 +123,7 @@ class StepStats:
     active_switches: tuple = (0, 0)      # ... springs that switched (on, off) this step
     max_stretch: float = 0.0               # FilamentStepper: the largest |l - l0| / l0 over the edges at the force evaluation
     max_curvature_deviation: float = 0.0   # ... the largest component of |kappa - kappa_rest| over the elements
+    num_pairs: int = 0  # FilamentStepper(contacts=): segment pairs in the neighbour list (max_overlap, num_sliding, rebuilt too)
 
 
 class ContactStepper:
@@ -1077,14 +1078,21 @@ class FilamentStepper:
     (CollidingOverdampedFrictionalSperm.cpp:1999-2027).  node_ptr [F + 1], center [N, 3], radius [N], edge_orientation
     [N, 4] (w, x, y, z; by left node: synth.filaments builds the reference's initial triad), arclength [N]; twist and
     rest_curvature default to 0; wave = dict(amplitude, wave_number, frequency) with phase [F].  Host arrays or tensors.
-    Contacts between filament segments are not part of it: external_force is where their node forces enter."""
+    contacts = None, or dict(skin, youngs_modulus, poisson_ratio, mu, damping=(0, 0), density=1.0, segment_radius=None,
+    history_dt=None, bonded_exclusion=1): frictional Hertzian contacts between the segments (ops.FilamentContacts), whose
+    node forces, added to the caller's external_force, enter the filament forces."""
 
     def __init__(self, node_ptr, center, radius, edge_orientation, arclength, *, twist=None, rest_curvature=None,
                  phase=None, youngs_modulus, poisson_ratio=0.3, rest_length, viscosity, wave=None, disable_twist=False,
-                 monolayer=False):
+                 monolayer=False, contacts=None):
         n = int(np.asarray(node_ptr.cpu() if isinstance(node_ptr, torch.Tensor) else node_ptr)[-1])
         if rest_curvature is None:
             rest_curvature = np.zeros((n, 3))
+        if contacts is not None:  # refused before anything is built
+            ops.check_dict_spec(contacts, "contacts", ("skin", "youngs_modulus", "poisson_ratio", "mu", "damping", "density",
+                                                       "segment_radius", "history_dt", "bonded_exclusion"),
+                                optional=("damping", "density", "segment_radius", "history_dt", "bonded_exclusion"))
+            ops.check_filament_contacts(n, **contacts)
         self.filaments = ops.Filaments(node_ptr, radius, rest_curvature, arclength, phase, youngs_modulus=youngs_modulus,
                                        poisson_ratio=poisson_ratio, rest_length=rest_length, viscosity=viscosity,
                                        wave=wave, disable_twist=disable_twist, monolayer=monolayer)
@@ -1093,23 +1101,38 @@ class FilamentStepper:
         self.n = n
         self.filaments.set_state(dev(center), dev(np.zeros(n) if twist is None else twist), dev(edge_orientation))
         self.step_index = 0
-        self._stats = torch.zeros(2, dtype=torch.float64, device="cuda")
+        # (max_stretch, max_curvature_deviation, max_overlap, num_sliding as int64 bits): one host read per step
+        self._stats = torch.zeros(4, dtype=torch.float64, device="cuda")
+        self.contacts = None if contacts is None else ops.FilamentContacts(self.filaments, **contacts)
 
     def close(self):
+        if self.contacts is not None:
+            self.contacts.close()
         self.filaments.close()
 
     def field(self, name):
         return self.filaments.field(name)
 
     def step(self, dt, external_force=None, read_stats=True):
-        """advance -> forces at x(t + dt), time = step_index * dt as the reference counts it -> velocities.
+        """advance -> forces at x(t + dt), time = step_index * dt as the reference counts it -> velocities.  With
+        contacts: save_velocity -> advance -> update -> contact force (with external_force) -> forces -> velocities.
         read_stats=False skips the one host read of the step (the statistics then stay at their defaults)."""
-        f = self.filaments
+        f, c = self.filaments, self.contacts
+        st = StepStats(num_bodies=self.n)
+        if c is not None:
+            c.save_velocity()
         f.advance(dt)
-        f.force(self.step_index * float(dt), external_force, self._stats)
+        if c is not None:
+            st.rebuilt = c.update()
+            c.force(dt, external_force, self._stats[2:])
+            external_force = c.node_force_ptr()
+        f.force(self.step_index * float(dt), external_force, self._stats[:2])
         f.velocity()
         self.step_index += 1
-        st = StepStats(num_bodies=self.n)
         if read_stats:
-            st.max_stretch, st.max_curvature_deviation = self._stats.tolist()
+            got = self._stats.cpu()
+            st.max_stretch, st.max_curvature_deviation = float(got[0]), float(got[1])
+            if c is not None:
+                st.max_overlap, st.num_sliding = float(got[2]), int(got.view(torch.int64)[3])
+                st.num_pairs = st.num_contacts = c.num_pairs
         return st

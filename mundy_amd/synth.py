@@ -201,3 +201,38 @@ def filaments(num_filaments, nodes, radius=0.5, segment_length=1.0, rest_curvatu
                 rest_curvature=np.ascontiguousarray(np.broadcast_to(np.asarray(rest_curvature, dtype=np.float64), (N, 3))),
                 arclength=np.tile(i * segment_length, F), edge_orientation=np.ascontiguousarray(quat.reshape(N, 4)),
                 phase=phase)
+
+
+def crossed_filaments(num_filaments, nodes, radius=0.5, segment_length=1.0, angle=0.5 * np.pi, overlap=0.125, pitch=None,
+                      offset=None, seed=None):
+    """Two layers of `num_filaments` straight filaments each, laid at an angle: the colliding filaments' test bed.
+    Layer 0 lies in the plane x = 0: filament j at y = j pitch, along +z from z = 0 (pitch defaults to 4 radius + 2
+    segment_length / nodes: parallel neighbours never touch).  Layer 1 is layer 0 turned by `angle` about the x axis
+    through the centre of the patch and moved by `offset` (default (2 radius - overlap, 0, 0): every crossing is a
+    contact of depth `overlap`).  Fields as synth.filaments returns them; layer 0 comes first."""
+    F, B = int(num_filaments), int(nodes)
+    if B < 2:
+        raise ValueError("a filament has at least 2 nodes, got %d" % B)
+    r, l0 = float(radius), float(segment_length)
+    pitch = 4.0 * r + 2.0 * l0 / B if pitch is None else float(pitch)
+    offset = np.array([2.0 * r - overlap, 0.0, 0.0] if offset is None else offset, dtype=np.float64)
+    i = np.arange(B, dtype=np.float64)
+    base = np.zeros((F, B, 3))
+    base[:, :, 1] = (np.arange(F, dtype=np.float64) * pitch)[:, None]
+    base[:, :, 2] = (i * l0)[None, :]
+    mid = np.array([0.0, 0.5 * (F - 1) * pitch, 0.5 * (B - 1) * l0])
+    ca, sa = np.cos(angle), np.sin(angle)
+    rot = np.array([[1.0, 0.0, 0.0], [0.0, ca, sa], [0.0, -sa, ca]])   # +z -> (0, sin a, cos a)
+    top = (base - mid) @ rot.T + mid + offset
+    center = np.concatenate([base, top]).reshape(2 * F * B, 3)
+    tangent = np.repeat(np.stack([[0.0, 0.0, 1.0], rot @ np.array([0.0, 0.0, 1.0])]), F * B, axis=0)
+    d1 = np.tile([1.0, 0.0, 0.0], (2 * F * B, 1))
+    d2 = np.cross(tangent, d1)
+    d2 = d2 / np.sqrt(d2[:, 0] * d2[:, 0] + (d2[:, 1] * d2[:, 1] + d2[:, 2] * d2[:, 2]))[:, None]
+    quat = triad_quaternion(d1, d2, tangent).reshape(2 * F, B, 4)
+    quat[:, -1] = (1.0, 0.0, 0.0, 0.0)
+    N = 2 * F * B
+    phase = None if seed is None else 2.0 * np.pi * uniform01(seed, np.arange(2 * F), 0)
+    return dict(node_ptr=(np.arange(2 * F + 1) * B).astype(np.int32), center=np.ascontiguousarray(center),
+                twist=np.zeros(N), radius=np.full(N, r), rest_curvature=np.zeros((N, 3)),
+                arclength=np.tile(i * l0, 2 * F), edge_orientation=np.ascontiguousarray(quat.reshape(N, 4)), phase=phase)
