@@ -272,6 +272,68 @@ int mhip_brownian_velocity(size_t n, const uint64_t* keys, uint64_t* counters /*
 int mhip_drag_velocity(size_t n, const double* mob_trans, const double* force, double* velocity /*[n][6]*/,
                        mhip_stream_t stream);
 
+/* N-body hydrodynamics as a velocity stage: u_t (+)= sum_s K(x_t - x_s, b_t, a_s) f_s, the long-range velocity the HP1
+ * app adds to the dry velocity every step (scrap/.../HP1.cpp:3942-4059 compute_rpy_hydro, :4744-4803 the main loop;
+ * kernels: scrap/.../periphery/Periphery.hpp:636-1085).  ns sources (centre [ns][3], radius a [ns], force [ns][3]), nt
+ * targets (centre [nt][3], radius b [nt]); the two sets may be the same arrays (beads to beads) or different ones of
+ * different sizes.  No self term is added (Periphery.hpp:946, HP1.cpp:4746): the dry drag stays the caller's.
+ * With d = x_t - x_s, r2 = (dx dx + dy dy) + dz dz, f.d = (fx dx + fy dy) + fz dz, every product and sum associated
+ * as the reference writes it (left to right), no contraction:
+ *   MHIP_HYDRO_STOKES  (apply_stokes_kernel, Periphery.hpp:719-743)  scale = 1.0 / (8.0 * M_PI * viscosity) [host]
+ *     rinv = r2 < 1e-12 ? 0 : quake_inv_sqrt(r2);  rinv3 = rinv rinv rinv
+ *     u += (scale rinv3) (r2 f + d (f.d))                                       radii are not read (may be NULL)
+ *   MHIP_HYDRO_RPY     (apply_rpy_kernel, :893-938)  the same scale and rinv; rinv5 = rinv rinv rinv3
+ *     c = f rinv3 - (3 (f.d) rinv5) d;   v = scale (f rinv + d ((f.d) rinv3) + ((1/3) a a) c)
+ *     u += v + ((1/6) b b) ((2 scale) c)
+ *   MHIP_HYDRO_RPYC    (apply_rpyc_kernel, :1000-1081; the app's default, HP1.cpp:5241, and the accurate kind)
+ *     r = sqrt(r2) (exact), r3 = r r2, rinv = r2 < 1e-12 ? 0 : 1.0 / r, h = d rinv, f.h = (fx hx + fy hy) + fz hz
+ *     inv_pi = 1.0 / 3.14159265358979323846, inv_mu = 1.0 / viscosity
+ *     a + b < r           far:  q = (a a + b b) rinv rinv,  s = (1/8) inv_pi inv_mu rinv
+ *                               u += (s (1 + q (1/3))) f + (s (1 - q)) ((f.h) h)
+ *     |a - b| < r, a > 1e-12 and b > 1e-12   overlapping:  s = (1/6) inv_pi inv_mu / (a b), e = (a - b)(a - b)
+ *                               t1 = s (16 r3 (a + b) - (e + 3 r2)(e + 3 r2)) (1/32) rinv3
+ *                               t2 = s 3 (e - r2) (e - r2) (1/32) rinv3;   u += t1 f + t2 ((f.h) h)
+ *     otherwise           local drag: u += ((1/6) inv_pi inv_mu / max(a, b)) f, skipped when r2 < 1e-12
+ *   quake_inv_sqrt (:71-82): i = 0x5fe6eb50c7b537a9 - (bits(x) >> 1) on the signed 64-bit pattern (arithmetic shift),
+ *     y = double(i), result y (1.5 - ((x / 2) y y)): ONE Newton step, relative error up to 1.75e-3.  It is part of what
+ *     STOKES and RPY are in the reference and is restated exactly; RPYC is the accurate kind.
+ * Summation order, a function of ns alone (not of nt, of which targets share a workgroup, of the grid or the device):
+ *   the sources are cut into consecutive chunks of MHIP_HYDRO_CHUNK; inside a chunk a target adds its terms in
+ *   ascending source index from +0.0, per component; the chunk sums are added in ascending chunk index from +0.0; with
+ *   accumulate != 0 that total is added to the old value last (otherwise it is stored).  One writer per target, no
+ *   floating-point atomics: two calls give the same bits, and a target evaluated alone gives the bits it has in any
+ *   larger target set.
+ * velocity row t starts at velocity + t * velocity_stride; velocity_stride = 3, or 6 for the [n][6] rows
+ * mhip_drag_velocity writes (the last three entries of a row are not touched).
+ * The handle owns the grow-only buffer of the chunk sums ([chunk][target][3]) that a call uses when the target tiles
+ * alone would not fill the chip; nothing is allocated once it is warm.  One call at a time per handle.
+ * mhip_hydro_set_path (tests and timing): MHIP_HYDRO_PATH_IN_LANE (a lane walks all chunks), MHIP_HYDRO_PATH_PARTIAL
+ * (chunk sums through the buffer, ordered second pass) instead of the launch rule's choice; the bits are the same.
+ * mhip_hydro_last_path: the shape the last call took.
+ * Refused with MHIP_ERR_INVALID_ARGUMENT before any HIP call: an unknown kind, a viscosity that is not finite or <= 0,
+ * a stride other than 3 or 6, a null array with a non-zero count (radii may be NULL for STOKES).  ns == 0 writes +0.0
+ * (accumulate: leaves velocity alone); nt == 0 does nothing.
+ * mhip_hydro_add_velocity: velocity[b][0..2] += u_hydro[b][0..2] (u_hydro [n][3]): a stored hydrodynamic velocity
+ * into the rows of U_ext. */
+#define MHIP_HYDRO_STOKES 0
+#define MHIP_HYDRO_RPY 1
+#define MHIP_HYDRO_RPYC 2
+#define MHIP_HYDRO_CHUNK 1024
+#define MHIP_HYDRO_PATH_AUTO 0
+#define MHIP_HYDRO_PATH_IN_LANE 1
+#define MHIP_HYDRO_PATH_PARTIAL 2
+typedef struct mhip_hydro* mhip_hydro_t;
+int mhip_hydro_create(mhip_hydro_t* handle);
+int mhip_hydro_destroy(mhip_hydro_t handle);
+int mhip_hydro_set_path(mhip_hydro_t handle, int path);
+int mhip_hydro_last_path(mhip_hydro_t handle, int* path /*[host]*/);
+int mhip_hydro_velocity(mhip_hydro_t handle, int kind, double viscosity, size_t ns, const double* source_center,
+                        const double* source_radius, const double* source_force, size_t nt,
+                        const double* target_center, const double* target_radius, double* velocity,
+                        int velocity_stride, int accumulate, mhip_stream_t stream);
+int mhip_hydro_add_velocity(size_t n, const double* u_hydro /*[n][3]*/, double* velocity, int velocity_stride,
+                            mhip_stream_t stream);
+
 /* Crosslinkers that bind and unbind: the kinetic Monte Carlo stage of the HP1 app (scrap/.../HP1.cpp:4728-4739 in the
  * step; :3264-3438 rates, :3440-3594 sampling, :3597-3748 state changes; NgpHP1.cpp:1830-2137 the same over a
  * per-crosslinker list of bind sites), which the reference runs serially on the host in an STK modification cycle.

@@ -15,6 +15,9 @@ SPACE_UNCONSTRAINED, SPACE_LOWER_BOUND, SPACE_UPPER_BOUND, SPACE_BOUNDED = 0, 1,
 RESIDUAL_PROJECTED_DIFF, RESIDUAL_PROJECTED_GRADIENT = 0, 1
 SPRING_HOOKEAN, SPRING_FENE = 0, 1
 PERIPHERY_SPHERE, PERIPHERY_ELLIPSOID, PERIPHERY_ELLIPSOID_FAST = 0, 1, 2
+HYDRO_STOKES, HYDRO_RPY, HYDRO_RPYC = 0, 1, 2
+HYDRO_CHUNK = 1024  # MHIP_HYDRO_CHUNK: the width of the summation order's chunks
+HYDRO_PATH_AUTO, HYDRO_PATH_IN_LANE, HYDRO_PATH_PARTIAL = 0, 1, 2
 
 
 class MhipError(RuntimeError):
@@ -190,6 +193,12 @@ SIGNATURES = {
     "mhip_philox4x32_10": [_sz, _vp, _vp, C.c_uint32, _vp, _vp],
     "mhip_brownian_velocity": [_sz, _vp, _vp, _d, _d, _vp, _vp, _vp],
     "mhip_drag_velocity": [_sz, _vp, _vp, _vp, _vp],
+    "mhip_hydro_create": [C.POINTER(_vp)],
+    "mhip_hydro_destroy": [_vp],
+    "mhip_hydro_set_path": [_vp, _i],
+    "mhip_hydro_last_path": [_vp, C.POINTER(_i)],
+    "mhip_hydro_velocity": [_vp, _i, _d, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _i, _i, _vp],
+    "mhip_hydro_add_velocity": [_sz, _vp, _vp, _i, _vp],
     "mhip_contact_spheres": [_sz, _vp, _vp, _vp, C.POINTER(_d), _vp, _vp, _vp],
     "mhip_contact_spherocylinders": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mhip_broadphase_create": [C.POINTER(_vp)],

@@ -1188,6 +1188,114 @@ def drag_velocity(mob_trans, force=None, out=None):
     return v
 
 
+# ---- n-body hydrodynamics as a velocity stage (Periphery.hpp:636-1085; HP1.cpp:3942-4059) ----------------------------
+HYDRO_KINDS = {"stokes": capi.HYDRO_STOKES, "rpy": capi.HYDRO_RPY, "rpyc": capi.HYDRO_RPYC}
+HYDRO_PATHS = {"auto": capi.HYDRO_PATH_AUTO, "in_lane": capi.HYDRO_PATH_IN_LANE, "partial": capi.HYDRO_PATH_PARTIAL}
+
+
+def _hydro_kind(kind):
+    if kind not in HYDRO_KINDS:
+        raise ValueError("hydrodynamics kind must be 'rpyc', 'rpy' or 'stokes', got %r" % (kind,))
+    return HYDRO_KINDS[kind]
+
+
+def check_hydrodynamics(spec, n):
+    """hydrodynamics=dict(kind=, radius=None, update_every=1) of the stepper -> (kind, radius, update_every); radius
+    None (the beads' own), a number or [n] numbers, finite and >= 0 -> None or a host array [n]"""
+    check_dict_spec(spec, "hydrodynamics", ("kind", "radius", "update_every"), optional=("radius", "update_every"))
+    _hydro_kind(spec["kind"])
+    radius = spec.get("radius")
+    if radius is not None:
+        a = radius.detach().cpu().numpy() if isinstance(radius, torch.Tensor) else np.asarray(radius, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(n, float(a))
+        if a.shape != (n,):
+            raise ValueError("hydrodynamics radius must be a number or have shape [%d], got %s" % (n, a.shape))
+        if a.size and not bool(np.all(np.isfinite(a) & (a >= 0.0))):
+            raise ValueError("hydrodynamics radius must be finite and >= 0")
+        radius = np.ascontiguousarray(a, dtype=np.float64)
+    every = spec.get("update_every", 1)
+    if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
+        raise ValueError("hydrodynamics update_every must be an integer >= 1, got %r" % (every,))
+    return spec["kind"], radius, int(every)
+
+
+class HydroWorkspace(_Handle):
+    """mhip_hydro_t: the grow-only buffer of chunk sums a call of hydro_velocity may use; one call at a time"""
+    _destroy = "mhip_hydro_destroy"
+
+    def __init__(self):
+        h = C.c_void_p()
+        capi.check(capi.load().mhip_hydro_create(C.byref(h)))
+        self._h = h
+
+    def set_path(self, path="auto"):
+        """tests and timing: "in_lane" / "partial" instead of the launch rule's choice ("auto"); the bits are the same"""
+        if path not in HYDRO_PATHS:
+            raise ValueError("path must be 'auto', 'in_lane' or 'partial'")
+        capi.check(capi.load().mhip_hydro_set_path(self._h, HYDRO_PATHS[path]))
+
+    def last_path(self):
+        p = C.c_int()
+        capi.check(capi.load().mhip_hydro_last_path(self._h, C.byref(p)))
+        return {v: k for k, v in HYDRO_PATHS.items()}[p.value]
+
+
+_hydro_default = None
+
+
+def hydro_velocity(kind, viscosity, src_center, src_radius, src_force, tgt_center=None, tgt_radius=None, out=None,
+                   accumulate=False, workspace=None):
+    """u_t (+)= sum_s K(x_t - x_s, b_t, a_s) f_s (mhip_hydro_velocity): kind "rpyc" (the accurate one) | "rpy" |
+    "stokes"; targets default to the sources (beads to beads; no self term).  out [nt, 3] or [nt, 6] (the first three
+    columns are written), default a new [nt, 3]; accumulate adds to what out holds.  Radii may be None for "stokes".
+    The sums are taken in the fixed order mundy_hip.h documents (a function of the source count alone)."""
+    global _hydro_default
+    k = _hydro_kind(kind)
+    mu = float(viscosity)
+    if not (mu > 0.0 and mu < float("inf")):
+        raise ValueError("viscosity must be finite and > 0, got %r" % (viscosity,))
+    if tgt_center is None:
+        tgt_center, tgt_radius = src_center, src_radius
+    ns, nt = src_center.shape[0], tgt_center.shape[0]
+    need_r = k != capi.HYDRO_STOKES
+    for name, t, rows, cols in (("src_force", src_force, ns, 3), ("src_center", src_center, ns, 3),
+                                ("tgt_center", tgt_center, nt, 3)):
+        if t.dim() != 2 or tuple(t.shape) != (rows, cols):
+            raise ValueError("%s must have shape [%d, %d], got %s" % (name, rows, cols, tuple(t.shape)))
+    for name, t, rows in (("src_radius", src_radius, ns), ("tgt_radius", tgt_radius, nt)):
+        if t is None and need_r:
+            raise ValueError("%s must not be None for kind %r" % (name, kind))
+        if t is not None and tuple(t.shape) != (rows,):
+            raise ValueError("%s must have shape [%d], got %s" % (name, rows, tuple(t.shape)))
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs out")
+        out = torch.empty((nt, 3), dtype=torch.float64, device=src_center.device)
+    if out.dim() != 2 or out.shape[0] != nt or out.shape[1] not in (3, 6):
+        raise ValueError("out must have shape [%d, 3] or [%d, 6], got %s" % (nt, nt, tuple(out.shape)))
+    if workspace is None:
+        if _hydro_default is None:
+            _hydro_default = HydroWorkspace()
+        workspace = _hydro_default
+    capi.check(capi.load().mhip_hydro_velocity(
+        workspace._h, k, mu, ns, _ptr(src_center, name="src_center"),
+        _ptr(src_radius, name="src_radius", allow_none=True), _ptr(src_force, name="src_force"), nt,
+        _ptr(tgt_center, name="tgt_center"), _ptr(tgt_radius, name="tgt_radius", allow_none=True),
+        _ptr(out, name="out"), int(out.shape[1]), 1 if accumulate else 0, _stream()))
+    return out
+
+
+def hydro_add_velocity(u_hydro, velocity):
+    """velocity[:, :3] += u_hydro (mhip_hydro_add_velocity): u_hydro [n, 3], velocity [n, 3] or [n, 6], in place"""
+    n = u_hydro.shape[0]
+    if velocity.dim() != 2 or velocity.shape[0] != n or velocity.shape[1] not in (3, 6):
+        raise ValueError("velocity must have shape [%d, 3] or [%d, 6], got %s" % (n, n, tuple(velocity.shape)))
+    capi.check(capi.load().mhip_hydro_add_velocity(n, _ptr(u_hydro, cols=3, name="u_hydro"),
+                                                   _ptr(velocity, name="velocity"), int(velocity.shape[1]), _stream()))
+    return velocity
+
+
 # ---- crosslinkers that bind and unbind (HP1.cpp:3264-3748, :4728-4739) ------------------------------------------------
 def check_crosslinkers(n, left, right, sites, kind, k, r, bind_rate, unbind_rate, kt, capture_radius):
     """host-side validation of a crosslinker set (no library call) -> (left int32 [m], right int32 [m], sites uint8

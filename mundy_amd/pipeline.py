@@ -40,6 +40,12 @@ of the nucleus and the active euchromatin force dipoles, in the reference's orde
         -> spring forces -> crosslinker springs -> periphery force -> active force dipoles (+ external_force)
         -> the chain step as above -> Euler update -> the active springs' timers advance by dt
 
+hydrodynamics= adds the long-range hydrodynamic velocity of the same app's default configuration to the chain step
+(HP1.cpp:4744-4803; compute_rpy_hydro :3942-4059), a velocity stage outside the solver:
+
+    ... -> forces F -> U_ext = M F -> += U_brown -> every update_every-th step u_hydro = sum_s K(x_t - x_s) F_s
+        (RPYC, RPY or Stokeslet, all pairs) -> += u_hydro (every step) -> contacts -> the chain step as above
+
 hertz_friction= replaces the frictionless Hertz force by the reference's frictional rod contact with a per-pair
 tangential history (SpherocylinderSegmentSpherocylinderSegmentFrictionalHertzianContact.cpp:384-518, run every step by
 CollidingOverdampedFrictionalSperm.cpp:1553-1731):
@@ -135,7 +141,7 @@ class ContactStepper:
                  conservative_ellipsoid_box=False, friction_method="apgd", contact_model="lcp", youngs_modulus=1000.0,
                  poisson_ratio=0.3, growth_rate=None, division_length=None, capacity=None, ids=None, springs=None,
                  brownian_kt=None, rng_keys=None, rng_counter=None, hertz_friction=None, hertz_damping=(0.0, 0.0),
-                 hertz_density=1.0, crosslinkers=None, periphery=None, active_forces=None):
+                 hertz_density=1.0, crosslinkers=None, periphery=None, active_forces=None, hydrodynamics=None):
         """kind = "sphere" | "spherocylinder" | "mixed".  Mixed systems (BASELINE configs[4]) pass kinds [n] int32
         (0 sphere, 1 spherocylinder, 2 ellipsoid) and shape [n, 3] = (r,-,-) / (r,L,-) / (r1,r2,r3) instead of
         radius / length.
@@ -176,7 +182,12 @@ class ContactStepper:
         springs [ma] (indices, no repeats) switch on at the rate kon and off at the rate koff (> 0) and push their
         beads apart with a force of magnitude sigma while on; keys (integers in [0, 2^63), default arange(ma)) and
         counter (default 0) key each one's Philox stream.  Needs springs=.  The timers advance by dt at the end of every
-        step that integrates."""
+        step that integrates.
+        hydrodynamics = dict(kind="rpyc" | "rpy" | "stokes", radius=None, update_every=1): the long-range hydrodynamic
+        velocity of the force stage's forces, added to U_ext after the noise (HP1.cpp:4744-4803); the chain step (spheres,
+        free space, either contact model).  radius: the hydrodynamic radii, None (the beads' own), a number or [n]
+        numbers >= 0; update_every k >= 1: recomputed on the steps 0, k, 2k, ... of this stepper and added on every
+        step.  The stepper then owns u_hydro [n, 3].  "rpyc" is the accurate kind."""
         if kind not in ("sphere", "spherocylinder", "mixed"):
             raise ValueError("kind must be 'sphere', 'spherocylinder' or 'mixed'")
         if contact_model not in ("lcp", "hertz"):
@@ -200,6 +211,13 @@ class ContactStepper:
         nucleus_spec = None
         if periphery is not None or active_forces is not None:  # (checked before anything reaches the device)
             nucleus_spec = self._check_nucleus(chain_only, center.shape[0], radius, springs, periphery, active_forces)
+        hydro_spec = None
+        if hydrodynamics is not None:  # (checked before anything reaches the device)
+            if (springs is None and brownian_kt is None and crosslinkers is None and periphery is None and
+                    active_forces is None):
+                raise ValueError("hydrodynamics belongs to the chain step: pass springs= or brownian_kt= (0.0: no noise)")
+            self._check_chain_only("hydrodynamics", "the kernels are free-space", *chain_only)
+            hydro_spec = ops.check_hydrodynamics(hydrodynamics, center.shape[0])
         self.hertz_friction = None
         if hertz_friction is not None:  # (checked before anything reaches the device)
             self._check_hertz_friction(contact_model, kind, rod_kinematics, growth_rate, springs, brownian_kt,
@@ -281,7 +299,7 @@ class ContactStepper:
         self.contact_cutoff = None if contact_cutoff is None else float(contact_cutoff)
         self.cutoff_fallbacks = 0
         self.ids = self.springs = self.rng_keys = self.rng_counter = self.crosslinkers = None
-        self.xl_sources = self.xl_sites = self.periphery = self.active = None
+        self.xl_sources = self.xl_sites = self.periphery = self.active = self.hydro = None
         if self.growth:
             self._init_growth(growth_rate, division_length, capacity, ids, search_buffer)
         if self.chain:
@@ -292,11 +310,13 @@ class ContactStepper:
             self._init_crosslinkers(xl_spec)
         if nucleus_spec is not None:
             self._init_nucleus(*nucleus_spec)
+        if hydro_spec is not None:
+            self._init_hydro(*hydro_spec)
         # the optional modes that carry state of their own: snapshot, restore and reorder_bodies call their
         # _snapshot_<mode>() / _restore_<mode>(saved) / _renumber_<mode>(perm, inv) hooks in this order
         on = dict(growth=self.growth, friction=self.hertz_friction is not None, springs=self.springs is not None,
                   crosslinkers=self.crosslinkers is not None, periphery=self.periphery is not None,
-                  active=self.active is not None)
+                  active=self.active is not None, hydro=self.hydro is not None)
         self._modes = [m for m, v in on.items() if v]
 
     @staticmethod
@@ -611,6 +631,43 @@ class ContactStepper:
     def _renumber_active(self, perm, inv):
         self.active.renumber(inv)  # endpoints; states and timers stay
 
+    # -- n-body hydrodynamics as a velocity stage (HP1.cpp:3942-4059, :4744-4803) -----------------------------------------
+    def _init_hydro(self, kind, radius, every):
+        n, dev = self.center.shape[0], self.center.device
+        self.hydro = dict(kind=kind, update_every=every)
+        self.hydro_radius = None if radius is None else torch.from_numpy(radius).to(dev)  # None: the beads' own
+        self.u_hydro = torch.zeros((n, 3), dtype=torch.float64, device=dev)  # the stored velocity, added every step
+        self.hydro_step = 0  # the reference's timestep_index_ of `% hydro_update_frequency_ == 0`
+        self._hydro_ws = ops.HydroWorkspace()
+
+    def _snapshot_hydro(self):
+        """the stored velocity, the step counter and the hydrodynamic radii"""
+        return (self.u_hydro.clone(), self.hydro_step, None if self.hydro_radius is None else self.hydro_radius.clone())
+
+    def _restore_hydro(self, saved):
+        u, self.hydro_step, radius = saved
+        self.u_hydro.copy_(u)
+        if radius is not None:
+            self.hydro_radius.copy_(radius)
+
+    def _renumber_hydro(self, perm, inv):
+        """the stored velocity and the radii move with their rows"""
+        self.u_hydro = ops.gather_rows(perm, self.u_hydro)
+        if self.hydro_radius is not None:
+            self.hydro_radius = ops.gather_rows(perm, self.hydro_radius)
+
+    def _hydro_velocity(self, force):
+        """every update_every-th step u_hydro = hydro(F) of the force stage's F; every step u_ext[:, :3] += u_hydro"""
+        if self.hydro_step % self.hydro["update_every"] == 0:
+            if force is None:
+                self.u_hydro.zero_()
+            else:
+                radius = self.radius if self.hydro_radius is None else self.hydro_radius
+                ops.hydro_velocity(self.hydro["kind"], self.viscosity, self.center, radius, force, out=self.u_hydro,
+                                   workspace=self._hydro_ws)
+        self.hydro_step += 1
+        ops.hydro_add_velocity(self.u_hydro, self.u_ext)
+
     def _force_stage(self, external_force):
         """the force stage in the reference's order (HP1.cpp:4733-4741): crosslinker KMC, active sampling, springs,
         crosslinker springs, periphery, active force dipoles, external force; every term after the first that writes is
@@ -642,14 +699,20 @@ class ContactStepper:
             ops.axpby(1.0, external_force.reshape(-1), 1.0, force.view(-1))
         return force
 
-    def external_velocity(self, external_force=None):
-        """U_ext = M (F_spring + F_crosslinker + F_periphery + F_active + F_ext) + U_brown into self.u_ext (the rng
-        counters advance; with crosslinkers, their KMC step runs first, then the active springs' sampling)"""
+    def external_velocity(self, external_force=None, mark=lambda name: None):
+        """U_ext = M (F_spring + F_crosslinker + F_periphery + F_active + F_ext) + U_brown (+ u_hydro) into self.u_ext
+        (the rng counters advance; with crosslinkers, their KMC step runs first, then the active springs' sampling);
+        mark(name) is told the stages (springs_brownian[, hydrodynamics]) as they are issued"""
         self._chain_stats.zero_()
-        ops.drag_velocity(self.mob_trans, self._force_stage(external_force), out=self.u_ext)
+        force = self._force_stage(external_force)
+        ops.drag_velocity(self.mob_trans, force, out=self.u_ext)
         if self.brownian_kt is not None:
             ops.brownian_velocity(self.rng_keys, self.rng_counter, self.brownian_kt, self.dt, self.mob_trans,
                                   self.u_ext)
+        mark("springs_brownian")
+        if self.hydro is not None:
+            self._hydro_velocity(force)
+            mark("hydrodynamics")
         return self.u_ext
 
     # -- growth mode (Bacteria.cpp:905-966, :685-748) ---------------------------------------------------------------
@@ -1025,8 +1088,7 @@ class ContactStepper:
             st.rebuilt = self.generate_neighbor_links(force=force_rebuild)
         mark("broadphase")
         if self.chain:
-            self.external_velocity(external_force)
-            mark("springs_brownian")
+            self.external_velocity(external_force, mark)
         elif self.hertz_friction is not None:
             self._fr_has_ext = external_force is not None
             if self._fr_has_ext:  # U_ext = (m_t F, 0)
