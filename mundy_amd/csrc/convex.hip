@@ -982,22 +982,24 @@ __global__ void __launch_bounds__(kBlock, MHIP_KBODY_WAVES)
   }
 }
 
-// one reduction record = kRed doubles (max residual term; sum dx^2 and sum dx dg as double-double pairs), stored as
-// planes `stride` apart
+// one reduction record = a max residual term and the sweep's sums as double-double pairs, stored as planes `stride`
+// apart.  BBPGD: kRed doubles (sum dx^2, sum dx dg); the scrap variant and APGD carry three sums, 7 doubles.
 constexpr int kRed = MHIP_BBPGD_REDUCTION_WIDTH;
 static_assert(kRed == 5, "record layout: max, num.hi, num.lo, den.hi, den.lo");
-__device__ inline void store_partial(double* __restrict__ p, size_t stride, size_t slot, double rmax, DD num, DD den) {
+template <class... Sums>  // DD
+__device__ inline void store_partial(double* __restrict__ p, size_t stride, size_t slot, double rmax, Sums... sums) {
   p[slot] = rmax;
-  p[stride + slot] = num.hi;
-  p[2 * stride + slot] = num.lo;
-  p[3 * stride + slot] = den.hi;
-  p[4 * stride + slot] = den.lo;
+  size_t k = 0;
+  ((p[(k + 1) * stride + slot] = sums.hi, p[(k + 2) * stride + slot] = sums.lo, k += 2), ...);
 }
 
-// dt * sdot of contact c from the body rows `vel`: sdot = -n . (v_src - v_tgt) at the contact points (NgpLcp.cpp:526-528)
+// velocities of the two contact points of contact c from the body rows `vel`, which hold (U, W) resp. (U, Z) for rods
+struct PointVelocities {
+  V3 vi, vj;
+};
 template <int KIN>
-__device__ inline double contact_dt_sdot(const OpView& op, const double* __restrict__ vel, size_t c, int2 ij) {
-  const V3 n = load3(op.normal, c);
+__device__ inline PointVelocities contact_point_velocities(const OpView& op, const double* __restrict__ vel, size_t c,
+                                                           int2 ij) {
   const double2* vi2 = reinterpret_cast<const double2*>(vel + 6 * (size_t)ij.x);
   const double2* vj2 = reinterpret_cast<const double2*>(vel + 6 * (size_t)ij.y);
   const double2 a0 = vi2[0], a1 = vi2[1], b0 = vj2[0], b1 = vj2[1];
@@ -1013,6 +1015,13 @@ __device__ inline double contact_dt_sdot(const OpView& op, const double* __restr
     vi = vi + ci * V3{a1.y, a2.x, a2.y};
     vj = vj + cj * V3{b1.y, b2.x, b2.y};
   }
+  return {vi, vj};
+}
+// dt * sdot of contact c from the body rows `vel`: sdot = -n . (v_src - v_tgt) at the contact points (NgpLcp.cpp:526-528)
+template <int KIN>
+__device__ inline double contact_dt_sdot(const OpView& op, const double* __restrict__ vel, size_t c, int2 ij) {
+  const V3 n = load3(op.normal, c);
+  const auto [vi, vj] = contact_point_velocities<KIN>(op, vel, c, ij);
   const double sdot = -n.x * (vi.x - vj.x) - n.y * (vi.y - vj.y) - n.z * (vi.z - vj.z);
   return op.dt * sdot;
 }
@@ -1152,6 +1161,7 @@ __device__ __forceinline__ void tier_service(const OpView& op, const SolverState
 
 // (Kept as its own body rather than an instantiation of constraint_sweep: as one, the same sweep ran 10 % slower --
 // 0.144 against 0.130 ms at 10^6 rods -- for reasons the ISA diff of the loop does not show.)
+// (For the same reason it and k_body keep their own text of contact_point_velocities, group_sum and body_row.)
 // (the waves-per-SIMD floor keeps the service path, which the compiler would otherwise schedule into 97 VGPRs, within
 // the sweep's own register budget)
 template <int MODE, int KIN, bool PACKED>
@@ -1286,22 +1296,21 @@ __global__ void __launch_bounds__(kBlock, (KIN == KIN_RIGID ? 6 : 7))
 }
 
 constexpr int kFinalBlock = 1024;  // threads of the single-workgroup final passes
-// ordered reduction of nparts (max, num, den) records of kRed doubles; element (i, k) sits at partials[i * si + k * sk]
+// ordered reduction of nparts records of a max and the given sums; element (i, k) sits at partials[i * si + k * sk]
 // (block partials: si = 1, sk = plane distance; the all-gathered per-rank records: si = kRed, sk = 1)
+template <class... Sums>  // DD&
 __device__ inline void reduce_records(int nparts, const double* __restrict__ partials, size_t si, size_t sk,
-                                      double* scratch, double& rmax, DD& num, DD& den) {
+                                      double* scratch, double& rmax, Sums&... sums) {
   rmax = kLowest;
-  num = DD{0.0, 0.0};
-  den = DD{0.0, 0.0};
+  ((sums = DD{0.0, 0.0}), ...);
   for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
     const double* r = partials + i * si;
     if (r[0] > rmax) rmax = r[0];
-    dd_add(num, DD{r[sk], r[2 * sk]});
-    dd_add(den, DD{r[3 * sk], r[4 * sk]});
+    size_t k = 0;
+    ((dd_add(sums, DD{r[(k + 1) * sk], r[(k + 2) * sk]}), k += 2), ...);
   }
   rmax = block_max(rmax, scratch);
-  num = block_sum(num, scratch);
-  den = block_sum(den, scratch);
+  ((sums = block_sum(sums, scratch)), ...);
 }
 
 // first level of the final reduction when there are tens of thousands of block partials: workgroup b folds the
@@ -1523,24 +1532,7 @@ __global__ void __launch_bounds__(kBlock)
     // UpdateConGammas (:532-548): max(lam_tmp - alpha * (sep + dt * sep_dot), 0)
     const double gu = first ? q[c] : gt[c];
     const double xc = INIT ? xt[c] : sp.project(xt[c] - step * gu);
-    const V3 n = load3(op.normal, c);
-    const double2* vi2 = reinterpret_cast<const double2*>(op.vel + 6 * (size_t)ij.x);
-    const double2* vj2 = reinterpret_cast<const double2*>(op.vel + 6 * (size_t)ij.y);
-    const double2 a0 = vi2[0], a1 = vi2[1], b0 = vj2[0], b1 = vj2[1];
-    V3 vi{a0.x, a0.y, a1.x}, vj{b0.x, b0.y, b1.x};
-    if (KIN == KIN_RIGID) {
-      const double2 a2 = vi2[2], b2 = vj2[2];
-      vi = vi + cross(V3{a1.y, a2.x, a2.y}, load3(op.ra, c));
-      vj = vj + cross(V3{b1.y, b2.x, b2.y}, load3(op.rb, c));
-    }
-    if (KIN == KIN_ROD) {
-      const double2 a2 = vi2[2], b2 = vj2[2];
-      const double ci = rod_arm_coef(op.arc_s[c]), cj = rod_arm_coef(op.arc_t[c]);
-      vi = vi + ci * V3{a1.y, a2.x, a2.y};
-      vj = vj + cj * V3{b1.y, b2.x, b2.y};
-    }
-    const double sdot = -n.x * (vi.x - vj.x) - n.y * (vi.y - vj.y) - n.z * (vi.z - vj.z);
-    const double gdt = op.dt * sdot;
+    const double gdt = contact_dt_sdot<KIN>(op, op.vel, c, ij);
     const double g = q[c] + gdt;  // sep_new = sep_old + dt * sep_dot
     gn[c] = g;
     dn[c] = gdt;
@@ -1557,11 +1549,7 @@ __global__ void __launch_bounds__(kBlock)
   }
   const double m = block_max(rmax, scratch);
   const DD s0 = block_sum(xx, scratch), s1 = block_sum(xg, scratch), s2 = block_sum(gg, scratch);
-  if (threadIdx.x == 0) {  // record of 7: max, then the three sums as double-double pairs
-    double* r = partials + 7 * blockIdx.x;
-    r[0] = m;
-    r[1] = s0.hi; r[2] = s0.lo; r[3] = s1.hi; r[4] = s1.lo; r[5] = s2.hi; r[6] = s2.lo;
-  }
+  if (threadIdx.x == 0) store_partial(partials, gridDim.x, blockIdx.x, m, s0, s1, s2);
 }
 
 // the first scrap iteration's body sweep must use the same (quirky) gradient as k_scrap_constraint: the host passes q
@@ -1572,19 +1560,9 @@ __global__ void __launch_bounds__(kBlock) k_scrap_finalize(int nparts, const dou
                                                           unsigned max_iters) {
   __shared__ double scratch[2 * kBlock / 64];
   if (!INIT && st->done) return;
-  double rmax = kLowest;
-  DD sxx{0.0, 0.0}, sxg{0.0, 0.0}, sgg{0.0, 0.0};
-  for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-    const double* r = partials + 7 * i;
-    if (r[0] > rmax) rmax = r[0];
-    dd_add(sxx, DD{r[1], r[2]});
-    dd_add(sxg, DD{r[3], r[4]});
-    dd_add(sgg, DD{r[5], r[6]});
-  }
-  rmax = block_max(rmax, scratch);
-  sxx = block_sum(sxx, scratch);
-  sxg = block_sum(sxg, scratch);
-  sgg = block_sum(sgg, scratch);
+  double rmax;
+  DD sxx, sxg, sgg;
+  reduce_records(nparts, partials, 1, nparts, scratch, rmax, sxx, sxg, sgg);
   if (threadIdx.x != 0) return;
   const double xx = dd_value(sxx), xg = dd_value(sxg), gg = dd_value(sgg);
   st->residual = rmax;
@@ -1935,6 +1913,44 @@ __global__ void __launch_bounds__(kBlock) k_assemble_velocity(size_t n, const do
   }
 }
 
+// The tail of a body sweep outside k_body: the butterfly that adds the double-double force and torque sums of a body's
+// G lanes, and the row a body's rounded sums give -- U = mt F beside W = mr T (vector arms) or Z = W x u with
+// W = mr (u x S) (rods, T holds S = sum coef f) -- which is stored as three 16-byte words.  w is the angular velocity.
+template <int G, int KIN>
+__device__ inline void group_sum(DD3& Fdd, DD3& Tdd) {
+#pragma unroll
+  for (int off = G / 2; off > 0; off >>= 1) {
+    dd_add(Fdd.x, dd_shfl_xor(Fdd.x, off));
+    dd_add(Fdd.y, dd_shfl_xor(Fdd.y, off));
+    dd_add(Fdd.z, dd_shfl_xor(Fdd.z, off));
+    if (KIN != KIN_TRANS) {
+      dd_add(Tdd.x, dd_shfl_xor(Tdd.x, off));
+      dd_add(Tdd.y, dd_shfl_xor(Tdd.y, off));
+      dd_add(Tdd.z, dd_shfl_xor(Tdd.z, off));
+    }
+  }
+}
+struct BodyRow {
+  V3 U, Z, w;
+};
+template <int KIN>
+__device__ inline BodyRow body_row(V3 F, V3 T, double mt, double mr, V3 axis) {
+  V3 w{0.0, 0.0, 0.0}, Z{0.0, 0.0, 0.0};
+  if (KIN == KIN_RIGID) Z = w = V3{mr * T.x, mr * T.y, mr * T.z};
+  if (KIN == KIN_ROD) {
+    const V3 tq = cross(axis, T);
+    w = V3{mr * tq.x, mr * tq.y, mr * tq.z};
+    Z = cross(w, axis);
+  }
+  return {V3{mt * F.x, mt * F.y, mt * F.z}, Z, w};
+}
+__device__ inline void store_body_row(double* __restrict__ vel, size_t b, const BodyRow& r) {
+  double2* v = reinterpret_cast<double2*>(vel + 6 * b);
+  v[0] = make_double2(r.U.x, r.U.y);
+  v[1] = make_double2(r.U.z, r.Z.x);
+  v[2] = make_double2(r.Z.y, r.Z.z);
+}
+
 // Body sweep of a VECTOR force per contact (mhip_contact_op_body_sweep_vector): F_c acts on body i, -F_c on body j, at the
 // operator's own lever arms.  The incidence index and the half-edge records are k_body's; of a record only the arm is
 // used (rods: the arclength coefficient, vector arms: r), and it is fetched only for a contact whose force is not zero
@@ -1959,33 +1975,13 @@ __global__ void __launch_bounds__(kBlock) k_body_vector(OpView op, const double*
     if (KIN == KIN_RIGID) dd_add(Tdd, cross(V3{H[3], H[4], H[5]}, f));  // torque r x f
     if (KIN == KIN_ROD) dd_add(Tdd, H[3] * f);  // S = sum coef f; the torque is u x S
   }
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) {
-    dd_add(Fdd.x, dd_shfl_xor(Fdd.x, off));
-    dd_add(Fdd.y, dd_shfl_xor(Fdd.y, off));
-    dd_add(Fdd.z, dd_shfl_xor(Fdd.z, off));
-    if (KIN != KIN_TRANS) {
-      dd_add(Tdd.x, dd_shfl_xor(Tdd.x, off));
-      dd_add(Tdd.y, dd_shfl_xor(Tdd.y, off));
-      dd_add(Tdd.z, dd_shfl_xor(Tdd.z, off));
-    }
-  }
+  group_sum<G, KIN>(Fdd, Tdd);
   if (sub != 0) return;
-  const V3 F = dd_value(Fdd), T = dd_value(Tdd);  // the one rounding of each sum
-  const double mt = op.mt[b], mr = (KIN != KIN_TRANS) ? op.mr[b] : 0.0;
-  V3 W{0.0, 0.0, 0.0};
-  if (KIN == KIN_RIGID) W = V3{mr * T.x, mr * T.y, mr * T.z};
-  if (KIN == KIN_ROD) {
-    const V3 axis = load3(op.axis, b);
-    const V3 tq = cross(axis, T);
-    const V3 w{mr * tq.x, mr * tq.y, mr * tq.z};
-    store3(op.omega, b, w);
-    W = cross(w, axis);  // the row carries Z = W x u
-  }
-  double2* v = reinterpret_cast<double2*>(op.vel + 6 * b);
-  v[0] = make_double2(mt * F.x, mt * F.y);
-  v[1] = make_double2(mt * F.z, W.x);
-  v[2] = make_double2(W.y, W.z);
+  const V3 axis = (KIN == KIN_ROD) ? load3(op.axis, b) : V3{0.0, 0.0, 0.0};
+  // (dd_value: the one rounding of each sum)
+  const BodyRow row = body_row<KIN>(dd_value(Fdd), dd_value(Tdd), op.mt[b], (KIN != KIN_TRANS) ? op.mr[b] : 0.0, axis);
+  if (KIN == KIN_ROD) store3(op.omega, b, row.w);
+  store_body_row(op.vel, b, row);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -2036,20 +2032,35 @@ __device__ inline V3 friction_iterate(size_t c, const double* __restrict__ Pt, c
   const V3 v = step_is_zero ? s.p : V3{s.p.x + (-step) * s.g.x, s.p.y + (-step) * s.g.y, s.p.z + (-step) * s.g.z};
   return project_cone(v, n, mu);
 }
-
-// body sweep (48-byte (n, r) half-edge records of the vector-arm operator)
-template <bool INIT, int G, int U>
-__global__ void __launch_bounds__(kBlock)
-    k_body_friction(OpView op, const SolverState* __restrict__ st, const double* __restrict__ P0,
-                    const double* __restrict__ P1, const double* __restrict__ p_init, double mu) {
-  const double* Pt = P0;
-  double step = 0.0;
-  if (!INIT) {
-    if (st->done) return;
-    if (st->flips & 1u) Pt = P1;
-    step = st->step;
+// ... as the body sweep asks for it: begin() reads what the sweep needs of the solver's state into a State (false: the
+// solve is over), then the impulse contact by contact
+template <bool INIT>
+struct BBImpulse {
+  const double *P0, *P1, *p_init;
+  struct State { const double* Pt; double step; bool step_is_zero; };
+  __device__ bool begin(const SolverState* __restrict__ st, State& s) const {
+    s.Pt = P0;
+    s.step = 0.0;
+    if (!INIT) {
+      if (st->done) return false;
+      if (st->flips & 1u) s.Pt = P1;
+      s.step = st->step;
+    }
+    s.step_is_zero = fabs(-s.step) < kZeroTol;
+    return true;
   }
-  const bool step_is_zero = fabs(-step) < kZeroTol;
+  __device__ V3 operator()(const State& s, size_t c, V3 n, double mu) const {
+    return friction_iterate<INIT>(c, s.Pt, p_init, n, mu, s.step, s.step_is_zero, nullptr, nullptr);
+  }
+};
+
+// body sweep of the cone solvers (48-byte (n, r) half-edge records of the vector-arm operator); Impulse yields the
+// contact's impulse: BBImpulse above or ApgdImpulse below
+template <class Impulse, int G, int U>
+__global__ void __launch_bounds__(kBlock)
+    k_body_cone(OpView op, const SolverState* __restrict__ st, Impulse impulse, double mu) {
+  typename Impulse::State state;
+  if (!impulse.begin(st, state)) return;
   const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   const int sub = static_cast<int>(t % G);
   if (t / G >= op.body_count) return;
@@ -2075,25 +2086,38 @@ __global__ void __launch_bounds__(kBlock)
     for (int u = 0; u < U; ++u) {
       if (e[u] < 0) continue;
       const V3 n{h0[u].x, h0[u].y, h1[u].x}, r{h1[u].y, h2[u].x, h2[u].y};
-      const V3 p = friction_iterate<INIT>(static_cast<size_t>(e[u] >> 1), Pt, p_init, n, mu, step, step_is_zero,
-                                          nullptr, nullptr);
+      const V3 p = impulse(state, static_cast<size_t>(e[u] >> 1), n, mu);
       const V3 f = (e[u] & 1) ? p : V3{-p.x, -p.y, -p.z};  // source: -p, target: +p
       dd_add(Fdd, f);
       dd_add(Tdd, cross(r, f));
     }
   }
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) {
-    dd_add(Fdd.x, dd_shfl_xor(Fdd.x, off)); dd_add(Fdd.y, dd_shfl_xor(Fdd.y, off)); dd_add(Fdd.z, dd_shfl_xor(Fdd.z, off));
-    dd_add(Tdd.x, dd_shfl_xor(Tdd.x, off)); dd_add(Tdd.y, dd_shfl_xor(Tdd.y, off)); dd_add(Tdd.z, dd_shfl_xor(Tdd.z, off));
-  }
+  group_sum<G, KIN_RIGID>(Fdd, Tdd);
   if (sub != 0) return;
-  const V3 F = dd_value(Fdd), T = dd_value(Tdd);
-  const double mt = op.mt[b], mr = op.mr[b];
-  double2* v = reinterpret_cast<double2*>(op.vel + 6 * b);
-  v[0] = make_double2(mt * F.x, mt * F.y);
-  v[1] = make_double2(mt * F.z, mr * T.x);
-  v[2] = make_double2(mr * T.y, mr * T.z);
+  store_body_row(op.vel, b, body_row<KIN_RIGID>(dd_value(Fdd), dd_value(Tdd), op.mt[b], op.mr[b], V3{0.0, 0.0, 0.0}));
+}
+
+// what the cone solvers' constraint sweeps share: the gradient g = dt (v_j - v_i) + sep n of contact c, the store of
+// the new (p, g) pair, and the contact's residual term, which raises rmax here (compared in the caller, behind the
+// returned flag, it cost the INIT sweep 8 VGPRs and a wave of occupancy).  counted: the contact belongs to this rank's
+// reductions, the caller adds its sums.
+struct ConeTerm {
+  V3 g;
+  bool counted;
+};
+__device__ inline ConeTerm cone_constraint_term(const OpView& op, double* __restrict__ Pn, size_t c, int2 ij, V3 n,
+                                                const double* __restrict__ sep, double mu, V3 p, double& rmax) {
+  const auto [vi, vj] = contact_point_velocities<KIN_RIGID>(op, op.vel, c, ij);
+  const double q = sep[c];
+  const V3 g{op.dt * (vj.x - vi.x) + q * n.x, op.dt * (vj.y - vi.y) + q * n.y, op.dt * (vj.z - vi.z) + q * n.z};
+  store_pg(Pn, c, p, g);
+  if (!(op.counted == nullptr || op.counted[c])) return {g, false};
+  // Linf projected-difference residual over the three components (the reference's policy, convex.hpp:468-496, with
+  // the cone projection)
+  const V3 w = project_cone(V3{p.x - kSmallStep * g.x, p.y - kSmallStep * g.y, p.z - kSmallStep * g.z}, n, mu);
+  const double r = fmax(fabs(p.x - w.x), fmax(fabs(p.y - w.y), fabs(p.z - w.z)));
+  if (r > rmax) rmax = r;
+  return {g, true};
 }
 
 // constraint sweep: one 256-contact tile per workgroup (grid-stride beyond the cap), block partials as k_constraint
@@ -2125,46 +2149,18 @@ __global__ void __launch_bounds__(kBlock)
     const V3 n = load3(op.normal, c);
     V3 p_old{0.0, 0.0, 0.0}, g_old{0.0, 0.0, 0.0};
     const V3 p = friction_iterate<INIT>(c, Pt, p_init, n, mu, step, step_is_zero, &p_old, &g_old);
-    const double2* vi2 = reinterpret_cast<const double2*>(op.vel + 6 * (size_t)ij.x);
-    const double2* vj2 = reinterpret_cast<const double2*>(op.vel + 6 * (size_t)ij.y);
-    const double2 a0 = vi2[0], a1 = vi2[1], a2 = vi2[2], b0 = vj2[0], b1 = vj2[1], b2 = vj2[2];
-    const V3 vi = V3{a0.x, a0.y, a1.x} + cross(V3{a1.y, a2.x, a2.y}, load3(op.ra, c));
-    const V3 vj = V3{b0.x, b0.y, b1.x} + cross(V3{b1.y, b2.x, b2.y}, load3(op.rb, c));
-    const double q = sep[c];
-    const V3 g{op.dt * (vj.x - vi.x) + q * n.x, op.dt * (vj.y - vi.y) + q * n.y, op.dt * (vj.z - vi.z) + q * n.z};
-    store_pg(Pn, c, p, g);
-    if (op.counted == nullptr || op.counted[c]) {
-      // Linf projected-difference residual over the three components (the reference's policy, convex.hpp:468-496,
-      // with the cone projection)
-      const V3 w = project_cone(V3{p.x - kSmallStep * g.x, p.y - kSmallStep * g.y, p.z - kSmallStep * g.z}, n, mu);
-      const double r = fmax(fabs(p.x - w.x), fmax(fabs(p.y - w.y), fabs(p.z - w.z)));
-      if (r > rmax) rmax = r;
-      if (!INIT) {
-        const V3 dp = p - p_old, dg = g - g_old;
-        dd_add(num, dot(dp, dp));
-        dd_add(den, dot(dp, dg));
-      }
+    const ConeTerm t = cone_constraint_term(op, Pn, c, ij, n, sep, mu, p, rmax);
+    if (!t.counted) continue;
+    if (!INIT) {
+      const V3 dp = p - p_old, dg = t.g - g_old;
+      dd_add(num, dot(dp, dp));
+      dd_add(den, dot(dp, dg));
     }
   }
   const double m = block_max(rmax, scratch);
   const DD s1 = block_sum(num, scratch);
   const DD s2 = block_sum(den, scratch);
   if (threadIdx.x == 0) store_partial(partials, gridDim.x, blockIdx.x, m, s1, s2);
-}
-
-// latest iterate -> caller's p [C][3], g [C][3]
-__global__ void __launch_bounds__(kBlock) k_finish_friction(size_t C, const SolverState* __restrict__ st,
-                                                           const double* __restrict__ P0,
-                                                           const double* __restrict__ P1, double* __restrict__ p,
-                                                           double* __restrict__ g) {
-  const bool odd = st->flips & 1u;
-  // converged at init / never iterated: P0; converged at parity q: the sweep wrote the "new" side; otherwise rolled forward
-  const double* cur = st->converged_at_init ? P0 : (st->converged ? (odd ? P0 : P1) : (odd ? P1 : P0));
-  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < C; c += (size_t)gridDim.x * blockDim.x) {
-    const PG s = load_pg(cur, c);
-    store3(p, c, s.p);
-    store3(g, c, s.g);
-  }
 }
 
 
@@ -2202,46 +2198,19 @@ __device__ inline V3 apgd_iterate(const ApgdBufs& B, const ApgdState& a, size_t 
   const double t = 1.0 / a.L;
   return project_cone(V3{y.x + (-t) * gy.x, y.y + (-t) * gy.y, y.z + (-t) * gy.z}, n, mu);
 }
-template <int G, int U>
-__global__ void __launch_bounds__(kBlock)
-    k_body_friction_apgd(OpView op, const SolverState* __restrict__ st, const ApgdState* __restrict__ as, ApgdBufs B,
-                         double mu) {
-  if (st->done) return;
-  const ApgdState a = *as;
-  const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-  const int sub = static_cast<int>(t % G);
-  if (t / G >= op.body_count) return;
-  const size_t b = op.body_first + t / G;
-  DD3 Fdd{{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}}, Tdd{{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
-  const int32_t beg = op.inc_ptr[b], end = op.inc_ptr[b + 1];
-  for (int32_t k0 = beg + sub; k0 < end; k0 += G * U) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int32_t k = k0 + u * G;
-      if (k >= end) continue;
-      const int32_t e = op.inc[k];
-      const double2* H2 = reinterpret_cast<const double2*>(op.half + (size_t)k * 6);
-      const double2 h0 = H2[0], h1 = H2[1], h2 = H2[2];
-      const V3 n{h0.x, h0.y, h1.x}, r{h1.y, h2.x, h2.y};
-      const V3 p = apgd_iterate(B, a, static_cast<size_t>(e >> 1), n, mu, nullptr, nullptr, nullptr);
-      const V3 f = (e & 1) ? p : V3{-p.x, -p.y, -p.z};
-      dd_add(Fdd, f);
-      dd_add(Tdd, cross(r, f));
-    }
+struct ApgdImpulse {  // for k_body_cone
+  const ApgdState* as;
+  ApgdBufs B;
+  using State = ApgdState;
+  __device__ bool begin(const SolverState* __restrict__ st, State& a) const {
+    if (st->done) return false;
+    a = *as;
+    return true;
   }
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) {
-    dd_add(Fdd.x, dd_shfl_xor(Fdd.x, off)); dd_add(Fdd.y, dd_shfl_xor(Fdd.y, off)); dd_add(Fdd.z, dd_shfl_xor(Fdd.z, off));
-    dd_add(Tdd.x, dd_shfl_xor(Tdd.x, off)); dd_add(Tdd.y, dd_shfl_xor(Tdd.y, off)); dd_add(Tdd.z, dd_shfl_xor(Tdd.z, off));
+  __device__ V3 operator()(const State& a, size_t c, V3 n, double mu) const {
+    return apgd_iterate(B, a, c, n, mu, nullptr, nullptr, nullptr);
   }
-  if (sub != 0) return;
-  const V3 F = dd_value(Fdd), T = dd_value(Tdd);
-  const double mt = op.mt[b], mr = op.mr[b];
-  double2* v = reinterpret_cast<double2*>(op.vel + 6 * b);
-  v[0] = make_double2(mt * F.x, mt * F.y);
-  v[1] = make_double2(mt * F.z, mr * T.x);
-  v[2] = make_double2(mr * T.y, mr * T.z);
-}
+};
 __global__ void __launch_bounds__(kBlock)
     k_constraint_friction_apgd(OpView op, const SolverState* __restrict__ st, const ApgdState* __restrict__ as,
                                ApgdBufs B, const double* __restrict__ sep, double mu, double* __restrict__ partials) {
@@ -2259,38 +2228,16 @@ __global__ void __launch_bounds__(kBlock)
     const V3 n = load3(op.normal, c);
     V3 y, gy, pk;
     const V3 p = apgd_iterate(B, a, c, n, mu, &y, &gy, &pk);
-    const double2* vi2 = reinterpret_cast<const double2*>(op.vel + 6 * (size_t)ij.x);
-    const double2* vj2 = reinterpret_cast<const double2*>(op.vel + 6 * (size_t)ij.y);
-    const double2 a0 = vi2[0], a1 = vi2[1], a2 = vi2[2], b0 = vj2[0], b1 = vj2[1], b2 = vj2[2];
-    const V3 vi = V3{a0.x, a0.y, a1.x} + cross(V3{a1.y, a2.x, a2.y}, load3(op.ra, c));
-    const V3 vj = V3{b0.x, b0.y, b1.x} + cross(V3{b1.y, b2.x, b2.y}, load3(op.rb, c));
-    const double q = sep[c];
-    const V3 g{op.dt * (vj.x - vi.x) + q * n.x, op.dt * (vj.y - vi.y) + q * n.y, op.dt * (vj.z - vi.z) + q * n.z};
-    store_pg(Pn, c, p, g);
-    if (op.counted == nullptr || op.counted[c]) {
-      const V3 w = project_cone(V3{p.x - kSmallStep * g.x, p.y - kSmallStep * g.y, p.z - kSmallStep * g.z}, n, mu);
-      const double r = fmax(fabs(p.x - w.x), fmax(fabs(p.y - w.y), fabs(p.z - w.z)));
-      if (r > rmax) rmax = r;
-      const V3 d = p - y;
-      dd_add(sa, dot(d, g - gy));
-      dd_add(sb, dot(d, d));
-      dd_add(sr, dot(gy, p - pk));
-    }
+    const ConeTerm t = cone_constraint_term(op, Pn, c, ij, n, sep, mu, p, rmax);
+    if (!t.counted) continue;
+    const V3 d = p - y;
+    dd_add(sa, dot(d, t.g - gy));
+    dd_add(sb, dot(d, d));
+    dd_add(sr, dot(gy, p - pk));
   }
   const double m = block_max(rmax, scratch);
-  const DD s1 = block_sum(sa, scratch);
-  const DD s2 = block_sum(sb, scratch);
-  const DD s3 = block_sum(sr, scratch);
-  if (threadIdx.x == 0) {
-    const size_t stride = gridDim.x, slot = blockIdx.x;
-    partials[slot] = m;
-    partials[stride + slot] = s1.hi;
-    partials[2 * stride + slot] = s1.lo;
-    partials[3 * stride + slot] = s2.hi;
-    partials[4 * stride + slot] = s2.lo;
-    partials[5 * stride + slot] = s3.hi;
-    partials[6 * stride + slot] = s3.lo;
-  }
+  const DD s1 = block_sum(sa, scratch), s2 = block_sum(sb, scratch), s3 = block_sum(sr, scratch);
+  if (threadIdx.x == 0) store_partial(partials, gridDim.x, blockIdx.x, m, s1, s2, s3);
 }
 // after the INIT sweeps (k_finalize<X_INIT> has set residual / converged): the APGD state of a new solve
 __global__ void k_apgd_begin(const SolverState* __restrict__ st, ApgdState* __restrict__ as) {
@@ -2308,18 +2255,9 @@ __global__ void __launch_bounds__(kFinalBlock)
                     ApgdState* __restrict__ as, double tol, unsigned max_iters) {
   __shared__ double scratch[2 * kFinalBlock / 64];
   if (st->done) return;
-  double rmax = kLowest;
-  DD sa{0.0, 0.0}, sb{0.0, 0.0}, sr{0.0, 0.0};
-  for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-    if (partials[i] > rmax) rmax = partials[i];
-    dd_add(sa, DD{partials[(size_t)nparts + i], partials[2 * (size_t)nparts + i]});
-    dd_add(sb, DD{partials[3 * (size_t)nparts + i], partials[4 * (size_t)nparts + i]});
-    dd_add(sr, DD{partials[5 * (size_t)nparts + i], partials[6 * (size_t)nparts + i]});
-  }
-  rmax = block_max(rmax, scratch);
-  sa = block_sum(sa, scratch);
-  sb = block_sum(sb, scratch);
-  sr = block_sum(sr, scratch);
+  double rmax;
+  DD sa, sb, sr;
+  reduce_records(nparts, partials, 1, nparts, scratch, rmax, sa, sb, sr);
   if (threadIdx.x != 0) return;
   const double A = dd_value(sa), Bq = dd_value(sb), R = dd_value(sr);
   st->iter += 1;  // every sweep counts
@@ -2336,7 +2274,7 @@ __global__ void __launch_bounds__(kFinalBlock)
   if (res <= tol) {
     st->converged = 1;
     st->done = 1;
-    as->cur = accepted;  // (k_finish_friction_apgd reads the solution from here)
+    as->cur = accepted;  // (cone_solution reads the solution from here)
     return;
   }
   const double th = as->theta;
@@ -2356,10 +2294,19 @@ __global__ void __launch_bounds__(kFinalBlock)
   st->flips += 1;
   if (st->iter >= max_iters) st->done = 1;
 }
+// which buffer holds the latest iterate of a cone solve (as == nullptr: BBPGD, whose pair of buffers ping-pongs)
+__device__ inline int cone_solution(const SolverState* __restrict__ st, const ApgdState* __restrict__ as) {
+  if (st->converged_at_init) return 0;  // converged at init / never iterated
+  if (as != nullptr) return as->cur;
+  // converged at parity q: the sweep wrote the "new" side; otherwise rolled forward
+  const bool odd = st->flips & 1u;
+  return st->converged ? (odd ? 0 : 1) : (odd ? 1 : 0);
+}
+// latest iterate -> caller's p [C][3], g [C][3]
 __global__ void __launch_bounds__(kBlock)
-    k_finish_friction_apgd(size_t C, const SolverState* __restrict__ st, const ApgdState* __restrict__ as, ApgdBufs B,
-                           double* __restrict__ p, double* __restrict__ g) {
-  const double* cur = st->converged_at_init ? B.P[0] : B.P[as->cur];
+    k_finish_cone(size_t C, const SolverState* __restrict__ st, const ApgdState* __restrict__ as, ApgdBufs B,
+                  double* __restrict__ p, double* __restrict__ g) {
+  const double* cur = B.P[cone_solution(st, as)];
   for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < C; c += (size_t)gridDim.x * blockDim.x) {
     const PG s = load_pg(cur, c);
     store3(p, c, s.p);
@@ -4006,19 +3953,21 @@ int mhip_bbpgd_solve_contact_friction(mhip_contact_op_t op, const double* sep, d
   const int G = 8;  // lanes per body of the body sweep, two half-edge chains each
   const unsigned bgrid = grid_exact(op->view.body_count * (size_t)G);
   op->last_stream = s;
-  if (op->view.body_count > 0) k_body_friction<true, 8, 2><<<bgrid, kBlock, 0, s>>>(op->view, st, P0, P1, p, mu);
+  if (op->view.body_count > 0)
+    k_body_cone<BBImpulse<true>, 8, 2><<<bgrid, kBlock, 0, s>>>(op->view, st, BBImpulse<true>{P0, P1, p}, mu);
   k_constraint_friction<true><<<cgrid, kBlock, 0, s>>>(op->view, st, P0, P1, p, sep, mu, parts);
   finalize_sweep<X_INIT>(op, cgrid, config, s);
   MHIP_LAUNCH_CHECK();
   if (int e = poll_loop(op, config->max_iters, s, [&](unsigned) -> int {
         if (op->view.body_count > 0)
-          k_body_friction<false, 8, 2><<<bgrid, kBlock, 0, s>>>(op->view, st, P0, P1, nullptr, mu);
+          k_body_cone<BBImpulse<false>, 8, 2><<<bgrid, kBlock, 0, s>>>(op->view, st, BBImpulse<false>{P0, P1, nullptr},
+                                                                       mu);
         k_constraint_friction<false><<<cgrid, kBlock, 0, s>>>(op->view, st, P0, P1, nullptr, sep, mu, parts);
         finalize_sweep<X_SOLVE>(op, cgrid, config, s);
         return MHIP_SUCCESS;
       }))
     return e;
-  k_finish_friction<<<grid_for(C), kBlock, 0, s>>>(C, st, P0, P1, p, g);
+  k_finish_cone<<<grid_for(C), kBlock, 0, s>>>(C, st, nullptr, ApgdBufs{{P0, P1, nullptr}}, p, g);
   MHIP_LAUNCH_CHECK();
   return solve_result(op, s, result);
 }
@@ -4048,19 +3997,21 @@ int mhip_apgd_solve_contact_friction(mhip_contact_op_t op, const double* sep, do
   const unsigned bgrid = grid_exact(op->view.body_count * (size_t)G);
   op->last_stream = s;
   // p_0, g_0 = N p_0 + q and the initial residual: the INIT sweeps of the BBPGD extension (buffer 0 receives them)
-  if (op->view.body_count > 0) k_body_friction<true, 8, 2><<<bgrid, kBlock, 0, s>>>(op->view, st, B.P[0], B.P[1], p, mu);
+  if (op->view.body_count > 0)
+    k_body_cone<BBImpulse<true>, 8, 2><<<bgrid, kBlock, 0, s>>>(op->view, st, BBImpulse<true>{B.P[0], B.P[1], p}, mu);
   k_constraint_friction<true><<<cgrid, kBlock, 0, s>>>(op->view, st, B.P[0], B.P[1], p, sep, mu, parts);
   finalize_sweep<X_INIT>(op, cgrid, config, s);
   k_apgd_begin<<<1, 1, 0, s>>>(st, as);
   MHIP_LAUNCH_CHECK();
   if (int e = poll_loop(op, config->max_iters, s, [&](unsigned) -> int {
-        if (op->view.body_count > 0) k_body_friction_apgd<8, 2><<<bgrid, kBlock, 0, s>>>(op->view, st, as, B, mu);
+        if (op->view.body_count > 0)
+          k_body_cone<ApgdImpulse, 8, 2><<<bgrid, kBlock, 0, s>>>(op->view, st, ApgdImpulse{as, B}, mu);
         k_constraint_friction_apgd<<<cgrid, kBlock, 0, s>>>(op->view, st, as, B, sep, mu, parts);
         k_apgd_finalize<<<1, kFinalBlock, 0, s>>>((int)cgrid, parts, st, as, config->tol, config->max_iters);
         return MHIP_SUCCESS;
       }))
     return e;
-  k_finish_friction_apgd<<<grid_for(C), kBlock, 0, s>>>(C, st, as, B, p, g);
+  k_finish_cone<<<grid_for(C), kBlock, 0, s>>>(C, st, as, B, p, g);
   MHIP_LAUNCH_CHECK();
   return solve_result(op, s, result);
 }

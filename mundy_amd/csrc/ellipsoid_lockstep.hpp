@@ -23,7 +23,7 @@
 // evaluations, and lanes are in different loops at any moment.)
 //
 // Results are bit-identical to the nested-loop form: the same evaluations at the same points in the same order per
-// lane (the tests build that form as their own checker, tests/cpp/ellipsoid_nested_ref.hip).
+// lane (the tests build that form as their own checker, oracle/ellipsoid_nested_ref.hip).
 #pragma once
 #include "ellipsoid_device.hpp"
 

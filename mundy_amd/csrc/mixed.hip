@@ -174,7 +174,7 @@ __global__ void __launch_bounds__(BLOCK)
 
 // The two minimisation classes (S-E, E-E) in lockstep form (ellipsoid_lockstep.hpp): persistent wavefronts, one
 // lane per pair of the class, objective evaluations converged, lanes refilled from a per-class counter.  Same
-// arithmetic per lane as the nested-loop form the tests build as their checker (tests/cpp/ellipsoid_nested_ref.hip).
+// arithmetic per lane as the nested-loop form the tests build as their checker (oracle/ellipsoid_nested_ref.hip).
 // Two waves per SIMD: 20 KB of LDS history per wave (ellipsoid_lockstep.hpp).
 template <int CLS>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
