@@ -6,6 +6,11 @@
  * as void* (NULL = the null stream).  Entry points that return host scalars synchronise `stream`, exactly where the
  * reference's Kokkos parallel_reduce / deep_copy-to-host calls block; everything else is asynchronous.
  * Handles are not thread safe; use one handle per host thread / stream.
+ * Handle-free entry points that need scratch (the orderings and the key sort, the ellipsoid and mixed distance
+ * routines, the history carry) keep it per host thread, whatever the stream: their calls from ONE host thread are
+ * ordered per scratch -- a call on another stream than the thread's previous call of the same family waits, on the
+ * device, for that call to finish (an event recorded on the previous stream, which must still exist).  Calls on one
+ * stream pay nothing for this; calls from different host threads share nothing.
  *
  * All floating point is fp64; the device code is built with -ffp-contract=off and follows the reference's operation
  * order (right-fold dot, q*(0,v)*inverse(q), tolerance constants, branch structure), so per-element results are
@@ -49,7 +54,7 @@ int mhip_device_info(int* device_count, char* arch_name, size_t arch_name_len);
 /* Plain device memory for hosts that do not bring their own allocator. */
 int mhip_malloc(void** ptr, size_t bytes);
 int mhip_free(void* ptr);
-int mhip_memcpy_h2d(void* dst, const void* src_host, size_t bytes, mhip_stream_t stream);
+int mhip_memcpy_h2d(void* dst, const void* src_host, size_t bytes, mhip_stream_t stream); /* synchronises: src_host is reusable */
 int mhip_memcpy_d2h(void* dst_host, const void* src, size_t bytes, mhip_stream_t stream); /* synchronises */
 int mhip_stream_synchronize(mhip_stream_t stream);
 
@@ -837,7 +842,9 @@ int mhip_gemv(size_t n, const double* A, const double* x, double* y, mhip_stream
  *           W = T/(8 pi mu r^3)), passed in as per-body scalars.
  * ra, rb, mob_rot may all be NULL (translation only, the sphere app).  The handle keeps views of the caller's
  * arrays (they must outlive it) and owns a body->constraint incidence index, so sums run in a fixed order (bitwise
- * reproducible, no atomics).
+ * reproducible, no atomics).  Both create calls synchronise `stream`: the pair list is validated on the device (an
+ * index outside [0, num_bodies) or a self pair is MHIP_ERR_INVALID_ARGUMENT) and its form read back before the index
+ * is laid out.  refresh and everything below up to the solvers is asynchronous.
  * priority [C] or NULL: a locality hint for that index only (never the result beyond summation-order rounding) -- each
  * body lists the contacts with priority < 0 first.  Pass the signed separations: the contacts that overlap at the
  * start of the step are the ones that will carry impulses, and the body sweep of the LCP solver only walks those.

@@ -3,6 +3,7 @@
 // wavefront stay converged and lanes refill from a global counter (ellipsoid_lockstep.hpp).  Compute bound (fp64
 // vector + transcendental), priced against the fp64 vector peak, not HBM.
 #include "ellipsoid_lockstep.hpp"
+#include "scratch_owner.hpp"
 
 namespace mhip {
 
@@ -113,6 +114,7 @@ __global__ void __launch_bounds__(kEllBlock) ELL_OCC
 
 struct EllipsoidScratch {
   DeviceBuffer counter, board;
+  ScratchOwner owner;
 };
 EllipsoidScratch& ellipsoid_scratch() {
   thread_local EllipsoidScratch s;
@@ -121,6 +123,7 @@ EllipsoidScratch& ellipsoid_scratch() {
 // persistent grid: every CU gets its waves, each lane keeps pulling pairs until the counter passes n
 int launch_ellipsoid_lockstep(size_t n, const EEInput& in, const EEOutput& out, hipStream_t s) {
   EllipsoidScratch& es = ellipsoid_scratch();
+  if (int e = es.owner.claim(s)) return e;
   if (int e = es.counter.reserve(64)) return e;
   MHIP_HIP(hipMemsetAsync(es.counter.ptr, 0, 2 * sizeof(unsigned long long), s));
   // the start board: the records of every pair, then the arrival counters (zeroed)
@@ -183,6 +186,7 @@ int mhip_ellipsoid_last_evaluations(unsigned long long* evaluations, mhip_stream
   EllipsoidScratch& es = ellipsoid_scratch();
   *evaluations = 0;
   if (!es.counter.ptr) return MHIP_SUCCESS;
+  if (int e = es.owner.claim(as_stream(stream))) return e;  // the counter was written on the last call's stream
   unsigned long long host[2] = {0, 0};
   MHIP_HIP(hipMemcpyAsync(host, es.counter.ptr, sizeof(host), hipMemcpyDeviceToHost, as_stream(stream)));
   MHIP_HIP(hipStreamSynchronize(as_stream(stream)));

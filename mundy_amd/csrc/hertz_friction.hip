@@ -9,6 +9,7 @@
 // they are not +0.0 already, so a list whose separated pairs stay separated is never written there.
 #include "mhip_internal.hpp"
 #include "force_device.hpp"
+#include "scratch_owner.hpp"
 
 #include <cmath>
 
@@ -139,6 +140,7 @@ __global__ void __launch_bounds__(kBlock)
 
 struct CarryScratch {
   DeviceBuffer keys, keys_tmp, vals, vals_tmp, ws, count;
+  ScratchOwner owner;
 };
 static CarryScratch& carry_scratch() {
   thread_local CarryScratch s;
@@ -205,6 +207,7 @@ int mhip_contact_history_carry(size_t c_old, const int32_t* pairs_old, const dou
   if (c_new == 0) return MHIP_SUCCESS;
   hipStream_t s = as_stream(stream);
   CarryScratch& cs = carry_scratch();
+  if (int e = cs.owner.claim(s)) return e;
   if (int e = cs.count.reserve(2 * sizeof(unsigned long long))) return e;  // (rows carried, disorder flag)
   MHIP_HIP(hipMemsetAsync(cs.count.ptr, 0, 2 * sizeof(unsigned long long), s));
   if (c_old > 0) {

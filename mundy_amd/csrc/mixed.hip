@@ -16,6 +16,7 @@
 
 #include "ellipsoid_lockstep.hpp"
 #include "segment_ellipsoid.hpp"
+#include "scratch_owner.hpp"
 
 // This file is compiled twice.  mixed.hip itself: everything, under the library's -ffp-contract=off (every a*b+c two
 // roundings: results bit-identical to the scalar reference order).  mixed_fma.hip (which only includes this file with
@@ -292,6 +293,7 @@ std::atomic<int> g_mixed_se_route{0};  // 0: S-E in closed form; 1: through the 
 struct MixedScratch {
   DeviceBuffer cls, flags, pos, order, start, scanws, counters, board;
   int32_t* host = nullptr;
+  ScratchOwner owner;
 };
 MixedScratch& mixed_scratch() {
   thread_local MixedScratch s;
@@ -362,6 +364,7 @@ static int contact_mixed_impl(size_t c, const int32_t* pairs, const int32_t* kin
   MHIP_REQUIRE(c < (1u << 31), MHIP_ERR_RUNTIME, "too many pairs");
   hipStream_t s = as_stream(stream);
   MixedScratch& ms = mixed_scratch();
+  if (int e = ms.owner.claim(s)) return e;
   for (DeviceBuffer* b : {&ms.cls, &ms.flags, &ms.pos, &ms.order})
     if (int e = b->reserve((c + 2) * sizeof(int32_t))) return e;
   if (int e = ms.start.reserve(16 * sizeof(int32_t))) return e;
@@ -444,6 +447,7 @@ int mhip_contact_mixed_last_evaluations(unsigned long long evaluations[3], mhip_
   MixedScratch& ms = mixed_scratch();
   evaluations[0] = evaluations[1] = evaluations[2] = 0;
   if (!ms.counters.ptr) return MHIP_SUCCESS;
+  if (int e = ms.owner.claim(as_stream(stream))) return e;  // the counters were written on the last call's stream
   unsigned long long host[8];
   MHIP_HIP(hipMemcpyAsync(host, ms.counters.ptr, sizeof(host), hipMemcpyDeviceToHost, as_stream(stream)));
   MHIP_HIP(hipStreamSynchronize(as_stream(stream)));

@@ -5,6 +5,7 @@
 // non-negative lattice points.  The sort is a counting sort over codes (histogram, scan, scatter) followed by a
 // per-code tie-break by body index, so the permutation is deterministic.  Integer work: HBM/atomic bound.
 #include "geom_device.hpp"
+#include "scratch_owner.hpp"
 
 namespace mhip {
 
@@ -149,6 +150,7 @@ __global__ void __launch_bounds__(kBlock) k_shift_image(size_t n, Triclinic pm, 
 
 struct ReorderScratch {
   DeviceBuffer code, hist, ptr, scanws;
+  ScratchOwner owner;
 };
 ReorderScratch& reorder_scratch() {
   thread_local ReorderScratch s;
@@ -175,6 +177,7 @@ int mhip_morton_order(size_t n, const double* center, const double* lo, double c
   while (bits < 8 && (size_t(1) << (3 * (bits + 1))) <= 8 * n) ++bits;
   const size_t ncodes = size_t(1) << (3 * bits);
   ReorderScratch& rs = reorder_scratch();
+  if (int e = rs.owner.claim(s)) return e;
   if (int e = rs.code.reserve(n * sizeof(unsigned))) return e;
   if (int e = rs.hist.reserve((ncodes + 2) * sizeof(int32_t))) return e;
   if (int e = rs.ptr.reserve((ncodes + 2) * sizeof(int32_t))) return e;
@@ -206,6 +209,7 @@ int mhip_curve_order(size_t n, const double* center, const double* lo, const dou
   hipStream_t s = as_stream(stream);
   const size_t ncodes = size_t(1) << (3 * level);
   ReorderScratch& rs = reorder_scratch();
+  if (int e = rs.owner.claim(s)) return e;
   if (int e = rs.code.reserve(n * sizeof(unsigned))) return e;
   if (int e = rs.hist.reserve((ncodes + 2) * sizeof(int32_t))) return e;
   if (int e = rs.ptr.reserve((ncodes + 2) * sizeof(int32_t))) return e;
@@ -235,6 +239,7 @@ int mhip_curve_keys(size_t n, const double* center, const double* lo, const doub
   hipStream_t s = as_stream(stream);
   const size_t ncodes = size_t(1) << (3 * level);
   ReorderScratch& rs = reorder_scratch();
+  if (int e = rs.owner.claim(s)) return e;
   if (int e = rs.hist.reserve((ncodes + 2) * sizeof(int32_t))) return e;  // the counting kernel also fills a histogram
   MHIP_HIP(hipMemsetAsync(rs.hist.ptr, 0, (ncodes + 1) * sizeof(int32_t), s));
   const V3 l{lo[0], lo[1], lo[2]}, span{hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
@@ -245,6 +250,7 @@ int mhip_curve_keys(size_t n, const double* center, const double* lo, const doub
 
 struct SortScratch {
   DeviceBuffer keys, keys_tmp, vals, vals_tmp, ws;
+  ScratchOwner owner;
 };
 static SortScratch& sort_scratch() {
   thread_local SortScratch s;
@@ -261,6 +267,7 @@ int mhip_sort_by_key_u64(size_t n, const uint64_t* keys, int32_t* perm, mhip_str
   if (n == 0) return MHIP_SUCCESS;
   hipStream_t s = as_stream(stream);
   SortScratch& ss = sort_scratch();
+  if (int e = ss.owner.claim(s)) return e;
   if (int e = ss.keys.reserve(n * sizeof(unsigned long long))) return e;
   if (int e = ss.keys_tmp.reserve(n * sizeof(unsigned long long))) return e;
   if (int e = ss.vals_tmp.reserve(n * sizeof(unsigned))) return e;
