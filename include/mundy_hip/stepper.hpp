@@ -15,6 +15,9 @@
 // mode: the largest overlap; growth mode: the birth count and the corner-test flag).
 // FilamentStepper is the elastic half of the sperm apps' step (CollidingOverdampedFrictionalSperm.cpp:1999-2027):
 //   advance -> edge pass + node pass (centerline-twist forces and twist torques at x(t + dt)) -> node drag
+// SphereChainStepper is the bead-spring chain step of the chromatin apps (NgpHP1.cpp:3802-3990) on spheres, in four
+// stages a host program puts its own force and velocity terms between:
+//   neighbour list -> spring forces -> U_ext = M F + U_brown -> contacts, LCP on sep + dt D^T U_ext, U_ext + M D lambda
 #pragma once
 #include <chrono>
 #include <cmath>
@@ -48,7 +51,22 @@ struct StepStats {
   size_t num_carried = 0;    // frictional Hertz mode: history rows carried to a rebuilt list this step
   double max_stretch = 0.0;              // FilamentStepper: the largest |l - l0| / l0 over the edges
   double max_curvature_deviation = 0.0;  // FilamentStepper: the largest component of |kappa - kappa_rest|
+  double max_spring_length = 0.0;        // SphereChainStepper: the longest spring at the start of the step
+  int springs_overstretched = 0;         // SphereChainStepper: springs past their limit (FENE: L >= r_max)
 };
+
+/// the LCP of a contact operator with right-hand side q: fused BBPGD from lambda = 0 (NgpLcp.cpp:890-891); x receives
+/// the multipliers, g, x_tmp and g_tmp [C] are work vectors
+inline mhip_solve_result solve_lcp_from_zero(ContactOperator& op, size_t C, const double* q,
+                                             const convex::PGDConfig<double>& cfg, double* x, double* g, double* x_tmp,
+                                             double* g_tmp) {
+  check(mhip_fill(C, x, 0.0, nullptr));
+  const mhip_space lcp{MHIP_SPACE_LOWER_BOUND, 0.0, 0.0};
+  const mhip_pgd_config pc{cfg.max_iters, cfg.tol, MHIP_RESIDUAL_PROJECTED_DIFF};
+  mhip_solve_result res{};
+  check(mhip_bbpgd_solve_contact(op.handle(), q, &lcp, &pc, x, g, x_tmp, g_tmp, &res, nullptr));
+  return res;
+}
 
 /// grow-only storage that keeps its first `live` doubles: reallocates with headroom only when `need` does not fit
 inline void grow_keep(DeviceVector& a, size_t need, size_t live) {
@@ -299,16 +317,12 @@ class SpherocylinderStepper {
     renumber_ = DeviceArray<int32_t>(inv);
     have_renumber_ = true;
   }
-  /// the LCP: fused BBPGD from lambda = 0 (NgpLcp.cpp:890-891)
+  /// the LCP on the separations
   void solve(ContactOperator& op, size_t C, const double* sep, StepStats& st) {
     double *x = workspace(lambda_, C), *g = workspace(w_g_, C), *x_tmp = workspace(w_xt_, C),
            *g_tmp = workspace(w_gt_, C);
-    check(mhip_fill(C, x, 0.0, nullptr));
     num_lambda_ = C;
-    const mhip_space lcp{MHIP_SPACE_LOWER_BOUND, 0.0, 0.0};
-    const mhip_pgd_config pc{cfg_.max_iters, cfg_.tol, MHIP_RESIDUAL_PROJECTED_DIFF};
-    mhip_solve_result res{};
-    check(mhip_bbpgd_solve_contact(op.handle(), sep, &lcp, &pc, x, g, x_tmp, g_tmp, &res, nullptr));
+    const mhip_solve_result res = solve_lcp_from_zero(op, C, sep, cfg_, x, g, x_tmp, g_tmp);
     st.num_iters = res.num_iters;
     st.residual = res.residual;
     st.converged = res.converged != 0;
@@ -663,6 +677,121 @@ class DistributedSpherocylinderStepper {
   DeviceArray<unsigned char> w_counted_;
   size_t num_lambda_ = 0, n_int_ = 0, num_contacts_ = 0;
   mhip_ghost_layout lay_{};  // of the last rebuild; its lists live in the communicator until the next plan
+  mesh::GenNeighborLinks links_;
+  std::unique_ptr<ContactOperator> op_;
+};
+
+/// The bead-spring chain step of the chromatin / HP1 family (NgpHP1.cpp:3802-3990) on spheres in free space, with the
+/// contact LCP: springs, Brownian noise, contacts, Euler update.  The step is four stages, called in this order; a host
+/// program adds its own terms to force() and u_ext() between them, where the reference's step has them
+/// (HP1.cpp:4733-4803):
+///   neighbors() -> forces() -> external_velocity() -> resolve()
+/// step() is the four in a row.  The only host reads of a step are the neighbour list's rebuild test, the solver's
+/// convergence polls and, at the end of every resolve(), two small blocking downloads: the longest spring and the
+/// overstretched count, whether the caller looks at them or not.  They are what resolve() waits for the step with.
+class SphereChainStepper {
+ public:
+  /// host arrays: center [n][3], radius [n], mob_trans [n]; spring_pairs [m][2] with one stiffness and one rest length
+  /// (Hookean) or r_max (FENE) for all, spring_type MHIP_SPRING_*; keys [n] of the noise or empty = the body indices
+  /// (the counters start at 0)
+  SphereChainStepper(const std::vector<double>& center, const std::vector<double>& radius,
+                     const std::vector<double>& mob_trans, double dt, double search_buffer,
+                     convex::PGDConfig<double> cfg, const std::vector<int32_t>& spring_pairs, int spring_type,
+                     double spring_k, double spring_r, double kt, const std::vector<std::uint64_t>& keys = {})
+      : n_(radius.size()), dt_(dt), kt_(kt), cfg_(cfg), center_(center), radius_(radius), mob_t_(mob_trans),
+        aabb_(6 * n_), force_(3 * n_), u_ext_(6 * n_), vel_(6 * n_), counters_(std::vector<std::uint64_t>(n_, 0)),
+        springs_(n_, spring_pairs, spring_type, {}, spring_k, {}, spring_r) {
+    if (!keys.empty() && keys.size() != n_) throw std::invalid_argument("SphereChainStepper: one key per body");
+    std::vector<std::uint64_t> k(keys);
+    if (k.empty())
+      for (size_t i = 0; i < n_; ++i) k.push_back(i);
+    keys_ = DeviceArray<std::uint64_t>(k);
+    links_.set_search_buffer(search_buffer).set_search_kind(MHIP_SEARCH_AABB).concretize();
+  }
+
+  /// the neighbour list by the rebuild rule; returns whether it was rebuilt (pairs() changes only then)
+  bool neighbors() {
+    check(mhip_compute_aabb_spheres(n_, center_.data(), radius_.data(), aabb_.data(), nullptr));
+    rebuilt_ = links_.generate(n_, aabb_.data(), center_.data(), radius_.data(), nullptr, false);
+    if (rebuilt_) links_.links_into(pairs_);
+    return rebuilt_;
+  }
+  /// the spring force into force() [n][3]; returns it for the caller to accumulate further terms into
+  double* forces() {
+    springs_.compute_forces(center_.data(), force_.data());
+    return force_.data();
+  }
+  /// U_ext = M F + U_brown into u_ext() [n][6] (the counters advance); returns it for the caller to add to
+  double* external_velocity() {
+    check(mhip_drag_velocity(n_, mob_t_.data(), force_.data(), u_ext_.data(), nullptr));
+    compute_brownian_velocity(n_, keys_.data(), counters_.data(), kt_, dt_, mob_t_.data(), u_ext_.data());
+    return u_ext_.data();
+  }
+  /// contacts -> operator (built after a rebuild, otherwise refreshed) -> q = sep + dt D^T U_ext (NgpHP1.cpp:1488-1531)
+  /// -> BBPGD from lambda = 0 -> U = U_ext + M D lambda -> Euler update
+  StepStats resolve(bool integrate = true) {
+    StepStats st;
+    st.rebuilt = rebuilt_;
+    const size_t C = links_.num_links(), cap = C ? C : 1;  // no workspace is null without contacts
+    st.num_contacts = C;
+    double *sep = workspace(w_sep_, cap), *normal = workspace(w_normal_, 3 * cap), *q = workspace(w_q_, cap),
+           *x = workspace(lambda_, cap), *g = workspace(w_g_, cap), *x_tmp = workspace(w_xt_, cap),
+           *g_tmp = workspace(w_gt_, cap);
+    check(mhip_contact_spheres(C, pairs_.data(), center_.data(), radius_.data(), nullptr, sep, normal, nullptr));
+    if (rebuilt_ || !op_)
+      op_.reset(new ContactOperator(C, n_, pairs_.data(), normal, nullptr, nullptr, mob_t_.data(), nullptr, dt_,
+                                    nullptr, /*priority=*/sep));
+    else
+      op_->refresh(normal, nullptr, nullptr);
+    rebuilt_ = false;
+    check(mhip_contact_op_constraint_rate(op_->handle(), u_ext_.data(), q, nullptr));
+    check(mhip_axpby(C, 1.0, sep, dt_, q, nullptr));
+    num_lambda_ = C;
+    const mhip_solve_result res = solve_lcp_from_zero(*op_, C, q, cfg_, x, g, x_tmp, g_tmp);
+    st.num_iters = res.num_iters;
+    st.residual = res.residual;
+    st.converged = res.converged != 0;
+    check(mhip_deep_copy(6 * n_, vel_.data(), op_->compute_generalized_velocity(), nullptr));
+    check(mhip_axpby(6 * n_, 1.0, u_ext_.data(), 1.0, vel_.data(), nullptr));
+    if (integrate) check(mhip_integrate_euler(n_, dt_, vel_.data(), center_.data(), nullptr, nullptr));
+    st.max_spring_length = springs_.max_length();  // these two reads wait for the step
+    st.springs_overstretched = springs_.overstretched();
+    ++step_index_;
+    return st;
+  }
+  /// the plain chain step
+  StepStats step(bool integrate = true) {
+    neighbors();
+    forces();
+    external_velocity();
+    return resolve(integrate);
+  }
+
+  size_t num_bodies() const { return n_; }
+  const DeviceVector& center() const { return center_; }
+  const DeviceVector& radius() const { return radius_; }
+  /// device pointers: the force [n][3] and U_ext [n][6] the stages work on, and U [n][6] of the last resolve()
+  double* force() { return force_.data(); }
+  double* u_ext() { return u_ext_.data(); }
+  const double* velocity() const { return vel_.data(); }
+  /// multipliers of the last step: the first num_lambda() entries (the buffer only ever grows)
+  const DeviceVector& lambda() const { return lambda_; }
+  size_t num_lambda() const { return num_lambda_; }
+  const DeviceArray<int32_t>& pairs() const { return pairs_; }
+  const Springs& springs() const { return springs_; }
+  size_t step_index() const { return step_index_; }
+
+ private:
+  size_t n_;
+  double dt_, kt_;
+  convex::PGDConfig<double> cfg_;
+  DeviceVector center_, radius_, mob_t_, aabb_, force_, u_ext_, vel_, lambda_;
+  DeviceVector w_sep_, w_normal_, w_q_, w_g_, w_xt_, w_gt_;  // per-step workspaces (grow-only)
+  DeviceArray<std::uint64_t> keys_, counters_;
+  Springs springs_;
+  size_t num_lambda_ = 0, step_index_ = 0;
+  bool rebuilt_ = false;
+  DeviceArray<int32_t> pairs_;
   mesh::GenNeighborLinks links_;
   std::unique_ptr<ContactOperator> op_;
 };

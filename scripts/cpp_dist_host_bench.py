@@ -7,7 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from mundy_amd import distributed as D, synth
-from test_adapter_cpp import _build_dist_app
+from cpp_apps import HIP_HOST_FLAGS, build_app
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
 b = synth.spherocylinders(n, seed=1234)
 order = D.hilbert_order(b["center"], 0.0, b["box"], level=7)
@@ -19,5 +19,5 @@ with open(path, "wb") as f:
     f.write(np.uint64(n).tobytes())
     for a in (c, q, r, ln, mt, mr):
         f.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
-p = subprocess.run([_build_dist_app(), path, "3", "0", "1", d], capture_output=True, text=True)
+p = subprocess.run([build_app("rod_dist_app", extra=HIP_HOST_FLAGS), path, "3", "0", "1", d], capture_output=True, text=True)
 print(p.stdout, p.stderr[-2000:])

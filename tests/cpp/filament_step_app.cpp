@@ -8,36 +8,10 @@
 //   radius[N] rest_curvature[3N] arclength[N] phase[F]
 // Prints the two statistics of every step as hexadecimal floats and bit-level checksums of the final state, so the test
 // can compare the whole trajectory with the Python stepper's.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
+#include "app_util.hpp"
 #include "mundy_hip/stepper.hpp"
 
 using namespace mundy_hip;
-
-template <class T>
-static std::vector<T> read_array(std::FILE* f, size_t count) {
-  std::vector<T> v(count);
-  if (count && std::fread(v.data(), sizeof(T), count, f) != count) {
-    std::fprintf(stderr, "short read\n");
-    std::exit(2);
-  }
-  return v;
-}
-static unsigned long long checksum(const double* dev, size_t count) {  // order-sensitive FNV-1a over the bit patterns
-  std::vector<double> v(count);
-  check(mhip_memcpy_d2h(v.data(), dev, count * sizeof(double), nullptr));
-  unsigned long long h = 1469598103934665603ull;
-  for (double d : v) {
-    unsigned long long b = 0;
-    std::memcpy(&b, &d, sizeof d);
-    h = (h ^ b) * 1099511628211ull;
-  }
-  return h;
-}
 
 int main(int argc, char** argv) {
   if (argc < 14) {
@@ -79,10 +53,10 @@ int main(int argc, char** argv) {
     std::printf("STEP %d max_stretch %a max_curvature_deviation %a\n", s, st.max_stretch, st.max_curvature_deviation);
   }
   const mhip_filament_fields fl = stepper.fields();
-  std::printf("CHECKSUM center %016llx\n", checksum(fl.center, 3 * N));
-  std::printf("CHECKSUM twist %016llx\n", checksum(fl.twist, N));
-  std::printf("CHECKSUM velocity %016llx\n", checksum(fl.velocity, 3 * N));
-  std::printf("CHECKSUM twist_velocity %016llx\n", checksum(fl.twist_velocity, N));
-  std::printf("CHECKSUM edge_orientation %016llx\n", checksum(fl.edge_orientation, 4 * N));
+  std::printf("CHECKSUM center %016llx\n", checksum_device(fl.center, 3 * N));
+  std::printf("CHECKSUM twist %016llx\n", checksum_device(fl.twist, N));
+  std::printf("CHECKSUM velocity %016llx\n", checksum_device(fl.velocity, 3 * N));
+  std::printf("CHECKSUM twist_velocity %016llx\n", checksum_device(fl.twist_velocity, N));
+  std::printf("CHECKSUM edge_orientation %016llx\n", checksum_device(fl.edge_orientation, 4 * N));
   return 0;
 }

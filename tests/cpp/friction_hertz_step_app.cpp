@@ -9,34 +9,10 @@
 //   reorder_cell <= 0: no Z-order reorder; otherwise one before step <reorder_at_step>
 // Prints one line per step with bit-level checksums of the centres, the linker forces and the tangential displacements,
 // so the test can compare the whole trajectory with the Python driver's.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
+#include "app_util.hpp"
 #include "mundy_hip/stepper.hpp"
 
 using namespace mundy_hip;
-
-static std::vector<double> read_doubles(std::FILE* f, size_t count) {
-  std::vector<double> v(count);
-  if (std::fread(v.data(), sizeof(double), count, f) != count) {
-    std::fprintf(stderr, "short read\n");
-    std::exit(2);
-  }
-  return v;
-}
-// order-sensitive FNV-1a over the bit patterns of the first `count` doubles
-static unsigned long long checksum(const std::vector<double>& v, size_t count) {
-  unsigned long long h = 1469598103934665603ull;
-  for (size_t k = 0; k < count; ++k) {
-    unsigned long long b;
-    std::memcpy(&b, &v[k], sizeof b);
-    h = (h ^ b) * 1099511628211ull;
-  }
-  return h;
-}
 
 int main(int argc, char** argv) {
   if (argc < 13) {
@@ -53,8 +29,9 @@ int main(int argc, char** argv) {
   }
   std::uint64_t n = 0;
   if (std::fread(&n, sizeof n, 1, f) != 1) return 2;
-  const auto center = read_doubles(f, 3 * n), quat = read_doubles(f, 4 * n), radius = read_doubles(f, n),
-             length = read_doubles(f, n), mob_t = read_doubles(f, n), mob_r = read_doubles(f, n);
+  const auto center = read_array<double>(f, 3 * n), quat = read_array<double>(f, 4 * n),
+             radius = read_array<double>(f, n), length = read_array<double>(f, n), mob_t = read_array<double>(f, n),
+             mob_r = read_array<double>(f, n);
   std::fclose(f);
   const int steps = std::atoi(argv[2]);
   const double cell = std::atof(argv[3]);

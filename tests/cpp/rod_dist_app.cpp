@@ -12,36 +12,15 @@
 #include <hip/hip_runtime_api.h>
 #include <unistd.h>
 
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <vector>
 
+#include "app_util.hpp"
 #include "mundy_hip/stepper.hpp"
 
 using namespace mundy_hip;
 
-static std::vector<double> read_doubles(std::FILE* f, size_t count) {
-  std::vector<double> v(count);
-  if (std::fread(v.data(), sizeof(double), count, f) != count) {
-    std::fprintf(stderr, "short read\n");
-    std::exit(2);
-  }
-  return v;
-}
 static std::vector<double> rows(const std::vector<double>& a, size_t width, size_t first, size_t count) {
   return std::vector<double>(a.begin() + width * first, a.begin() + width * (first + count));
-}
-static unsigned long long checksum(const std::vector<double>& v) {  // order-sensitive FNV-1a over the bit patterns
-  unsigned long long h = 1469598103934665603ull;
-  for (double d : v) {
-    unsigned long long b;
-    std::memcpy(&b, &d, sizeof b);
-    h = (h ^ b) * 1099511628211ull;
-  }
-  return h;
 }
 
 int main(int argc, char** argv) {
@@ -61,8 +40,9 @@ int main(int argc, char** argv) {
   }
   std::uint64_t n = 0;
   if (std::fread(&n, sizeof n, 1, f) != 1) return 2;
-  const auto center = read_doubles(f, 3 * n), quat = read_doubles(f, 4 * n), radius = read_doubles(f, n),
-             length = read_doubles(f, n), mob_t = read_doubles(f, n), mob_r = read_doubles(f, n);
+  const auto center = read_array<double>(f, 3 * n), quat = read_array<double>(f, 4 * n),
+             radius = read_array<double>(f, n), length = read_array<double>(f, n), mob_t = read_array<double>(f, n),
+             mob_r = read_array<double>(f, n);
   std::fclose(f);
 
   int ndev = 0;

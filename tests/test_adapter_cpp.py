@@ -5,60 +5,14 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "test_adapter")
-
-
-def _build():
-    from mundy_amd import build
-    lib = build.build()
-    libdir = os.path.dirname(lib)
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", os.path.join(ROOT, "tests", "cpp", "test_adapter.cpp"),
-           "-I", os.path.join(ROOT, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-           "-Wl,-rpath-link,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", EXE]
-    subprocess.check_call(cmd)
-    return EXE
-
-
-def _build_app():
-    from mundy_amd import build
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(ROOT, "tests", "cpp", "ngp_lcp_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", os.path.join(ROOT, "tests", "cpp", "ngp_lcp_app.cpp"),
-                           "-I", os.path.join(ROOT, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-                           "-Wl,-rpath-link,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    return exe
-
-
-def _build_rod_app():
-    from mundy_amd import build
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(ROOT, "tests", "cpp", "rod_step_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", os.path.join(ROOT, "tests", "cpp", "rod_step_app.cpp"),
-                           "-I", os.path.join(ROOT, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-                           "-Wl,-rpath-link,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    return exe
-
-
-def _build_dist_app():
-    from mundy_amd import build
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(ROOT, "tests", "cpp", "rod_dist_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__",
-                           os.path.join(ROOT, "tests", "cpp", "rod_dist_app.cpp"),
-                           "-I", os.path.join(ROOT, "include"), "-I/opt/rocm/include", "-L", libdir, "-lmundy_hip",
-                           "-Wl,-rpath," + libdir, "-Wl,-rpath-link,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
-    return exe
+from cpp_apps import HIP_HOST_FLAGS, build_app, fnv1a_bits as checksum
 
 
 def test_adapter_header_compiles_and_links():
-    assert os.path.exists(_build())
-    assert os.path.exists(_build_app())
-    assert os.path.exists(_build_rod_app())
-    assert os.path.exists(_build_dist_app())
+    assert os.path.exists(build_app("test_adapter"))
+    assert os.path.exists(build_app("ngp_lcp_app"))
+    assert os.path.exists(build_app("rod_step_app"))
+    assert os.path.exists(build_app("rod_dist_app", extra=HIP_HOST_FLAGS))
 
 
 @pytest.mark.gpu
@@ -79,7 +33,7 @@ def test_cpp_distributed_stepper_over_rccl(tmp_path):
         f.write(np.uint64(n).tobytes())
         for a in (c, q, r, ln, mt, mr):
             f.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
-    exe = _build_dist_app()
+    exe = build_app("rod_dist_app", extra=HIP_HOST_FLAGS)
     p = subprocess.run([exe, str(inp), "3", "0", "1", str(tmp_path)], capture_output=True, text=True, timeout=600)
     print(p.stdout[-3000:], p.stderr[-2000:])
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
@@ -94,11 +48,6 @@ def test_cpp_distributed_stepper_over_rccl(tmp_path):
         assert float(steps[k][9]) == s.residual and int(steps[k][11]) == int(s.converged)
         assert int(steps[k][13]) == 0 and int(steps[k][15]) == s.num_contacts      # one rank: no ghosts, all interior
 
-    def checksum(a):
-        h = 1469598103934665603
-        for v in np.ascontiguousarray(a).view(np.uint64).ravel().tolist():
-            h = ((h ^ v) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-        return "%016x" % h
     line = [ln_ for ln_ in p.stdout.splitlines() if ln_.startswith("CHECKSUM")][0].split()
     assert line[4] == checksum(st.center.cpu().numpy()) and line[6] == checksum(st.quat.cpu().numpy())
 
@@ -161,7 +110,7 @@ def test_cpp_rod_stepper_reproduces_the_python_driver(tmp_path, periodic):
         f.write(np.uint64(n).tobytes())
         for a in (b["center"], b["quat"], b["radius"], b["length"], mt, mr):
             f.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
-    exe = _build_rod_app()
+    exe = build_app("rod_step_app")
     box = [float(b["box"])] * 3 if periodic else None   # periodic search, nearest-image contacts, wrap_rigid
     p = subprocess.run([exe, str(inp), "3", "3.0"] + (["%.17g" % b["box"]] if periodic else []), capture_output=True,
                        text=True, timeout=600)
@@ -180,11 +129,6 @@ def test_cpp_rod_stepper_reproduces_the_python_driver(tmp_path, periodic):
         assert int(steps[k][3]) == s.num_contacts and int(steps[k][5]) == s.num_iters
         assert float(steps[k][7]) == s.residual and int(steps[k][9]) == int(s.converged)
 
-    def checksum(a):
-        h = 1469598103934665603
-        for v in np.ascontiguousarray(a).view(np.uint64).ravel().tolist():
-            h = ((h ^ v) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-        return "%016x" % h
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("CHECKSUM")][0].split()
     assert line[2] == checksum(st.center.cpu().numpy()) and line[4] == checksum(st.quat.cpu().numpy())
 
@@ -192,7 +136,7 @@ def test_cpp_rod_stepper_reproduces_the_python_driver(tmp_path, periodic):
 @pytest.mark.gpu
 def test_cpp_host_step_loop_like_the_reference_app():
     # the reference's scrap/lcp_spheres/NgpLcp.cpp main(), as a C++ host loop over the C ABI: 3 steps of 20k spheres at 8 % volume fraction
-    exe = _build_app()
+    exe = build_app("ngp_lcp_app")
     p = subprocess.run([exe, "100", "20000", "3"], capture_output=True, text=True, timeout=300)
     print(p.stdout[-3000:], p.stderr[-2000:])
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-2000:]
@@ -202,7 +146,7 @@ def test_cpp_host_step_loop_like_the_reference_app():
 
 @pytest.mark.gpu
 def test_adapter_reference_tests_on_gpu():
-    exe = _build()
+    exe = build_app("test_adapter")
     p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     print(p.stdout[-4000:], p.stderr[-2000:])
     assert p.returncode == 0, p.stdout[-4000:]

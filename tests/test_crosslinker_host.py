@@ -3,7 +3,6 @@ the stepper and of mhip_crosslinkers_create (before any HIP call), the new entry
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,7 +10,6 @@ import torch
 
 import crosslinker_model as xm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PAR = dict(kind="hookean", k=5.0, r=0.5, A=2.0, k_off=3.0, kt=1.0, capture_radius=1.0, dt=0.05)
 
 
@@ -305,12 +303,6 @@ def test_null_handles_and_pointers_are_refused(lib):
 
 
 def test_crosslinker_step_app_compiles_and_links():
-    from mundy_amd import build
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(ROOT, "tests", "cpp", "crosslinker_step_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror",
-                           os.path.join(ROOT, "tests", "cpp", "crosslinker_step_app.cpp"), "-I",
-                           os.path.join(ROOT, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-                           "-Wl,-rpath-link,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
+    from cpp_apps import build_app
+    exe = build_app("crosslinker_step_app")
     assert os.path.exists(exe)

@@ -256,8 +256,7 @@ def test_cpp_set_entity_ids_refuses_ids_outside_the_composed_key(tmp_path):
     # DistributedSpherocylinderStepper::set_entity_ids runs the same check on the host (check_entity_ids) before it
     # copies anything to the device
     import subprocess
-    from mundy_amd import build
-    libdir = os.path.dirname(build.build())
+    from cpp_apps import compile_cpp
     src = tmp_path / "ids.cpp"
     src.write_text(r'''
 #include <cmath>
@@ -280,9 +279,6 @@ int main() {
   return 0;
 }
 ''')
-    exe = str(tmp_path / "ids")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", str(src), "-I", os.path.join(ROOT, "include"),
-                           "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath-link,/opt/rocm/lib",
-                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = compile_cpp(src, tmp_path / "ids")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=60, check=True).stdout.strip()
     assert out == "11111111 0 0", out

@@ -248,14 +248,6 @@ def test_step_stats_gain_num_sliding_with_default_zero():
 def test_friction_hertz_step_app_compiles_and_links():
     # the C++ frictional stepper (include/mundy_hip/stepper.hpp, set_hertz_friction) and its driver build on the CPU box
     import os
-    import subprocess
-    from mundy_amd import build
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(root, "tests", "cpp", "friction_hertz_step_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror",
-                           os.path.join(root, "tests", "cpp", "friction_hertz_step_app.cpp"), "-I",
-                           os.path.join(root, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-                           "-Wl,-rpath-link,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
+    from cpp_apps import build_app
+    exe = build_app("friction_hertz_step_app")
     assert os.path.exists(exe)

@@ -18,7 +18,6 @@ from gpu_util import (PAST_FULL_GRID, STAT_POSITIONS, all_pos_zero, assert_bits_
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MASK63 = (1 << 63) - 1
 
 
@@ -446,7 +445,8 @@ def test_hertz_chain_velocity_is_external_plus_contact():
 
 
 def test_chain_step_app_matches_python():
-    from mundy_amd import build, pipeline, synth
+    from cpp_apps import build_app, fnv1a
+    from mundy_amd import pipeline, synth
     d = synth.chains(2, 1000, seed=8)
     n = d["center"].shape[0]
     mt, _ = synth.dry_mobility(d["radius"], viscosity=d["viscosity"])
@@ -459,11 +459,7 @@ def test_chain_step_app_matches_python():
         lines.append("STEP %d contacts %d iterations %d max_spring_length %.17g" % (k, s.num_contacts, s.num_iters,
                                                                                      s.max_spring_length))
     import tempfile
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(ROOT, "tests", "cpp", "chain_step_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", os.path.join(ROOT, "tests", "cpp", "chain_step_app.cpp"), "-I",
-                           os.path.join(ROOT, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_app("chain_step_app")
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "in.bin")
         with open(path, "wb") as f:
@@ -478,10 +474,7 @@ def test_chain_step_app_matches_python():
     got = [ln for ln in out.stdout.splitlines() if ln.startswith("STEP")]
     assert [" ".join(g.split()[:8]) for g in got] == lines
     cs = [ln for ln in out.stdout.splitlines() if ln.startswith("CHECKSUM")][0].split()
-    h = 1469598103934665603
-    for b in host(st.center).reshape(-1).view(np.uint64).tolist():
-        h = ((h ^ b) * 1099511628211) & (2 ** 64 - 1)
-    assert cs[2] == "%016x" % h
+    assert cs[2] == fnv1a(host(st.center).reshape(-1).view(np.uint64).tolist())
 
 
 def test_one_step_at_full_size():

@@ -14,7 +14,6 @@ from gpu_util import (PAST_FULL_GRID, STAT_POSITIONS, all_pos_zero, assert_bits_
                       renumberings, star_and_random_graph, star_graph)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _i64(a):
@@ -506,7 +505,8 @@ def test_crosslinkers_alone_make_a_chain_step():
 
 # ---- 6. the C++ driver -------------------------------------------------------------------------------------------------
 def test_crosslinker_step_app_matches_python():
-    from mundy_amd import build, pipeline, synth
+    from cpp_apps import build_app, checksums, fnv1a as fnv
+    from mundy_amd import pipeline, synth
     d = synth.chains(2, 1000, seed=8)
     n = d["center"].shape[0]
     mt, _ = synth.dry_mobility(d["radius"], viscosity=d["viscosity"])
@@ -523,11 +523,7 @@ def test_crosslinker_step_app_matches_python():
             k, s.num_contacts, s.num_iters, s.crosslinker_bound, s.crosslinker_binds, s.crosslinker_unbinds))
     assert s.crosslinker_bound > 0 and sum(int(ln.split()[-1]) for ln in lines) > 0
     import tempfile
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(ROOT, "tests", "cpp", "crosslinker_step_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", os.path.join(ROOT, "tests", "cpp", "crosslinker_step_app.cpp"),
-                           "-I", os.path.join(ROOT, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_app("crosslinker_step_app")
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "in.bin")
         with open(path, "wb") as f:
@@ -545,13 +541,7 @@ def test_crosslinker_step_app_matches_python():
     assert out.returncode == 0, out.stderr
     got = [ln for ln in out.stdout.splitlines() if ln.startswith("STEP")]
     assert [" ".join(g.split()[:12]) for g in got] == lines
-
-    def fnv(words):
-        h = 1469598103934665603
-        for b in words:
-            h = ((h ^ b) * 1099511628211) & (2 ** 64 - 1)
-        return "%016x" % h
-    cs = {ln.split()[1]: ln.split()[2] for ln in out.stdout.splitlines() if ln.startswith("CHECKSUM")}
+    cs = checksums(out.stdout)
     assert cs["center"] == fnv(host(st.center).reshape(-1).view(np.uint64).tolist())
     assert cs["right"] == fnv(host(st.crosslinker_state()[1]).astype(np.int64).tolist())
 

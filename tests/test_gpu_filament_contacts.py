@@ -18,7 +18,6 @@ from gpu_util import PAST_FULL_GRID, STAT_POSITIONS, all_pos_zero, assert_bits_e
 from test_gpu_filaments import BORDER_COUNTS, COMPARED, STATE, device_kwargs, make_case, new_device, new_model, params
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 MATERIAL = dict(youngs_modulus=200.0, poisson_ratio=0.3)
 LINKER_FIELDS = ("sep", "tang_disp", "force", "share")
@@ -467,7 +466,7 @@ def test_pressed_filaments_rest_at_the_hertz_overlap():
 
 # ---- 8. the C++ driver ----------------------------------------------------------------------------------------------------
 def test_filament_contact_app_matches_python():
-    from mundy_amd import build
+    from cpp_apps import build_app, checksums, fnv1a as fnv
     case = stepper_case(False)
     prm = fm.Params(**dict(params(wave=True).__dict__, eta=WAVE_CASE["eta"]))
     contacts = dict(skin=WAVE_CASE["skin"], mu=WAVE_CASE["mu"], damping=(0.1, 0.05), **MATERIAL)
@@ -475,11 +474,7 @@ def test_filament_contact_app_matches_python():
     dt, steps = WAVE_CASE["dt"], 20
     lines = [st.step(dt) for _ in range(steps)]
     assert sum(s.num_sliding for s in lines) > 0 and sum(s.rebuilt for s in lines) >= 2
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(ROOT, "tests", "cpp", "filament_contact_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", os.path.join(ROOT, "tests", "cpp", "filament_contact_app.cpp"),
-                           "-I", os.path.join(ROOT, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_app("filament_contact_app")
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "in.bin")
         with open(path, "wb") as f:
@@ -499,13 +494,7 @@ def test_filament_contact_app_matches_python():
                           np.array([s.max_stretch, s.max_curvature_deviation, s.max_overlap]), "step %d" % k)
         assert (int(w[7]), int(w[11]), int(w[13])) == (s.num_pairs, s.num_sliding, int(s.rebuilt)), k
 
-    def fnv(words):
-        h = 1469598103934665603
-        for b in words:
-            h = ((h ^ int(b)) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-        return "%016x" % h
-
-    sums = dict(ln.split()[1:3] for ln in out.stdout.splitlines() if ln.startswith("CHECKSUM"))
+    sums = checksums(out.stdout)
     for name in ("center", "twist", "velocity", "twist_velocity", "edge_orientation"):
         assert sums[name] == fnv(np.ascontiguousarray(host(st.field(name))).reshape(-1).view(np.uint64)), name
     for name in ("node_force", "tang_disp"):

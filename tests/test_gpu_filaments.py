@@ -14,7 +14,6 @@ import filament_model as fm
 from gpu_util import PAST_FULL_GRID, STAT_POSITIONS, all_pos_zero, assert_bits_equal, dev, host
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # filament ends on (256), one before (511) and one after (513) a border of the 256-node tiles; then short ones, and two
 # that span whole tiles
@@ -227,18 +226,14 @@ def test_relaxation_to_an_arc_on_the_device():
 
 # ---- 4. the C++ driver ------------------------------------------------------------------------------------------------------
 def test_filament_step_app_matches_python():
-    from mundy_amd import build
+    from cpp_apps import build_app, checksums, fnv1a as fnv
     case = make_case(26, BORDER_COUNTS)
     prm = params(wave=True)
     st = new_stepper(case, prm)
     dt, steps = 0.01, 20
     lines = [st.step(dt) for _ in range(steps)]
     import tempfile
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(ROOT, "tests", "cpp", "filament_step_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", os.path.join(ROOT, "tests", "cpp", "filament_step_app.cpp"),
-                           "-I", os.path.join(ROOT, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_app("filament_step_app")
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "in.bin")
         with open(path, "wb") as f:
@@ -256,13 +251,7 @@ def test_filament_step_app_matches_python():
         assert_bits_equal(np.array([float.fromhex(words[3]), float.fromhex(words[5])]),
                           np.array([s.max_stretch, s.max_curvature_deviation]), "step %d" % k)
 
-    def fnv(words):
-        h = 1469598103934665603
-        for b in words:
-            h = ((h ^ int(b)) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-        return "%016x" % h
-
-    sums = dict(ln.split()[1:3] for ln in out.stdout.splitlines() if ln.startswith("CHECKSUM"))
+    sums = checksums(out.stdout)
     for name in ("center", "twist", "velocity", "twist_velocity", "edge_orientation"):
         words = np.ascontiguousarray(host(st.field(name))).reshape(-1).view(np.uint64)
         assert sums[name] == fnv(words), name

@@ -2,7 +2,6 @@
 vector body sweep and the history carry against the numpy model in tests/friction_hertz_model.py, the stepper's
 trajectory with rebuilds, a reorder and a restore, the two-rod sled's closed-form steady states, the unchanged
 frictionless step, the C++ stepper against the Python one, and one step at full size."""
-import os
 import subprocess
 
 import numpy as np
@@ -12,8 +11,6 @@ import friction_hertz_model as fm
 from hertz_model import hertz_force, rod_arms, stiffness
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _rods(rng, n, box):
@@ -538,26 +535,8 @@ def test_hertz_step_without_the_keyword_is_the_step_through_the_old_entry_points
 
 
 # ---- 9: the C++ stepper -------------------------------------------------------------------------------------------------
-def _build_app():
-    from mundy_amd import build
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(ROOT, "tests", "cpp", "friction_hertz_step_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra",
-                           os.path.join(ROOT, "tests", "cpp", "friction_hertz_step_app.cpp"), "-I",
-                           os.path.join(ROOT, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-                           "-Wl,-rpath-link,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    return exe
-
-
-def _checksum(a):
-    h = 1469598103934665603
-    for v in np.ascontiguousarray(a).view(np.uint64).ravel().tolist():
-        h = ((h ^ v) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return "%016x" % h
-
-
 def test_cpp_frictional_stepper_reproduces_the_python_driver(tmp_path, trajectory_setup):
+    from cpp_apps import build_app, fnv1a_bits as _checksum
     from gpu_util import host
     from mundy_amd import synth
     b, dt, buffer = trajectory_setup
@@ -568,7 +547,7 @@ def test_cpp_frictional_stepper_reproduces_the_python_driver(tmp_path, trajector
         f.write(np.uint64(n).tobytes())
         for a in (b["center"], b["quat"], b["radius"], b["length"], mt, mr):
             f.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
-    exe = _build_app()
+    exe = build_app("friction_hertz_step_app")
     steps, reorder_at = 30, 12
     p = subprocess.run([exe, str(inp), str(steps), "3.0", str(reorder_at), repr(dt), "1000.0", "0.3", repr(MU),
                         repr(DAMPING[0]), repr(DAMPING[1]), "1.0", repr(buffer)], capture_output=True, text=True,

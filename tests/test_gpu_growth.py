@@ -2,7 +2,6 @@
 stepper -- lengths and counts against the length recursion, the corner rebuild rule (no missed contact), no stale state
 after births, determinism and reordering, the periodic box, the C++ stepper against the Python one, one step at full
 size."""
-import os
 import subprocess
 
 import numpy as np
@@ -12,7 +11,6 @@ import growth_model as gm
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SENTINEL = np.array([0x7FF4DEADBEEF0123], dtype=np.uint64).view(np.float64)[0]  # a signalling-NaN pattern
 
 
@@ -320,29 +318,11 @@ def test_runs_are_deterministic_and_reordering_changes_nothing_but_numbering():
     assert np.array_equal(l2, l0[m])
 
 
-def _build_app():
-    from mundy_amd import build
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(ROOT, "tests", "cpp", "bacteria_step_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra",
-                           os.path.join(ROOT, "tests", "cpp", "bacteria_step_app.cpp"), "-I",
-                           os.path.join(ROOT, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-                           "-Wl,-rpath-link,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    return exe
-
-
-def _checksum(a):
-    h = 1469598103934665603
-    for v in np.ascontiguousarray(a).view(np.uint64).ravel().tolist():
-        h = ((h ^ v) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return "%016x" % h
-
-
 def _cpp_against_python(tmp_path, b, box, steps, viscosity=1.0, rate=5.0):
     """runs bacteria_step_app and the Python stepper on the same rods: per step the body count, births, contacts, the
     largest overlap and the rebuild flag must agree, and the final checksums of the live rows.  Returns the Python
     stepper and the total births."""
+    from cpp_apps import build_app, fnv1a_bits as _checksum
     from gpu_util import dev, host
     from mundy_amd import synth
     n = len(b["radius"])
@@ -352,7 +332,7 @@ def _cpp_against_python(tmp_path, b, box, steps, viscosity=1.0, rate=5.0):
         f.write(np.uint64(n).tobytes())
         for a in (b["center"], b["quat"], b["radius"], b["length"], mt, mr):
             f.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
-    exe = _build_app()
+    exe = build_app("bacteria_step_app")
     dt, E, nu, D, buf = 1e-3, 1000.0, 0.3, 2.0, 0.5
     p = subprocess.run([exe, str(inp), str(steps), "0", repr(box or 0.0), repr(dt), repr(E), repr(nu), repr(rate),
                         repr(D), repr(buf)], capture_output=True, text=True, timeout=600)

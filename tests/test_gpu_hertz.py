@@ -1,7 +1,6 @@
 """Hertzian soft contact on the GPU (contact_model="hertz"): the per-linker force kernel and the operator's body sweep
 against the numpy restatement in tests/hertz_model.py, conservation, order independence, the dynamics of the step, the
 periodic box, the C++ stepper against the Python one, and one step at full size."""
-import os
 import subprocess
 
 import numpy as np
@@ -10,8 +9,6 @@ import pytest
 from hertz_model import body_force_torque, elastic_energy, hertz_force, rod_arms, stiffness
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _spheres(rng, n, box):
@@ -270,27 +267,10 @@ def test_lattice_translation_leaves_velocities_unchanged(kind):
     op.close()
 
 
-def _build_hertz_app():
-    from mundy_amd import build
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(ROOT, "tests", "cpp", "hertz_step_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", os.path.join(ROOT, "tests", "cpp", "hertz_step_app.cpp"),
-                           "-I", os.path.join(ROOT, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-                           "-Wl,-rpath-link,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    return exe
-
-
-def _checksum(a):
-    h = 1469598103934665603
-    for v in np.ascontiguousarray(a).view(np.uint64).ravel().tolist():
-        h = ((h ^ v) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return "%016x" % h
-
-
 @pytest.mark.parametrize("periodic", [False, True])
 def test_cpp_hertz_stepper_reproduces_the_python_driver(tmp_path, periodic):
     import torch
+    from cpp_apps import build_app, fnv1a_bits as _checksum
     from gpu_util import dev
     from mundy_amd import pipeline, synth
     n = 30_000
@@ -301,7 +281,7 @@ def test_cpp_hertz_stepper_reproduces_the_python_driver(tmp_path, periodic):
         f.write(np.uint64(n).tobytes())
         for a in (b["center"], b["quat"], b["radius"], b["length"], mt, mr):
             f.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
-    exe = _build_hertz_app()
+    exe = build_app("hertz_step_app")
     dt, E, nu = 1e-7, 1000.0, 0.3
     box = [float(b["box"])] * 3 if periodic else None
     p = subprocess.run([exe, str(inp), "3", "3.0", "%.17g" % (b["box"] if periodic else 0.0), repr(dt), repr(E), repr(nu)],

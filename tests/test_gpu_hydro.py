@@ -13,7 +13,6 @@ from gpu_util import all_pos_zero, assert_bits_equal, dev, host
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C = hm.CHUNK
 MU = 0.7
 SIZES = (1, 2, 63, 64, 65, 257, C - 1, C, C + 1, 2 * C + 77)
@@ -355,7 +354,8 @@ def test_stepper_runs_with_both_contact_models(model):
 def test_hydro_step_app_matches_python():
     import tempfile
 
-    from mundy_amd import build, capi, synth
+    from cpp_apps import build_app, fnv1a
+    from mundy_amd import capi, synth
     d = _chains()
     n = d["center"].shape[0]
     mt, _ = synth.dry_mobility(d["radius"], viscosity=d["viscosity"])
@@ -365,11 +365,7 @@ def test_hydro_step_app_matches_python():
         s = st.step()
         lines.append("STEP %d contacts %d iterations %d max_spring_length %.17g" % (k, s.num_contacts, s.num_iters,
                                                                                      s.max_spring_length))
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(ROOT, "tests", "cpp", "hydro_step_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", os.path.join(ROOT, "tests", "cpp", "hydro_step_app.cpp"), "-I",
-                           os.path.join(ROOT, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_app("hydro_step_app")
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "in.bin")
         with open(path, "wb") as f:
@@ -385,10 +381,7 @@ def test_hydro_step_app_matches_python():
     got = [ln for ln in out.stdout.splitlines() if ln.startswith("STEP")]
     assert [" ".join(g.split()[:8]) for g in got] == lines
     cs = [ln for ln in out.stdout.splitlines() if ln.startswith("CHECKSUM")][0].split()
-    h = 1469598103934665603
-    for b in host(st.center).reshape(-1).view(np.uint64).tolist():
-        h = ((h ^ b) * 1099511628211) & (2 ** 64 - 1)
-    assert cs[2] == "%016x" % h
+    assert cs[2] == fnv1a(host(st.center).reshape(-1).view(np.uint64).tolist())
 
 
 # ---- 8. one larger call --------------------------------------------------------------------------------------------------

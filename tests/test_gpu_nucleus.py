@@ -17,7 +17,6 @@ from gpu_util import (PAST_FULL_GRID, STAT_POSITIONS, all_pos_zero, assert_bits_
                       renumberings, star_and_random_graph, star_graph)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PAST_GRID_CAP = 2048 * 256 + 77   # grid_for caps the grid at 2048 workgroups of 256: lanes take a second body here
 SIZES = (1, 63, 257, 20001)
 
@@ -657,7 +656,8 @@ def test_force_stage_is_the_models_sum_for_every_choice_of_terms(terms):
 
 # ---- 5. the C++ driver ----------------------------------------------------------------------------------------------------
 def test_nucleus_step_app_matches_python():
-    from mundy_amd import build, capi, pipeline, synth
+    from cpp_apps import build_app, checksums, fnv1a as fnv
+    from mundy_amd import capi, pipeline, synth
     d = synth.chains(2, 1000, seed=8)
     n = d["center"].shape[0]
     mt, _ = synth.dry_mobility(d["radius"], viscosity=d["viscosity"])
@@ -680,11 +680,7 @@ def test_nucleus_step_app_matches_python():
             s.active_switches[1]))
     assert s.periphery_colliding > 0 and s.active_springs > 0
     import tempfile
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(ROOT, "tests", "cpp", "nucleus_step_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", os.path.join(ROOT, "tests", "cpp", "nucleus_step_app.cpp"),
-                           "-I", os.path.join(ROOT, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_app("nucleus_step_app")
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "in.bin")
         with open(path, "wb") as f:
@@ -701,13 +697,7 @@ def test_nucleus_step_app_matches_python():
     assert out.returncode == 0, out.stderr
     got = [ln for ln in out.stdout.splitlines() if ln.startswith("STEP")]
     assert [" ".join(g.split()[:14]) for g in got] == lines
-
-    def fnv(words):
-        h = 1469598103934665603
-        for b in words:
-            h = ((h ^ b) * 1099511628211) & (2 ** 64 - 1)
-        return "%016x" % h
-    cs = {ln.split()[1]: ln.split()[2] for ln in out.stdout.splitlines() if ln.startswith("CHECKSUM")}
+    cs = checksums(out.stdout)
     state, next_time = (host(t) for t in st.active_state()[:2])
     assert cs["center"] == fnv(host(st.center).reshape(-1).view(np.uint64).tolist())
     assert cs["state"] == fnv(state.astype(np.int64).tolist())

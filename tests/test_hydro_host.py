@@ -308,12 +308,7 @@ def test_step_stats_timings_name():
 
 
 def test_hydro_step_app_compiles_and_links():
-    from mundy_amd import build
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(ROOT, "tests", "cpp", "hydro_step_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra",
-                           os.path.join(ROOT, "tests", "cpp", "hydro_step_app.cpp"), "-I",
-                           os.path.join(ROOT, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    from cpp_apps import build_app
+    exe = build_app("hydro_step_app")
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 1 and "Usage" in out.stderr

@@ -4,7 +4,6 @@ stepper, of ops and of the library (before any HIP call); the new entry points e
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,7 +11,6 @@ import torch
 
 import periphery_model as pm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RADII = (3.0, 2.0, 1.5)
 
 
@@ -401,12 +399,6 @@ def test_active_null_handles_and_bad_dt_are_refused(lib):
 
 
 def test_nucleus_step_app_compiles_and_links():
-    from mundy_amd import build
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(ROOT, "tests", "cpp", "nucleus_step_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror",
-                           os.path.join(ROOT, "tests", "cpp", "nucleus_step_app.cpp"), "-I",
-                           os.path.join(ROOT, "include"), "-L", libdir, "-lmundy_hip", "-Wl,-rpath," + libdir,
-                           "-Wl,-rpath-link,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
+    from cpp_apps import build_app
+    exe = build_app("nucleus_step_app")
     assert os.path.exists(exe)
