@@ -54,6 +54,15 @@ int mhip_device_info(int* device_count, char* arch_name, size_t arch_name_len);
 /* Plain device memory for hosts that do not bring their own allocator. */
 int mhip_malloc(void** ptr, size_t bytes);
 int mhip_free(void* ptr);
+/* What the library itself holds in this process, without a HIP call (any pointer may be null):
+ *   handle_bytes   device bytes owned by live handles (broad phase, operators, communicators, force handles, ...), the
+ *                  spare workspace set of destroyed operators included (mhip_release_cached_workspaces frees that);
+ *   scratch_bytes  device bytes of the grow-only per-thread / per-process scratch, which lives until the process exits;
+ *   pinned_bytes   pinned host bytes owned by live handles and the spare set;
+ *   allocations    how many hipMalloc / hipHostMalloc calls those three have made so far (never decreases): constant
+ *                  across the warm steps of a time loop.
+ * Not counted: mhip_malloc, the IPC-mapped boxes of a communicator, the scratch's 64-byte pinned words. */
+int mhip_memory_stats(size_t* handle_bytes, size_t* scratch_bytes, size_t* pinned_bytes, size_t* allocations);
 int mhip_memcpy_h2d(void* dst, const void* src_host, size_t bytes, mhip_stream_t stream); /* synchronises: src_host is reusable */
 int mhip_memcpy_d2h(void* dst_host, const void* src, size_t bytes, mhip_stream_t stream); /* synchronises */
 int mhip_stream_synchronize(mhip_stream_t stream);

@@ -116,6 +116,7 @@ SIGNATURES = {
     "mhip_device_info": [C.POINTER(C.c_int), C.c_char_p, _sz],
     "mhip_malloc": [C.POINTER(_vp), _sz],
     "mhip_free": [_vp],
+    "mhip_memory_stats": [C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)],
     "mhip_memcpy_h2d": [_vp, _vp, _sz, _vp],
     "mhip_memcpy_d2h": [_vp, _vp, _sz, _vp],
     "mhip_stream_synchronize": [_vp],

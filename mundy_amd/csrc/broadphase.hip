@@ -967,16 +967,16 @@ struct mhip_broadphase {
   size_t n = 0, num_pairs = 0;
   int method_used = MHIP_SEARCH_METHOD_GRID;
   bool min_image_complete = true;  // last build: no two volumes could have met through any image but the nearest
-  DeviceBuffer recs, cell_of, slot_cell, cell_cnt, cell_ptr, cursor, counts, row_ptr, col, pairs, old_center, params,
+  HandleBuffer recs, cell_of, slot_cell, cell_cnt, cell_ptr, cursor, counts, row_ptr, col, pairs, old_center, params,
       partials, scanws, flag, longrows, coltmp;
   // LBVH
-  DeviceBuffer keys, keys_tmp, order, order_tmp, sortws, nodes, right, parent, ticket, pending, leaf_rope, slot_of, slab;
+  HandleBuffer keys, keys_tmp, order, order_tmp, sortws, nodes, right, parent, ticket, pending, leaf_rope, slot_of, slab;
   // seam S3: source / target sets, identities, exclusion lists (copies owned by the handle)
   size_t sets_n = 0, ident_n = 0, excl_n = 0;
   bool has_source = false, has_target = false, has_ident = false, has_excl = false;
-  DeviceBuffer is_source, is_target, entity_id, owner_rank, ex_ptr, ex_idx;
-  double* host_summary = nullptr;  // pinned, 8 doubles
-  int* host_scalar = nullptr;      // pinned
+  HandleBuffer is_source, is_target, entity_id, owner_rank, ex_ptr, ex_idx;
+  PinnedBlock<double> host_summary;  // 8 doubles
+  PinnedBlock<int> host_scalar;
 };
 
 extern "C" {
@@ -988,26 +988,16 @@ int mhip_broadphase_create(mhip_broadphase_t* handle) {
 }
 
 static int ensure_host_scalar(mhip_broadphase* h) {
-  if (!h->host_scalar) MHIP_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->host_scalar), 64));
-  if (!h->host_summary) MHIP_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->host_summary), 8 * sizeof(double)));
-  return MHIP_SUCCESS;
+  if (int e = h->host_scalar.reserve(64)) return e;
+  return h->host_summary.reserve(8 * sizeof(double));
 }
 
 int mhip_broadphase_destroy(mhip_broadphase_t h) {
-  if (!h) return MHIP_SUCCESS;
-  for (DeviceBuffer* b : {&h->recs, &h->cell_of, &h->slot_cell, &h->cell_cnt, &h->cell_ptr, &h->cursor, &h->counts,
-                          &h->row_ptr, &h->col, &h->pairs, &h->old_center, &h->params, &h->partials, &h->scanws,
-                          &h->flag, &h->longrows, &h->coltmp, &h->keys, &h->keys_tmp, &h->order, &h->order_tmp,
-                          &h->sortws, &h->nodes, &h->right, &h->parent, &h->ticket, &h->pending, &h->leaf_rope, &h->slot_of, &h->slab,
-                          &h->is_source, &h->is_target, &h->entity_id, &h->owner_rank, &h->ex_ptr, &h->ex_idx})
-    b->release();
-  if (h->host_scalar) (void)hipHostFree(h->host_scalar);
-  if (h->host_summary) (void)hipHostFree(h->host_summary);
   delete h;
   return MHIP_SUCCESS;
 }
 
-static int copy_in(DeviceBuffer& dst, const void* src, size_t bytes, hipStream_t s) {
+static int copy_in(HandleBuffer& dst, const void* src, size_t bytes, hipStream_t s) {
   if (int e = dst.reserve(bytes + 16)) return e;
   if (bytes) MHIP_HIP(hipMemcpyAsync(dst.ptr, src, bytes, hipMemcpyDeviceToDevice, s));
   return MHIP_SUCCESS;
@@ -1387,7 +1377,7 @@ int mhip_links_export_crs(mhip_broadphase_t h, uint64_t first_link_id, unsigned 
                MHIP_ERR_INVALID_ARGUMENT, "null output array");
   hipStream_t s = as_stream(stream);
   // entity -> links that name it (either ordinal): degrees, offsets, fill, each list ascending by link
-  DeviceBuffer &deg = h->cell_cnt, &ptr = h->cell_ptr, &cur = h->cursor, &conn = h->keys, &tmp = h->keys_tmp;
+  HandleBuffer &deg = h->cell_cnt, &ptr = h->cell_ptr, &cur = h->cursor, &conn = h->keys, &tmp = h->keys_tmp;
   if (int e = deg.reserve((n + 2) * sizeof(int32_t))) return e;
   if (int e = ptr.reserve((n + 2) * sizeof(int32_t))) return e;
   if (int e = cur.reserve((n + 2) * sizeof(int32_t))) return e;

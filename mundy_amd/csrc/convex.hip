@@ -15,6 +15,7 @@
 // flip); mhip_bbpgd_solve_* writes the caller's x, g, x_tmp, g_tmp once at the end with the reference's
 // post-conditions (which array holds what).
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <type_traits>
 #include <vector>
@@ -2318,22 +2319,52 @@ __global__ void __launch_bounds__(kBlock)
 
 using namespace mhip;
 
-struct mhip_contact_op {
+// An operator lives for one solve (its lists follow the contacts), but its workspaces -- two dozen device buffers, a
+// pinned state block, timing events -- are the same size step after step.  They form ONE struct that moves as a whole:
+// a destroyed operator leaves it as the process-wide spare set, the next create adopts it (see "spare set" below).
+struct ProfilingEvents {  // 3 per enqueued iteration: before body, between, after constraint
+  std::vector<hipEvent_t> v;
+  ProfilingEvents() = default;
+  ProfilingEvents(ProfilingEvents&& o) noexcept : v(std::move(o.v)) { o.v.clear(); }
+  ProfilingEvents& operator=(ProfilingEvents&& o) noexcept {
+    if (this != &o) {
+      destroy();
+      v = std::move(o.v);
+      o.v.clear();
+    }
+    return *this;
+  }
+  ~ProfilingEvents() { destroy(); }
+  void destroy() {
+    for (auto ev : v) (void)hipEventDestroy(ev);
+    v.clear();
+  }
+};
+struct OpWorkspaces {
+  HandleBuffer inc_ptr, inc, cursor, vel, partials, state, scanws, half, axis, omega, vel_out;
+  HandleBuffer iterate;  // packed (x, g) ping-pong pair of the fused / staged solvers: 2 x C x 16 bytes
+  HandleBuffer rate_rows;  // (U, W x u) rows of a caller's velocity (mhip_contact_op_constraint_rate, rods)
+  HandleBuffer body_mask, pos;  // activity masks of the packed LCP solves (see OpView)
+  HandleBuffer sort_tmp, sort_list;  // workspaces of the incidence-list sort
+  HandleBuffer aptr, aent, arec, snap_mask, acnt;  // active lists (see OpView)
+  // cold tier (its other state is mhip_contact_op::Tier)
+  HandleBuffer tier_geo[2], tier_iter[2], tier_misc, tier_vel2, tier_drift, tier_arm, tier_xprev;
+  PinnedBlock<SolverState> host_state;  // + 64 spare bytes: the length of the compact active lists
+  ProfilingEvents events;  // optional per-kernel timing (mhip_contact_op_set_profiling)
+  int device = -1;  // the device current at create: where every buffer of this set lives
+};
+static_assert(std::is_nothrow_move_constructible_v<OpWorkspaces> && std::is_nothrow_move_assignable_v<OpWorkspaces> &&
+                  !std::is_copy_constructible_v<OpWorkspaces>,
+              "the workspace set is handed over whole");
+
+struct mhip_contact_op : OpWorkspaces {
   OpView view{};
   bool rot = false;  // any rotational kinematics (KIN_RIGID or KIN_ROD)
   int kin = KIN_TRANS;
   hipStream_t last_stream = nullptr;
-  DeviceBuffer inc_ptr, inc, cursor, vel, partials, state, scanws, half, axis, omega, vel_out;
-  DeviceBuffer iterate;  // packed (x, g) ping-pong pair of the fused / staged solvers: 2 x C x 16 bytes
-  DeviceBuffer rate_rows;  // (U, W x u) rows of a caller's velocity (mhip_contact_op_constraint_rate, rods)
-  DeviceBuffer body_mask, pos;  // activity masks of the packed LCP solves (see OpView)
-  DeviceBuffer sort_tmp, sort_list;  // workspaces of the incidence-list sort
-  DeviceBuffer aptr, aent, arec, snap_mask, acnt;  // active lists (see OpView)
-  int device = -1;  // the device current at create: where every buffer of this operator lives
   int tiering = 1;         // the fused solve may use the cold tier (mhip_contact_op_set_tiering); 2: test hook
   int drift_source = 0;    // tiered solves: 0 = by size (op_drift_source), 1 = rows, 2 = registers (time only)
   int lanes_per_body = 2;  // k_body's G (2, 4, 8 or 16), each lane keeping 4 (2 and 16 lanes: 2) half-edge chains in flight
-  SolverState* host_state = nullptr;  // pinned
   // staged (multi-rank) solve context, set by mhip_bbpgd_stage_begin
   struct Stage {
     const double* q = nullptr;
@@ -2363,7 +2394,6 @@ struct mhip_contact_op {
     size_t I = 0;           // contacts [I, C) never go cold (the staged solver's boundary contacts: a ghost body's drift
                             // is not known here); the fused solve has I = C
     bool pingpong = false;  // the body rows alternate between two buffers (fused solve)
-    DeviceBuffer geo[2], iter[2], misc, vel2, drift, arm, xprev;
     OpView saved{};         // the operator's own view, restored when the tiers are left
     // statistics of the last solve
     size_t tiered_iterations = 0, retiers = 0, wakeups = 0;
@@ -2372,7 +2402,6 @@ struct mhip_contact_op {
   } tier;
   // optional per-kernel timing (mhip_contact_op_set_profiling)
   bool profile = false;
-  std::vector<hipEvent_t> events;  // 3 per enqueued iteration: before body, between, after constraint
   double body_ms = 0.0, constraint_ms = 0.0;
   size_t timed_iterations = 0;
 };
@@ -2834,28 +2863,28 @@ int tier_update(mhip_contact_op* op, TierPairs& cur, unsigned iters_done, unsign
   OpView& v = op->view;
   const size_t C = v.C, N = v.N;
   if (I > C) I = C;
-  if (int e = t.misc.reserve(tier_misc_bytes(C, N))) return e;
+  if (int e = op->tier_misc.reserve(tier_misc_bytes(C, N))) return e;
   if (int e = op->scanws.reserve(scan_workspace_bytes(C + 2) + 64)) return e;
-  const TierMisc m = tier_misc_at(t.misc.ptr, C, N);
+  const TierMisc m = tier_misc_at(op->tier_misc.ptr, C, N);
   const bool cur_is_p1 = op->host_state->flips & 1u;
   if (!t.tracking) {
-    if (int e = t.vel2.reserve((6 * N + 8) * sizeof(double))) return e;
-    if (int e = t.drift.reserve((N + 8) * sizeof(double))) return e;
-    MHIP_HIP(hipMemsetAsync(t.drift.ptr, 0, N * sizeof(double), s));
+    if (int e = op->tier_vel2.reserve((6 * N + 8) * sizeof(double))) return e;
+    if (int e = op->tier_drift.reserve((N + 8) * sizeof(double))) return e;
+    MHIP_HIP(hipMemsetAsync(op->tier_drift.ptr, 0, N * sizeof(double), s));
     MHIP_HIP(hipMemsetAsync(m.drift_prev, 0, N * sizeof(double), s));
     // the body rows start to ping-pong: the current rows must sit in the buffer of the current parity
     if (pingpong && cur_is_p1)
-      MHIP_HIP(hipMemcpyAsync(t.vel2.ptr, v.vel, 6 * N * sizeof(double), hipMemcpyDeviceToDevice, s));
+      MHIP_HIP(hipMemcpyAsync(op->tier_vel2.ptr, v.vel, 6 * N * sizeof(double), hipMemcpyDeviceToDevice, s));
     if (op->kin == KIN_RIGID) {  // the drift of a body with vector arms is scaled by its longest arm
-      if (int e = t.arm.reserve((N + 8) * sizeof(double))) return e;
-      k_tier_arm_max<<<grid_for(N), kBlock, 0, s>>>(N, v.inc_ptr, v.half, t.arm.as<double>());
+      if (int e = op->tier_arm.reserve((N + 8) * sizeof(double))) return e;
+      k_tier_arm_max<<<grid_for(N), kBlock, 0, s>>>(N, v.inc_ptr, v.half, op->tier_arm.as<double>());
       MHIP_LAUNCH_CHECK();
-      v.arm_max = t.arm.as<double>();
+      v.arm_max = op->tier_arm.as<double>();
     }
     t.saved_vel = v.vel;
     t.pingpong = pingpong;
-    v.vel_alt = pingpong ? t.vel2.as<double>() : nullptr;
-    v.drift = t.drift.as<double>();
+    v.vel_alt = pingpong ? op->tier_vel2.as<double>() : nullptr;
+    v.drift = op->tier_drift.as<double>();
     t.tracking = true;
     t.polled_at = iters_done;
     return MHIP_SUCCESS;
@@ -2873,14 +2902,14 @@ int tier_update(mhip_contact_op* op, TierPairs& cur, unsigned iters_done, unsign
   // iterations: 1 130 000 / 136 000 / 3 700 contacts woken and 259 / 170 / 156 ms per step before this floor.)
   const unsigned horizon = next_period > kTierHorizon ? next_period : kTierHorizon;
   const double scale = static_cast<double>(horizon) / static_cast<double>(last_period);
-  k_tier_budget<<<grid_for(N), kBlock, 0, s>>>(N, t.drift.as<double>(), m.drift_prev, scale, m.budget);
+  k_tier_budget<<<grid_for(N), kBlock, 0, s>>>(N, op->tier_drift.as<double>(), m.drift_prev, scale, m.budget);
   MHIP_LAUNCH_CHECK();
   const double2* Pc = reinterpret_cast<const double2*>(cur_is_p1 ? cur.P1 : cur.P0);
   const double2* Pp = reinterpret_cast<const double2*>(cur_is_p1 ? cur.P0 : cur.P1);
   const double* wake_old = t.active ? m.wake[t.set] : m.wake[0];
   const size_t H_old = t.active ? t.H : C;
   if (I == 0) return MHIP_SUCCESS;
-  k_tier_classify<<<grid_for(I), kBlock, 0, s>>>(I, v.pairs, Pc, Pp, m.budget, t.drift.as<double>(), wake_old, H_old,
+  k_tier_classify<<<grid_for(I), kBlock, 0, s>>>(I, v.pairs, Pc, Pp, m.budget, op->tier_drift.as<double>(), wake_old, H_old,
                                                  m.flags);
   MHIP_LAUNCH_CHECK();
   if (int e = exclusive_scan_i32(m.flags, m.rank, I, op->scanws.ptr, s)) return e;
@@ -2906,14 +2935,14 @@ int tier_update(mhip_contact_op* op, TierPairs& cur, unsigned iters_done, unsign
     return MHIP_SUCCESS;  // (almost) everything is hot: nothing to gain yet
   }
   const int dst_set = t.active ? (t.set ^ 1) : 0;
-  if (int e = t.geo[dst_set].reserve(tier_geo_bytes(C, op->kin == KIN_RIGID))) return e;
-  if (int e = t.iter[dst_set].reserve(2 * (C + 1) * sizeof(double2))) return e;
-  const TierGeo dst = tier_geo_at(t.geo[dst_set].ptr, C);
-  double2* P0d = t.iter[dst_set].as<double2>();
+  if (int e = op->tier_geo[dst_set].reserve(tier_geo_bytes(C, op->kin == KIN_RIGID))) return e;
+  if (int e = op->tier_iter[dst_set].reserve(2 * (C + 1) * sizeof(double2))) return e;
+  const TierGeo dst = tier_geo_at(op->tier_geo[dst_set].ptr, C);
+  double2* P0d = op->tier_iter[dst_set].as<double2>();
   double2* P1d = P0d + C;
   const int32_t* orig_src = nullptr;
   if (t.active)
-    orig_src = tier_geo_at(t.geo[t.set].ptr, C).orig;
+    orig_src = tier_geo_at(op->tier_geo[t.set].ptr, C).orig;
   else
     t.saved = v;
   if (int e = mhip_fill(N, m.fire_at, __builtin_huge_val(), reinterpret_cast<mhip_stream_t>(s))) return e;
@@ -2921,7 +2950,7 @@ int tier_update(mhip_contact_op* op, TierPairs& cur, unsigned iters_done, unsign
     k_tier_permute<decltype(kin)::value><<<grid_for(C), kBlock, 0, s>>>(
         C, I, H, cur_is_p1 ? 1 : 0, v.pairs, v.normal, v.arc_s, v.arc_t, v.ra, v.rb, cur.q, orig_src, v.pos, dst,
         reinterpret_cast<const double2*>(cur.P0), reinterpret_cast<const double2*>(cur.P1), P0d, P1d, m.flags, m.rank,
-        m.new_of, wake_old, H_old, m.wake[dst_set], t.drift.as<double>(), m.fire_at);
+        m.new_of, wake_old, H_old, m.wake[dst_set], op->tier_drift.as<double>(), m.fire_at);
   });
   MHIP_LAUNCH_CHECK();
   k_tier_remap_inc<<<grid_for(2 * C), kBlock, 0, s>>>(2 * C, op->inc.as<int32_t>(), m.new_of);
@@ -2959,7 +2988,7 @@ int tier_stop_tracking(mhip_contact_op* op, hipStream_t s) {
   const SolverState& hs = *op->host_state;
   const unsigned curv = (hs.converged && !hs.converged_at_init) ? ((hs.flips + 1u) & 1u) : (hs.flips & 1u);
   if (t.pingpong && curv == 1u)
-    MHIP_HIP(hipMemcpyAsync(t.saved_vel, t.vel2.ptr, 6 * op->view.N * sizeof(double), hipMemcpyDeviceToDevice, s));
+    MHIP_HIP(hipMemcpyAsync(t.saved_vel, op->tier_vel2.ptr, 6 * op->view.N * sizeof(double), hipMemcpyDeviceToDevice, s));
   op->view.vel_alt = nullptr;
   op->view.drift = nullptr;
   t.tracking = false;
@@ -2974,8 +3003,8 @@ int tier_release(mhip_contact_op* op, TierPairs& cur, bool final, double* P0, do
   if (!t.active) return tier_stop_tracking(op, s);
   OpView& v = op->view;
   const size_t C = v.C, N = v.N;
-  const TierMisc m = tier_misc_at(t.misc.ptr, C, N);
-  const TierGeo geo = tier_geo_at(t.geo[t.set].ptr, C);
+  const TierMisc m = tier_misc_at(op->tier_misc.ptr, C, N);
+  const TierGeo geo = tier_geo_at(op->tier_geo[t.set].ptr, C);
   const SolverState* st = op->state.as<SolverState>();
   double2* T0 = reinterpret_cast<double2*>(cur.P0);
   double2* T1 = reinterpret_cast<double2*>(cur.P1);
@@ -2991,11 +3020,11 @@ int tier_release(mhip_contact_op* op, TierPairs& cur, bool final, double* P0, do
       // one row buffer (the staged solver's, filled by the halo as well): the rows of the previous iterate are rebuilt
       // from its multipliers -- the same sums of the same terms, each a double-double pair rounded once: the same bits.
       // Sleepers only touch owned bodies, whose rows the body sweep computes.
-      if (int e = t.vel2.reserve((10 * N + 16) * sizeof(double))) return e;
-      if (int e = t.xprev.reserve((C + 2) * sizeof(double))) return e;
-      k_tier_prev_x<<<grid_for(C), kBlock, 0, s>>>(C, cur1 ? T0 : T1, t.xprev.as<double>());
+      if (int e = op->tier_vel2.reserve((10 * N + 16) * sizeof(double))) return e;
+      if (int e = op->tier_xprev.reserve((C + 2) * sizeof(double))) return e;
+      k_tier_prev_x<<<grid_for(C), kBlock, 0, s>>>(C, cur1 ? T0 : T1, op->tier_xprev.as<double>());
       MHIP_LAUNCH_CHECK();
-      double* rows = t.vel2.as<double>();
+      double* rows = op->tier_vel2.as<double>();
       double* const keep_vel = v.vel;
       double* const keep_omega = v.omega;
       double* const keep_drift = v.drift;
@@ -3004,7 +3033,7 @@ int tier_release(mhip_contact_op* op, TierPairs& cur, bool final, double* P0, do
       v.omega = rows + 6 * N;  // (the integrator's angular velocities belong to the latest iterate: untouched)
       v.drift = nullptr;
       v.aptr = nullptr;
-      const int e = op_launch_body(op, X_APPLY, t.xprev.as<double>(), t.xprev.as<double>(), nullptr, nullptr,
+      const int e = op_launch_body(op, X_APPLY, op->tier_xprev.as<double>(), op->tier_xprev.as<double>(), nullptr, nullptr,
                                    Space{MHIP_SPACE_UNCONSTRAINED, 0.0, 0.0}, s);
       v.vel = keep_vel;
       v.omega = keep_omega;
@@ -3058,7 +3087,7 @@ int op_launch_constraint_tiered(mhip_contact_op* op, const TierPairs& cur, Space
   const size_t C = op->view.C, N = op->view.N;
   const SolverState* st = op->state.as<SolverState>();
   double* parts = op->partials.as<double>();
-  const TierMisc m = tier_misc_at(t.misc.ptr, C, N);
+  const TierMisc m = tier_misc_at(op->tier_misc.ptr, C, N);
   const unsigned ghot = t.H ? constraint_grid(t.H) : 0u;
   // the tail is served by the first workgroups of the hot launch
   const unsigned gcheck = t.H < t.I ? t.service_blocks : 0u;
@@ -3302,50 +3331,24 @@ int mhip_gemv(size_t n, const double* A, const double* x, double* y, mhip_stream
   return MHIP_SUCCESS;
 }
 
-// An operator lives for one solve (its lists follow the contacts), but its workspaces -- a dozen device buffers, a
-// pinned state block, timing events -- are the same size step after step.  A destroyed operator therefore leaves them
-// in one process-wide spare set that the next create adopts: no hipMalloc / hipFree in the steady state (hipFree
-// alone cost 1.6 ms per step at 10^6 rods).  mhip_release_cached_workspaces() frees the spare set.
-constexpr int kOpBuffers = 31;
-struct OpWorkspaces {
-  DeviceBuffer buf[kOpBuffers];
-  SolverState* host_state = nullptr;
-  std::vector<hipEvent_t> events;
-  bool held = false;
-  int device = -1;  // the spare set is only handed to an operator on the device that allocated it
-};
+// The spare set: a destroyed operator leaves its OpWorkspaces here and the next create adopts them -- no hipMalloc /
+// hipFree in the steady state (hipFree alone cost 1.6 ms per step at 10^6 rods).  One set, only handed to an operator
+// on the device that allocated it; mhip_release_cached_workspaces() frees it.  Kept behind a plain pointer that nothing
+// deletes at process exit: a static OpWorkspaces would run its destructor, hence hipFree, during teardown (the hazard
+// DeviceBuffer avoids for the scratch).
 static std::mutex g_spare_mutex;
-static OpWorkspaces g_spare;
-static DeviceBuffer* op_buffers(mhip_contact_op* op, int k) {
-  DeviceBuffer* all[kOpBuffers] = {&op->inc_ptr, &op->inc,     &op->cursor,   &op->vel,      &op->partials, &op->state,
-                                   &op->scanws,  &op->half,    &op->axis,     &op->omega,    &op->vel_out,  &op->iterate,
-                                   &op->body_mask, &op->pos,   &op->sort_tmp, &op->sort_list, &op->aptr,    &op->aent,
-                                   &op->arec,    &op->snap_mask, &op->acnt,  &op->rate_rows,
-                                   &op->tier.geo[0], &op->tier.geo[1], &op->tier.iter[0], &op->tier.iter[1],
-                                   &op->tier.misc, &op->tier.vel2, &op->tier.drift, &op->tier.arm, &op->tier.xprev};
-  return all[k];
-}
-static void free_workspaces(OpWorkspaces& w) {
-  for (auto& b : w.buf) b.release();
-  if (w.host_state) (void)hipHostFree(w.host_state);
-  w.host_state = nullptr;
-  for (auto& ev : w.events) (void)hipEventDestroy(ev);
-  w.events.clear();
-  w.held = false;
-}
+static OpWorkspaces* g_spare = nullptr;
 static void adopt_spare_workspaces(mhip_contact_op* op) {
   std::lock_guard<std::mutex> lock(g_spare_mutex);
-  int dev = -1;
-  if (!g_spare.held || hipGetDevice(&dev) != hipSuccess || dev != g_spare.device) return;
-  for (int k = 0; k < kOpBuffers; ++k) {
-    *op_buffers(op, k) = g_spare.buf[k];
-    g_spare.buf[k] = DeviceBuffer{};
-  }
-  op->host_state = g_spare.host_state;
-  g_spare.host_state = nullptr;
-  op->events.swap(g_spare.events);
-  g_spare.held = false;
+  if (!g_spare || op->device != g_spare->device) return;
+  static_cast<OpWorkspaces&>(*op) = std::move(*g_spare);
+  delete g_spare;
+  g_spare = nullptr;
 }
+// a create that fails hands its buffers on like any destroyed operator
+struct ContactOpDestroy {
+  void operator()(mhip_contact_op* op) const { (void)mhip_contact_op_destroy(op); }
+};
 
 static int create_contact_op(mhip_contact_op_t* handle, int kin, size_t num_constraints, size_t num_bodies,
                              const int32_t* pairs, const double* normal, const double* ra, const double* rb,
@@ -3359,99 +3362,84 @@ static int create_contact_op(mhip_contact_op_t* handle, int kin, size_t num_cons
   MHIP_REQUIRE(N == 0 || mob_trans, MHIP_ERR_INVALID_ARGUMENT, "mob_trans must not be null");
   MHIP_REQUIRE(C < (1u << 30) && N < (1u << 31), MHIP_ERR_RUNTIME, "problem too large for 32-bit incidence entries");
   hipStream_t s = as_stream(stream);
-  mhip_contact_op* op = new mhip_contact_op();
+  std::unique_ptr<mhip_contact_op, ContactOpDestroy> owner(new mhip_contact_op());
+  mhip_contact_op* op = owner.get();
   op->last_stream = s;
   (void)hipGetDevice(&op->device);
   adopt_spare_workspaces(op);
-  auto bail = [&](int e) {
-    mhip_contact_op_destroy(op);
-    return e;
-  };
   op->kin = kin;
   op->rot = (kin != KIN_TRANS);
-  if (int e = op->inc_ptr.reserve((N + 2) * sizeof(int32_t))) return bail(e);
-  if (int e = op->cursor.reserve((N + 2) * sizeof(int32_t))) return bail(e);
-  if (int e = op->inc.reserve((2 * C + 2) * sizeof(int32_t))) return bail(e);
-  if (int e = op->vel.reserve((6 * N + 2) * sizeof(double))) return bail(e);
-  if (int e = op->partials.reserve(((size_t)kRed * kStageStride + kRed * kFoldGroups + 64) * sizeof(double))) return bail(e);
-  if (int e = op->state.reserve(sizeof(SolverState) + 64)) return bail(e);
-  if (int e = op->scanws.reserve(scan_workspace_bytes(N + 1) + 64)) return bail(e);
-  if (!op->host_state) {
-    hipError_t he = hipHostMalloc(reinterpret_cast<void**>(&op->host_state), sizeof(SolverState) + 64);
-    if (he != hipSuccess) return bail(fail(MHIP_ERR_HIP, "hipHostMalloc failed: %s", hipGetErrorString(he)));
-  }
+  if (int e = op->inc_ptr.reserve((N + 2) * sizeof(int32_t))) return e;
+  if (int e = op->cursor.reserve((N + 2) * sizeof(int32_t))) return e;
+  if (int e = op->inc.reserve((2 * C + 2) * sizeof(int32_t))) return e;
+  if (int e = op->vel.reserve((6 * N + 2) * sizeof(double))) return e;
+  if (int e = op->partials.reserve(((size_t)kRed * kStageStride + kRed * kFoldGroups + 64) * sizeof(double))) return e;
+  if (int e = op->state.reserve(sizeof(SolverState) + 64)) return e;
+  if (int e = op->scanws.reserve(scan_workspace_bytes(N + 1) + 64)) return e;
+  if (int e = op->host_state.reserve(sizeof(SolverState) + 64)) return e;
   *reinterpret_cast<int32_t*>(op->host_state + 1) = 0;  // length of the compact active lists: not known yet
   int32_t* deg = op->cursor.as<int32_t>();
   int* bad = reinterpret_cast<int*>(op->state.as<char>() + sizeof(SolverState));
-  hipError_t he = hipMemsetAsync(deg, 0, (N + 1) * sizeof(int32_t), s);
-  if (he == hipSuccess) he = hipMemsetAsync(op->state.ptr, 0, sizeof(SolverState) + 64, s);
-  if (he == hipSuccess) he = hipMemsetAsync(op->vel.ptr, 0, (6 * N + 2) * sizeof(double), s);
-  if (he != hipSuccess) return bail(fail(MHIP_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(he)));
+  MHIP_HIP(hipMemsetAsync(deg, 0, (N + 1) * sizeof(int32_t), s));
+  MHIP_HIP(hipMemsetAsync(op->state.ptr, 0, sizeof(SolverState) + 64, s));
+  MHIP_HIP(hipMemsetAsync(op->vel.ptr, 0, (6 * N + 2) * sizeof(double), s));
   const int2* p2 = reinterpret_cast<const int2*>(pairs);
-  if (int e = op->body_mask.reserve((N + 2) * sizeof(unsigned long long))) return bail(e);
-  if (int e = op->pos.reserve(2 * C + 16)) return bail(e);
+  if (int e = op->body_mask.reserve((N + 2) * sizeof(unsigned long long))) return e;
+  if (int e = op->pos.reserve(2 * C + 16)) return e;
   bool pos_built = false;
   bool sorted_rows = false;   // the list has the broad phase's form: rows sorted by the lower body, i < j
   if (C > 0) {
     // first the fast path's count (it validates the indices as well); a list of another form takes the general path
-    if (int e = op->acnt.reserve((N + 2) * sizeof(int32_t))) return bail(e);
-    if (int e = op->aptr.reserve((N + 2) * sizeof(int32_t))) return bail(e);
+    if (int e = op->acnt.reserve((N + 2) * sizeof(int32_t))) return e;
+    if (int e = op->aptr.reserve((N + 2) * sizeof(int32_t))) return e;
     int32_t* row_start = op->aptr.as<int32_t>();   // (both free until the first snapshot of the active lists)
     k_inc_count_sorted<<<grid_for(C), kBlock, 0, s>>>(C, N, p2, deg, row_start, bad);
     // (the degrees too before the one host read: deg -> tdeg, deg = tdeg + rows; meaningless if the list is of another
     //  form, and then not used)
-    he = hipMemcpyAsync(op->acnt.ptr, deg, (N + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s);
-    if (he != hipSuccess) return bail(fail(MHIP_ERR_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(he)));
+    MHIP_HIP(hipMemcpyAsync(op->acnt.ptr, deg, (N + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     k_inc_deg<<<grid_for(N), kBlock, 0, s>>>(N, op->acnt.as<int32_t>(), row_start, deg, bad);
     int hflags[3] = {0, 0, 0};
-    he = hipMemcpyAsync(hflags, bad, 3 * sizeof(int), hipMemcpyDeviceToHost, s);
-    if (he == hipSuccess) he = hipStreamSynchronize(s);
-    if (he != hipSuccess) return bail(fail(MHIP_ERR_HIP, "pair validation failed: %s", hipGetErrorString(he)));
-    if (hflags[0])
-      return bail(fail(MHIP_ERR_INVALID_ARGUMENT, "pairs contain an index outside [0, %zu) or a self pair", N));
+    MHIP_HIP(hipMemcpyAsync(hflags, bad, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+    MHIP_HIP(hipStreamSynchronize(s));
+    MHIP_REQUIRE(!hflags[0], MHIP_ERR_INVALID_ARGUMENT, "pairs contain an index outside [0, %zu) or a self pair", N);
     sorted_rows = hflags[1] == 0 && hflags[2] == 0;
     if (!sorted_rows) {
-      he = hipMemsetAsync(deg, 0, (N + 1) * sizeof(int32_t), s);
-      if (he == hipSuccess) he = hipMemsetAsync(bad, 0, 3 * sizeof(int), s);
-      if (he != hipSuccess) return bail(fail(MHIP_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(he)));
+      MHIP_HIP(hipMemsetAsync(deg, 0, (N + 1) * sizeof(int32_t), s));
+      MHIP_HIP(hipMemsetAsync(bad, 0, 3 * sizeof(int), s));
       k_inc_count<<<grid_for(C), kBlock, 0, s>>>(C, N, p2, deg, bad);
     }
   }
   if (sorted_rows) {
     int32_t* tdeg = op->acnt.as<int32_t>();      // (the target counts; deg holds the lists' lengths: see above)
     int32_t* row_start = op->aptr.as<int32_t>();
-    if (int e = exclusive_scan_i32(deg, op->inc_ptr.as<int32_t>(), N, op->scanws.ptr, s)) return bail(e);
-    he = hipMemsetAsync(deg, 0, (N + 1) * sizeof(int32_t), s);   // now the targets' cursors
-    if (he != hipSuccess) return bail(fail(MHIP_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(he)));
-    if (int e = op->sort_tmp.reserve((2 * C + 2) * sizeof(unsigned))) return bail(e);
+    if (int e = exclusive_scan_i32(deg, op->inc_ptr.as<int32_t>(), N, op->scanws.ptr, s)) return e;
+    MHIP_HIP(hipMemsetAsync(deg, 0, (N + 1) * sizeof(int32_t), s));   // now the targets' cursors
+    if (int e = op->sort_tmp.reserve((2 * C + 2) * sizeof(unsigned))) return e;
     k_inc_fill_sorted<<<grid_for(C), kBlock, 0, s>>>(C, p2, op->inc_ptr.as<int32_t>(), tdeg, deg, row_start,
                                                     op->sort_tmp.as<unsigned>(), priority);
     k_inc_arrange<<<grid_for(N), kBlock, 0, s>>>(N, op->inc_ptr.as<int32_t>(), tdeg, op->sort_tmp.as<unsigned>(),
                                                 op->inc.as<int32_t>(), op->pos.as<unsigned char>());
     pos_built = true;
   } else {
-    if (int e = exclusive_scan_i32(deg, op->inc_ptr.as<int32_t>(), N, op->scanws.ptr, s)) return bail(e);
-    he = hipMemcpyAsync(deg, op->inc_ptr.ptr, (N + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s);
-    if (he != hipSuccess) return bail(fail(MHIP_ERR_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(he)));
+    if (int e = exclusive_scan_i32(deg, op->inc_ptr.as<int32_t>(), N, op->scanws.ptr, s)) return e;
+    MHIP_HIP(hipMemcpyAsync(deg, op->inc_ptr.ptr, (N + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     if (C > 0) {
       k_inc_fill<<<grid_for(C), kBlock, 0, s>>>(C, p2, deg, op->inc.as<int32_t>(), priority);
-      if (int e = op->sort_tmp.reserve((2 * C + 2) * sizeof(unsigned))) return bail(e);
-      if (int e = op->sort_list.reserve((N + 32) * sizeof(int32_t))) return bail(e);
+      if (int e = op->sort_tmp.reserve((2 * C + 2) * sizeof(unsigned))) return e;
+      if (int e = op->sort_list.reserve((N + 32) * sizeof(int32_t))) return e;
       if (int e = sort_segments_u32(N, op->inc_ptr.as<int32_t>(), op->inc.as<unsigned>(), op->sort_tmp.as<unsigned>(), 32,
                                     op->sort_list.as<int32_t>(), s))
-        return bail(e);
+        return e;
       if (priority) k_clear_class_bit<<<grid_for(2 * C), kBlock, 0, s>>>(2 * C, op->inc.as<int32_t>());
     }
   }
-  he = hipGetLastError();
-  if (he != hipSuccess) return bail(fail(MHIP_ERR_HIP, "incidence build failed: %s", hipGetErrorString(he)));
+  MHIP_LAUNCH_CHECK();  // the incidence build
   const int hw = (kin == KIN_RIGID) ? 6 : (kin == KIN_ROD ? 4 : 3);
-  if (int e = op->half.reserve((2 * C + 2) * hw * sizeof(double))) return bail(e);
+  if (int e = op->half.reserve((2 * C + 2) * hw * sizeof(double))) return e;
   if (kin == KIN_ROD) {
-    if (int e = op->axis.reserve((3 * N + 2) * sizeof(double))) return bail(e);
-    if (int e = op->omega.reserve((3 * N + 2) * sizeof(double))) return bail(e);
-    he = hipMemsetAsync(op->omega.ptr, 0, (3 * N + 2) * sizeof(double), s);
-    if (he != hipSuccess) return bail(fail(MHIP_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(he)));
+    if (int e = op->axis.reserve((3 * N + 2) * sizeof(double))) return e;
+    if (int e = op->omega.reserve((3 * N + 2) * sizeof(double))) return e;
+    MHIP_HIP(hipMemsetAsync(op->omega.ptr, 0, (3 * N + 2) * sizeof(double), s));
     if (N > 0) k_rod_axes<<<grid_for(N), kBlock, 0, s>>>(N, seg, op->axis.as<double>());
   }
   if (C > 0) {
@@ -3462,8 +3450,7 @@ static int create_contact_op(mhip_contact_op_t* handle, int kin, size_t num_cons
     else if (kin == KIN_RIGID) k_half_build<KIN_RIGID><<<grid_for(ne), kBlock, 0, s>>>(ne, inc, normal, ra, rb, arc_s, arc_t, half);
     else k_half_build<KIN_TRANS><<<grid_for(ne), kBlock, 0, s>>>(ne, inc, normal, ra, rb, arc_s, arc_t, half);
   }
-  he = hipGetLastError();
-  if (he != hipSuccess) return bail(fail(MHIP_ERR_HIP, "half-edge build failed: %s", hipGetErrorString(he)));
+  MHIP_LAUNCH_CHECK();  // the half-edge build
   {
     // G lanes per body, each keeping U half-edge chains in flight.  Measured at 10^6 rods (mean degree 15.2, a third
     // of it active; MI355X), walking every entry: (16,1) 0.198 ms, (8,1) 0.164, (8,2) 0.154, (4,4) 0.157, (8,4) 0.150
@@ -3483,8 +3470,7 @@ static int create_contact_op(mhip_contact_op_t* handle, int kin, size_t num_cons
   if (N > 0 && C > 0 && !pos_built) {
     k_pos_build<<<grid_for(N), kBlock, 0, s>>>(N, op->inc_ptr.as<int32_t>(), op->inc.as<int32_t>(),
                                               op->pos.as<unsigned char>());
-    he = hipGetLastError();
-    if (he != hipSuccess) return bail(fail(MHIP_ERR_HIP, "slot table build failed: %s", hipGetErrorString(he)));
+    MHIP_LAUNCH_CHECK();  // the slot table build
   }
   op->view.body_mask = op->body_mask.as<unsigned long long>();
   op->view.pos = op->pos.as<unsigned char>();
@@ -3492,7 +3478,7 @@ static int create_contact_op(mhip_contact_op_t* handle, int kin, size_t num_cons
   // FETCH_SIZE per launch 740 -> 637 MB (k_constraint) and 683 -> 621 MB (k_body), k_constraint 0.1305 -> 0.128 ms,
   // k_body unchanged.  mhip_contact_op_set_work_mapping overrides (0 = identity mapping).
   op->view.xcd_aware = 32;
-  *handle = op;
+  *handle = owner.release();
   return MHIP_SUCCESS;
 }
 
@@ -3575,28 +3561,17 @@ int mhip_contact_op_destroy(mhip_contact_op_t op) {
   // whatever still runs on the operator's stream reads these buffers: wait before they can be handed on
   // (hipFree, which this replaces, synchronised the whole device)
   (void)hipStreamSynchronize(op->last_stream);
-  OpWorkspaces w;
-  for (int k = 0; k < kOpBuffers; ++k) w.buf[k] = *op_buffers(op, k);
-  w.host_state = op->host_state;
-  w.events.swap(op->events);
-  const int home = op->device;  // the device the buffers were allocated on, whatever device is current now
+  std::unique_ptr<OpWorkspaces> w(new OpWorkspaces(std::move(*op)));
   delete op;
-  {
-    std::lock_guard<std::mutex> lock(g_spare_mutex);
-    if (!g_spare.held && home >= 0) {
-      g_spare = std::move(w);
-      g_spare.held = true;
-      g_spare.device = home;
-      return MHIP_SUCCESS;
-    }
-  }
-  free_workspaces(w);
-  return MHIP_SUCCESS;
+  std::lock_guard<std::mutex> lock(g_spare_mutex);
+  if (!g_spare && w->device >= 0) g_spare = w.release();  // (the device the buffers were allocated on)
+  return MHIP_SUCCESS;  // a second destroyed operator's set is freed here, with w
 }
 
 int mhip_release_cached_workspaces(void) {
   std::lock_guard<std::mutex> lock(g_spare_mutex);
-  free_workspaces(g_spare);
+  delete g_spare;
+  g_spare = nullptr;
   return MHIP_SUCCESS;
 }
 
@@ -3773,9 +3748,9 @@ int mhip_bbpgd_solve_contact(mhip_contact_op_t op, const double* q, const mhip_s
   MHIP_LAUNCH_CHECK();
   unsigned enqueued = 0, chunk = 8, last_todo = 0, iter_before = 0;
   const bool prof = op->profile;
-  if (prof && op->events.empty()) {
-    op->events.resize(3 * 64);
-    for (auto& ev : op->events) MHIP_HIP(hipEventCreate(&ev));
+  if (prof && op->events.v.empty()) {
+    op->events.v.resize(3 * 64);
+    for (auto& ev : op->events.v) MHIP_HIP(hipEventCreate(&ev));
   }
   // cold tier (see "Cold tier"): from the first snapshot on, where the problem is of the kind it covers
   mhip_contact_op::Tier& tier = op->tier;
@@ -3795,7 +3770,7 @@ int mhip_bbpgd_solve_contact(mhip_contact_op_t op, const double* q, const mhip_s
       }
       op->tier.tracking = false;
       const size_t C2 = op->view.C;
-      const TierGeo geo = tier_geo_at(op->tier.geo[op->tier.set].ptr, C2);
+      const TierGeo geo = tier_geo_at(op->tier_geo[op->tier.set].ptr, C2);
       k_tier_remap_inc<<<grid_for(2 * C2), kBlock, 0, op->last_stream>>>(2 * C2, op->inc.as<int32_t>(), geo.orig);
       (void)hipStreamSynchronize(op->last_stream);
       const int xa = op->view.xcd_aware;
@@ -3815,8 +3790,8 @@ int mhip_bbpgd_solve_contact(mhip_contact_op_t op, const double* q, const mhip_s
       if (eff > last_todo) eff = last_todo;
       for (unsigned k = 0; k < eff; k += kProfileStride) {  // every kProfileStride-th iteration is bracketed
         float a = 0.f, b = 0.f;
-        MHIP_HIP(hipEventElapsedTime(&a, op->events[3 * k], op->events[3 * k + 1]));
-        MHIP_HIP(hipEventElapsedTime(&b, op->events[3 * k + 1], op->events[3 * k + 2]));
+        MHIP_HIP(hipEventElapsedTime(&a, op->events.v[3 * k], op->events.v[3 * k + 1]));
+        MHIP_HIP(hipEventElapsedTime(&b, op->events.v[3 * k + 1], op->events.v[3 * k + 2]));
         op->body_ms += a;
         op->constraint_ms += b;
         op->timed_iterations += 1;
@@ -3868,9 +3843,9 @@ int mhip_bbpgd_solve_contact(mhip_contact_op_t op, const double* q, const mhip_s
 #endif
     for (unsigned k = 0; k < todo; ++k) {
       const bool pk = prof && (k % kProfileStride == 0);
-      if (pk) MHIP_HIP(hipEventRecord(op->events[3 * k], s));
+      if (pk) MHIP_HIP(hipEventRecord(op->events.v[3 * k], s));
       if (int e = op_launch_body(op, X_SOLVE, cur.P0, cur.P1, nullptr, nullptr, sp, s, true)) return e;
-      if (pk) MHIP_HIP(hipEventRecord(op->events[3 * k + 1], s));
+      if (pk) MHIP_HIP(hipEventRecord(op->events.v[3 * k + 1], s));
       unsigned np = cgrid;
       size_t ps = cgrid;
       if (tier.active) {
@@ -3879,7 +3854,7 @@ int mhip_bbpgd_solve_contact(mhip_contact_op_t op, const double* q, const mhip_s
       } else {
         if (int e = op_launch_constraint(op, X_SOLVE, cur.P0, cur.P1, nullptr, nullptr, q, sp, rk, cgrid, s, true)) return e;
       }
-      if (pk) MHIP_HIP(hipEventRecord(op->events[3 * k + 2], s));
+      if (pk) MHIP_HIP(hipEventRecord(op->events.v[3 * k + 2], s));
       double* pp = parts;
       if (np > MHIP_FOLD_ABOVE) {
         // (folded records behind the kRed planes of partials, as fold_partials places them; the ticket word lives in
@@ -4146,7 +4121,7 @@ int mhip_bbpgd_stage_begin(mhip_contact_op_t op, const double* q, const mhip_spa
   op->stage.pause_on_bad_step = op->tiering != 0 && tier_problem_kind(sp, config->residual_kind);
   mhip_contact_op::Tier& tier = op->tier;
   if (tier.active) {  // a staged solve that ended in an error left the operator in the tier numbering
-    const TierGeo geo = tier_geo_at(tier.geo[tier.set].ptr, C);
+    const TierGeo geo = tier_geo_at(op->tier_geo[tier.set].ptr, C);
     k_tier_remap_inc<<<grid_for(2 * C), kBlock, 0, as_stream(stream)>>>(2 * C, op->inc.as<int32_t>(), geo.orig);
     MHIP_LAUNCH_CHECK();
     op->view.pairs = tier.saved.pairs;   // (the caller's arrays; everything else of the view is the caller's to set)
@@ -4199,7 +4174,7 @@ int mhip_bbpgd_stage_constraint_range(mhip_contact_op_t op, int init, size_t c_f
     hipStream_t s = as_stream(stream);
     const SolverState* sst = op->state.as<SolverState>();
     double* parts = op->partials.as<double>();
-    const TierMisc m = tier_misc_at(tier.misc.ptr, op->view.C, op->view.N);
+    const TierMisc m = tier_misc_at(op->tier_misc.ptr, op->view.C, op->view.N);
     OpView vw = op->view;
     vw.part_offset = st.part_used;
     vw.part_stride = kStageStride;

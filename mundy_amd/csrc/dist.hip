@@ -101,8 +101,8 @@ struct mhip_comm {
     bool open = false;
     void* own = nullptr;             // this rank's box
     std::vector<void*> mapped;       // the other ranks' boxes as mapped here (null at this rank's place)
-    DeviceBuffer peers;              // [world] device array of box pointers
-    DeviceBuffer status;             // [0] != 0: an exchange timed out (sticky); [1] = exchanges made (device-counted)
+    HandleBuffer peers;              // [world] device array of box pointers
+    HandleBuffer status;             // [0] != 0: an exchange timed out (sticky); [1] = exchanges made (device-counted)
   } mbox;
   // Velocity halo without the collective library (mhip_comm_halo_ipc_enable): every rank owns an INBOX of fine-grained
   // memory, one slot of kHaloWords 8-byte words per local body row, IPC-mapped by all the others.  After its body sweep
@@ -129,7 +129,7 @@ struct mhip_comm {
   // what the last distributed solve used (mhip_dist_profile reports it)
   int last_halo_path = 0, last_record_path = 0;
   // work buffers of the distributed solve
-  DeviceBuffer send_rows, triples;
+  HandleBuffer send_rows, triples;
   std::vector<hipEvent_t> events;
   // ghost plan of the last mhip_ghost_plan: who gets which owned rows, where the ghosts' rows land
   struct GhostPlan {
@@ -137,10 +137,10 @@ struct mhip_comm {
     size_t n = 0, n_lo = 0, n_hi = 0, total_send = 0;
     std::vector<int> send_peer, recv_peer;
     std::vector<size_t> send_rows, recv_first_row, recv_rows;
-    DeviceBuffer send_index;        // owned indices (0-based in the owned block), peer after peer
-    DeviceBuffer send_index_local;  // the same as local indices (+ n_lo): what the velocity halo gathers
-    DeviceBuffer stage;             // counts on their way through the all-gather; packed send rows
-    DeviceBuffer regions;           // this rank's chunk boxes + everybody's, all-gathered
+    HandleBuffer send_index;        // owned indices (0-based in the owned block), peer after peer
+    HandleBuffer send_index_local;  // the same as local indices (+ n_lo): what the velocity halo gathers
+    HandleBuffer stage;             // counts on their way through the all-gather; packed send rows
+    HandleBuffer regions;           // this rank's chunk boxes + everybody's, all-gathered
   } ghost;
   // migration plan of the last mhip_migrate_plan: which owned rows leave for which rank, how many arrive from whom
   struct MigratePlan {
@@ -148,8 +148,9 @@ struct mhip_comm {
     size_t n = 0, n_new = 0, keep = 0, keep_first = 0;
     std::vector<int> send_peer, recv_peer;
     std::vector<size_t> send_first_row, send_rows, recv_rows;
-    DeviceBuffer dest, sortkey, order, hist, stage;
+    HandleBuffer dest, sortkey, order, hist, stage;
   } migrate;
+  ~mhip_comm();  // closes the boxes and the transport in order; the buffers then free themselves
 };
 
 namespace mhip {
@@ -473,7 +474,7 @@ int halo_ipc_plan(mhip_comm* c, const std::vector<size_t>& counts /*[s * W + d]*
     const size_t nl = gp.n_lo + gp.n + gp.n_hi, ng = gp.n_lo + gp.n_hi;
     // (whatever fails on this rank -- an allocation, a copy, a launch -- is a failed trial, never an early return: the
     //  peers are on their way into the all-gather of the outcomes below and must find this rank there)
-    DeviceBuffer tv;
+    HandleBuffer tv;
     std::vector<double> hv(6 * nl, -1.0);
     for (size_t r = gp.n_lo; r < gp.n_lo + gp.n; ++r)
       for (int k = 0; k < 6; ++k) hv[6 * r + k] = 1000.0 * (double)(c->rank + 1) + 0.125 * k;
@@ -576,9 +577,7 @@ void mailbox_close(mhip_comm* c) {
   for (void* p : c->mbox.mapped)
     if (p) (void)hipIpcCloseMemHandle(p);
   if (c->mbox.own) (void)hipFree(c->mbox.own);
-  c->mbox.peers.release();
-  c->mbox.status.release();
-  c->mbox = mhip_comm::Mailbox{};
+  c->mbox = mhip_comm::Mailbox{};  // (the move assignment releases `peers` and `status`)
 }
 
 }  // namespace mhip
@@ -744,7 +743,7 @@ int mhip_comm_create_rccl(mhip_comm_t* comm, const unsigned char* id, int rank, 
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ready, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->done, hipEventDisableTiming);
   if (e != hipSuccess) {
-    mhip_comm_destroy(c);
+    delete c;
     return fail(MHIP_ERR_HIP, "communicator stream / events: %s", hipGetErrorString(e));
   }
   *comm = c;
@@ -767,24 +766,18 @@ int mhip_comm_create_host(mhip_comm_t* comm, int rank, int world, mhip_comm_exch
   return MHIP_SUCCESS;
 }
 
+mhip_comm::~mhip_comm() {
+  for (auto ev : events) (void)hipEventDestroy(ev);
+  mailbox_close(this);
+  if (comm_stream) (void)hipStreamSynchronize(comm_stream);
+  halo_ipc_close(this);
+  if (nccl) (void)rccl().CommDestroy(nccl);
+  if (ready) (void)hipEventDestroy(ready);
+  if (done) (void)hipEventDestroy(done);
+  if (comm_stream) (void)hipStreamDestroy(comm_stream);
+}
+
 int mhip_comm_destroy(mhip_comm_t c) {
-  if (!c) return MHIP_SUCCESS;
-  for (auto ev : c->events) (void)hipEventDestroy(ev);
-  c->send_rows.release();
-  c->triples.release();
-  c->ghost.send_index.release();
-  c->ghost.send_index_local.release();
-  c->ghost.stage.release();
-  c->ghost.regions.release();
-  for (DeviceBuffer* b : {&c->migrate.dest, &c->migrate.sortkey, &c->migrate.order, &c->migrate.hist, &c->migrate.stage})
-    b->release();
-  mailbox_close(c);
-  if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
-  halo_ipc_close(c);
-  if (c->nccl) (void)rccl().CommDestroy(c->nccl);
-  if (c->ready) (void)hipEventDestroy(c->ready);
-  if (c->done) (void)hipEventDestroy(c->done);
-  if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
   delete c;
   return MHIP_SUCCESS;
 }

@@ -1,8 +1,8 @@
 // force_device.hpp -- what the soft-force sources (hertz.hip, hertz_friction.hip, chain.hip, crosslink.hip, periphery.hip,
 // active.hip) share: the statistic epilogues, the spring and Hertz pair terms, the counter-based generator every
 // reference app draws from, the per-body force write, the body -> entry incidence build, the run-time flag -> template
-// argument dispatch and the lifetime of a handle's buffers.  (Not in mhip_internal.hpp: that header is part of the stamp
-// the measured solver traffic carries, build.py::sweep_kernels_stamp.)
+// argument dispatch.  (The lifetime of a handle's buffers -- HandleBuffer -- lives in mhip_internal.hpp, next to the
+// destructor-less DeviceBuffer of the process-lifetime scratch, so that every handle of the library shares one type.)
 #pragma once
 #include "mhip_internal.hpp"
 
@@ -11,25 +11,7 @@
 
 namespace mhip {
 
-// ---- host: handle buffers, HIP status, flag dispatch -------------------------------------------------------------
-// A buffer owned by a heap-allocated handle: released with it.  (DeviceBuffer itself has no destructor: static and
-// thread_local buffers would call hipFree during process teardown.)
-struct HandleBuffer : DeviceBuffer {
-  HandleBuffer() = default;
-  HandleBuffer(const HandleBuffer&) = delete;
-  HandleBuffer& operator=(const HandleBuffer&) = delete;
-  ~HandleBuffer() { release(); }
-};
-
-// a HIP error as the status of the function `fn`: hip_status(__func__, hipMemcpyAsync(...))
-inline int hip_status(const char* fn, hipError_t err) {
-  return err == hipSuccess ? MHIP_SUCCESS : fail(MHIP_ERR_HIP, "%s: %s", fn, hipGetErrorString(err));
-}
-// a caller's host array into a handle's buffer
-inline int upload(const char* fn, HandleBuffer& dst, const void* src, size_t bytes, hipStream_t s) {
-  return hip_status(fn, hipMemcpyAsync(dst.ptr, src, bytes, hipMemcpyHostToDevice, s));
-}
-
+// ---- host: flag dispatch (HandleBuffer, hip_status and upload live in mhip_internal.hpp) ----------------------------
 // A run-time flag (a bool or a small enum) becomes a template argument: f(std::integral_constant<T, V>{}) for the first V
 // of the list equal to v, for the last one when none is; inside f, decltype(arg)::value.  (convex.hip keeps its own
 // pick<> of the same shape: that file is part of the solver stamp and is not edited for this.)

@@ -284,7 +284,7 @@ static void launch_hydro(bool partial, dim3 grid, const HydroArgs& a, hipStream_
 using namespace mhip;
 
 struct mhip_hydro {
-  DeviceBuffer partial;  // grow-only: [chunk][target][3] of the largest partial-shape call so far
+  HandleBuffer partial;  // grow-only: [chunk][target][3] of the largest partial-shape call so far
   int path = MHIP_HYDRO_PATH_AUTO;
   int last_path = MHIP_HYDRO_PATH_AUTO;
 };
@@ -298,7 +298,6 @@ int mhip_hydro_create(mhip_hydro_t* handle) {
 }
 
 int mhip_hydro_destroy(mhip_hydro_t h) {
-  if (h) h->partial.release();
   delete h;
   return MHIP_SUCCESS;
 }

@@ -2,11 +2,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 
 #include "../../include/mundy_hip.h"
 
@@ -55,30 +57,129 @@ inline unsigned grid_exact(size_t n, int block = kBlock) {
   return static_cast<unsigned>(g == 0 ? 1 : g);
 }
 
-// A device buffer that only ever grows (workspace owned by a handle; never allocated inside a timed loop once warm).
+// ------------------------------------------------------------------------------------------------------------------
+// memory the library owns: two device buffer types and a pinned block, counted for mhip_memory_stats
+// ------------------------------------------------------------------------------------------------------------------
+// Relaxed counters, touched by reserve / release only (neither runs in a warm step).  Not counted: mhip_malloc, the
+// IPC boxes of dist.hip (hipExtMallocWithFlags / hipIpcOpenMemHandle) and the 64-byte pinned words of the scratch
+// structs.
+struct MemoryCounters {
+  std::atomic<size_t> handle_bytes{0}, scratch_bytes{0}, pinned_bytes{0}, allocations{0};
+};
+inline MemoryCounters g_memory;
+
+// A device buffer that only ever grows, with NO destructor.  The only place it may appear is the per-thread or
+// per-process scratch that lives until the process exits (ReduceScratch, ReorderScratch, SortScratch, MixedScratch,
+// CarryScratch, GrowthScratch, EllipsoidScratch, HaloScratch): a destructor there would call hipFree during process
+// teardown, after the runtime may be gone.  Everything a heap-allocated handle owns is a HandleBuffer (below); a local
+// variable of this type is a leak by construction.
 struct DeviceBuffer {
   void* ptr = nullptr;
   size_t bytes = 0;
-  int reserve(size_t need) {
-    if (need <= bytes) return MHIP_SUCCESS;
-    if (ptr) MHIP_HIP(hipFree(ptr));
-    ptr = nullptr;
-    bytes = 0;
-    const size_t want = need + need / 4 + 256;
-    MHIP_HIP(hipMalloc(&ptr, want));
-    bytes = want;
-    return MHIP_SUCCESS;
-  }
-  void release() {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    bytes = 0;
-  }
+  int reserve(size_t need) { return reserve_counted(need, g_memory.scratch_bytes); }
+  void release() { release_counted(g_memory.scratch_bytes); }
   template <class T>
   T* as() const {
     return static_cast<T*>(ptr);
   }
+
+ protected:
+  int reserve_counted(size_t need, std::atomic<size_t>& held) {
+    if (need <= bytes) return MHIP_SUCCESS;
+    release_counted(held);
+    const size_t want = need + need / 4 + 256;
+    MHIP_HIP(hipMalloc(&ptr, want));
+    bytes = want;
+    held.fetch_add(want, std::memory_order_relaxed);
+    g_memory.allocations.fetch_add(1, std::memory_order_relaxed);
+    return MHIP_SUCCESS;
+  }
+  void release_counted(std::atomic<size_t>& held) {
+    if (ptr) (void)hipFree(ptr);
+    held.fetch_sub(bytes, std::memory_order_relaxed);
+    ptr = nullptr;
+    bytes = 0;
+  }
 };
+
+// The same buffer owned by a heap-allocated handle (or by a local variable): released with its owner, movable, not
+// copyable.  Move assignment releases what the target held first.
+struct HandleBuffer : DeviceBuffer {
+  HandleBuffer() = default;
+  HandleBuffer(const HandleBuffer&) = delete;
+  HandleBuffer& operator=(const HandleBuffer&) = delete;
+  HandleBuffer(HandleBuffer&& o) noexcept { take(o); }
+  HandleBuffer& operator=(HandleBuffer&& o) noexcept {
+    if (this != &o) {
+      release();
+      take(o);
+    }
+    return *this;
+  }
+  ~HandleBuffer() { release(); }
+  int reserve(size_t need) { return reserve_counted(need, g_memory.handle_bytes); }
+  void release() { release_counted(g_memory.handle_bytes); }
+
+ private:
+  void take(HandleBuffer& o) {
+    ptr = o.ptr;
+    bytes = o.bytes;
+    o.ptr = nullptr;
+    o.bytes = 0;
+  }
+};
+static_assert(std::is_trivially_destructible_v<DeviceBuffer>, "scratch buffers must not run a destructor at exit");
+static_assert(!std::is_copy_constructible_v<HandleBuffer> && std::is_nothrow_move_constructible_v<HandleBuffer> &&
+                  !std::is_trivially_destructible_v<HandleBuffer>,
+              "a handle's buffer has one owner and is freed with it");
+
+// A pinned host block owned by a handle: T followed by whatever spare bytes the owner asked for.  Used like the T* it
+// replaces (block->field, block[i], block + 1).  The scratch structs keep raw `host` pointers, for DeviceBuffer's reason.
+template <class T>
+struct PinnedBlock {
+  PinnedBlock() = default;
+  PinnedBlock(const PinnedBlock&) = delete;
+  PinnedBlock& operator=(const PinnedBlock&) = delete;
+  PinnedBlock(PinnedBlock&& o) noexcept : ptr_(o.ptr_), bytes_(o.bytes_) { o.ptr_ = nullptr, o.bytes_ = 0; }
+  PinnedBlock& operator=(PinnedBlock&& o) noexcept {
+    if (this != &o) {
+      release();
+      ptr_ = o.ptr_, bytes_ = o.bytes_;
+      o.ptr_ = nullptr, o.bytes_ = 0;
+    }
+    return *this;
+  }
+  ~PinnedBlock() { release(); }
+  int reserve(size_t need) {  // allocated once: a later call asks for the same size
+    if (need <= bytes_) return MHIP_SUCCESS;
+    release();
+    MHIP_HIP(hipHostMalloc(reinterpret_cast<void**>(&ptr_), need));
+    bytes_ = need;
+    g_memory.pinned_bytes.fetch_add(need, std::memory_order_relaxed);
+    g_memory.allocations.fetch_add(1, std::memory_order_relaxed);
+    return MHIP_SUCCESS;
+  }
+  void release() {
+    if (ptr_) (void)hipHostFree(ptr_);
+    g_memory.pinned_bytes.fetch_sub(bytes_, std::memory_order_relaxed);
+    ptr_ = nullptr, bytes_ = 0;
+  }
+  operator T*() const { return ptr_; }
+  T* operator->() const { return ptr_; }
+
+ private:
+  T* ptr_ = nullptr;
+  size_t bytes_ = 0;
+};
+
+// a HIP error as the status of the function `fn`: hip_status(__func__, hipMemcpyAsync(...))
+inline int hip_status(const char* fn, hipError_t err) {
+  return err == hipSuccess ? MHIP_SUCCESS : fail(MHIP_ERR_HIP, "%s: %s", fn, hipGetErrorString(err));
+}
+// a caller's host array into a handle's buffer
+inline int upload(const char* fn, HandleBuffer& dst, const void* src, size_t bytes, hipStream_t s) {
+  return hip_status(fn, hipMemcpyAsync(dst.ptr, src, bytes, hipMemcpyHostToDevice, s));
+}
 
 // ------------------------------------------------------------------------------------------------------------------
 // device math: the mundy::math subset the path needs, same operation order as the reference

@@ -213,6 +213,13 @@ int mhip_free(void* ptr) {
   if (ptr) MHIP_HIP(hipFree(ptr));
   return MHIP_SUCCESS;
 }
+int mhip_memory_stats(size_t* handle_bytes, size_t* scratch_bytes, size_t* pinned_bytes, size_t* allocations) {
+  if (handle_bytes) *handle_bytes = g_memory.handle_bytes.load(std::memory_order_relaxed);
+  if (scratch_bytes) *scratch_bytes = g_memory.scratch_bytes.load(std::memory_order_relaxed);
+  if (pinned_bytes) *pinned_bytes = g_memory.pinned_bytes.load(std::memory_order_relaxed);
+  if (allocations) *allocations = g_memory.allocations.load(std::memory_order_relaxed);
+  return MHIP_SUCCESS;
+}
 int mhip_memcpy_h2d(void* dst, const void* src_host, size_t bytes, mhip_stream_t stream) {
   if (bytes == 0) return MHIP_SUCCESS;
   MHIP_HIP(hipMemcpyAsync(dst, src_host, bytes, hipMemcpyHostToDevice, as_stream(stream)));

@@ -5,8 +5,8 @@
 // record, and every entry point that touches the scratch claims it before its first use (its reserve() included: a
 // growing buffer is freed).  Entry points whose scratch is only ever used by calls that synchronise before they return
 // (growth.hip, halo.hip, the blocking reductions of convex.hip) need none.
-// (Not in mhip_internal.hpp: that header is part of the stamp the measured solver traffic carries,
-// build.py::sweep_kernels_stamp.)
+// The scratch is made of mhip_internal.hpp's DeviceBuffer, which has no destructor (thread_local objects would call
+// hipFree during teardown); what a heap-allocated handle owns is a HandleBuffer, defined next to it.
 #pragma once
 #include "mhip_internal.hpp"
 

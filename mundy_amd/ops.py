@@ -97,6 +97,15 @@ def device_info():
     return n.value, name.value.decode()
 
 
+def memory_stats():
+    """What the library holds in this process (mhip_memory_stats; no HIP call): device bytes owned by live handles and
+    the spare workspace set, device bytes of the process-lifetime scratch, pinned host bytes, allocation calls so far."""
+    names = ("handle_bytes", "scratch_bytes", "pinned_bytes", "allocations")
+    vals = [C.c_size_t(0) for _ in names]
+    capi.check(capi.load().mhip_memory_stats(*[C.byref(v) for v in vals]))
+    return {k: v.value for k, v in zip(names, vals)}
+
+
 # ---- per-body geometry (compute_aabb.hpp / compute_bounding_radius.hpp) --------------------------------------------
 def compute_aabb_spheres(center, radius):
     n = radius.shape[0]

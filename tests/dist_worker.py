@@ -1,6 +1,7 @@
 """Worker of tests/test_gpu_distributed.py: `python -m torch.distributed.run --nproc-per-node W tests/dist_worker.py`.
 All ranks share cuda:0 (gloo carries the halo through the host), each owns a Hilbert range of one global rod system;
 rank 0 also solves the whole system on one rank and checks the distributed result against it."""
+import gc
 import os
 import sys
 
@@ -18,7 +19,7 @@ def main():
     dist.init_process_group(backend="gloo")
     rank, world = dist.get_rank(), dist.get_world_size()
     torch.cuda.set_device(0)
-    from mundy_amd import distributed as D, ops, pipeline, synth
+    from mundy_amd import capi, distributed as D, ops, pipeline, synth
 
     mixed = os.environ.get("DIST_MIXED", "0") == "1"   # BASELINE configs[4]: spheres + rods + ellipsoids
     phi, buf = float(os.environ.get("DIST_PHI", "0.4")), float(os.environ.get("DIST_BUFFER", "0.1"))
@@ -206,6 +207,23 @@ def main():
                 good = good and same
             ok = ok and good
             print("DIST_TRAJECTORY", "PASS" if good else "FAIL")
+    # everything closed, the spare set released: the library holds no device or pinned memory of its own (the
+    # communicator's destructor; where the inboxes opened, the trial exchange's table too)
+    handles = [st.op, st.links, st.comm] + ([ref.op, ref.links] if rank == 0 else [])
+    st = ref = None
+    for h in handles:
+        if h is not None:
+            h.close()
+    gc.collect()
+    capi.check(capi.load().mhip_release_cached_workspaces())
+    m = ops.memory_stats()
+    left = [None] * world if rank == 0 else None
+    dist.gather_object((m["handle_bytes"], m["pinned_bytes"]), left, dst=0)
+    if rank == 0:
+        checks["handle bytes 0 after close"] = all(v == (0, 0) for v in left)
+        print(("ok   " if checks["handle bytes 0 after close"] else "FAIL ") +
+              "handle bytes 0 after close: (handle, pinned) per rank %s" % left)
+        ok = ok and checks["handle bytes 0 after close"]
     flag = torch.tensor([1 if ok else 0])
     dist.broadcast(flag, src=0)
     dist.destroy_process_group()

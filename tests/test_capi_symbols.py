@@ -39,6 +39,17 @@ def test_version_and_error_channel(lib):
     assert isinstance(lib.mhip_last_error(), bytes)
 
 
+def test_memory_stats_without_a_device(lib):
+    # counters only, no HIP call: nothing has been reserved in a process that never reached a device
+    import torch
+    from mundy_amd import ops
+    m = ops.memory_stats()
+    assert sorted(m) == ["allocations", "handle_bytes", "pinned_bytes", "scratch_bytes"]
+    if not torch.cuda.is_available():   # (with a device, earlier tests of the same process have allocated)
+        assert m == dict(handle_bytes=0, scratch_bytes=0, pinned_bytes=0, allocations=0)
+    assert lib.mhip_memory_stats(None, None, None, None) == 0   # any pointer may be null
+
+
 def test_missing_library_is_loud(monkeypatch, tmp_path):
     from mundy_amd import capi
     monkeypatch.setattr(capi, "_lib", None)
