@@ -317,6 +317,22 @@ SIGNATURES = {
                                              C.POINTER(PgdConfig), _vp, _vp, _vp, _vp, C.c_uint,
                                              C.POINTER(SolveResult), C.POINTER(DistProfile), _vp],
 }
+# include/mundy_hip_hydro_periphery.h, a header of its own (its first comment says why): name -> argtypes, every
+# function returns int status.  tests/test_hydro_periphery_host.py checks this table against that header and the library.
+HYDRO_PERIPHERY_EMPTY, HYDRO_PERIPHERY_MATRIX, HYDRO_PERIPHERY_INVERSE, HYDRO_PERIPHERY_DOUBLE_LAYER = 0, 1, 2, 3
+PERIPHERY_SIGNATURES = {
+    "mhip_hydro_periphery_create": [C.POINTER(_vp), _sz, _vp, _vp, _vp, _d, _vp],
+    "mhip_hydro_periphery_destroy": [_vp],
+    "mhip_hydro_periphery_fill_double_layer": [_vp, _vp],
+    "mhip_hydro_periphery_fill_matrix": [_vp, _vp],
+    "mhip_hydro_periphery_set_matrix": [_vp, _vp, _vp],
+    "mhip_hydro_periphery_invert": [_vp, C.POINTER(_d), _vp],
+    "mhip_hydro_periphery_set_inverse": [_vp, _vp, _vp],
+    "mhip_hydro_periphery_matrix": [_vp, C.POINTER(_vp), C.POINTER(_i)],
+    "mhip_hydro_periphery_surface_forces": [_vp, _vp, _vp, _vp],
+    "mhip_hydro_double_layer": [_vp, _d, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _i, _i, _vp],
+    "mhip_hydro_periphery_correct": [_vp, _vp, _i, _sz, _vp, _vp, _vp, _vp, _i, _i, _vp],
+}
 OTHER_SYMBOLS = {"mhip_last_error": ([], C.c_char_p), "mhip_version": ([], C.c_int),
                  "mhip_release_cached_workspaces": ([], C.c_int)}
 
@@ -335,7 +351,7 @@ def load():
         # cannot see torch's device context)
         import torch  # noqa: F401
         lib = C.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
+        for name, argtypes in list(SIGNATURES.items()) + list(PERIPHERY_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = C.c_int

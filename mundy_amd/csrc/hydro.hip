@@ -12,7 +12,11 @@
 //   in-lane   grid = target tiles; a lane walks every chunk with a chunk accumulator and a running total
 //   partial   grid = target tiles x chunk groups (fills the chip when the tiles alone do not); a workgroup writes the
 //             chunk sums of its group to partial[chunk][target][3], k_hydro_reduce adds them in chunk order
+// The Stokes double layer of surface nodes onto points (apply_stokes_double_layer_kernel, Periphery.hpp:1221-1313;
+// mhip_hydro_double_layer of mundy_hip_hydro_periphery.h) is a fourth pair term on the same machinery, with a staged
+// source record of its own (80 bytes) and the reference's `t == s` skip behind a flag.
 #include "mhip_internal.hpp"
+#include "../../include/mundy_hip_hydro_periphery.h"
 
 namespace mhip {
 
@@ -26,8 +30,27 @@ struct __align__(16) HydroSource {  // 64 bytes: (x, y, z, a) (fx, fy, fz, -)
   double x, y, z, a, fx, fy, fz, pad;
 };
 
+// The Stokes double layer of surface nodes onto points (Periphery.hpp:1221-1313), one more pair term on this machinery
+// (mhip_hydro_double_layer, mundy_hip_hydro_periphery.h): not a kind of mhip_hydro_velocity, which refuses it.
+constexpr int kHydroDoubleLayer = 3;
+
+// its staged source: the centre and the six symmetric combinations of s_ij = (n_i f_j) w, which depend on the source
+// alone and are formed once when the tile is staged (the same bits as the reference's per-pair products); 80 bytes
+struct __align__(16) HydroDlSource {
+  double x, y, z, sxx, syy, szz, sxy, sxz, syz, pad;
+};
+
+template <int KIND>
+struct HydroSourceOf {
+  using type = HydroSource;
+};
+template <>
+struct HydroSourceOf<kHydroDoubleLayer> {
+  using type = HydroDlSource;
+};
+
 struct HydroConst {
-  double scale;  // 1 / (8 pi mu), formed once on the host (STOKES, RPY)
+  double scale;  // 1 / (8 pi mu), formed once on the host (STOKES, RPY); double layer: -(3 / (4 pi mu))
   double c8;     // (1/8) (1/pi) (1/mu), the product RPYC's far field starts from
   double c6;     // (1/6) (1/pi) (1/mu), overlapping and local drag
 };
@@ -132,10 +155,36 @@ __device__ inline V3 hydro_term(double dx, double dy, double dz, const HydroSour
   }
 }
 
-// the terms of the sources tile[0 .. cnt) added to acc in ascending order; kHydroInFlight sources in flight
-template <int KIND>
-__device__ inline void hydro_add_tile(const HydroSource* tile, int cnt, double tx, double ty, double tz, double b,
-                                      const HydroConst& k, V3& acc) {
+// Periphery.hpp:1279-1308 with the source's products staged: coeff and d coeff, associated as the reference's lines
+__device__ inline V3 hydro_dl_term(double dx, double dy, double dz, const HydroDlSource& s, const HydroConst& k) {
+  const double r2 = dx * dx + dy * dy + dz * dz;
+  const double rinv = r2 < kHydroZero ? 0.0 : quake_inv_sqrt(r2);
+  const double rinv2 = rinv * rinv;
+  const double rinv5 = rinv * rinv2 * rinv2;
+  double coeff = s.sxx * dx * dx + s.syy * dy * dy + s.szz * dz * dz;
+  coeff += s.sxy * dx * dy;
+  coeff += s.sxz * dx * dz;
+  coeff += s.syz * dy * dz;
+  coeff *= k.scale * rinv5;
+  return {dx * coeff, dy * coeff, dz * coeff};
+}
+
+template <int KIND, class SRC>
+__device__ inline V3 hydro_pair(double dx, double dy, double dz, const SRC& s, double b, const HydroConst& k,
+                                bool* near) {
+  if constexpr (KIND == kHydroDoubleLayer) {
+    *near = false;
+    return hydro_dl_term(dx, dy, dz, s, k);
+  } else {
+    return hydro_term<KIND>(dx, dy, dz, s, b, k, near);
+  }
+}
+
+// the terms of the sources tile[0 .. cnt) added to acc in ascending order; kHydroInFlight sources in flight.
+// skip_j (double layer only): the tile entry whose term is +0.0, the reference's `t == s` return; -1: none
+template <int KIND, class SRC>
+__device__ inline void hydro_add_tile(const SRC* tile, int cnt, double tx, double ty, double tz, double b,
+                                      const HydroConst& k, int skip_j, V3& acc) {
   int j = 0;
   for (; j + kHydroInFlight <= cnt; j += kHydroInFlight) {
     V3 v[kHydroInFlight];
@@ -143,16 +192,19 @@ __device__ inline void hydro_add_tile(const HydroSource* tile, int cnt, double t
     bool any_near = false;
 #pragma unroll
     for (int u = 0; u < kHydroInFlight; ++u) {
-      const HydroSource src = tile[j + u];
-      v[u] = hydro_term<KIND>(tx - src.x, ty - src.y, tz - src.z, src, b, k, &near[u]);
+      const SRC src = tile[j + u];
+      v[u] = hydro_pair<KIND>(tx - src.x, ty - src.y, tz - src.z, src, b, k, &near[u]);
+      if (KIND == kHydroDoubleLayer && j + u == skip_j) v[u] = V3{0.0, 0.0, 0.0};
       any_near |= near[u];
     }
-    if (KIND == MHIP_HYDRO_RPYC && any_near) {
+    if constexpr (KIND == MHIP_HYDRO_RPYC) {  // (the only kind with a near field: the other records have no radius)
+      if (any_near) {
 #pragma unroll
-      for (int u = 0; u < kHydroInFlight; ++u) {
-        if (near[u]) {
-          const HydroSource src = tile[j + u];
-          v[u] = rpyc_near_term(tx - src.x, ty - src.y, tz - src.z, src, b, k);
+        for (int u = 0; u < kHydroInFlight; ++u) {
+          if (near[u]) {
+            const HydroSource src = tile[j + u];
+            v[u] = rpyc_near_term(tx - src.x, ty - src.y, tz - src.z, src, b, k);
+          }
         }
       }
     }
@@ -164,10 +216,13 @@ __device__ inline void hydro_add_tile(const HydroSource* tile, int cnt, double t
     }
   }
   for (; j < cnt; ++j) {
-    const HydroSource src = tile[j];
+    const SRC src = tile[j];
     bool near;
-    V3 v = hydro_term<KIND>(tx - src.x, ty - src.y, tz - src.z, src, b, k, &near);
-    if (KIND == MHIP_HYDRO_RPYC && near) v = rpyc_near_term(tx - src.x, ty - src.y, tz - src.z, src, b, k);
+    V3 v = hydro_pair<KIND>(tx - src.x, ty - src.y, tz - src.z, src, b, k, &near);
+    if constexpr (KIND == MHIP_HYDRO_RPYC) {
+      if (near) v = rpyc_near_term(tx - src.x, ty - src.y, tz - src.z, src, b, k);
+    }
+    if (KIND == kHydroDoubleLayer && j == skip_j) v = V3{0.0, 0.0, 0.0};
     acc.x = acc.x + v.x;
     acc.y = acc.y + v.y;
     acc.z = acc.z + v.z;
@@ -177,14 +232,49 @@ __device__ inline void hydro_add_tile(const HydroSource* tile, int cnt, double t
 struct HydroArgs {
   size_t ns, nt, nchunks, chunks_per_group;
   const double *sc, *sa, *sf, *tc, *tb;
+  const double *sn, *sw;  // double layer: the sources' normals [ns][3] and weights [ns] (sa and tb are not read)
+  int skip_same;          // double layer: the term of source t onto target t is skipped
   double* out;       // in-lane: velocity (stride, accumulate); partial: partial[chunk][target][3]
   int stride, accumulate;
   HydroConst k;
 };
 
+// source s as the kernel stages it in LDS
+template <int KIND>
+__device__ inline typename HydroSourceOf<KIND>::type hydro_stage(const HydroArgs& p, size_t s) {
+  if constexpr (KIND == kHydroDoubleLayer) {
+    const double n0 = p.sn[3 * s], n1 = p.sn[3 * s + 1], n2 = p.sn[3 * s + 2];
+    const double f0 = p.sf[3 * s], f1 = p.sf[3 * s + 1], f2 = p.sf[3 * s + 2];
+    const double w = p.sw[s];
+    HydroDlSource src;
+    src.x = p.sc[3 * s];
+    src.y = p.sc[3 * s + 1];
+    src.z = p.sc[3 * s + 2];
+    src.sxx = n0 * f0 * w;
+    src.syy = n1 * f1 * w;
+    src.szz = n2 * f2 * w;
+    src.sxy = n0 * f1 * w + n1 * f0 * w;
+    src.sxz = n0 * f2 * w + n2 * f0 * w;
+    src.syz = n1 * f2 * w + n2 * f1 * w;
+    src.pad = 0.0;
+    return src;
+  } else {
+    HydroSource src;
+    src.x = p.sc[3 * s];
+    src.y = p.sc[3 * s + 1];
+    src.z = p.sc[3 * s + 2];
+    src.a = (KIND != MHIP_HYDRO_STOKES) ? p.sa[s] : 0.0;
+    src.fx = p.sf[3 * s];
+    src.fy = p.sf[3 * s + 1];
+    src.fz = p.sf[3 * s + 2];
+    src.pad = 0.0;
+    return src;
+  }
+}
+
 template <int KIND, bool PARTIAL>
 __global__ void __launch_bounds__(kBlock) k_hydro(HydroArgs p) {
-  __shared__ HydroSource tile[kBlock];
+  __shared__ typename HydroSourceOf<KIND>::type tile[kBlock];
   const size_t t = blockIdx.x * (size_t)kBlock + threadIdx.x;
   const bool valid = t < p.nt;
   double tx = 0.0, ty = 0.0, tz = 0.0, b = 0.0;
@@ -192,7 +282,7 @@ __global__ void __launch_bounds__(kBlock) k_hydro(HydroArgs p) {
     tx = p.tc[3 * t];
     ty = p.tc[3 * t + 1];
     tz = p.tc[3 * t + 2];
-    if (KIND != MHIP_HYDRO_STOKES) b = p.tb[t];
+    if (KIND != MHIP_HYDRO_STOKES && KIND != kHydroDoubleLayer) b = p.tb[t];
   }
   const size_t c0 = PARTIAL ? blockIdx.y * p.chunks_per_group : 0;
   size_t c1 = PARTIAL ? c0 + p.chunks_per_group : p.nchunks;
@@ -205,21 +295,12 @@ __global__ void __launch_bounds__(kBlock) k_hydro(HydroArgs p) {
     for (size_t s0 = s_begin; s0 < s_end; s0 += kBlock) {
       __syncthreads();  // the previous tile has been read by every wave
       const size_t s = s0 + threadIdx.x;
-      if (s < s_end) {
-        HydroSource src;
-        src.x = p.sc[3 * s];
-        src.y = p.sc[3 * s + 1];
-        src.z = p.sc[3 * s + 2];
-        src.a = (KIND != MHIP_HYDRO_STOKES) ? p.sa[s] : 0.0;
-        src.fx = p.sf[3 * s];
-        src.fy = p.sf[3 * s + 1];
-        src.fz = p.sf[3 * s + 2];
-        src.pad = 0.0;
-        tile[threadIdx.x] = src;
-      }
+      if (s < s_end) tile[threadIdx.x] = hydro_stage<KIND>(p, s);
       __syncthreads();
       const int cnt = s_end - s0 < (size_t)kBlock ? static_cast<int>(s_end - s0) : kBlock;
-      hydro_add_tile<KIND>(tile, cnt, tx, ty, tz, b, p.k, acc);
+      int skip_j = -1;
+      if (KIND == kHydroDoubleLayer && p.skip_same && t >= s0 && t - s0 < (size_t)cnt) skip_j = static_cast<int>(t - s0);
+      hydro_add_tile<KIND>(tile, cnt, tx, ty, tz, b, p.k, skip_j, acc);
     }
     if (PARTIAL) {
       if (valid) store3(p.out, c * p.nt + t, acc);
@@ -283,6 +364,10 @@ static void launch_hydro(bool partial, dim3 grid, const HydroArgs& a, hipStream_
 
 using namespace mhip;
 
+namespace mhip {
+int hydro_launch(mhip_hydro* h, int kind, HydroArgs a, double* velocity, hipStream_t s);
+}
+
 struct mhip_hydro {
   HandleBuffer partial;  // grow-only: [chunk][target][3] of the largest partial-shape call so far
   int path = MHIP_HYDRO_PATH_AUTO;
@@ -336,11 +421,9 @@ int mhip_hydro_velocity(mhip_hydro_t h, int kind, double viscosity, size_t ns, c
                "too many sources or targets");
   if (nt == 0) return MHIP_SUCCESS;
   if (ns == 0 && accumulate) return MHIP_SUCCESS;  // an empty sum: velocity stays as it is
-  hipStream_t s = as_stream(stream);
   HydroArgs a{};
   a.ns = ns;
   a.nt = nt;
-  a.nchunks = (ns + kHydroChunk - 1) / kHydroChunk;
   a.sc = source_center;
   a.sa = source_radius;
   a.sf = source_force;
@@ -355,6 +438,16 @@ int mhip_hydro_velocity(mhip_hydro_t h, int kind, double viscosity, size_t ns, c
   a.k.scale = 1.0 / (8.0 * M_PI * viscosity);
   a.k.c8 = one_over_eight * inv_pi * inv_viscosity;
   a.k.c6 = one_over_six * inv_pi * inv_viscosity;
+  return hydro_launch(h, kind, a, velocity, as_stream(stream));
+}
+
+}  // extern "C"
+
+// the launch both entry points share: the launch rule, the grow-only buffer and the ordered second pass
+int mhip::hydro_launch(mhip_hydro* h, int kind, HydroArgs a, double* velocity, hipStream_t s) {
+  const size_t nt = a.nt;
+  const int velocity_stride = a.stride;
+  a.nchunks = (a.ns + kHydroChunk - 1) / kHydroChunk;
   // launch rule: target tiles alone when they fill the chip (or there is one chunk at most), otherwise tiles x groups
   const size_t tiles = (nt + kBlock - 1) / kBlock;
   size_t groups = (kHydroFillGroups + tiles - 1) / tiles;
@@ -375,7 +468,8 @@ int mhip_hydro_velocity(mhip_hydro_t h, int kind, double viscosity, size_t ns, c
   switch (kind) {
     case MHIP_HYDRO_STOKES: launch_hydro<MHIP_HYDRO_STOKES>(partial, grid, a, s); break;
     case MHIP_HYDRO_RPY: launch_hydro<MHIP_HYDRO_RPY>(partial, grid, a, s); break;
-    default: launch_hydro<MHIP_HYDRO_RPYC>(partial, grid, a, s); break;
+    case MHIP_HYDRO_RPYC: launch_hydro<MHIP_HYDRO_RPYC>(partial, grid, a, s); break;
+    default: launch_hydro<kHydroDoubleLayer>(partial, grid, a, s); break;
   }
   MHIP_LAUNCH_CHECK();
   if (partial) {
@@ -384,6 +478,40 @@ int mhip_hydro_velocity(mhip_hydro_t h, int kind, double viscosity, size_t ns, c
     MHIP_LAUNCH_CHECK();
   }
   return MHIP_SUCCESS;
+}
+
+extern "C" {
+
+int mhip_hydro_double_layer(mhip_hydro_t h, double viscosity, size_t ns, const double* center, const double* normal,
+                            const double* weight, const double* force, size_t nt, const double* target_center,
+                            double* velocity, int velocity_stride, int accumulate, int skip_same_index,
+                            mhip_stream_t stream) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "hydro handle is null");
+  MHIP_REQUIRE(std::isfinite(viscosity) && viscosity > 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "viscosity must be finite and > 0, got %g", viscosity);
+  MHIP_REQUIRE(velocity_stride == 3 || velocity_stride == 6, MHIP_ERR_INVALID_ARGUMENT,
+               "velocity_stride must be 3 or 6, got %d", velocity_stride);
+  MHIP_REQUIRE(ns == 0 || (center && normal && weight && force), MHIP_ERR_INVALID_ARGUMENT,
+               "center / normal / weight / force is null");
+  MHIP_REQUIRE(nt == 0 || (target_center && velocity), MHIP_ERR_INVALID_ARGUMENT, "target_center / velocity is null");
+  MHIP_REQUIRE(ns < (1ull << 40) && nt < (1ull << 31) * (size_t)kBlock, MHIP_ERR_INVALID_ARGUMENT,
+               "too many sources or targets");
+  if (nt == 0) return MHIP_SUCCESS;
+  if (ns == 0 && accumulate) return MHIP_SUCCESS;  // an empty sum: velocity stays as it is
+  HydroArgs a{};
+  a.ns = ns;
+  a.nt = nt;
+  a.sc = center;
+  a.sn = normal;
+  a.sw = weight;
+  a.sf = force;
+  a.tc = target_center;
+  a.skip_same = skip_same_index ? 1 : 0;
+  a.stride = velocity_stride;
+  a.accumulate = accumulate ? 1 : 0;
+  const double scale_dl = 3.0 / (4.0 * M_PI * viscosity);
+  a.k.scale = -scale_dl;
+  return hydro_launch(h, kHydroDoubleLayer, a, velocity, as_stream(stream));
 }
 
 int mhip_hydro_add_velocity(size_t n, const double* u_hydro, double* velocity, int velocity_stride,

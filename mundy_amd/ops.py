@@ -1209,10 +1209,14 @@ def _hydro_kind(kind):
 
 
 def check_hydrodynamics(spec, n):
-    """hydrodynamics=dict(kind=, radius=None, update_every=1) of the stepper -> (kind, radius, update_every); radius
-    None (the beads' own), a number or [n] numbers, finite and >= 0 -> None or a host array [n]"""
-    check_dict_spec(spec, "hydrodynamics", ("kind", "radius", "update_every"), optional=("radius", "update_every"))
+    """hydrodynamics=dict(kind=, radius=None, update_every=1, periphery=None) of the stepper -> (kind, radius,
+    update_every); radius None (the beads' own), a number or [n] numbers, finite and >= 0 -> None or a host array [n];
+    periphery: checked by check_hydro_periphery"""
+    check_dict_spec(spec, "hydrodynamics", ("kind", "radius", "update_every", "periphery"),
+                    optional=("radius", "update_every", "periphery"))
     _hydro_kind(spec["kind"])
+    if spec.get("periphery") is not None:  # (the stepper takes its checked form from check_hydro_periphery)
+        check_hydro_periphery(spec["periphery"])
     radius = spec.get("radius")
     if radius is not None:
         a = radius.detach().cpu().numpy() if isinstance(radius, torch.Tensor) else np.asarray(radius, dtype=np.float64)
@@ -1303,6 +1307,211 @@ def hydro_add_velocity(u_hydro, velocity):
     capi.check(capi.load().mhip_hydro_add_velocity(n, _ptr(u_hydro, cols=3, name="u_hydro"),
                                                    _ptr(velocity, name="velocity"), int(velocity.shape[1]), _stream()))
     return velocity
+
+
+# ---- the periphery's no-slip correction of the hydrodynamics (mundy_hip_hydro_periphery.h; HP1.cpp:4005-4037) -----------
+HYDRO_PERIPHERY_STATES = {capi.HYDRO_PERIPHERY_EMPTY: "empty", capi.HYDRO_PERIPHERY_MATRIX: "matrix",
+                          capi.HYDRO_PERIPHERY_INVERSE: "inverse", capi.HYDRO_PERIPHERY_DOUBLE_LAYER: "double_layer"}
+_HYDRO_PERIPHERY_KEYS = ("shape", "radius", "spectral_order", "points", "weights", "normals", "inverse",
+                         "skip_same_index")
+
+
+def _host_f64(a):
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a, dtype=np.float64)
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def check_hydro_periphery(spec):
+    """periphery= of hydrodynamics=: dict(shape="sphere", radius=, spectral_order=) or dict(points=, weights=, normals=),
+    with optional inverse= ([3S, 3S], a precomputed Minv) and skip_same_index=True (the reference's quirk)
+    -> dict(points [S, 3], weights [S], normals [S, 3], inverse or None, skip_same_index), host arrays; no library call"""
+    check_dict_spec(spec, "hydrodynamics periphery", _HYDRO_PERIPHERY_KEYS, optional=_HYDRO_PERIPHERY_KEYS)
+    if "shape" in spec:
+        if spec["shape"] != "sphere":
+            raise ValueError("hydrodynamics periphery shape must be 'sphere' (or pass points, weights, normals), got %r"
+                             % (spec["shape"],))
+        for k in ("points", "weights", "normals"):
+            if k in spec:
+                raise ValueError("hydrodynamics periphery takes shape= or points=, weights=, normals=, not both")
+        for k in ("radius", "spectral_order"):
+            if k not in spec:
+                raise ValueError("hydrodynamics periphery shape='sphere' is missing key %r" % k)
+        radius, order = spec["radius"], spec["spectral_order"]
+        if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or \
+                not (float(radius) > 0.0 and float(radius) < float("inf")):
+            raise ValueError("hydrodynamics periphery radius must be finite and > 0, got %r" % (radius,))
+        if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or order < 1:
+            raise ValueError("hydrodynamics periphery spectral_order must be an integer >= 1, got %r" % (order,))
+        from . import synth
+        points, weights, normals = synth.sphere_quadrature(int(order), float(radius), include_poles=False, invert=True)
+    else:
+        for k in ("points", "weights", "normals"):
+            if k not in spec:
+                raise ValueError("hydrodynamics periphery is missing key %r (or pass shape='sphere')" % k)
+        for k in ("radius", "spectral_order"):
+            if k in spec:
+                raise ValueError("hydrodynamics periphery %s belongs to shape='sphere'" % k)
+        points, weights, normals = (_host_f64(spec[k]) for k in ("points", "weights", "normals"))
+        S = points.shape[0]
+        if points.ndim != 2 or points.shape[1] != 3 or S == 0:
+            raise ValueError("hydrodynamics periphery points must have shape [S, 3] with S >= 1, got %s" % (points.shape,))
+        if weights.shape != (S,) or normals.shape != (S, 3):
+            raise ValueError("hydrodynamics periphery weights / normals must have shapes [%d] / [%d, 3], got %s / %s"
+                             % (S, S, weights.shape, normals.shape))
+        if not bool(np.all(np.isfinite(points)) and np.all(np.isfinite(weights)) and np.all(np.isfinite(normals))):
+            raise ValueError("hydrodynamics periphery points, weights and normals must be finite")
+    S = points.shape[0]
+    if 3 * S > 65535:
+        raise ValueError("hydrodynamics periphery has too many surface nodes: 3 S = %d > 65535" % (3 * S))
+    inverse = spec.get("inverse")
+    if inverse is not None:
+        shape = tuple(inverse.shape) if hasattr(inverse, "shape") else np.shape(inverse)
+        if shape != (3 * S, 3 * S):
+            raise ValueError("hydrodynamics periphery inverse must have shape [%d, %d], got %s" % (3 * S, 3 * S, shape))
+    skip = spec.get("skip_same_index", True)
+    if not isinstance(skip, (bool, np.bool_)):
+        raise ValueError("hydrodynamics periphery skip_same_index must be True or False, got %r" % (skip,))
+    return dict(points=points, weights=weights, normals=normals, inverse=inverse, skip_same_index=bool(skip))
+
+
+class HydroPeriphery(_Handle):
+    """mhip_hydro_periphery_t: the surface (points [S, 3], weights [S], inward normals [S, 3]; device tensors, copied),
+    its boundary-integral matrix M and the inverse, in ONE [3S, 3S] buffer (`state`: which of the two it holds), and the
+    surface velocity and density of the correction.  fill_matrix() / set_matrix(M) -> invert() (returns the smallest
+    pivot magnitude; synchronises) or set_inverse(Minv) -> surface_forces(u) / correct(...)."""
+    _destroy = "mhip_hydro_periphery_destroy"
+
+    def __init__(self, points, weights, normals, viscosity):
+        S = points.shape[0]
+        if points.dim() != 2 or points.shape[1] != 3 or S == 0:
+            raise ValueError("points must have shape [S, 3] with S >= 1, got %s" % (tuple(points.shape),))
+        if tuple(weights.shape) != (S,) or tuple(normals.shape) != (S, 3):
+            raise ValueError("weights / normals must have shapes [%d] / [%d, 3]" % (S, S))
+        mu = float(viscosity)
+        if not (mu > 0.0 and mu < float("inf")):
+            raise ValueError("viscosity must be finite and > 0, got %r" % (viscosity,))
+        self.num_nodes, self.n, self.viscosity, self.device = S, 3 * S, mu, points.device
+        h = C.c_void_p()
+        capi.check(capi.load().mhip_hydro_periphery_create(C.byref(h), S, _ptr(points, name="points"),
+                                                           _ptr(weights, name="weights"),
+                                                           _ptr(normals, name="normals"), mu, _stream()))
+        self._h = h
+
+    def fill_double_layer(self):
+        """tests: the double-layer block T alone (state "double_layer")"""
+        capi.check(capi.load().mhip_hydro_periphery_fill_double_layer(self._h, _stream()))
+        return self
+
+    def fill_matrix(self):
+        capi.check(capi.load().mhip_hydro_periphery_fill_matrix(self._h, _stream()))
+        return self
+
+    def _square(self, m, name):
+        if tuple(m.shape) != (self.n, self.n):
+            raise ValueError("%s must have shape [%d, %d], got %s" % (name, self.n, self.n, tuple(m.shape)))
+        return _ptr(m, name=name)
+
+    def set_matrix(self, matrix):
+        capi.check(capi.load().mhip_hydro_periphery_set_matrix(self._h, self._square(matrix, "matrix"), _stream()))
+        return self
+
+    def set_inverse(self, inverse):
+        capi.check(capi.load().mhip_hydro_periphery_set_inverse(self._h, self._square(inverse, "inverse"), _stream()))
+        return self
+
+    def invert(self):
+        """M -> Minv in place; -> the smallest pivot magnitude (a host number: synchronises)"""
+        m = C.c_double()
+        capi.check(capi.load().mhip_hydro_periphery_invert(self._h, C.byref(m), _stream()))
+        return m.value
+
+    @property
+    def state(self):
+        return self._matrix()[1]
+
+    def _matrix(self):
+        p, st = C.c_void_p(), C.c_int()
+        capi.check(capi.load().mhip_hydro_periphery_matrix(self._h, C.byref(p), C.byref(st)))
+        return p.value, HYDRO_PERIPHERY_STATES[st.value]
+
+    def matrix(self):
+        """a copy [3S, 3S] of what the buffer holds (M, Minv or T), made on the current stream"""
+        p, st = self._matrix()
+        if st == "empty":
+            raise AssertionError("the periphery holds no matrix")
+        out = torch.empty((self.n, self.n), dtype=torch.float64, device=self.device)
+        capi.check(capi.load().mhip_deep_copy(self.n * self.n, _ptr(out), C.c_void_p(p), _stream()))
+        return out
+
+    def surface_forces(self, u_surf, out=None):
+        """f_surf = -(Minv u_surf), [3S] or [S, 3]"""
+        if u_surf.numel() != self.n:
+            raise ValueError("u_surf must hold %d numbers, got %d" % (self.n, u_surf.numel()))
+        if out is None:
+            out = torch.empty_like(u_surf)
+        if out.numel() != self.n:
+            raise ValueError("out must hold %d numbers, got %d" % (self.n, out.numel()))
+        capi.check(capi.load().mhip_hydro_periphery_surface_forces(self._h, _ptr(u_surf, name="u_surf"),
+                                                                   _ptr(out, name="out"), _stream()))
+        return out
+
+    def correct(self, kind, center, radius, force, velocity, skip_same_index=True, workspace=None):
+        """velocity[:, :3] += DL(nodes -> beads)(-(Minv K(beads -> nodes) force)) (mhip_hydro_periphery_correct)"""
+        global _hydro_default
+        k = _hydro_kind(kind)
+        n = center.shape[0]
+        for name, t in (("center", center), ("force", force)):
+            if t.dim() != 2 or tuple(t.shape) != (n, 3):
+                raise ValueError("%s must have shape [%d, 3], got %s" % (name, n, tuple(t.shape)))
+        if radius is None and k != capi.HYDRO_STOKES:
+            raise ValueError("radius must not be None for kind %r" % (kind,))
+        if radius is not None and tuple(radius.shape) != (n,):
+            raise ValueError("radius must have shape [%d], got %s" % (n, tuple(radius.shape)))
+        if velocity.dim() != 2 or velocity.shape[0] != n or velocity.shape[1] not in (3, 6):
+            raise ValueError("velocity must have shape [%d, 3] or [%d, 6], got %s" % (n, n, tuple(velocity.shape)))
+        if workspace is None:
+            if _hydro_default is None:
+                _hydro_default = HydroWorkspace()
+            workspace = _hydro_default
+        capi.check(capi.load().mhip_hydro_periphery_correct(
+            self._h, workspace._h, k, n, _ptr(center, name="center"), _ptr(radius, name="radius", allow_none=True),
+            _ptr(force, name="force"), _ptr(velocity, name="velocity"), int(velocity.shape[1]),
+            1 if skip_same_index else 0, _stream()))
+        return velocity
+
+
+def hydro_double_layer(viscosity, center, normal, weight, force, tgt_center, out=None, accumulate=False,
+                       skip_same_index=True, workspace=None):
+    """u_t (+)= sum_s DL(x_t - y_s; n_s, w_s, f_s) (mhip_hydro_double_layer): the Stokes double layer of the surface
+    nodes (center, normal [ns, 3], weight [ns], force [ns, 3]) at the targets [nt, 3]; out [nt, 3] or [nt, 6], default
+    a new [nt, 3].  skip_same_index (the reference's quirk): the term of source t onto target t is skipped.  The sums
+    are those of hydro_velocity."""
+    global _hydro_default
+    mu = float(viscosity)
+    if not (mu > 0.0 and mu < float("inf")):
+        raise ValueError("viscosity must be finite and > 0, got %r" % (viscosity,))
+    ns, nt = center.shape[0], tgt_center.shape[0]
+    for name, t, rows in (("center", center, ns), ("normal", normal, ns), ("force", force, ns),
+                          ("tgt_center", tgt_center, nt)):
+        if t.dim() != 2 or tuple(t.shape) != (rows, 3):
+            raise ValueError("%s must have shape [%d, 3], got %s" % (name, rows, tuple(t.shape)))
+    if tuple(weight.shape) != (ns,):
+        raise ValueError("weight must have shape [%d], got %s" % (ns, tuple(weight.shape)))
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs out")
+        out = torch.empty((nt, 3), dtype=torch.float64, device=center.device)
+    if out.dim() != 2 or out.shape[0] != nt or out.shape[1] not in (3, 6):
+        raise ValueError("out must have shape [%d, 3] or [%d, 6], got %s" % (nt, nt, tuple(out.shape)))
+    if workspace is None:
+        if _hydro_default is None:
+            _hydro_default = HydroWorkspace()
+        workspace = _hydro_default
+    capi.check(capi.load().mhip_hydro_double_layer(
+        workspace._h, mu, ns, _ptr(center, name="center"), _ptr(normal, name="normal"), _ptr(weight, name="weight"),
+        _ptr(force, name="force"), nt, _ptr(tgt_center, name="tgt_center"), _ptr(out, name="out"), int(out.shape[1]),
+        1 if accumulate else 0, 1 if skip_same_index else 0, _stream()))
+    return out
 
 
 # ---- crosslinkers that bind and unbind (HP1.cpp:3264-3748, :4728-4739) ------------------------------------------------

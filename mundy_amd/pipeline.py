@@ -187,7 +187,11 @@ class ContactStepper:
         velocity of the force stage's forces, added to U_ext after the noise (HP1.cpp:4744-4803); the chain step (spheres,
         free space, either contact model).  radius: the hydrodynamic radii, None (the beads' own), a number or [n]
         numbers >= 0; update_every k >= 1: recomputed on the steps 0, k, 2k, ... of this stepper and added on every
-        step.  The stepper then owns u_hydro [n, 3].  "rpyc" is the accurate kind."""
+        step.  The stepper then owns u_hydro [n, 3].  "rpyc" is the accurate kind.  Its optional key
+        periphery = dict(shape="sphere", radius=, spectral_order=) or dict(points=, weights=, normals=) (+ inverse=,
+        skip_same_index=True) adds the no-slip correction of a confining surface to u_hydro on the same steps
+        (HP1.cpp:4005-4037): the surface's boundary-integral matrix is filled and inverted at
+        construction (or inverse=, a precomputed [3S, 3S] one, is loaded)."""
         if kind not in ("sphere", "spherocylinder", "mixed"):
             raise ValueError("kind must be 'sphere', 'spherocylinder' or 'mixed'")
         if contact_model not in ("lcp", "hertz"):
@@ -218,6 +222,8 @@ class ContactStepper:
                 raise ValueError("hydrodynamics belongs to the chain step: pass springs= or brownian_kt= (0.0: no noise)")
             self._check_chain_only("hydrodynamics", "the kernels are free-space", *chain_only)
             hydro_spec = ops.check_hydrodynamics(hydrodynamics, center.shape[0])
+            if hydrodynamics.get("periphery") is not None:
+                hydro_spec += (ops.check_hydro_periphery(hydrodynamics["periphery"]),)
         self.hertz_friction = None
         if hertz_friction is not None:  # (checked before anything reaches the device)
             self._check_hertz_friction(contact_model, kind, rod_kinematics, growth_rate, springs, brownian_kt,
@@ -632,13 +638,28 @@ class ContactStepper:
         self.active.renumber(inv)  # endpoints; states and timers stay
 
     # -- n-body hydrodynamics as a velocity stage (HP1.cpp:3942-4059, :4744-4803) -----------------------------------------
-    def _init_hydro(self, kind, radius, every):
+    def _init_hydro(self, kind, radius, every, periphery=None):
         n, dev = self.center.shape[0], self.center.device
         self.hydro = dict(kind=kind, update_every=every)
         self.hydro_radius = None if radius is None else torch.from_numpy(radius).to(dev)  # None: the beads' own
         self.u_hydro = torch.zeros((n, 3), dtype=torch.float64, device=dev)  # the stored velocity, added every step
         self.hydro_step = 0  # the reference's timestep_index_ of `% hydro_update_frequency_ == 0`
         self._hydro_ws = ops.HydroWorkspace()
+        self.hydro_periphery = None
+        if periphery is not None:  # the surface, its matrix and the inverse: built once, here
+            to = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)  # noqa: E731
+            hp = ops.HydroPeriphery(to(periphery["points"]), to(periphery["weights"]), to(periphery["normals"]),
+                                    self.viscosity)
+            inverse = periphery["inverse"]
+            if inverse is None:
+                hp.fill_matrix()
+                self.hydro["periphery_min_pivot"] = hp.invert()
+            else:
+                if not isinstance(inverse, torch.Tensor):
+                    inverse = torch.from_numpy(np.ascontiguousarray(inverse, dtype=np.float64))
+                hp.set_inverse(inverse.to(device=dev, dtype=torch.float64).contiguous())
+            self.hydro_periphery = hp
+            self.hydro["skip_same_index"] = periphery["skip_same_index"]
 
     def _snapshot_hydro(self):
         """the stored velocity, the step counter and the hydrodynamic radii"""
@@ -665,6 +686,10 @@ class ContactStepper:
                 radius = self.radius if self.hydro_radius is None else self.hydro_radius
                 ops.hydro_velocity(self.hydro["kind"], self.viscosity, self.center, radius, force, out=self.u_hydro,
                                    workspace=self._hydro_ws)
+                if self.hydro_periphery is not None:  # the no-slip correction of the periphery, into the same u_hydro
+                    self.hydro_periphery.correct(self.hydro["kind"], self.center, radius, force, self.u_hydro,
+                                                 skip_same_index=self.hydro["skip_same_index"],
+                                                 workspace=self._hydro_ws)
         self.hydro_step += 1
         ops.hydro_add_velocity(self.u_hydro, self.u_ext)
 

@@ -236,3 +236,32 @@ def crossed_filaments(num_filaments, nodes, radius=0.5, segment_length=1.0, angl
     return dict(node_ptr=(np.arange(2 * F + 1) * B).astype(np.int32), center=np.ascontiguousarray(center),
                 twist=np.zeros(N), radius=np.full(N, r), rest_curvature=np.zeros((N, 3)),
                 arclength=np.tile(i * l0, 2 * F), edge_orientation=np.ascontiguousarray(quat.reshape(N, 4)), phase=phase)
+
+
+def sphere_quadrature(order, radius, include_poles=False, invert=False):
+    """gen_sphere_quadrature (periphery/Periphery.hpp:90-167) -> (points [S, 3], weights [S], normals [S, 3]): the
+    Gauss-Legendre rule of order + 1 nodes in cos(theta) times 2 order + 2 equispaced azimuths, ring j from the north
+    pole down (cos theta_j = nodes_gl[order - j]), k around (phi_k = 2 pi k / (2 order + 2)); weights
+    radius^2 2 pi / (2 order + 2) weights_gl[order - j]; normals = +-points of the unit sphere (invert: inward); the
+    points are scaled by the radius last.  include_poles adds the two poles with weight 0 (first and last).  The
+    Gauss-Legendre rule is numpy.polynomial.legendre.leggauss (ascending nodes, as the reference's)."""
+    order = int(order)
+    if order < 0:
+        raise ValueError("order must be non-negative, got %d" % order)
+    if not (radius > 0):
+        raise ValueError("radius must be positive, got %r" % (radius,))
+    nodes_gl, weights_gl = np.polynomial.legendre.leggauss(order + 1)
+    nphi = 2 * order + 2
+    j = np.repeat(np.arange(order + 1), nphi)
+    k = np.tile(np.arange(nphi), order + 1)
+    cos_t = nodes_gl[order - j]
+    phi = 2 * np.pi * k / nphi
+    sin_t = np.sqrt(1 - cos_t * cos_t)
+    points = np.stack([sin_t * np.cos(phi), sin_t * np.sin(phi), cos_t], axis=1)
+    weights = (radius * radius * 2 * np.pi / nphi) * weights_gl[order - j]
+    if include_poles:
+        points = np.concatenate([[[0.0, 0.0, 1.0]], points, [[0.0, 0.0, -1.0]]])
+        weights = np.concatenate([[0.0], weights, [0.0]])
+    normals = (-1.0 if invert else 1.0) * points
+    points = points * radius
+    return np.ascontiguousarray(points), np.ascontiguousarray(weights), np.ascontiguousarray(normals)
