@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../mundy_hip.h"
+#include "../mundy_hip_contact_force.h"
 
 namespace mundy_hip {
 
@@ -860,6 +861,19 @@ class ContactOperator {
   /// the same for a force VECTOR per linker, force [C][3] on body i (body j gets its negative)
   void linker_potential_force_reduction_vector(const double* force, mhip_stream_t stream = nullptr) const {
     check(mhip_contact_op_body_sweep_vector(h_, force, stream));
+  }
+  /// LinkerPotentialForceReduction alone (.../linker_potential_force_reduction/kernels/Spherocylinder.cpp:173-207;
+  /// SumCollisionForce, NgpLcp.cpp:442-474): the force, and with stride 6 the torque about the centre, that per-linker
+  /// multipliers x [C] put on every body, out [num_bodies][stride] of the caller, the mobility not applied; accumulate
+  /// adds to what out holds.  The velocity rows are left as they are (mhip_contact_op_body_force).
+  void body_force(const double* x, double* out, int stride = 6, bool accumulate = false,
+                  mhip_stream_t stream = nullptr) const {
+    check(mhip_contact_op_body_force(h_, x, out, stride, accumulate ? 1 : 0, stream));
+  }
+  /// the same for a force VECTOR per linker, force [C][3] on body i (body j gets its negative)
+  void body_force_vector(const double* force, double* out, int stride = 6, bool accumulate = false,
+                         mhip_stream_t stream = nullptr) const {
+    check(mhip_contact_op_body_force_vector(h_, force, out, stride, accumulate ? 1 : 0, stream));
   }
   /// [num_bodies][6] (U, W) of the last apply / body sweep / solve (device pointer, valid in stream order)
   const double* compute_generalized_velocity() const {

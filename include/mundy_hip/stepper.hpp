@@ -686,7 +686,11 @@ class DistributedSpherocylinderStepper {
 /// program adds its own terms to force() and u_ext() between them, where the reference's step has them
 /// (HP1.cpp:4733-4803):
 ///   neighbors() -> forces() -> external_velocity() -> resolve()
-/// step() is the four in a row.  The only host reads of a step are the neighbour list's rebuild test, the solver's
+/// set_hertz_contact(E, nu, true) makes it the reference's own order with the Hertzian soft contact (HP1.cpp:4728-4803):
+/// the contact force is the first term of the force field, so everything computed from force() sees it, and no solve
+/// and no body sweep follow:
+///   neighbors() -> contact_forces() -> forces() -> external_velocity() -> resolve()      (U = U_ext)
+/// step() is the stages in a row.  The only host reads of a step are the neighbour list's rebuild test, the solver's
 /// convergence polls and, at the end of every resolve(), two small blocking downloads: the longest spring and the
 /// overstretched count, whether the caller looks at them or not.  They are what resolve() waits for the step with.
 class SphereChainStepper {
@@ -716,8 +720,47 @@ class SphereChainStepper {
     if (rebuilt_) links_.links_into(pairs_);
     return rebuilt_;
   }
-  /// the spring force into force() [n][3]; returns it for the caller to accumulate further terms into
+  /// The Hertzian soft contact (E > 0, 0 < nu < 1) instead of the LCP.  contact_forces_in_force_stage must be true: the
+  /// Hertz force is then the first term of force() (contact_forces()), as the reference has it; the other order -- a body
+  /// sweep after U_ext -- is the Python stepper's default and is not wired here.
+  void set_hertz_contact(double youngs_modulus, double poisson_ratio, bool contact_forces_in_force_stage) {
+    if (!(youngs_modulus > 0.0) || !(poisson_ratio > 0.0 && poisson_ratio < 1.0))
+      throw std::invalid_argument("SphereChainStepper: youngs_modulus must be > 0 and 0 < poisson_ratio < 1");
+    if (!contact_forces_in_force_stage)
+      throw std::invalid_argument("SphereChainStepper: the Hertz contact runs with its force in the force stage only");
+    material_.youngs_modulus = youngs_modulus;
+    material_.poisson_ratio = poisson_ratio;
+    hertz_ = true;
+    if (max_overlap_.size() == 0) max_overlap_ = DeviceVector(1);
+    if (spring_term_.size() == 0) spring_term_ = DeviceVector(3 * n_);
+  }
+  /// Hertz mode, between neighbors() and forces(): contacts -> Hertz force per linker -> operator (built after a rebuild,
+  /// otherwise refreshed) -> the contact force of every body F = D f into force() [n][3]; returns it
+  double* contact_forces() {
+    if (!hertz_) throw std::logic_error("SphereChainStepper: contact_forces() needs set_hertz_contact");
+    const size_t C = links_.num_links(), cap = C ? C : 1;  // no workspace is null without contacts
+    double *sep = workspace(w_sep_, cap), *normal = workspace(w_normal_, 3 * cap), *f = workspace(lambda_, cap);
+    check(mhip_contact_spheres(C, pairs_.data(), center_.data(), radius_.data(), nullptr, sep, normal, nullptr));
+    linkers::evaluate_linker_potentials(C, n_, pairs_.data(), sep, radius_.data(), material_, f, max_overlap_.data());
+    if (rebuilt_ || !op_)
+      op_.reset(new ContactOperator(C, n_, pairs_.data(), normal, nullptr, nullptr, mob_t_.data(), nullptr, dt_,
+                                    nullptr, /*priority=*/sep));
+    else
+      op_->refresh(normal, nullptr, nullptr);
+    num_lambda_ = C;
+    op_->body_force(f, force_.data(), 3);
+    have_contact_force_ = true;
+    return force_.data();
+  }
+  /// the spring force into force() [n][3] (Hertz mode: added to the contact force that contact_forces() left there);
+  /// returns it for the caller to accumulate further terms into
   double* forces() {
+    if (hertz_) {  // (the spring kernel overwrites: its term goes through a buffer of its own)
+      if (!have_contact_force_) throw std::logic_error("SphereChainStepper: forces() before contact_forces()");
+      springs_.compute_forces(center_.data(), spring_term_.data());
+      check(mhip_axpby(3 * n_, 1.0, spring_term_.data(), 1.0, force_.data(), nullptr));
+      return force_.data();
+    }
     springs_.compute_forces(center_.data(), force_.data());
     return force_.data();
   }
@@ -729,9 +772,24 @@ class SphereChainStepper {
   }
   /// contacts -> operator (built after a rebuild, otherwise refreshed) -> q = sep + dt D^T U_ext (NgpHP1.cpp:1488-1531)
   /// -> BBPGD from lambda = 0 -> U = U_ext + M D lambda -> Euler update
+  /// Hertz mode: U = U_ext (the contact force is inside it) -> Euler update; max_overlap is read with the springs' two
   StepStats resolve(bool integrate = true) {
     StepStats st;
     st.rebuilt = rebuilt_;
+    if (hertz_) {
+      if (!have_contact_force_) throw std::logic_error("SphereChainStepper: resolve() before contact_forces()");
+      have_contact_force_ = false;
+      rebuilt_ = false;
+      st.num_contacts = num_lambda_;
+      st.converged = true;
+      check(mhip_deep_copy(6 * n_, vel_.data(), u_ext_.data(), nullptr));
+      if (integrate) check(mhip_integrate_euler(n_, dt_, vel_.data(), center_.data(), nullptr, nullptr));
+      st.max_overlap = max_overlap_.download()[0];
+      st.max_spring_length = springs_.max_length();  // these reads wait for the step
+      st.springs_overstretched = springs_.overstretched();
+      ++step_index_;
+      return st;
+    }
     const size_t C = links_.num_links(), cap = C ? C : 1;  // no workspace is null without contacts
     st.num_contacts = C;
     double *sep = workspace(w_sep_, cap), *normal = workspace(w_normal_, 3 * cap), *q = workspace(w_q_, cap),
@@ -762,6 +820,7 @@ class SphereChainStepper {
   /// the plain chain step
   StepStats step(bool integrate = true) {
     neighbors();
+    if (hertz_) contact_forces();
     forces();
     external_velocity();
     return resolve(integrate);
@@ -791,6 +850,10 @@ class SphereChainStepper {
   Springs springs_;
   size_t num_lambda_ = 0, step_index_ = 0;
   bool rebuilt_ = false;
+  // the Hertzian contact (set_hertz_contact): material, the device word of max_overlap, the springs' own term
+  bool hertz_ = false, have_contact_force_ = false;
+  linkers::HertzMaterial material_;
+  DeviceVector max_overlap_, spring_term_;
   DeviceArray<int32_t> pairs_;
   mesh::GenNeighborLinks links_;
   std::unique_ptr<ContactOperator> op_;

@@ -333,6 +333,12 @@ PERIPHERY_SIGNATURES = {
     "mhip_hydro_double_layer": [_vp, _d, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _i, _i, _vp],
     "mhip_hydro_periphery_correct": [_vp, _vp, _i, _sz, _vp, _vp, _vp, _vp, _i, _i, _vp],
 }
+# include/mundy_hip_contact_force.h, a header of its own for the same reason: name -> argtypes, every function returns int
+# status.  tests/test_contact_force_host.py checks this table against that header and the library.
+CONTACT_FORCE_SIGNATURES = {
+    "mhip_contact_op_body_force": [_vp, _vp, _vp, _i, _i, _vp],
+    "mhip_contact_op_body_force_vector": [_vp, _vp, _vp, _i, _i, _vp],
+}
 OTHER_SYMBOLS = {"mhip_last_error": ([], C.c_char_p), "mhip_version": ([], C.c_int),
                  "mhip_release_cached_workspaces": ([], C.c_int)}
 
@@ -351,7 +357,8 @@ def load():
         # cannot see torch's device context)
         import torch  # noqa: F401
         lib = C.CDLL(LIB_PATH)
-        for name, argtypes in list(SIGNATURES.items()) + list(PERIPHERY_SIGNATURES.items()):
+        for name, argtypes in (list(SIGNATURES.items()) + list(PERIPHERY_SIGNATURES.items()) +
+                               list(CONTACT_FORCE_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = C.c_int

@@ -20,6 +20,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "../../include/mundy_hip_contact_force.h"
 #include "mhip_internal.hpp"
 
 namespace mhip {
@@ -1957,8 +1958,66 @@ __device__ inline void store_body_row(double* __restrict__ vel, size_t b, const 
 // used (rods: the arclength coefficient, vector arms: r), and it is fetched only for a contact whose force is not zero
 // (a zero row adds +/-0 to sums that start at +0.0: nothing).  G lanes per body, double-double sums in fixed order,
 // and the rows are written as k_body's X_APPLY sweep writes them: (U, W) resp. (U, W x u) and omega for rods.
-template <int KIN, int G>
-__global__ void __launch_bounds__(kBlock) k_body_vector(OpView op, const double* __restrict__ force) {
+// (The sweep itself is body_gather below: Term says what an entry adds, Sink where a body's rounded sums go.  This kernel
+// and k_body_force are its instances.)
+// Term of the vector sweeps: +F_c on side i, -F_c on side j.  A Term reads what the contact carries (an all-zero value:
+// the entry is skipped) and then forms the force on this side of it.
+struct VectorTerm {
+  const double* __restrict__ force;
+  __device__ __forceinline__ V3 carried(int32_t e) const { return load3(force, static_cast<size_t>(e >> 1)); }
+  template <int HW>
+  __device__ __forceinline__ V3 on_side(const OpView& op, int32_t e, int32_t k, V3 f) const {
+    if (e & 1) f = V3{-f.x, -f.y, -f.z};  // side j receives -F_c
+    return f;
+  }
+};
+// Term of a multiplier along the normal, k_body's: -(x_c n_c) at the source, +(x_c n_c) at the target; the normal is the
+// head of the entry's own record, fetched only where x_c is not zero
+struct NormalTerm {
+  const double* __restrict__ x;
+  __device__ __forceinline__ V3 carried(int32_t e) const { return V3{x[static_cast<size_t>(e >> 1)], 0.0, 0.0}; }
+  template <int HW>
+  __device__ __forceinline__ V3 on_side(const OpView& op, int32_t e, int32_t k, V3 c) const {
+    const double lam = c.x;
+    const double* H = op.half + static_cast<size_t>(k) * HW;
+    V3 f{lam * H[0], lam * H[1], lam * H[2]};
+    if (!(e & 1)) f = V3{-f.x, -f.y, -f.z};  // F_src += -lam n, F_tgt += +lam n  (NgpLcp.cpp:467-472)
+    return f;
+  }
+};
+// Sink of the sweeps: the rows k_body's X_APPLY sweep writes, (U, W) resp. (U, W x u) and omega for rods
+struct RowSink {
+  template <int KIN>
+  __device__ __forceinline__ void operator()(const OpView& op, size_t b, DD3 Fdd, DD3 Tdd) const {
+    const V3 axis = (KIN == KIN_ROD) ? load3(op.axis, b) : V3{0.0, 0.0, 0.0};
+    // (dd_value: the one rounding of each sum)
+    const BodyRow row = body_row<KIN>(dd_value(Fdd), dd_value(Tdd), op.mt[b], (KIN != KIN_TRANS) ? op.mr[b] : 0.0, axis);
+    if (KIN == KIN_ROD) store3(op.omega, b, row.w);
+    store_body_row(op.vel, b, row);
+  }
+};
+// Sink of the body force: (F, T) themselves into the caller's [N][stride] array, the mobility never applied.  The
+// torque about the body centre is T (vector arms), u x S (rods: body_row's expression, so m_r T is its W bit for bit) or
+// +0.0 (spheres); accumulate adds the rounded sum to the old value, one more rounding.
+struct ForceSink {
+  double* __restrict__ out;
+  int stride, accumulate;
+  template <int KIN>
+  __device__ __forceinline__ void operator()(const OpView& op, size_t b, DD3 Fdd, DD3 Tdd) const {
+    double* o = out + b * static_cast<size_t>(stride);
+    V3 F = dd_value(Fdd), T = dd_value(Tdd);  // (the one rounding of each sum)
+    if (KIN == KIN_ROD) T = cross(load3(op.axis, b), T);
+    if (KIN == KIN_TRANS) T = V3{0.0, 0.0, 0.0};
+    if (accumulate) {
+      F = V3{o[0] + F.x, o[1] + F.y, o[2] + F.z};
+      if (stride == 6) T = V3{o[3] + T.x, o[4] + T.y, o[5] + T.z};
+    }
+    o[0] = F.x; o[1] = F.y; o[2] = F.z;
+    if (stride == 6) { o[3] = T.x; o[4] = T.y; o[5] = T.z; }
+  }
+};
+template <int KIN, int G, class Term, class Sink>
+__device__ __forceinline__ void body_gather(const OpView& op, const Term term, const Sink sink) {
   constexpr int HW = (KIN == KIN_RIGID) ? 6 : (KIN == KIN_ROD ? 4 : 3);
   const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   const int sub = static_cast<int>(t % G);
@@ -1968,9 +2027,9 @@ __global__ void __launch_bounds__(kBlock) k_body_vector(OpView op, const double*
   const int32_t beg = op.inc_ptr[b], end = op.inc_ptr[b + 1];
   for (int32_t k = beg + sub; k < end; k += G) {
     const int32_t e = op.inc[k];
-    V3 f = load3(force, static_cast<size_t>(e >> 1));
+    V3 f = term.carried(e);
     if (f.x == 0.0 && f.y == 0.0 && f.z == 0.0) continue;
-    if (e & 1) f = V3{-f.x, -f.y, -f.z};  // side j receives -F_c
+    f = term.template on_side<HW>(op, e, k, f);
     dd_add(Fdd, f);
     const double* H = op.half + static_cast<size_t>(k) * HW;
     if (KIN == KIN_RIGID) dd_add(Tdd, cross(V3{H[3], H[4], H[5]}, f));  // torque r x f
@@ -1978,11 +2037,21 @@ __global__ void __launch_bounds__(kBlock) k_body_vector(OpView op, const double*
   }
   group_sum<G, KIN>(Fdd, Tdd);
   if (sub != 0) return;
-  const V3 axis = (KIN == KIN_ROD) ? load3(op.axis, b) : V3{0.0, 0.0, 0.0};
-  // (dd_value: the one rounding of each sum)
-  const BodyRow row = body_row<KIN>(dd_value(Fdd), dd_value(Tdd), op.mt[b], (KIN != KIN_TRANS) ? op.mr[b] : 0.0, axis);
-  if (KIN == KIN_ROD) store3(op.omega, b, row.w);
-  store_body_row(op.vel, b, row);
+  sink.template operator()<KIN>(op, b, Fdd, Tdd);
+}
+template <int KIN, int G>
+__global__ void __launch_bounds__(kBlock) k_body_vector(OpView op, const double* __restrict__ force) {
+  body_gather<KIN, G>(op, VectorTerm{force}, RowSink{});
+}
+// The body force of a contact operator (mhip_contact_op_body_force[_vector]): F_b = sum f and T_b, no mobility, into
+// the caller's array; nothing of the operator is written.  SCALAR: in = x [C], else in = F [C][3].
+template <int KIN, int G, bool SCALAR>
+__global__ void __launch_bounds__(kBlock)
+    k_body_force(OpView op, const double* __restrict__ in, double* __restrict__ out, int stride, int accumulate) {
+  if (SCALAR)
+    body_gather<KIN, G>(op, NormalTerm{in}, ForceSink{out, stride, accumulate});
+  else
+    body_gather<KIN, G>(op, VectorTerm{in}, ForceSink{out, stride, accumulate});
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -3611,6 +3680,49 @@ int mhip_contact_op_body_sweep_vector(mhip_contact_op_t op, const double* force,
   with_kin(op, [&](auto kin) { k_body_vector<decltype(kin)::value, G><<<grid, kBlock, 0, s>>>(op->view, force); });
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
+}
+
+// The per-body contact force and torque F = D x (include/mundy_hip_contact_force.h): the sums of the two body sweeps
+// above without the mobility, into the caller's array.  Reads the operator, writes nothing of it.
+static int body_force(mhip_contact_op_t op, const double* in, const char* what, bool scalar, double* out, int stride,
+                      int accumulate, mhip_stream_t stream) {
+  // (what the arguments alone decide comes first: refused without a handle too)
+  MHIP_REQUIRE(stride == 3 || stride == 6, MHIP_ERR_INVALID_ARGUMENT, "stride must be 3 or 6, got %d", stride);
+  MHIP_REQUIRE(accumulate == 0 || accumulate == 1, MHIP_ERR_INVALID_ARGUMENT, "accumulate must be 0 or 1, got %d",
+               accumulate);
+  MHIP_REQUIRE(op != nullptr, MHIP_ERR_INVALID_ARGUMENT, "operator handle is null");
+  MHIP_REQUIRE(op->view.C == 0 || in, MHIP_ERR_INVALID_ARGUMENT, "%s must not be null", what);
+  MHIP_REQUIRE(op->view.N == 0 || out, MHIP_ERR_INVALID_ARGUMENT, "out must not be null");
+  MHIP_REQUIRE(!op->stage.active, MHIP_ERR_RUNTIME, "a staged solve is in progress");
+  MHIP_REQUIRE(op->view.body_first == 0 && op->view.body_count == op->view.N && op->view.counted == nullptr,
+               MHIP_ERR_LOGIC, "the body force of a partitioned operator is not supported");
+  const size_t N = op->view.N;
+  if (N == 0) return MHIP_SUCCESS;
+  hipStream_t s = as_stream(stream);
+  op->last_stream = s;
+  if (op->view.C == 0) {  // no contact: +0.0 rows, or the old values
+    if (!accumulate) MHIP_HIP(hipMemsetAsync(out, 0, N * static_cast<size_t>(stride) * sizeof(double), s));
+    return MHIP_SUCCESS;
+  }
+  constexpr int G = 4;  // lanes per body (the sums do not depend on it)
+  const unsigned grid = grid_exact(N * (size_t)G);
+  with_kin(op, [&](auto kin) {
+    constexpr int K = decltype(kin)::value;
+    if (scalar)
+      k_body_force<K, G, true><<<grid, kBlock, 0, s>>>(op->view, in, out, stride, accumulate);
+    else
+      k_body_force<K, G, false><<<grid, kBlock, 0, s>>>(op->view, in, out, stride, accumulate);
+  });
+  MHIP_LAUNCH_CHECK();
+  return MHIP_SUCCESS;
+}
+int mhip_contact_op_body_force(mhip_contact_op_t op, const double* x, double* out, int stride, int accumulate,
+                               mhip_stream_t stream) {
+  return body_force(op, x, "x", true, out, stride, accumulate, stream);
+}
+int mhip_contact_op_body_force_vector(mhip_contact_op_t op, const double* force, double* out, int stride,
+                                      int accumulate, mhip_stream_t stream) {
+  return body_force(op, force, "force", false, out, stride, accumulate, stream);
 }
 
 // The constraint sweep of apply alone, on a velocity the caller gives: sep_dot = D^T U.  The operator's own view with

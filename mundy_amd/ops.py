@@ -754,6 +754,38 @@ class ContactOperator(_Handle):
             raise ValueError("force must have shape [%d, 3], got %s" % (self.num_constraints, tuple(force.shape)))
         capi.check(capi.load().mhip_contact_op_body_sweep_vector(self._h, _ptr(force, name="force"), _stream()))
 
+    def _body_force(self, fn, arr, name, out, stride, accumulate):
+        if stride not in (3, 6):
+            raise ValueError("stride must be 3 or 6, got %r" % (stride,))
+        if not isinstance(accumulate, (bool, np.bool_)):
+            raise ValueError("accumulate must be a bool, got %r" % (accumulate,))
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate needs out")
+            out = torch.empty((self.num_bodies, stride), dtype=torch.float64, device=self._device)
+        elif tuple(out.shape) != (self.num_bodies, stride):
+            raise ValueError("out must have shape [%d, %d], got %s" % (self.num_bodies, stride, tuple(out.shape)))
+        capi.check(getattr(capi.load(), fn)(self._h, _ptr(arr, name=name), _ptr(out, name="out"), int(stride),
+                                            1 if accumulate else 0, _stream()))
+        return out
+
+    def body_force(self, x, out=None, stride=6, accumulate=False):
+        """the per-body contact force (and, stride 6, torque about the centre) D x of per-contact multipliers x [C]:
+        F_b = sum -/+ x_c n_c (source / target), T_b from the operator's lever arms, the mobility never applied
+        (mhip_contact_op_body_force; include/mundy_hip_contact_force.h).  out [N, stride] (default: a new one);
+        accumulate adds the rounded sums to what out holds.  body_velocity() is left as it is.
+        body_velocity_of(x)[:, :3] == mob_trans[:, None] * body_force(x)[:, :3] bit for bit."""
+        if tuple(x.shape) != (self.num_constraints,):
+            raise ValueError("x must have shape [%d], got %s" % (self.num_constraints, tuple(x.shape)))
+        return self._body_force("mhip_contact_op_body_force", x, "x", out, stride, accumulate)
+
+    def body_force_vector(self, force, out=None, stride=6, accumulate=False):
+        """the same sums of a vector force per contact, force [C, 3]: body i gets +F_c, body j -F_c
+        (mhip_contact_op_body_force_vector).  body_force_vector(-x[:, None] * n) equals body_force(x) bit for bit."""
+        if tuple(force.shape) != (self.num_constraints, 3):
+            raise ValueError("force must have shape [%d, 3], got %s" % (self.num_constraints, tuple(force.shape)))
+        return self._body_force("mhip_contact_op_body_force_vector", force, "force", out, stride, accumulate)
+
     def constraint_rate(self, velocity, out=None):
         """sep_dot [C] = D^T U of a velocity [N, 6] (U, W): n_c . [(U_j + W_j x rb) - (U_i + W_i x ra)] with this
         operator's kinematics -- the adjoint of body_sweep, without apply's dt (mhip_contact_op_constraint_rate)"""
@@ -1209,11 +1241,13 @@ def _hydro_kind(kind):
 
 
 def check_hydrodynamics(spec, n):
-    """hydrodynamics=dict(kind=, radius=None, update_every=1, periphery=None) of the stepper -> (kind, radius,
-    update_every); radius None (the beads' own), a number or [n] numbers, finite and >= 0 -> None or a host array [n];
-    periphery: checked by check_hydro_periphery"""
-    check_dict_spec(spec, "hydrodynamics", ("kind", "radius", "update_every", "periphery"),
-                    optional=("radius", "update_every", "periphery"))
+    """hydrodynamics=dict(kind=, radius=None, update_every=1, periphery=None, contact_forces=False) of the stepper ->
+    (kind, radius, update_every); radius None (the beads' own), a number or [n] numbers, finite and >= 0 -> None or a
+    host array [n]; periphery: checked by check_hydro_periphery; contact_forces: a bool, which the stepper reads"""
+    check_dict_spec(spec, "hydrodynamics", ("kind", "radius", "update_every", "periphery", "contact_forces"),
+                    optional=("radius", "update_every", "periphery", "contact_forces"))
+    if not isinstance(spec.get("contact_forces", False), bool):
+        raise ValueError("hydrodynamics contact_forces must be a bool, got %r" % (spec["contact_forces"],))
     _hydro_kind(spec["kind"])
     if spec.get("periphery") is not None:  # (the stepper takes its checked form from check_hydro_periphery)
         check_hydro_periphery(spec["periphery"])

@@ -46,6 +46,15 @@ hydrodynamics= adds the long-range hydrodynamic velocity of the same app's defau
     ... -> forces F -> U_ext = M F -> += U_brown -> every update_every-th step u_hydro = sum_s K(x_t - x_s) F_s
         (RPYC, RPY or Stokeslet, all pairs) -> += u_hydro (every step) -> contacts -> the chain step as above
 
+hydrodynamics=dict(..., contact_forces=True) with contact_model="hertz" is that step in the reference's own order
+(HP1.cpp:4728-4803): the Hertz force is the first term of the force field, so the dry velocity, the hydrodynamic
+velocity and the periphery's no-slip correction all see it, and no body sweep follows:
+
+    ... -> broad phase -> contacts -> Hertz force per linker -> operator -> F = D f (ContactOperator.body_force)
+        -> += springs, crosslinkers, periphery, active, external force -> U_ext = M F + U_brown
+        -> every update_every-th step u_hydro = hydro(F) (+ the periphery's correction of F) -> U_ext += u_hydro
+        -> U = U_ext -> Euler update
+
 hertz_friction= replaces the frictionless Hertz force by the reference's frictional rod contact with a per-pair
 tangential history (SpherocylinderSegmentSpherocylinderSegmentFrictionalHertzianContact.cpp:384-518, run every step by
 CollidingOverdampedFrictionalSperm.cpp:1553-1731):
@@ -191,7 +200,11 @@ class ContactStepper:
         periphery = dict(shape="sphere", radius=, spectral_order=) or dict(points=, weights=, normals=) (+ inverse=,
         skip_same_index=True) adds the no-slip correction of a confining surface to u_hydro on the same steps
         (HP1.cpp:4005-4037): the surface's boundary-integral matrix is filled and inverted at
-        construction (or inverse=, a precomputed [3S, 3S] one, is loaded)."""
+        construction (or inverse=, a precomputed [3S, 3S] one, is loaded).  Its optional key contact_forces=True
+        (contact_model="hertz" only; default False: the step above, unchanged) makes the Hertz contact force the first
+        term of F, as the reference has it: contacts are evaluated before the forces, F = D f + springs + ..., the
+        hydrodynamics and the periphery's correction see the contact forces, and U = U_ext with no body sweep (DESIGN.md
+        5p).  With "lcp" it is refused: the multipliers do not exist when U_ext is formed."""
         if kind not in ("sphere", "spherocylinder", "mixed"):
             raise ValueError("kind must be 'sphere', 'spherocylinder' or 'mixed'")
         if contact_model not in ("lcp", "hertz"):
@@ -222,8 +235,14 @@ class ContactStepper:
                 raise ValueError("hydrodynamics belongs to the chain step: pass springs= or brownian_kt= (0.0: no noise)")
             self._check_chain_only("hydrodynamics", "the kernels are free-space", *chain_only)
             hydro_spec = ops.check_hydrodynamics(hydrodynamics, center.shape[0])
+            if hydrodynamics.get("contact_forces", False) and contact_model != "hertz":
+                raise ValueError("hydrodynamics contact_forces needs contact_model='hertz': the LCP's multipliers do not "
+                                 "exist when U_ext is formed")
             if hydrodynamics.get("periphery") is not None:
                 hydro_spec += (ops.check_hydro_periphery(hydrodynamics["periphery"]),)
+        # the Hertz force as the first term of the chain step's force field (HP1.cpp:4737-4741) instead of a body sweep
+        # after U_ext
+        self.hydro_contact_forces = hydrodynamics is not None and bool(hydrodynamics.get("contact_forces", False))
         self.hertz_friction = None
         if hertz_friction is not None:  # (checked before anything reaches the device)
             self._check_hertz_friction(contact_model, kind, rod_kinematics, growth_rate, springs, brownian_kt,
@@ -318,6 +337,8 @@ class ContactStepper:
             self._init_nucleus(*nucleus_spec)
         if hydro_spec is not None:
             self._init_hydro(*hydro_spec)
+        if self.hydro_contact_forces and self.springs is not None:  # the springs' own term, added to F = D f
+            self._spring_term = torch.zeros((n, 3), dtype=torch.float64, device=center.device)
         # the optional modes that carry state of their own: snapshot, restore and reorder_bodies call their
         # _snapshot_<mode>() / _restore_<mode>(saved) / _renumber_<mode>(perm, inv) hooks in this order
         on = dict(growth=self.growth, friction=self.hertz_friction is not None, springs=self.springs is not None,
@@ -697,13 +718,19 @@ class ContactStepper:
         """the force stage in the reference's order (HP1.cpp:4733-4741): crosslinker KMC, active sampling, springs,
         crosslinker springs, periphery, active force dipoles, external force; every term after the first that writes is
         added into self.spring_force.  With no such term the caller's external_force (or None: no force at all) is
-        returned as it is, not copied."""
-        st, force, written = self._chain_stats, self.spring_force, False
+        returned as it is, not copied.  With hydrodynamics contact_forces the buffer already holds the contact force
+        F = D f (contact_forces()), the first term as in the reference, and every term here is added to it:
+        F = ((((D f + F_spring) + F_crosslinker) + F_periphery) + F_active) + F_ext, each + one rounding."""
+        st, force, written = self._chain_stats, self.spring_force, self.hydro_contact_forces
         if self.crosslinkers is not None:
             self.crosslinker_kmc()
         if self.active is not None:
             self.active.sample(switches=stat(st, "active_switches"))
-        if self.springs is not None:
+        if self.springs is not None and written:  # (the spring kernel overwrites: its term goes through a buffer of its own)
+            self.springs.force(self.center, out=self._spring_term,
+                               stats=(stat(st, "springs_overstretched"), stat(st, "max_spring_length")))
+            ops.axpby(1.0, self._spring_term.view(-1), 1.0, force.view(-1))
+        elif self.springs is not None:
             self.springs.force(self.center, out=force,
                                stats=(stat(st, "springs_overstretched"), stat(st, "max_spring_length")))
             written = True
@@ -727,8 +754,10 @@ class ContactStepper:
     def external_velocity(self, external_force=None, mark=lambda name: None):
         """U_ext = M (F_spring + F_crosslinker + F_periphery + F_active + F_ext) + U_brown (+ u_hydro) into self.u_ext
         (the rng counters advance; with crosslinkers, their KMC step runs first, then the active springs' sampling);
-        mark(name) is told the stages (springs_brownian[, hydrodynamics]) as they are issued"""
-        self._chain_stats.zero_()
+        mark(name) is told the stages (springs_brownian[, hydrodynamics]) as they are issued.  With hydrodynamics
+        contact_forces, contact_forces() comes first: it has zeroed the statistics and written max_overlap and F = D f"""
+        if not self.hydro_contact_forces:
+            self._chain_stats.zero_()
         force = self._force_stage(external_force)
         ops.drag_velocity(self.mob_trans, force, out=self.u_ext)
         if self.brownian_kt is not None:
@@ -980,6 +1009,9 @@ class ContactStepper:
     def resolve_collisions(self, rebuilt, mark=lambda name: None):
         """the contact stage of either model; mark(name) is told the Hertz stages ([history_carry,] hertz_force,
         operator, body_sweep) as they are issued"""
+        if self.hydro_contact_forces:  # contact_forces() was the contact stage; U = U_ext, nothing to sweep
+            self.contact_pairs = self.links.pairs
+            return ops.SolveResult(num_iters=0, residual=0.0, converged=True)
         if self.contact_model == "hertz":
             self.contact_pairs = self.links.pairs
             return (self._hertz if self.hertz_friction is None else self._hertz_friction)(rebuilt, mark)
@@ -1067,7 +1099,44 @@ class ContactStepper:
         mark("body_sweep")
         return ops.SolveResult(num_iters=0, residual=0.0, converged=True)
 
+    def contact_forces(self, rebuilt, mark=lambda name: None):
+        """hydrodynamics contact_forces: the stage between compute_contacts() and external_velocity() (HP1.cpp:4737):
+        Hertz force per linker, operator build / refresh, then the contact force of every body F = D f into the force
+        buffer, which the force stage adds to.  The step's statistics start here; mark(name) is told hertz_force,
+        operator, body_force."""
+        if not self.hydro_contact_forces:
+            raise ValueError("contact_forces() is the stage of hydrodynamics=dict(..., contact_forces=True)")
+        self._chain_stats.zero_()
+        c, pairs = self.contacts, self.links.pairs
+        self.contact_pairs = pairs
+        self.lam, self.max_overlap = ops.hertz_contact_force(pairs, c["sep"], self._contact_radius(),
+                                                             self.youngs_modulus, self.poisson_ratio,
+                                                             max_overlap=stat(self._chain_stats, "max_overlap"))
+        mark("hertz_force")
+        self._operator(rebuilt, pairs)
+        mark("operator")
+        self.op.body_force(self.lam, out=self.spring_force, stride=3)
+        mark("body_force")
+        return self.spring_force
+
+    def body_contact_force(self):
+        """[n, 6] (F, T): the force and the torque about its centre that the last step's contacts put on every body
+        (ContactOperator.body_force[_vector]; the mobility is not applied) -- from the multipliers (LCP), the Hertz
+        forces, the frictional Hertz force vectors or the cone solver's impulses -p.  Raises before a first step, and
+        after reorder_bodies until the next one."""
+        if self.op is None or not self.op._h or self.lam is None and self.hertz_friction is None:
+            raise RuntimeError("body_contact_force needs a step: there are no contacts yet")
+        if self.hertz_friction is not None:
+            return self.op.body_force_vector(self.contact_force)
+        if self.friction is not None:
+            return self.op.body_force_vector(-self.impulse)
+        return self.op.body_force(self.lam)
+
     def integrate(self):
+        if self.hydro_contact_forces:  # U = U_ext: the contact force is inside it
+            vel = self.velocity = self.u_ext.clone()
+            ops.integrate_euler(self.dt, vel, self.center, self.quat)
+            return
         vel = self.op.body_velocity()
         if self.chain:  # U = U_ext + U_contact
             ops.axpby(1.0, self.u_ext.view(-1), 1.0, vel.view(-1))
@@ -1112,14 +1181,20 @@ class ContactStepper:
         else:
             st.rebuilt = self.generate_neighbor_links(force=force_rebuild)
         mark("broadphase")
-        if self.chain:
+        if self.hydro_contact_forces:  # the reference's order: contacts first, their force the first term of F
+            self.compute_contacts()
+            mark("narrowphase")
+            self.contact_forces(st.rebuilt, mark)
+            self.external_velocity(external_force, mark)
+        elif self.chain:
             self.external_velocity(external_force, mark)
         elif self.hertz_friction is not None:
             self._fr_has_ext = external_force is not None
             if self._fr_has_ext:  # U_ext = (m_t F, 0)
                 self._fr_u_ext = ops.drag_velocity(self.mob_trans, external_force, out=self._fr_u_ext)
-        self.compute_contacts()
-        mark("narrowphase")
+        if not self.hydro_contact_forces:
+            self.compute_contacts()
+            mark("narrowphase")
         res = self.resolve_collisions(st.rebuilt, mark)
         if self.contact_model == "lcp":
             mark("solve")
