@@ -339,6 +339,13 @@ CONTACT_FORCE_SIGNATURES = {
     "mhip_contact_op_body_force": [_vp, _vp, _vp, _i, _i, _vp],
     "mhip_contact_op_body_force_vector": [_vp, _vp, _vp, _i, _i, _vp],
 }
+# include/mundy_hip_periphery_binding.h, a header of its own for the same reason: name -> argtypes, every function returns
+# int status.  tests/test_periphery_binding_host.py checks this table against that header and the library.
+PERIPHERY_BINDING_SIGNATURES = {
+    "mhip_crosslinkers_set_periphery_sites": [_vp, _sz, _vp, _d, _d, _d, _d, _d, _vp],
+    "mhip_crosslinkers_set_periphery_candidates": [_vp, _vp, _vp, _sz, C.c_int32, _vp],
+    "mhip_crosslinkers_kmc_step_periphery": [_vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp],
+}
 OTHER_SYMBOLS = {"mhip_last_error": ([], C.c_char_p), "mhip_version": ([], C.c_int),
                  "mhip_release_cached_workspaces": ([], C.c_int)}
 
@@ -358,7 +365,7 @@ def load():
         import torch  # noqa: F401
         lib = C.CDLL(LIB_PATH)
         for name, argtypes in (list(SIGNATURES.items()) + list(PERIPHERY_SIGNATURES.items()) +
-                               list(CONTACT_FORCE_SIGNATURES.items())):
+                               list(CONTACT_FORCE_SIGNATURES.items()) + list(PERIPHERY_BINDING_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = C.c_int

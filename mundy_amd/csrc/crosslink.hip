@@ -10,8 +10,16 @@
 //                    (rebuilt after every KMC step: count, scan, fill, per-body sort)
 //   force            one lane per body, its left and right lists merged in ascending crosslinker index, no atomics
 // All of it gathers a few rows per lane: bound by the latency of those gathers.
+//
+// Periphery bind sites (include/mundy_hip_periphery_binding.h; HP1.cpp:3340-3398 their rates, :3473-3529 the
+// one draw over both kinds of site): P immobile points with rate constants of their own.  right[c] == -(s + 1) is "bound
+// to site s".  The KMC lane walks a second candidate row (sites, ascending index) after the bead row in the same two
+// sums; the force lane takes the far end from the site array; nothing indexed by a body ever sees a negative right.
+// The kernels without sites are the kernels they were, instruction for instruction: the force kernels share one body
+// with a SITES template flag, the KMC and renumber kernels have siblings (k_xl_kmc_periphery, k_xl_renumber_periphery).
 #include "mhip_internal.hpp"
 #include "force_device.hpp"
+#include "../../include/mundy_hip_periphery_binding.h"
 
 #include <cmath>
 
@@ -112,11 +120,170 @@ __global__ void __launch_bounds__(kBlock)
   wave_stat_add(unbinds, &events[1]);
 }
 
+// The periphery's bind sites as the KMC lane sees them: the second candidate row of every bead (ptr [n + 1], col: site
+// indices, ascending), the P site positions, the sites' own (k, r, A, k_off, 1 / kT, capture radius), and where the
+// number of periphery-bound crosslinkers after the step is added (null: nowhere).
+struct XlSites {
+  const int32_t* ptr;
+  const int32_t* col;
+  const double* center;
+  uint32_t count;
+  XlParams p;
+  int* bound;
+};
+
+// k_xl_kmc with the periphery's row: the same draw, the two sums run on over the site row after the bead row, a
+// doubly bound crosslinker unbinds at the rate of what it is bound to.  A kernel of its own and not a flag of
+// k_xl_kmc's: with the body shared, the compiler grouped the scalar loads of k_xl_kmc's arguments differently, and the
+// kernel without sites is to stay the kernel it was, instruction for instruction.
+template <int TYPE>
+__global__ void __launch_bounds__(kBlock)
+    k_xl_kmc_periphery(size_t m, const int32_t* __restrict__ left, int32_t* __restrict__ right,
+                       const int32_t* __restrict__ ptr, const int32_t* __restrict__ col,
+                       const double* __restrict__ center, const uint64_t* __restrict__ keys,
+                       uint64_t* __restrict__ ctrs, XlParams p, double dt, int* __restrict__ events,
+                       double* __restrict__ z_out, XlSites ps) {
+  int binds = 0, unbinds = 0, at_wall = 0;
+  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
+    const uint64_t ctr = ctrs[c];
+    const uint4 w = philox_draw(keys[c], ctr, 0u);
+    ctrs[c] = ctr + 1;
+    const double u = static_cast<double>(philox_u53(w)) * 0x1p-53;
+    const int32_t l = left[c];
+    const int32_t r0 = right[c];
+    if (r0 != l) {  // doubly bound, to a bead or (r0 < 0) to a site: the rate constant goes by the sign
+      if (u < 1.0 - exp(-(dt * (r0 < 0 ? ps.p.k_off : p.k_off)))) {
+        right[c] = l;
+        ++unbinds;
+      } else if (r0 < 0) {
+        ++at_wall;
+      }
+      if (z_out) z_out[c] = 0.0;
+      continue;
+    }
+    const V3 xl = load3(center, l);
+    const int32_t lo = ptr[l], hi = ptr[l + 1];
+    const int32_t plo = ps.ptr[l], phi = ps.ptr[l + 1];
+    double z_tot = 0.0;
+    for (int32_t e = lo; e < hi; ++e) {
+      const int32_t s = col[e];
+      if (s == l) continue;  // the self site (HP1.cpp:3298-3306)
+      const double d = norm(load3(center, s) - xl);
+      if (!(d <= p.cap)) continue;  // beyond the capture radius: rate 0 exactly, whatever the list still holds
+      z_tot += dt * xl_rate<TYPE>(d, p);
+    }
+    for (int32_t e = plo; e < phi; ++e) {  // the same sum goes on over the periphery row
+      const uint32_t s = static_cast<uint32_t>(ps.col[e]);
+      if (s >= ps.count) continue;  // (a column that is no site is never followed)
+      const double d = norm(load3(ps.center, s) - xl);
+      if (!(d <= ps.p.cap)) continue;
+      z_tot += dt * xl_rate<TYPE>(d, ps.p);
+    }
+    if (z_out) z_out[c] = z_tot;
+    const double p_bind = 1.0 - exp(-z_tot);
+    if (!(u < p_bind)) continue;  // (z_tot = 0: p_bind = 0, never)
+    const double scale = p_bind * dt / z_tot;
+    double cumsum = 0.0;
+    bool chosen = false;
+    for (int32_t e = lo; e < hi; ++e) {
+      const int32_t s = col[e];
+      if (s == l) continue;
+      const double d = norm(load3(center, s) - xl);
+      if (!(d <= p.cap)) continue;
+      cumsum += scale * xl_rate<TYPE>(d, p);
+      if (u < cumsum) {  // HP1.cpp:3518-3527
+        right[c] = s;
+        ++binds;
+        chosen = true;
+        break;
+      }
+    }
+    for (int32_t e = plo; e < phi && !chosen; ++e) {
+      const uint32_t s = static_cast<uint32_t>(ps.col[e]);
+      if (s >= ps.count) continue;
+      const double d = norm(load3(ps.center, s) - xl);
+      if (!(d <= ps.p.cap)) continue;
+      cumsum += scale * xl_rate<TYPE>(d, ps.p);
+      if (u < cumsum) {
+        right[c] = -(static_cast<int32_t>(s) + 1);
+        ++binds;
+        ++at_wall;
+        chosen = true;
+      }
+    }
+  }
+  wave_stat_add(binds, &events[0]);
+  wave_stat_add(unbinds, &events[1]);
+  wave_stat_add(at_wall, ps.bound);  // one atomic per wave, none for 0 or a null counter
+}
+
 __global__ void __launch_bounds__(kBlock) k_xl_renumber(size_t m, const int32_t* __restrict__ new_of_old,
                                                        int32_t* __restrict__ left, int32_t* __restrict__ right) {
   for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
     left[c] = new_of_old[left[c]];
     right[c] = new_of_old[right[c]];
+  }
+}
+// with sites: a periphery-bound head keeps its value (the sites are not bodies) and never indexes new_of_old
+__global__ void __launch_bounds__(kBlock) k_xl_renumber_periphery(size_t m, const int32_t* __restrict__ new_of_old,
+                                                                 int32_t* __restrict__ left,
+                                                                 int32_t* __restrict__ right) {
+  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
+    left[c] = new_of_old[left[c]];
+    const int32_t r = right[c];
+    if (r >= 0) right[c] = new_of_old[r];
+  }
+}
+
+// ---- the periphery's candidate rows: site index = column - col_offset, every row ascending ---------------------------
+__global__ void __launch_bounds__(kBlock) k_xl_site_cols(size_t entries, const int32_t* __restrict__ col_in,
+                                                        int32_t col_offset, int32_t* __restrict__ col,
+                                                        int64_t* __restrict__ key) {
+  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < entries; e += (size_t)gridDim.x * blockDim.x) {
+    const int32_t s = col_in[e] - col_offset;
+    col[e] = s;
+    key[e] = s;
+  }
+}
+
+// ---- right-end incidence with sites: only the heads that sit on a body are listed -----------------------------------
+// (force_device.hpp's ListedAt would list a periphery-bound crosslinker at body -(s + 1); that functor, and the build
+//  chain.hip instantiates for it, are shared with the springs and stay as they are)
+struct RightAtBody {
+  const int32_t* right;
+  const int32_t* left;
+  __device__ bool operator()(size_t c, int32_t& b) const {
+    b = right[c];
+    return b >= 0 && left[c] != b;
+  }
+};
+__global__ void __launch_bounds__(kBlock) k_xl_right_count(size_t m, RightAtBody src, int32_t* __restrict__ deg) {
+  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
+    int32_t b;
+    if (src(c, b)) atomicAdd(&deg[b], 1);
+  }
+}
+__global__ void __launch_bounds__(kBlock) k_xl_right_fill(size_t m, RightAtBody src, const int32_t* __restrict__ ptr,
+                                                         int32_t* __restrict__ cursor, int32_t* __restrict__ ent) {
+  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
+    int32_t b;
+    if (src(c, b)) ent[ptr[b] + atomicAdd(&cursor[b], 1)] = static_cast<int32_t>(c);
+  }
+}
+// the fill order depends on atomic arrival: each body sorts its own short list
+__global__ void __launch_bounds__(kBlock) k_xl_list_sort(size_t n, const int32_t* __restrict__ ptr,
+                                                        int32_t* __restrict__ ent) {
+  for (size_t b = blockIdx.x * (size_t)blockDim.x + threadIdx.x; b < n; b += (size_t)gridDim.x * blockDim.x) {
+    const int32_t lo = ptr[b], hi = ptr[b + 1];
+    for (int32_t a = lo + 1; a < hi; ++a) {
+      const int32_t v = ent[a];
+      int32_t k = a - 1;
+      while (k >= lo && ent[k] > v) {
+        ent[k + 1] = ent[k];
+        --k;
+      }
+      ent[k + 1] = v;
+    }
   }
 }
 
@@ -125,15 +292,19 @@ __global__ void __launch_bounds__(kBlock) k_xl_renumber(size_t m, const int32_t*
 // head sits here) are merged in ascending crosslinker index.  A doubly bound crosslinker is the spring (left, right) of
 // mhip_springs_force: d = x_right - x_left, L, fm and fm d in the same operations at both ends, + at the left end and -
 // at the right, summed from +0.0.  Its statistics are taken at the left end only.
-template <int TYPE, bool ACCUMULATE>
-__global__ void __launch_bounds__(kBlock)
-    k_xl_force(size_t n, const int32_t* __restrict__ lptr, const int32_t* __restrict__ lent,
-               const int32_t* __restrict__ rptr, const int32_t* __restrict__ rent, const int32_t* __restrict__ left,
-               const int32_t* __restrict__ right, const double* __restrict__ center, double k, double r,
-               double* __restrict__ force, int* __restrict__ overstretched,
-               unsigned long long* __restrict__ max_length_bits) {
+// SITES: a crosslinker of the left list with right == -(s + 1) is the spring between x_left and the site y_s, the same
+// term at its place in the merge, added to the left bead only (the site receives nothing: nothing ever moves it).
+template <int TYPE, bool ACCUMULATE, bool SITES>
+__device__ __forceinline__ void xl_force(size_t first, size_t stride, size_t n, const int32_t* __restrict__ lptr,
+                                         const int32_t* __restrict__ lent, const int32_t* __restrict__ rptr,
+                                         const int32_t* __restrict__ rent, const int32_t* __restrict__ left,
+                                         const int32_t* __restrict__ right, const double* __restrict__ center,
+                                         double k, double r, double* __restrict__ force,
+                                         int* __restrict__ overstretched,
+                                         unsigned long long* __restrict__ max_length_bits,
+                                         [[maybe_unused]] const double* __restrict__ site) {
   double lmax = 0.0;
-  for (size_t b = blockIdx.x * (size_t)blockDim.x + threadIdx.x; b < n; b += (size_t)gridDim.x * blockDim.x) {
+  for (size_t b = first; b < n; b += stride) {
     V3 f{0.0, 0.0, 0.0};
     int32_t a = lptr[b], e = rptr[b];
     const int32_t ae = lptr[b + 1], ee = rptr[b + 1];
@@ -147,7 +318,9 @@ __global__ void __launch_bounds__(kBlock)
       const int32_t i = at_left ? static_cast<int32_t>(b) : left[c];
       const int32_t j = at_left ? right[c] : static_cast<int32_t>(b);
       if (i == j) continue;  // singly bound: no force
-      const V3 d = load3(center, j) - load3(center, i);
+      V3 d;
+      if constexpr (SITES) d = (j < 0 ? load3(site, -(j + 1)) : load3(center, j)) - load3(center, i);
+      else d = load3(center, j) - load3(center, i);
       const SpringTerm t = spring_term<TYPE>(d, k, r);
       if (TYPE == MHIP_SPRING_FENE && at_left && !(t.L < r)) atomicAdd(overstretched, 1);
       if (at_left) lmax = t.L > lmax ? t.L : lmax;
@@ -156,6 +329,30 @@ __global__ void __launch_bounds__(kBlock)
     write_force<ACCUMULATE>(force, b, f);
   }
   block_stat_max(lmax, max_length_bits);
+}
+
+template <int TYPE, bool ACCUMULATE>
+__global__ void __launch_bounds__(kBlock)
+    k_xl_force(size_t n, const int32_t* __restrict__ lptr, const int32_t* __restrict__ lent,
+               const int32_t* __restrict__ rptr, const int32_t* __restrict__ rent, const int32_t* __restrict__ left,
+               const int32_t* __restrict__ right, const double* __restrict__ center, double k, double r,
+               double* __restrict__ force, int* __restrict__ overstretched,
+               unsigned long long* __restrict__ max_length_bits) {
+  xl_force<TYPE, ACCUMULATE, false>(blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, n,
+                                    lptr, lent, rptr, rent, left, right, center, k, r, force, overstretched,
+                                    max_length_bits, nullptr);
+}
+template <int TYPE, bool ACCUMULATE>
+__global__ void __launch_bounds__(kBlock)
+    k_xl_force_periphery(size_t n, const int32_t* __restrict__ lptr, const int32_t* __restrict__ lent,
+                         const int32_t* __restrict__ rptr, const int32_t* __restrict__ rent,
+                         const int32_t* __restrict__ left, const int32_t* __restrict__ right,
+                         const double* __restrict__ center, double k, double r, double* __restrict__ force,
+                         int* __restrict__ overstretched, unsigned long long* __restrict__ max_length_bits,
+                         const double* __restrict__ site) {
+  xl_force<TYPE, ACCUMULATE, true>(blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, n,
+                                   lptr, lent, rptr, rent, left, right, center, k, r, force, overstretched,
+                                   max_length_bits, site);
 }
 
 }  // namespace mhip
@@ -169,6 +366,11 @@ struct mhip_crosslinkers {
   HandleBuffer left, right, lptr, lent, rptr, rent, cursor, ws, cptr, ccol, ckey;
   size_t cand_entries = 0;
   bool has_candidates = false;
+  // periphery bind sites (mundy_hip_periphery_binding.h): positions, their candidate rows, their own constants
+  HandleBuffer site, pptr, pcol, pkey;
+  size_t num_sites = 0;
+  XlParams pp{};
+  bool has_sites = false, has_site_candidates = false;
 };
 
 namespace {
@@ -179,8 +381,65 @@ int build_left(mhip_crosslinkers* h, hipStream_t s) {
                          h->lptr.as<int32_t>(), h->lent.as<int32_t>(), h->ws.ptr, s);
 }
 int build_right(mhip_crosslinkers* h, hipStream_t s) {
+  if (h->has_sites) {  // build_incidence's steps with a source that leaves the periphery-bound heads out
+    const RightAtBody src{h->right.as<int32_t>(), h->left.as<int32_t>()};
+    int32_t *deg = h->cursor.as<int32_t>(), *ptr = h->rptr.as<int32_t>(), *ent = h->rent.as<int32_t>();
+    MHIP_HIP(hipMemsetAsync(deg, 0, (h->n + 1) * sizeof(int32_t), s));
+    if (h->m > 0) k_xl_right_count<<<grid_for(h->m), kBlock, 0, s>>>(h->m, src, deg);
+    MHIP_LAUNCH_CHECK();
+    if (h->n > 0) {
+      if (int e = exclusive_scan_i32(deg, ptr, h->n, h->ws.ptr, s)) return e;
+    } else {
+      MHIP_HIP(hipMemsetAsync(ptr, 0, sizeof(int32_t), s));
+    }
+    MHIP_HIP(hipMemsetAsync(deg, 0, (h->n + 1) * sizeof(int32_t), s));
+    if (h->m > 0) {
+      k_xl_right_fill<<<grid_for(h->m), kBlock, 0, s>>>(h->m, src, ptr, deg, ent);
+      MHIP_LAUNCH_CHECK();
+      k_xl_list_sort<<<grid_for(h->n), kBlock, 0, s>>>(h->n, ptr, ent);
+      MHIP_LAUNCH_CHECK();
+    }
+    return MHIP_SUCCESS;
+  }
   return build_incidence(h->n, h->m, ListedAt{h->right.as<int32_t>(), h->left.as<int32_t>()}, h->cursor.as<int32_t>(),
                          h->rptr.as<int32_t>(), h->rent.as<int32_t>(), h->ws.ptr, s);
+}
+
+// one KMC step: mhip_crosslinkers_kmc_step and, with the periphery's rows, mhip_crosslinkers_kmc_step_periphery
+int kmc_step(mhip_crosslinkers* h, const double* center, double dt, const uint64_t* keys, uint64_t* counters,
+             int* events, int* periphery_bound, double* z_total, bool need_sites, mhip_stream_t stream) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "crosslinkers handle is null");
+  MHIP_REQUIRE(std::isfinite(dt) && dt > 0.0, MHIP_ERR_INVALID_ARGUMENT, "dt must be finite and > 0, got %g", dt);
+  MHIP_REQUIRE(events != nullptr, MHIP_ERR_INVALID_ARGUMENT, "events is null");
+  MHIP_REQUIRE(h->m == 0 || (center && keys && counters), MHIP_ERR_INVALID_ARGUMENT,
+               "center / keys / counters is null");
+  MHIP_REQUIRE(h->has_candidates, MHIP_ERR_RUNTIME,
+               "mhip_crosslinkers_set_candidates has not been called since the handle was created or renumbered");
+  MHIP_REQUIRE(h->has_site_candidates || !(need_sites || h->has_sites), MHIP_ERR_RUNTIME,
+               "mhip_crosslinkers_set_periphery_candidates has not been called since the sites were set or the handle "
+               "was renumbered");
+  hipStream_t s = as_stream(stream);
+  MHIP_HIP(hipMemsetAsync(events, 0, 2 * sizeof(int), s));
+  if (h->m == 0) return MHIP_SUCCESS;
+  const unsigned grid = grid_for(h->m);
+  if (h->has_sites) {
+    const XlSites ps{h->pptr.as<int32_t>(), h->pcol.as<int32_t>(), h->site.as<double>(),
+                     static_cast<uint32_t>(h->num_sites), h->pp, periphery_bound};
+    dispatch<MHIP_SPRING_FENE, MHIP_SPRING_HOOKEAN>(h->type, [&](auto type) {
+      k_xl_kmc_periphery<decltype(type)::value><<<grid, kBlock, 0, s>>>(
+          h->m, h->left.as<int32_t>(), h->right.as<int32_t>(), h->cptr.as<int32_t>(), h->ccol.as<int32_t>(), center,
+          keys, counters, h->p, dt, events, z_total, ps);
+    });
+  } else {
+    dispatch<MHIP_SPRING_FENE, MHIP_SPRING_HOOKEAN>(h->type, [&](auto type) {
+      k_xl_kmc<decltype(type)::value><<<grid, kBlock, 0, s>>>(
+          h->m, h->left.as<int32_t>(), h->right.as<int32_t>(), h->cptr.as<int32_t>(), h->ccol.as<int32_t>(), center,
+          keys, counters, h->p, dt, events, z_total);
+    });
+  }
+  MHIP_LAUNCH_CHECK();
+  // the right ends moved (or not: the rebuild is cheaper than a host round trip to find out, DESIGN.md 5f)
+  return build_right(h, s);
 }
 
 }  // namespace
@@ -275,25 +534,70 @@ int mhip_crosslinkers_set_candidates(mhip_crosslinkers_t h, const int32_t* row_p
 
 int mhip_crosslinkers_kmc_step(mhip_crosslinkers_t h, const double* center, double dt, const uint64_t* keys,
                                uint64_t* counters, int* events, double* z_total, mhip_stream_t stream) {
+  return kmc_step(h, center, dt, keys, counters, events, nullptr, z_total, false, stream);
+}
+
+int mhip_crosslinkers_kmc_step_periphery(mhip_crosslinkers_t h, const double* center, double dt, const uint64_t* keys,
+                                         uint64_t* counters, int* events, int* periphery_bound, double* z_total,
+                                         mhip_stream_t stream) {
+  return kmc_step(h, center, dt, keys, counters, events, periphery_bound, z_total, true, stream);
+}
+
+int mhip_crosslinkers_set_periphery_sites(mhip_crosslinkers_t h, size_t P, const double* site_center, double bind_rate,
+                                          double k, double r, double unbind_rate, double capture_radius,
+                                          mhip_stream_t stream) {
+  // what needs no handle first, so that every refusal can be checked without a device
+  MHIP_REQUIRE(P > 0, MHIP_ERR_INVALID_ARGUMENT, "periphery sites: P must be > 0");
+  MHIP_REQUIRE(P < (1ull << 31), MHIP_ERR_INVALID_ARGUMENT, "too many periphery sites for a 32-bit right head");
+  MHIP_REQUIRE(std::isfinite(bind_rate) && bind_rate >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "periphery bind_rate must be finite and >= 0, got %g", bind_rate);
+  MHIP_REQUIRE(std::isfinite(unbind_rate) && unbind_rate >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "periphery unbind_rate must be finite and >= 0, got %g", unbind_rate);
+  MHIP_REQUIRE(std::isfinite(k) && k >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "periphery spring constant k must be finite and >= 0, got %g", k);
+  MHIP_REQUIRE(std::isfinite(r) && r >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "periphery rest length / r_max must be finite and >= 0, got %g", r);
+  MHIP_REQUIRE(std::isfinite(capture_radius) && capture_radius > 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "periphery capture_radius must be finite and > 0, got %g", capture_radius);
   MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "crosslinkers handle is null");
-  MHIP_REQUIRE(std::isfinite(dt) && dt > 0.0, MHIP_ERR_INVALID_ARGUMENT, "dt must be finite and > 0, got %g", dt);
-  MHIP_REQUIRE(events != nullptr, MHIP_ERR_INVALID_ARGUMENT, "events is null");
-  MHIP_REQUIRE(h->m == 0 || (center && keys && counters), MHIP_ERR_INVALID_ARGUMENT,
-               "center / keys / counters is null");
-  MHIP_REQUIRE(h->has_candidates, MHIP_ERR_RUNTIME,
-               "mhip_crosslinkers_set_candidates has not been called since the handle was created or renumbered");
+  MHIP_REQUIRE(site_center != nullptr, MHIP_ERR_INVALID_ARGUMENT, "site_center is null");
+  MHIP_REQUIRE(h->type != MHIP_SPRING_FENE || r > 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "periphery r_max must be > 0 for FENE crosslinkers, got %g", r);
+  MHIP_REQUIRE(!h->has_sites || P == h->num_sites, MHIP_ERR_INVALID_ARGUMENT,
+               "periphery sites: P = %zu, but an earlier call set %zu sites", P, h->num_sites);
   hipStream_t s = as_stream(stream);
-  MHIP_HIP(hipMemsetAsync(events, 0, 2 * sizeof(int), s));
-  if (h->m == 0) return MHIP_SUCCESS;
-  const unsigned grid = grid_for(h->m);
-  dispatch<MHIP_SPRING_FENE, MHIP_SPRING_HOOKEAN>(h->type, [&](auto type) {
-    k_xl_kmc<decltype(type)::value><<<grid, kBlock, 0, s>>>(
-        h->m, h->left.as<int32_t>(), h->right.as<int32_t>(), h->cptr.as<int32_t>(), h->ccol.as<int32_t>(), center, keys,
-        counters, h->p, dt, events, z_total);
-  });
-  MHIP_LAUNCH_CHECK();
-  // the right ends moved (or not: the rebuild is cheaper than a host round trip to find out, DESIGN.md 5f)
-  return build_right(h, s);
+  h->has_site_candidates = false;
+  if (int e = h->site.reserve(P * 3 * sizeof(double))) return e;
+  MHIP_HIP(hipMemcpyAsync(h->site.ptr, site_center, P * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
+  h->num_sites = P;
+  h->pp = XlParams{k, r, bind_rate, unbind_rate, h->p.inv_kt, capture_radius};
+  h->has_sites = true;
+  return MHIP_SUCCESS;
+}
+
+int mhip_crosslinkers_set_periphery_candidates(mhip_crosslinkers_t h, const int32_t* row_ptr, const int32_t* col,
+                                               size_t num_entries, int32_t col_offset, mhip_stream_t stream) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "crosslinkers handle is null");
+  MHIP_REQUIRE(row_ptr != nullptr, MHIP_ERR_INVALID_ARGUMENT, "row_ptr is null");
+  MHIP_REQUIRE(num_entries == 0 || col, MHIP_ERR_INVALID_ARGUMENT, "col is null");
+  MHIP_REQUIRE(num_entries < (1ull << 31), MHIP_ERR_INVALID_ARGUMENT, "too many candidates for a 32-bit row_ptr");
+  MHIP_REQUIRE(h->has_sites, MHIP_ERR_RUNTIME, "mhip_crosslinkers_set_periphery_sites has not been called");
+  hipStream_t s = as_stream(stream);
+  h->has_site_candidates = false;
+  if (int e = h->pptr.reserve((h->n + 1) * sizeof(int32_t))) return e;
+  if (int e = h->pcol.reserve(num_entries * sizeof(int32_t) + 8)) return e;
+  if (int e = h->pkey.reserve(num_entries * sizeof(int64_t) + 8)) return e;
+  MHIP_HIP(hipMemcpyAsync(h->pptr.ptr, row_ptr, (h->n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  if (num_entries > 0) {
+    k_xl_site_cols<<<grid_for(num_entries), kBlock, 0, s>>>(num_entries, col, col_offset, h->pcol.as<int32_t>(),
+                                                           h->pkey.as<int64_t>());
+    MHIP_LAUNCH_CHECK();
+    k_xl_row_sort<<<grid_for(h->n), kBlock, 0, s>>>(h->n, h->pptr.as<int32_t>(), h->pkey.as<int64_t>(),
+                                                   h->pcol.as<int32_t>());
+    MHIP_LAUNCH_CHECK();
+  }
+  h->has_site_candidates = true;
+  return MHIP_SUCCESS;
 }
 
 int mhip_crosslinkers_force(mhip_crosslinkers_t h, const double* center, double* force, int accumulate,
@@ -310,9 +614,15 @@ int mhip_crosslinkers_force(mhip_crosslinkers_t h, const double* center, double*
   unsigned long long* mx = reinterpret_cast<unsigned long long*>(max_length);
   dispatch<MHIP_SPRING_FENE, MHIP_SPRING_HOOKEAN>(h->type, [&](auto type) {
     dispatch<true, false>(accumulate != 0, [&](auto acc) {
-      k_xl_force<decltype(type)::value, decltype(acc)::value><<<grid, kBlock, 0, s>>>(
-          h->n, h->lptr.as<int32_t>(), h->lent.as<int32_t>(), h->rptr.as<int32_t>(), h->rent.as<int32_t>(),
-          h->left.as<int32_t>(), h->right.as<int32_t>(), center, h->p.k, h->p.r, force, overstretched, mx);
+      if (h->has_sites)
+        k_xl_force_periphery<decltype(type)::value, decltype(acc)::value><<<grid, kBlock, 0, s>>>(
+            h->n, h->lptr.as<int32_t>(), h->lent.as<int32_t>(), h->rptr.as<int32_t>(), h->rent.as<int32_t>(),
+            h->left.as<int32_t>(), h->right.as<int32_t>(), center, h->p.k, h->p.r, force, overstretched, mx,
+            h->site.as<double>());
+      else
+        k_xl_force<decltype(type)::value, decltype(acc)::value><<<grid, kBlock, 0, s>>>(
+            h->n, h->lptr.as<int32_t>(), h->lent.as<int32_t>(), h->rptr.as<int32_t>(), h->rent.as<int32_t>(),
+            h->left.as<int32_t>(), h->right.as<int32_t>(), center, h->p.k, h->p.r, force, overstretched, mx);
     });
   });
   MHIP_LAUNCH_CHECK();
@@ -347,8 +657,13 @@ int mhip_crosslinkers_renumber(mhip_crosslinkers_t h, const int32_t* new_of_old,
   MHIP_REQUIRE(h->n == 0 || new_of_old, MHIP_ERR_INVALID_ARGUMENT, "new_of_old is null");
   hipStream_t s = as_stream(stream);
   h->has_candidates = false;  // the candidate rows are in the old numbering
+  h->has_site_candidates = false;
   if (h->m > 0) {
-    k_xl_renumber<<<grid_for(h->m), kBlock, 0, s>>>(h->m, new_of_old, h->left.as<int32_t>(), h->right.as<int32_t>());
+    if (h->has_sites)
+      k_xl_renumber_periphery<<<grid_for(h->m), kBlock, 0, s>>>(h->m, new_of_old, h->left.as<int32_t>(),
+                                                               h->right.as<int32_t>());
+    else
+      k_xl_renumber<<<grid_for(h->m), kBlock, 0, s>>>(h->m, new_of_old, h->left.as<int32_t>(), h->right.as<int32_t>());
     MHIP_LAUNCH_CHECK();
   }
   if (int e = build_left(h, s)) return e;

@@ -1549,9 +1549,11 @@ def hydro_double_layer(viscosity, center, normal, weight, force, tgt_center, out
 
 
 # ---- crosslinkers that bind and unbind (HP1.cpp:3264-3748, :4728-4739) ------------------------------------------------
-def check_crosslinkers(n, left, right, sites, kind, k, r, bind_rate, unbind_rate, kt, capture_radius):
+def check_crosslinkers(n, left, right, sites, kind, k, r, bind_rate, unbind_rate, kt, capture_radius,
+                       num_periphery_sites=0):
     """host-side validation of a crosslinker set (no library call) -> (left int32 [m], right int32 [m], sites uint8
-    [n], type, k, r, bind_rate, unbind_rate, kt, capture_radius)"""
+    [n], type, k, r, bind_rate, unbind_rate, kt, capture_radius).  num_periphery_sites = P > 0: right may also hold
+    -(s + 1), s in [0, P): bound to periphery site s"""
 
     def host(a):
         return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
@@ -1581,9 +1583,11 @@ def check_crosslinkers(n, left, right, sites, kind, k, r, bind_rate, unbind_rate
         ri = host(right)
         if ri.shape != (m,) or not (ri.dtype.kind in "iu" or ri.size == 0):
             raise ValueError("crosslinker right must be integers of shape [%d], got %s %s" % (m, ri.dtype, ri.shape))
-        if ri.size and (ri.min() < 0 or ri.max() >= n):
-            raise ValueError("crosslinker right: an index outside [0, %d)" % n)
-        bad = (ri != le) & (si[ri] == 0)
+        if ri.size and (ri.min() < -int(num_periphery_sites) or ri.max() >= n):
+            raise ValueError("crosslinker right: an index outside [0, %d)" % n if not num_periphery_sites else
+                             "crosslinker right: an index outside [0, %d) and no periphery site -(s + 1), s in [0, %d)"
+                             % (n, num_periphery_sites))
+        bad = (ri != le) & (ri >= 0) & (si[np.maximum(ri, 0)] == 0)
         if bad.any():
             c = int(np.argmax(bad))
             raise ValueError("crosslinker %d: right head at body %d, which is not a bind site" % (c, int(ri[c])))
@@ -1598,6 +1602,39 @@ def check_crosslinkers(n, left, right, sites, kind, k, r, bind_rate, unbind_rate
             k0, r0, a0, off, kt0, cap)
 
 
+_PERIPHERY_SITE_KEYS = ("points", "bind_rate", "k", "r", "unbind_rate", "capture_radius")
+
+
+def check_periphery_sites(spec, kind, unbind_rate, capture_radius):
+    """host-side validation of periphery bind sites dict(points= [P, 3], bind_rate=, k=, r=, unbind_rate=None,
+    capture_radius=None) for crosslinkers of spring type `kind` (no library call) -> (points float64 [P, 3] host,
+    bind_rate, k, r, unbind_rate, capture_radius); unbind_rate and capture_radius default to the crosslinkers' own"""
+    check_dict_spec(spec, "periphery_sites", _PERIPHERY_SITE_KEYS, optional=("unbind_rate", "capture_radius"))
+    if kind not in SPRING_TYPES:
+        raise ValueError("crosslinker spring type must be 'hookean' or 'fene', got %r" % (kind,))
+    pts = spec["points"]
+    pts = pts.detach().cpu().numpy() if isinstance(pts, torch.Tensor) else np.asarray(pts)
+    if pts.ndim != 2 or pts.shape[1] != 3 or pts.dtype.kind not in "fiu":
+        raise ValueError("periphery_sites points must be numbers of shape [P, 3], got %s %s" % (pts.dtype, pts.shape))
+    if pts.shape[0] == 0:
+        raise ValueError("periphery_sites points: P must be > 0")
+    if pts.shape[0] >= 2 ** 31:
+        raise ValueError("periphery_sites points: too many sites for a 32-bit right head")
+    pts = np.ascontiguousarray(pts, dtype=np.float64)
+    if not np.isfinite(pts).all():
+        raise ValueError("periphery_sites points must be finite")
+    fene = kind == "fene"
+    _, a0 = _spring_param(float(spec["bind_rate"]), 1, "periphery_sites bind_rate", False)
+    _, k0 = _spring_param(float(spec["k"]), 1, "periphery_sites spring constant k", False)
+    _, r0 = _spring_param(float(spec["r"]), 1, "periphery_sites r_max" if fene else "periphery_sites rest length r0",
+                          fene)
+    off = spec.get("unbind_rate")
+    _, off = _spring_param(float(unbind_rate if off is None else off), 1, "periphery_sites unbind_rate", False)
+    cap = spec.get("capture_radius")
+    _, cap = _spring_param(float(capture_radius if cap is None else cap), 1, "periphery_sites capture_radius", True)
+    return pts, a0, k0, r0, off, cap
+
+
 class Crosslinkers(_Handle):
     """m crosslinkers over n bodies (mhip_crosslinkers_*): fixed left heads, right heads that bind to the bodies of the
     `sites` mask and unbind (right == left: singly bound); a doubly bound one is a spring of `kind` / k / r.
@@ -1608,7 +1645,8 @@ class Crosslinkers(_Handle):
         le, ri, si, t, k0, r0, a0, off, kt0, cap = check_crosslinkers(n, left, right, sites, kind, k, r, bind_rate,
                                                                        unbind_rate, kt, capture_radius)
         self.n, self.num_crosslinkers, self.kind = int(n), le.shape[0], kind
-        self.k, self.r, self.capture_radius = k0, r0, cap
+        self.k, self.r, self.capture_radius, self.unbind_rate = k0, r0, cap, off
+        self.num_periphery_sites = 0
         h = C.c_void_p()
         cp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
         capi.check(capi.load().mhip_crosslinkers_create(C.byref(h), self.n, le.shape[0], cp(le), cp(ri), cp(si), t, k0,
@@ -1625,9 +1663,41 @@ class Crosslinkers(_Handle):
             self._h, _ptr(row_ptr, torch.int32, name="row_ptr"), _ptr(col, torch.int32, name="col"), col.shape[0],
             _ptr(ids, torch.int64, allow_none=True, name="ids"), _stream()))
 
-    def kmc_step(self, center, dt, keys, counters, events=None, z_total=None):
+    def set_periphery_sites(self, points, bind_rate, k, r, unbind_rate=None, capture_radius=None):
+        """P immobile bind sites of the periphery (mhip_crosslinkers_set_periphery_sites): points float64 [P, 3] on the
+        device, copied; their own bind_rate, k, r, unbind_rate (default: the crosslinkers'), capture_radius (default:
+        the crosslinkers').  right == -(s + 1) then means bound to site s.  Again with the same P: the sites move.  The
+        periphery candidates are dropped."""
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("points must have shape [P, 3], got %s" % (tuple(points.shape),))
+        _, a0, k0, r0, off, cap = check_periphery_sites(
+            dict(points=np.zeros((max(points.shape[0], 0), 3)), bind_rate=bind_rate, k=k, r=r, unbind_rate=unbind_rate,
+                 capture_radius=capture_radius), self.kind, self.unbind_rate, self.capture_radius)
+        if self.num_periphery_sites and points.shape[0] != self.num_periphery_sites:
+            raise ValueError("periphery sites: P = %d, but an earlier call set %d sites" % (points.shape[0],
+                                                                                         self.num_periphery_sites))
+        capi.check(capi.load().mhip_crosslinkers_set_periphery_sites(
+            self._h, points.shape[0], _ptr(points, cols=3, name="points"), a0, k0, r0, off, cap, _stream()))
+        self.num_periphery_sites = points.shape[0]
+        self.periphery_capture_radius = cap
+
+    def set_periphery_candidates(self, row_ptr, col, col_offset=0):
+        """the first n rows of a CSR whose columns are site index + col_offset (a neighbour search over beads followed
+        by sites: col_offset = n; row_ptr may be longer than n + 1); every row is sorted by site index here, once"""
+        if row_ptr.dim() != 1 or row_ptr.shape[0] < self.n + 1:
+            raise ValueError("row_ptr must hold at least %d entries, got %s" % (self.n + 1, tuple(row_ptr.shape)))
+        off = int(col_offset)
+        if not (0 <= off < 2 ** 31):
+            raise ValueError("col_offset must be in [0, 2^31), got %r" % (col_offset,))
+        capi.check(capi.load().mhip_crosslinkers_set_periphery_candidates(
+            self._h, _ptr(row_ptr, torch.int32, name="row_ptr"), _ptr(col, torch.int32, name="col"), col.shape[0], off,
+            _stream()))
+
+    def kmc_step(self, center, dt, keys, counters, events=None, z_total=None, periphery_bound=None):
         """one KMC step at `center`; counters += 1; -> events int32 [2] = (binds, unbinds), left on the device;
-        z_total (optional float64 [m]) receives every singly bound crosslinker's total rate x dt"""
+        z_total (optional float64 [m]) receives every singly bound crosslinker's total rate x dt; periphery_bound
+        (optional int32 [1], needs periphery sites): the number of periphery-bound crosslinkers after the step is added
+        to it"""
         m = self.num_crosslinkers
         if tuple(center.shape) != (self.n, 3):
             raise ValueError("center must have shape [%d, 3], got %s" % (self.n, tuple(center.shape)))
@@ -1636,6 +1706,14 @@ class Crosslinkers(_Handle):
         if z_total is not None and tuple(z_total.shape) != (m,):
             raise ValueError("z_total must have shape [%d]" % m)
         ev = torch.empty(2, dtype=torch.int32, device=center.device) if events is None else events
+        if periphery_bound is not None:
+            if tuple(periphery_bound.shape) != (1,):
+                raise ValueError("periphery_bound must have shape [1]")
+            capi.check(capi.load().mhip_crosslinkers_kmc_step_periphery(
+                self._h, _ptr(center, cols=3, name="center"), float(dt), _u64(keys, "keys"), _u64(counters, "counters"),
+                _ptr(ev, torch.int32, name="events"), _ptr(periphery_bound, torch.int32, name="periphery_bound"),
+                _ptr(z_total, allow_none=True, name="z_total"), _stream()))
+            return ev
         capi.check(capi.load().mhip_crosslinkers_kmc_step(self._h, _ptr(center, cols=3, name="center"), float(dt),
                                                           _u64(keys, "keys"), _u64(counters, "counters"),
                                                           _ptr(ev, torch.int32, name="events"),

@@ -90,7 +90,8 @@ STATS = {
     "max_crosslinker_length": ("crosslinkers", 4, None), "crosslinkers_overstretched": ("crosslinkers", 5, 0),
     "max_periphery_overlap": ("nucleus", 6, None), "periphery_colliding": ("nucleus", 7, 0),
     "active_springs": ("nucleus", 7, 1), "active_switches_on": ("nucleus", 8, 0),
-    "active_switches_off": ("nucleus", 8, 1)}
+    "active_switches_off": ("nucleus", 8, 1),
+    "crosslinker_periphery_bound": ("crosslinkers", 5, 1)}
 STATS_LENGTH = {"chain": 3, "crosslinkers": 6, "nucleus": 9}  # float64 slots of the array, by the last mode switched on
 # two-int records that one kernel writes at once: name -> its entries, lanes 0 and 1 of one slot
 STAT_PAIRS = {"crosslinker_events": ("crosslinker_binds", "crosslinker_unbinds"),
@@ -132,6 +133,7 @@ class StepStats:
     crosslinker_binds: int = 0    # ... right heads that bound this step
     crosslinker_unbinds: int = 0  # ... and that unbound
     max_crosslinker_length: float = 0.0  # ... the longest doubly bound crosslinker at this step's force evaluation
+    crosslinker_periphery_bound: int = 0  # ... periphery_sites=: of crosslinker_bound, those bound to a periphery site
     periphery_colliding: int = 0         # periphery=: beads in contact with the wall at this step's force evaluation
     max_periphery_overlap: float = 0.0   # ... the deepest of them (ellipsoid_fast: the largest level-set value)
     active_springs: int = 0              # active_forces=: springs in the active state at this step's force evaluation
@@ -181,7 +183,12 @@ class ContactStepper:
         the spring a doubly bound crosslinker is; bind_rate (A) and unbind_rate (k_off) >= 0, kt > 0 (the Boltzmann
         weight of binding), capture_radius > 0 (no binding beyond it), skin >= 0 (buffer of the candidate search).  keys
         (integers in [0, 2^63), default arange(m)) and counter (default 0) key each crosslinker's Philox stream.  The
-        stepper then owns ids [n] (int64, arange(n): the order candidates are walked in, kept by reorder_bodies).
+        stepper then owns ids [n] (int64, arange(n): the order candidates are walked in, kept by reorder_bodies).  Its
+        optional key periphery_sites = dict(points= [P, 3], bind_rate=, k=, r=, unbind_rate=None, capture_radius=None)
+        adds P immobile bind sites on the nuclear envelope (HP1.cpp:3340-3398) with rate constants of
+        their own (unbind_rate and capture_radius default to the crosslinkers'): right may then hold -(s + 1), bound to
+        site s, and a periphery-bound crosslinker is a spring between its bead and the site.  scale_periphery does not
+        move the sites.
         periphery = dict(shape="sphere" | "ellipsoid" | "ellipsoid_fast", radius= (sphere) or radii= (3 semi-axes), k=,
         center=(0, 0, 0), quat=(1, 0, 0, 0)): the wall of the nucleus, a linear spring of constant k >= 0 on every bead
         that touches it ("ellipsoid": exact distance; "ellipsoid_fast": the reference's level-set force, no quat); the
@@ -503,25 +510,46 @@ class ContactStepper:
 
     # -- crosslinkers that bind and unbind (HP1.cpp:3264-3748, :4728-4739) ------------------------------------------------
     _XL_KEYS = ("left", "right", "sites", "kind", "k", "r", "bind_rate", "unbind_rate", "kt", "capture_radius", "skin",
-                "keys", "counter")
+                "keys", "counter", "periphery_sites")
 
     @staticmethod
     def _check_crosslinkers(chain_only, n, spec):
         ContactStepper._check_chain_only("crosslinkers", "no minimum-image crosslinkers", *chain_only)
-        ops.check_dict_spec(spec, "crosslinkers", ContactStepper._XL_KEYS, optional=("right", "keys", "counter"))
+        ops.check_dict_spec(spec, "crosslinkers", ContactStepper._XL_KEYS,
+                            optional=("right", "keys", "counter", "periphery_sites"))
+        per = None
+        if spec.get("periphery_sites") is not None:
+            per = ops.check_periphery_sites(spec["periphery_sites"], spec["kind"], spec["unbind_rate"],
+                                            spec["capture_radius"])
         checked = ops.check_crosslinkers(n, spec["left"], spec.get("right"), spec["sites"], spec["kind"], spec["k"],
                                          spec["r"], spec["bind_rate"], spec["unbind_rate"], spec["kt"],
-                                         spec["capture_radius"])
+                                         spec["capture_radius"], num_periphery_sites=0 if per is None else per[0].shape[0])
         skin = ops._finite_nonneg(spec["skin"], "crosslinker skin")
         m = checked[0].shape[0]
         return (checked, spec["kind"], skin, ops.check_philox_ints(spec.get("keys"), m, "crosslinker keys"),
-                ops.check_philox_ints(spec.get("counter"), m, "crosslinker counter"))
+                ops.check_philox_ints(spec.get("counter"), m, "crosslinker counter"), per)
 
     def _init_crosslinkers(self, xl_spec):
-        (le, ri, si, _, k, r, a, off, kt, cap), skind, skin, keys, counter = xl_spec
+        (le, ri, si, _, k, r, a, off, kt, cap), skind, skin, keys, counter, per = xl_spec
         n, dev = self.center.shape[0], self.center.device
         m = le.shape[0]
-        self.crosslinkers = ops.Crosslinkers(n, le, ri, si, skind, k, r, a, off, kt, cap)
+        self.xl_site_links = self.xl_site_points = None
+        if per is None:
+            self.crosslinkers = ops.Crosslinkers(n, le, ri, si, skind, k, r, a, off, kt, cap)
+        else:  # a periphery-bound initial state arrives through set_state, after the sites are set
+            pts, pa, pk, pr, poff, pcap = per
+            self.crosslinkers = ops.Crosslinkers(n, le, np.where(ri < 0, le, ri), si, skind, k, r, a, off, kt, cap)
+            self.xl_site_points = torch.from_numpy(pts).to(dev)
+            self.crosslinkers.set_periphery_sites(self.xl_site_points, pa, pk, pr, poff, pcap)
+            if (ri < 0).any():
+                self.crosslinkers.set_state(None, torch.from_numpy(ri).to(dev))
+            # the candidate search over beads followed by sites: the beads' rows are copied in every step, the sites
+            # never move, so the displacement rule rebuilds the list when a bead has moved
+            P = pts.shape[0]
+            self._xl_site_all = torch.cat([self.center, self.xl_site_points])
+            self._xl_site_reach = torch.full((n + P,), 0.5 * pcap, dtype=torch.float64, device=dev)
+            self._xl_site_targets = torch.cat([torch.zeros(n, dtype=torch.uint8, device=dev),
+                                               torch.ones(P, dtype=torch.uint8, device=dev)])
         self.crosslinker_skin = skin
         self.xl_keys = torch.arange(m, dtype=torch.int64, device=dev) if keys is None else torch.from_numpy(keys).to(dev)
         self.xl_counter = (torch.zeros(m, dtype=torch.int64, device=dev) if counter is None else
@@ -536,6 +564,7 @@ class ContactStepper:
         self._chain_stats = torch.zeros(STATS_LENGTH["crosslinkers"], dtype=torch.float64, device=dev)
         self.xl_links = None
         self.crosslinker_rebuilds = 0  # candidate lists built so far
+        self.crosslinker_site_rebuilds = 0  # ... and periphery candidate lists
         self._new_crosslinker_search()
 
     def _new_crosslinker_search(self):
@@ -546,6 +575,13 @@ class ContactStepper:
         self.xl_links = (ops.GenNeighborLinks().set_search_buffer(self.crosslinker_skin)
                          .set_search_kind(ops.SEARCH_SPHERES).set_enforce_source_target_symmetry(True)
                          .acts_on(self.xl_sources, self.xl_sites).concretize())
+        if self.xl_site_points is not None:  # periphery_sites=: sources the same beads, targets the sites
+            if self.xl_site_links is not None:
+                self.xl_site_links.close()
+            src = torch.cat([self.xl_sources, torch.zeros_like(self._xl_site_targets[self.xl_sources.shape[0]:])])
+            self.xl_site_links = (ops.GenNeighborLinks().set_search_buffer(self.crosslinker_skin)
+                                  .set_search_kind(ops.SEARCH_SPHERES).set_enforce_source_target_symmetry(True)
+                                  .acts_on(src, self._xl_site_targets).concretize())
 
     def crosslinker_kmc(self):
         """candidate list (rebuilt by the displacement rule, rows sorted by id once per build) -> one KMC step at the
@@ -553,11 +589,22 @@ class ContactStepper:
         if self.xl_links.generate(None, self.center, self.xl_reach):
             self.crosslinker_rebuilds += 1
             self.crosslinkers.set_candidates(self.xl_links.row_ptr, self.xl_links.col, self.ids)
+        if self.xl_site_links is None:
+            self.crosslinkers.kmc_step(self.center, self.dt, self.xl_keys, self.xl_counter,
+                                       events=stat(self._chain_stats, "crosslinker_events"))
+            return
+        n = self.center.shape[0]
+        self._xl_site_all[:n].copy_(self.center)
+        if self.xl_site_links.generate(None, self._xl_site_all, self._xl_site_reach):
+            self.crosslinker_site_rebuilds += 1
+            self.crosslinkers.set_periphery_candidates(self.xl_site_links.row_ptr, self.xl_site_links.col, col_offset=n)
         self.crosslinkers.kmc_step(self.center, self.dt, self.xl_keys, self.xl_counter,
-                                   events=stat(self._chain_stats, "crosslinker_events"))
+                                   events=stat(self._chain_stats, "crosslinker_events"),
+                                   periphery_bound=stat(self._chain_stats, "crosslinker_periphery_bound"))
 
     def crosslinker_state(self):
-        """-> (left, right) int32 [m] device tensors in the current body numbering; right == left: singly bound"""
+        """-> (left, right) int32 [m] device tensors in the current body numbering; right == left: singly bound,
+        right == -(s + 1): bound to periphery site s"""
         return self.crosslinkers.state(self.center.device)
 
     def _snapshot_crosslinkers(self):
@@ -1216,6 +1263,7 @@ class ContactStepper:
                 self.crosslinker_bound += st.crosslinker_binds - st.crosslinker_unbinds
                 st.crosslinker_bound = self.crosslinker_bound
                 st.max_crosslinker_length = got["max_crosslinker_length"]
+                st.crosslinker_periphery_bound = got["crosslinker_periphery_bound"]
                 if got["crosslinkers_overstretched"]:
                     raise RuntimeError("%d FENE crosslinker(s) stretched to L >= r_max: no force (reduce dt)"
                                        % got["crosslinkers_overstretched"])

@@ -265,3 +265,43 @@ def sphere_quadrature(order, radius, include_poles=False, invert=False):
     normals = (-1.0 if invert else 1.0) * points
     points = points * radius
     return np.ascontiguousarray(points), np.ascontiguousarray(weights), np.ascontiguousarray(normals)
+
+
+def periphery_bind_sites(shape, radii, count, seed=1234):
+    """The reference's RANDOM periphery bind sites (HP1.cpp:2907-2963), generated on the host once -> points
+    [count, 3] on the surface, about the origin in the periphery's own frame.  shape "sphere" (radii: the radius, or
+    three equal ones) or "ellipsoid" (radii: the semi-axes a, b, c).  Sphere: theta = 2 pi u1, phi = acos(2 u2 - 1),
+    R (sin phi cos theta, sin phi sin theta, cos phi): uniform in area.  Ellipsoid: the same point of the unit sphere
+    is kept iff sqrt((b c x)^2 + (a c y)^2 + (a b z)^2) / max(b c, a c, a b) > u3 (the area element of the push
+    forward, so that the kept points are uniform in the ellipsoid's area) and then scaled by (a, b, c); a rejected
+    attempt draws three new uniforms.  The uniforms are numpy's default_rng(seed), three per attempt (the sphere uses
+    the first two): the reference's openrand stream is not pinned."""
+    count = int(count)
+    if count <= 0:
+        raise ValueError("count must be > 0, got %r" % (count,))
+    if shape not in ("sphere", "ellipsoid"):
+        raise ValueError("shape must be 'sphere' or 'ellipsoid', got %r" % (shape,))
+    r = np.atleast_1d(np.asarray(radii, dtype=np.float64))
+    if shape == "sphere":
+        if r.shape not in ((1,), (3,)) or not (r == r[0]).all():
+            raise ValueError("a sphere takes one radius, got %r" % (radii,))
+        r = np.full(3, r[0])
+    if r.shape != (3,) or not (np.isfinite(r) & (r > 0.0)).all():
+        raise ValueError("radii must be finite and > 0, got %r" % (radii,))
+    a, b, c = (float(v) for v in r)
+    rng = np.random.default_rng(seed)
+    inv_mu_max = 1.0 / max(b * c, a * c, a * b)
+    kept, have = [], 0
+    while have < count:
+        u = rng.random((count - have, 3))
+        theta = 2.0 * np.pi * u[:, 0]
+        phi = np.arccos(2.0 * u[:, 1] - 1.0)
+        x, y, z = np.sin(phi) * np.cos(theta), np.sin(phi) * np.sin(theta), np.cos(phi)
+        if shape == "sphere":
+            keep = np.ones(x.shape[0], bool)
+        else:
+            mu = np.sqrt((b * c * x) * (b * c * x) + (a * c * y) * (a * c * y) + (a * b * z) * (a * b * z))
+            keep = inv_mu_max * mu > u[:, 2]
+        kept.append(np.stack([a * x[keep], b * y[keep], c * z[keep]], axis=1))
+        have += int(keep.sum())
+    return np.ascontiguousarray(np.concatenate(kept)[:count])
