@@ -114,6 +114,7 @@ int build_incidence(size_t n, size_t m, SRC src, int32_t* deg, int32_t* ptr, int
 }
 template int build_incidence(size_t, size_t, PairEnds, int32_t*, int32_t*, int32_t*, void*, hipStream_t);
 template int build_incidence(size_t, size_t, ListedAt, int32_t*, int32_t*, int32_t*, void*, hipStream_t);
+template int build_incidence(size_t, size_t, ListedAtBody, int32_t*, int32_t*, int32_t*, void*, hipStream_t);
 
 // ---- springs -----------------------------------------------------------------------------------------------------
 // One body per lane: walk its springs in ascending index, recompute each spring's d = x_j - x_i, L = |d| and term

@@ -15,8 +15,9 @@
 // one draw over both kinds of site): P immobile points with rate constants of their own.  right[c] == -(s + 1) is "bound
 // to site s".  The KMC lane walks a second candidate row (sites, ascending index) after the bead row in the same two
 // sums; the force lane takes the far end from the site array; nothing indexed by a body ever sees a negative right.
-// The kernels without sites are the kernels they were, instruction for instruction: the force kernels share one body
-// with a SITES template flag, the KMC and renumber kernels have siblings (k_xl_kmc_periphery, k_xl_renumber_periphery).
+// One text serves both: the force, KMC and renumber kernels are SITES = false / true instantiations of one body each (the
+// KMC's behind two entry points, k_xl_kmc and k_xl_kmc_periphery, which keep the grid-stride loop and their own argument
+// lists), and one incidence source (force_device.hpp's ListedAtBody) builds the right lists of either kind of handle.
 #include "mhip_internal.hpp"
 #include "force_device.hpp"
 #include "../../include/mundy_hip_periphery_binding.h"
@@ -67,57 +68,55 @@ __global__ void __launch_bounds__(kBlock) k_xl_row_sort(size_t n, const int32_t*
 // (HP1.cpp:3487-3491, :3560-3565).  Every lane reads and writes the state of its own crosslinker only and the rates do
 // not depend on the other crosslinkers (no site exclusivity in the reference), so sampling from the state at the start
 // of the step and applying afterwards (:3757-3764) is what the in-place update computes.
-template <int TYPE>
-__global__ void __launch_bounds__(kBlock)
-    k_xl_kmc(size_t m, const int32_t* __restrict__ left, int32_t* __restrict__ right, const int32_t* __restrict__ ptr,
-             const int32_t* __restrict__ col, const double* __restrict__ center, const uint64_t* __restrict__ keys,
-             uint64_t* __restrict__ ctrs, XlParams p, double dt, int* __restrict__ events,
-             double* __restrict__ z_out) {
-  int binds = 0, unbinds = 0;
-  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
-    const uint64_t ctr = ctrs[c];
-    const uint4 w = philox_draw(keys[c], ctr, 0u);
-    ctrs[c] = ctr + 1;
-    const double u = static_cast<double>(philox_u53(w)) * 0x1p-53;
-    const int32_t l = left[c];
-    if (right[c] != l) {  // doubly bound: what HP1.cpp:3554-3573 reduces to
-      if (u < 1.0 - exp(-(dt * p.k_off))) {
-        right[c] = l;
-        ++unbinds;
-      }
-      if (z_out) z_out[c] = 0.0;
-      continue;
-    }
-    const V3 xl = load3(center, l);
-    const int32_t lo = ptr[l], hi = ptr[l + 1];
-    double z_tot = 0.0;
-    for (int32_t e = lo; e < hi; ++e) {
-      const int32_t s = col[e];
-      if (s == l) continue;  // the self site (HP1.cpp:3298-3306)
-      const double d = norm(load3(center, s) - xl);
-      if (!(d <= p.cap)) continue;  // beyond the capture radius: rate 0 exactly, whatever the list still holds
-      z_tot += dt * xl_rate<TYPE>(d, p);
-    }
-    if (z_out) z_out[c] = z_tot;
-    const double p_bind = 1.0 - exp(-z_tot);
-    if (!(u < p_bind)) continue;  // (z_tot = 0: p_bind = 0, never)
-    const double scale = p_bind * dt / z_tot;
-    double cumsum = 0.0;
-    for (int32_t e = lo; e < hi; ++e) {
-      const int32_t s = col[e];
-      if (s == l) continue;
-      const double d = norm(load3(center, s) - xl);
-      if (!(d <= p.cap)) continue;
-      cumsum += scale * xl_rate<TYPE>(d, p);
-      if (u < cumsum) {  // HP1.cpp:3518-3527
-        right[c] = s;
-        ++binds;
-        break;
-      }
-    }
+__device__ __forceinline__ double xl_draw(const uint64_t* __restrict__ keys, uint64_t* __restrict__ ctrs, size_t c) {
+  const uint64_t ctr = ctrs[c];
+  const uint4 w = philox_draw(keys[c], ctr, 0u);
+  ctrs[c] = ctr + 1;
+  return static_cast<double>(philox_u53(w)) * 0x1p-53;
+}
+
+// One candidate row of a left bead: entries col[lo .. hi), the positions the columns index and the constants that rate
+// them.  The bead row (SITE = false) holds body indices and never follows `skip`, the left bead itself (the self site,
+// HP1.cpp:3298-3306); the site row holds site indices and never follows a column outside [0, skip = P).
+template <bool SITE>
+struct XlRow {
+  int32_t lo, hi;
+  const int32_t* col;
+  const double* pos;
+  const XlParams& p;
+  int32_t skip;
+};
+// f(column, rate) for every entry of the row that can be bound to, in row order, until f returns true
+template <int TYPE, bool SITE, class F>
+__device__ __forceinline__ void xl_row_walk(const XlRow<SITE>& row, V3 xl, F&& f) {
+  for (int32_t e = row.lo; e < row.hi; ++e) {
+    const int32_t s = row.col[e];
+    if (SITE ? static_cast<uint32_t>(s) >= static_cast<uint32_t>(row.skip) : s == row.skip) continue;
+    const double d = norm(load3(row.pos, s) - xl);
+    if (!(d <= row.p.cap)) continue;  // beyond the capture radius: rate 0 exactly, whatever the list still holds
+    if (f(s, xl_rate<TYPE>(d, row.p))) break;
   }
-  wave_stat_add(binds, &events[0]);
-  wave_stat_add(unbinds, &events[1]);
+}
+// the running sum z of dt rate, continued over the row
+template <int TYPE, bool SITE>
+__device__ __forceinline__ double xl_row_total(const XlRow<SITE>& row, V3 xl, double dt, double z) {
+  xl_row_walk<TYPE>(row, xl, [&](int32_t, double rate) {
+    z += dt * rate;
+    return false;
+  });
+  return z;
+}
+// the running sum of scale rate, continued over the row: the first column at which it exceeds u (HP1.cpp:3518-3527), -1
+// where none does
+template <int TYPE, bool SITE>
+__device__ __forceinline__ int32_t xl_row_pick(const XlRow<SITE>& row, V3 xl, double scale, double u, double& cumsum) {
+  int32_t chosen = -1;
+  xl_row_walk<TYPE>(row, xl, [&](int32_t s, double rate) {
+    cumsum += scale * rate;
+    if (u < cumsum) chosen = s;
+    return chosen >= 0;
+  });
+  return chosen;
 }
 
 // The periphery's bind sites as the KMC lane sees them: the second candidate row of every bead (ptr [n + 1], col: site
@@ -132,10 +131,72 @@ struct XlSites {
   int* bound;
 };
 
-// k_xl_kmc with the periphery's row: the same draw, the two sums run on over the site row after the bead row, a
-// doubly bound crosslinker unbinds at the rate of what it is bound to.  A kernel of its own and not a flag of
-// k_xl_kmc's: with the body shared, the compiler grouped the scalar loads of k_xl_kmc's arguments differently, and the
-// kernel without sites is to stay the kernel it was, instruction for instruction.
+// What one lane does for crosslinker c.  Doubly bound, to a bead or (right < 0) to a site: it unbinds at the rate
+// constant of what it is bound to (what HP1.cpp:3554-3573 reduces to).  Singly bound: z_tot over the bead row, then
+// (SITES) on over the site row; with u < 1 - exp(-z_tot) the second pass over the same rows picks the column.
+// -> what happened, for the launch's counts: kXlBound / kXlUnbound, and kXlAtWall where it ends the step on a site
+// (returned and counted by the kernel: counters handed in by reference, the compiler kept in scratch).
+enum : int { kXlBound = 1, kXlUnbound = 2, kXlAtWall = 4 };
+template <int TYPE, bool SITES>
+__device__ __forceinline__ int xl_kmc_one(size_t c, const int32_t* __restrict__ left, int32_t* __restrict__ right,
+                                          const int32_t* __restrict__ ptr, const int32_t* __restrict__ col,
+                                          const double* __restrict__ center, const uint64_t* __restrict__ keys,
+                                          uint64_t* __restrict__ ctrs, const XlParams& p, double dt,
+                                          double* __restrict__ z_out, [[maybe_unused]] const XlSites& ps) {
+  const double u = xl_draw(keys, ctrs, c);
+  const int32_t l = left[c];
+  const int32_t r0 = right[c];
+  if (r0 != l) {
+    bool on_site = false;
+    if constexpr (SITES) on_site = r0 < 0;
+    const bool unbinds = u < 1.0 - exp(-(dt * (on_site ? ps.p.k_off : p.k_off)));
+    if (unbinds) right[c] = l;
+    if (z_out) z_out[c] = 0.0;
+    return unbinds ? kXlUnbound : on_site ? kXlAtWall : 0;
+  }
+  const V3 xl = load3(center, l);
+  const XlRow<false> beads{ptr[l], ptr[l + 1], col, center, p, l};
+  const XlRow<true> sites{SITES ? ps.ptr[l] : 0, SITES ? ps.ptr[l + 1] : 0, ps.col, ps.center, ps.p,
+                          static_cast<int32_t>(ps.count)};  // (without SITES: never walked)
+  double z_tot = xl_row_total<TYPE>(beads, xl, dt, 0.0);
+  if constexpr (SITES) z_tot = xl_row_total<TYPE>(sites, xl, dt, z_tot);
+  if (z_out) z_out[c] = z_tot;
+  const double p_bind = 1.0 - exp(-z_tot);
+  if (!(u < p_bind)) return 0;  // (z_tot = 0: p_bind = 0, never)
+  const double scale = p_bind * dt / z_tot;
+  double cumsum = 0.0;
+  int32_t s = xl_row_pick<TYPE>(beads, xl, scale, u, cumsum);
+  if (s >= 0) {
+    right[c] = s;
+    return kXlBound;
+  }
+  if constexpr (SITES) {
+    s = xl_row_pick<TYPE>(sites, xl, scale, u, cumsum);
+    if (s >= 0) {
+      right[c] = -(s + 1);
+      return kXlBound | kXlAtWall;
+    }
+  }
+  return 0;
+}
+
+// The two entry points keep the grid-stride loop and their argument lists: with the loop in the shared function, or one
+// argument list for both, the compiler groups the scalar loads of the kernel without sites differently.
+template <int TYPE>
+__global__ void __launch_bounds__(kBlock)
+    k_xl_kmc(size_t m, const int32_t* __restrict__ left, int32_t* __restrict__ right, const int32_t* __restrict__ ptr,
+             const int32_t* __restrict__ col, const double* __restrict__ center, const uint64_t* __restrict__ keys,
+             uint64_t* __restrict__ ctrs, XlParams p, double dt, int* __restrict__ events,
+             double* __restrict__ z_out) {
+  int binds = 0, unbinds = 0;
+  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
+    const int what = xl_kmc_one<TYPE, false>(c, left, right, ptr, col, center, keys, ctrs, p, dt, z_out, XlSites{});
+    binds += (what & kXlBound) != 0;
+    unbinds += (what & kXlUnbound) != 0;
+  }
+  wave_stat_add(binds, &events[0]);
+  wave_stat_add(unbinds, &events[1]);
+}
 template <int TYPE>
 __global__ void __launch_bounds__(kBlock)
     k_xl_kmc_periphery(size_t m, const int32_t* __restrict__ left, int32_t* __restrict__ right,
@@ -145,93 +206,24 @@ __global__ void __launch_bounds__(kBlock)
                        double* __restrict__ z_out, XlSites ps) {
   int binds = 0, unbinds = 0, at_wall = 0;
   for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
-    const uint64_t ctr = ctrs[c];
-    const uint4 w = philox_draw(keys[c], ctr, 0u);
-    ctrs[c] = ctr + 1;
-    const double u = static_cast<double>(philox_u53(w)) * 0x1p-53;
-    const int32_t l = left[c];
-    const int32_t r0 = right[c];
-    if (r0 != l) {  // doubly bound, to a bead or (r0 < 0) to a site: the rate constant goes by the sign
-      if (u < 1.0 - exp(-(dt * (r0 < 0 ? ps.p.k_off : p.k_off)))) {
-        right[c] = l;
-        ++unbinds;
-      } else if (r0 < 0) {
-        ++at_wall;
-      }
-      if (z_out) z_out[c] = 0.0;
-      continue;
-    }
-    const V3 xl = load3(center, l);
-    const int32_t lo = ptr[l], hi = ptr[l + 1];
-    const int32_t plo = ps.ptr[l], phi = ps.ptr[l + 1];
-    double z_tot = 0.0;
-    for (int32_t e = lo; e < hi; ++e) {
-      const int32_t s = col[e];
-      if (s == l) continue;  // the self site (HP1.cpp:3298-3306)
-      const double d = norm(load3(center, s) - xl);
-      if (!(d <= p.cap)) continue;  // beyond the capture radius: rate 0 exactly, whatever the list still holds
-      z_tot += dt * xl_rate<TYPE>(d, p);
-    }
-    for (int32_t e = plo; e < phi; ++e) {  // the same sum goes on over the periphery row
-      const uint32_t s = static_cast<uint32_t>(ps.col[e]);
-      if (s >= ps.count) continue;  // (a column that is no site is never followed)
-      const double d = norm(load3(ps.center, s) - xl);
-      if (!(d <= ps.p.cap)) continue;
-      z_tot += dt * xl_rate<TYPE>(d, ps.p);
-    }
-    if (z_out) z_out[c] = z_tot;
-    const double p_bind = 1.0 - exp(-z_tot);
-    if (!(u < p_bind)) continue;  // (z_tot = 0: p_bind = 0, never)
-    const double scale = p_bind * dt / z_tot;
-    double cumsum = 0.0;
-    bool chosen = false;
-    for (int32_t e = lo; e < hi; ++e) {
-      const int32_t s = col[e];
-      if (s == l) continue;
-      const double d = norm(load3(center, s) - xl);
-      if (!(d <= p.cap)) continue;
-      cumsum += scale * xl_rate<TYPE>(d, p);
-      if (u < cumsum) {  // HP1.cpp:3518-3527
-        right[c] = s;
-        ++binds;
-        chosen = true;
-        break;
-      }
-    }
-    for (int32_t e = plo; e < phi && !chosen; ++e) {
-      const uint32_t s = static_cast<uint32_t>(ps.col[e]);
-      if (s >= ps.count) continue;
-      const double d = norm(load3(ps.center, s) - xl);
-      if (!(d <= ps.p.cap)) continue;
-      cumsum += scale * xl_rate<TYPE>(d, ps.p);
-      if (u < cumsum) {
-        right[c] = -(static_cast<int32_t>(s) + 1);
-        ++binds;
-        ++at_wall;
-        chosen = true;
-      }
-    }
+    const int what = xl_kmc_one<TYPE, true>(c, left, right, ptr, col, center, keys, ctrs, p, dt, z_out, ps);
+    binds += (what & kXlBound) != 0;
+    unbinds += (what & kXlUnbound) != 0;
+    at_wall += (what & kXlAtWall) != 0;
   }
   wave_stat_add(binds, &events[0]);
   wave_stat_add(unbinds, &events[1]);
   wave_stat_add(at_wall, ps.bound);  // one atomic per wave, none for 0 or a null counter
 }
 
+// a periphery-bound head (SITES, right < 0) keeps its value -- the sites are not bodies -- and never indexes new_of_old
+template <bool SITES>
 __global__ void __launch_bounds__(kBlock) k_xl_renumber(size_t m, const int32_t* __restrict__ new_of_old,
                                                        int32_t* __restrict__ left, int32_t* __restrict__ right) {
   for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
     left[c] = new_of_old[left[c]];
-    right[c] = new_of_old[right[c]];
-  }
-}
-// with sites: a periphery-bound head keeps its value (the sites are not bodies) and never indexes new_of_old
-__global__ void __launch_bounds__(kBlock) k_xl_renumber_periphery(size_t m, const int32_t* __restrict__ new_of_old,
-                                                                 int32_t* __restrict__ left,
-                                                                 int32_t* __restrict__ right) {
-  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
-    left[c] = new_of_old[left[c]];
     const int32_t r = right[c];
-    if (r >= 0) right[c] = new_of_old[r];
+    if (!SITES || r >= 0) right[c] = new_of_old[r];
   }
 }
 
@@ -243,47 +235,6 @@ __global__ void __launch_bounds__(kBlock) k_xl_site_cols(size_t entries, const i
     const int32_t s = col_in[e] - col_offset;
     col[e] = s;
     key[e] = s;
-  }
-}
-
-// ---- right-end incidence with sites: only the heads that sit on a body are listed -----------------------------------
-// (force_device.hpp's ListedAt would list a periphery-bound crosslinker at body -(s + 1); that functor, and the build
-//  chain.hip instantiates for it, are shared with the springs and stay as they are)
-struct RightAtBody {
-  const int32_t* right;
-  const int32_t* left;
-  __device__ bool operator()(size_t c, int32_t& b) const {
-    b = right[c];
-    return b >= 0 && left[c] != b;
-  }
-};
-__global__ void __launch_bounds__(kBlock) k_xl_right_count(size_t m, RightAtBody src, int32_t* __restrict__ deg) {
-  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
-    int32_t b;
-    if (src(c, b)) atomicAdd(&deg[b], 1);
-  }
-}
-__global__ void __launch_bounds__(kBlock) k_xl_right_fill(size_t m, RightAtBody src, const int32_t* __restrict__ ptr,
-                                                         int32_t* __restrict__ cursor, int32_t* __restrict__ ent) {
-  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < m; c += (size_t)gridDim.x * blockDim.x) {
-    int32_t b;
-    if (src(c, b)) ent[ptr[b] + atomicAdd(&cursor[b], 1)] = static_cast<int32_t>(c);
-  }
-}
-// the fill order depends on atomic arrival: each body sorts its own short list
-__global__ void __launch_bounds__(kBlock) k_xl_list_sort(size_t n, const int32_t* __restrict__ ptr,
-                                                        int32_t* __restrict__ ent) {
-  for (size_t b = blockIdx.x * (size_t)blockDim.x + threadIdx.x; b < n; b += (size_t)gridDim.x * blockDim.x) {
-    const int32_t lo = ptr[b], hi = ptr[b + 1];
-    for (int32_t a = lo + 1; a < hi; ++a) {
-      const int32_t v = ent[a];
-      int32_t k = a - 1;
-      while (k >= lo && ent[k] > v) {
-        ent[k + 1] = ent[k];
-        --k;
-      }
-      ent[k + 1] = v;
-    }
   }
 }
 
@@ -363,46 +314,79 @@ struct mhip_crosslinkers {
   size_t n = 0, m = 0;
   int type = MHIP_SPRING_HOOKEAN;
   XlParams p{};
-  HandleBuffer left, right, lptr, lent, rptr, rent, cursor, ws, cptr, ccol, ckey;
-  size_t cand_entries = 0;
-  bool has_candidates = false;
-  // periphery bind sites (mundy_hip_periphery_binding.h): positions, their candidate rows, their own constants
-  HandleBuffer site, pptr, pcol, pkey;
+  HandleBuffer left, right, lptr, lent, rptr, rent, cursor, ws;
+  struct Candidates {  // the rows of every bead, sorted; valid: set since the last event that outdates them
+    HandleBuffer ptr, col, key;
+    bool valid = false;
+  } beads, sites;
+  // periphery bind sites (mundy_hip_periphery_binding.h): positions, their own constants (their rows: `sites`)
+  HandleBuffer site;
   size_t num_sites = 0;
   XlParams pp{};
-  bool has_sites = false, has_site_candidates = false;
+  bool has_sites = false;
 };
 
 namespace {
+
+// The five constants of one kind of bind site, refused in each caller's words: `spring` goes before the spring's two
+// ("crosslinker " / "periphery "), `rate` before the other three ("" / "periphery "), r is called r_name and must be
+// > 0 (r_positive) or >= 0.
+int check_constants(const char* spring, const char* rate, const char* r_name, bool r_positive, double k, double r,
+                    double bind_rate, double unbind_rate, double capture_radius) {
+  MHIP_REQUIRE(std::isfinite(k) && k >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "%sspring constant k must be finite and >= 0, got %g", spring, k);
+  MHIP_REQUIRE(std::isfinite(r) && (r_positive ? r > 0.0 : r >= 0.0), MHIP_ERR_INVALID_ARGUMENT,
+               "%s%s must be finite and %s 0, got %g", spring, r_name, r_positive ? ">" : ">=", r);
+  MHIP_REQUIRE(std::isfinite(bind_rate) && bind_rate >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "%sbind_rate must be finite and >= 0, got %g", rate, bind_rate);
+  MHIP_REQUIRE(std::isfinite(unbind_rate) && unbind_rate >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "%sunbind_rate must be finite and >= 0, got %g", rate, unbind_rate);
+  MHIP_REQUIRE(std::isfinite(capture_radius) && capture_radius > 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "%scapture_radius must be finite and > 0, got %g", rate, capture_radius);
+  return MHIP_SUCCESS;
+}
 
 // the crosslinkers listed at their left ends, and at their right ends where doubly bound
 int build_left(mhip_crosslinkers* h, hipStream_t s) {
   return build_incidence(h->n, h->m, ListedAt{h->left.as<int32_t>(), nullptr}, h->cursor.as<int32_t>(),
                          h->lptr.as<int32_t>(), h->lent.as<int32_t>(), h->ws.ptr, s);
 }
-int build_right(mhip_crosslinkers* h, hipStream_t s) {
-  if (h->has_sites) {  // build_incidence's steps with a source that leaves the periphery-bound heads out
-    const RightAtBody src{h->right.as<int32_t>(), h->left.as<int32_t>()};
-    int32_t *deg = h->cursor.as<int32_t>(), *ptr = h->rptr.as<int32_t>(), *ent = h->rent.as<int32_t>();
-    MHIP_HIP(hipMemsetAsync(deg, 0, (h->n + 1) * sizeof(int32_t), s));
-    if (h->m > 0) k_xl_right_count<<<grid_for(h->m), kBlock, 0, s>>>(h->m, src, deg);
-    MHIP_LAUNCH_CHECK();
-    if (h->n > 0) {
-      if (int e = exclusive_scan_i32(deg, ptr, h->n, h->ws.ptr, s)) return e;
+int build_right(mhip_crosslinkers* h, hipStream_t s) {  // (a periphery-bound head is listed at no body)
+  return build_incidence(h->n, h->m, ListedAtBody{h->right.as<int32_t>(), h->left.as<int32_t>()},
+                         h->cursor.as<int32_t>(), h->rptr.as<int32_t>(), h->rent.as<int32_t>(), h->ws.ptr, s);
+}
+
+// The first n rows of a device CSR become the handle's bead rows (sites = false: columns are bodies, sorted by ids, or
+// by index where ids is null) or its periphery rows (columns - col_offset are sites, sorted by index).
+int set_candidates(mhip_crosslinkers* h, bool sites, const int32_t* row_ptr, const int32_t* col, size_t num_entries,
+                   const int64_t* ids, int32_t col_offset, mhip_stream_t stream) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "crosslinkers handle is null");
+  MHIP_REQUIRE(row_ptr != nullptr, MHIP_ERR_INVALID_ARGUMENT, "row_ptr is null");
+  MHIP_REQUIRE(num_entries == 0 || col, MHIP_ERR_INVALID_ARGUMENT, "col is null");
+  MHIP_REQUIRE(num_entries < (1ull << 31), MHIP_ERR_INVALID_ARGUMENT, "too many candidates for a 32-bit row_ptr");
+  MHIP_REQUIRE(!sites || h->has_sites, MHIP_ERR_RUNTIME, "mhip_crosslinkers_set_periphery_sites has not been called");
+  hipStream_t s = as_stream(stream);
+  mhip_crosslinkers::Candidates& c = sites ? h->sites : h->beads;
+  c.valid = false;
+  if (int e = c.ptr.reserve((h->n + 1) * sizeof(int32_t))) return e;
+  if (int e = c.col.reserve(num_entries * sizeof(int32_t) + 8)) return e;
+  if (int e = c.key.reserve(num_entries * sizeof(int64_t) + 8)) return e;
+  MHIP_HIP(hipMemcpyAsync(c.ptr.ptr, row_ptr, (h->n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  if (num_entries > 0) {
+    if (sites) {
+      k_xl_site_cols<<<grid_for(num_entries), kBlock, 0, s>>>(num_entries, col, col_offset, c.col.as<int32_t>(),
+                                                             c.key.as<int64_t>());
     } else {
-      MHIP_HIP(hipMemsetAsync(ptr, 0, sizeof(int32_t), s));
+      MHIP_HIP(hipMemcpyAsync(c.col.ptr, col, num_entries * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+      k_xl_entry_keys<<<grid_for(num_entries), kBlock, 0, s>>>(num_entries, c.col.as<int32_t>(), ids,
+                                                              c.key.as<int64_t>());
     }
-    MHIP_HIP(hipMemsetAsync(deg, 0, (h->n + 1) * sizeof(int32_t), s));
-    if (h->m > 0) {
-      k_xl_right_fill<<<grid_for(h->m), kBlock, 0, s>>>(h->m, src, ptr, deg, ent);
-      MHIP_LAUNCH_CHECK();
-      k_xl_list_sort<<<grid_for(h->n), kBlock, 0, s>>>(h->n, ptr, ent);
-      MHIP_LAUNCH_CHECK();
-    }
-    return MHIP_SUCCESS;
+    MHIP_LAUNCH_CHECK();
+    k_xl_row_sort<<<grid_for(h->n), kBlock, 0, s>>>(h->n, c.ptr.as<int32_t>(), c.key.as<int64_t>(), c.col.as<int32_t>());
+    MHIP_LAUNCH_CHECK();
   }
-  return build_incidence(h->n, h->m, ListedAt{h->right.as<int32_t>(), h->left.as<int32_t>()}, h->cursor.as<int32_t>(),
-                         h->rptr.as<int32_t>(), h->rent.as<int32_t>(), h->ws.ptr, s);
+  c.valid = true;
+  return MHIP_SUCCESS;
 }
 
 // one KMC step: mhip_crosslinkers_kmc_step and, with the periphery's rows, mhip_crosslinkers_kmc_step_periphery
@@ -413,9 +397,9 @@ int kmc_step(mhip_crosslinkers* h, const double* center, double dt, const uint64
   MHIP_REQUIRE(events != nullptr, MHIP_ERR_INVALID_ARGUMENT, "events is null");
   MHIP_REQUIRE(h->m == 0 || (center && keys && counters), MHIP_ERR_INVALID_ARGUMENT,
                "center / keys / counters is null");
-  MHIP_REQUIRE(h->has_candidates, MHIP_ERR_RUNTIME,
+  MHIP_REQUIRE(h->beads.valid, MHIP_ERR_RUNTIME,
                "mhip_crosslinkers_set_candidates has not been called since the handle was created or renumbered");
-  MHIP_REQUIRE(h->has_site_candidates || !(need_sites || h->has_sites), MHIP_ERR_RUNTIME,
+  MHIP_REQUIRE(h->sites.valid || !(need_sites || h->has_sites), MHIP_ERR_RUNTIME,
                "mhip_crosslinkers_set_periphery_candidates has not been called since the sites were set or the handle "
                "was renumbered");
   hipStream_t s = as_stream(stream);
@@ -423,18 +407,18 @@ int kmc_step(mhip_crosslinkers* h, const double* center, double dt, const uint64
   if (h->m == 0) return MHIP_SUCCESS;
   const unsigned grid = grid_for(h->m);
   if (h->has_sites) {
-    const XlSites ps{h->pptr.as<int32_t>(), h->pcol.as<int32_t>(), h->site.as<double>(),
+    const XlSites ps{h->sites.ptr.as<int32_t>(), h->sites.col.as<int32_t>(), h->site.as<double>(),
                      static_cast<uint32_t>(h->num_sites), h->pp, periphery_bound};
     dispatch<MHIP_SPRING_FENE, MHIP_SPRING_HOOKEAN>(h->type, [&](auto type) {
       k_xl_kmc_periphery<decltype(type)::value><<<grid, kBlock, 0, s>>>(
-          h->m, h->left.as<int32_t>(), h->right.as<int32_t>(), h->cptr.as<int32_t>(), h->ccol.as<int32_t>(), center,
-          keys, counters, h->p, dt, events, z_total, ps);
+          h->m, h->left.as<int32_t>(), h->right.as<int32_t>(), h->beads.ptr.as<int32_t>(), h->beads.col.as<int32_t>(),
+          center, keys, counters, h->p, dt, events, z_total, ps);
     });
   } else {
     dispatch<MHIP_SPRING_FENE, MHIP_SPRING_HOOKEAN>(h->type, [&](auto type) {
       k_xl_kmc<decltype(type)::value><<<grid, kBlock, 0, s>>>(
-          h->m, h->left.as<int32_t>(), h->right.as<int32_t>(), h->cptr.as<int32_t>(), h->ccol.as<int32_t>(), center,
-          keys, counters, h->p, dt, events, z_total);
+          h->m, h->left.as<int32_t>(), h->right.as<int32_t>(), h->beads.ptr.as<int32_t>(), h->beads.col.as<int32_t>(),
+          center, keys, counters, h->p, dt, events, z_total);
     });
   }
   MHIP_LAUNCH_CHECK();
@@ -457,17 +441,10 @@ int mhip_crosslinkers_create(mhip_crosslinkers_t* handle, size_t n, size_t m, co
   MHIP_REQUIRE(n < (1ull << 31), MHIP_ERR_INVALID_ARGUMENT, "too many bodies for 32-bit crosslinker heads");
   MHIP_REQUIRE(m < (1ull << 31), MHIP_ERR_INVALID_ARGUMENT, "too many crosslinkers for 32-bit incidence entries");
   const bool fene = type == MHIP_SPRING_FENE;
-  MHIP_REQUIRE(std::isfinite(k) && k >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
-               "crosslinker spring constant k must be finite and >= 0, got %g", k);
-  MHIP_REQUIRE(std::isfinite(r) && (fene ? r > 0.0 : r >= 0.0), MHIP_ERR_INVALID_ARGUMENT,
-               "crosslinker %s must be finite and %s 0, got %g", fene ? "r_max" : "rest length", fene ? ">" : ">=", r);
-  MHIP_REQUIRE(std::isfinite(bind_rate) && bind_rate >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
-               "bind_rate must be finite and >= 0, got %g", bind_rate);
-  MHIP_REQUIRE(std::isfinite(unbind_rate) && unbind_rate >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
-               "unbind_rate must be finite and >= 0, got %g", unbind_rate);
+  if (int e = check_constants("crosslinker ", "", fene ? "r_max" : "rest length", fene, k, r, bind_rate, unbind_rate,
+                              capture_radius))
+    return e;
   MHIP_REQUIRE(std::isfinite(kt) && kt > 0.0, MHIP_ERR_INVALID_ARGUMENT, "kt must be finite and > 0, got %g", kt);
-  MHIP_REQUIRE(std::isfinite(capture_radius) && capture_radius > 0.0, MHIP_ERR_INVALID_ARGUMENT,
-               "capture_radius must be finite and > 0, got %g", capture_radius);
   // host arrays: every crosslinker is checked here, before anything reaches the device
   for (size_t c = 0; c < m; ++c) {
     const int32_t l = left[c], rr = right ? right[c] : l;
@@ -508,28 +485,7 @@ int mhip_crosslinkers_destroy(mhip_crosslinkers_t h) {
 
 int mhip_crosslinkers_set_candidates(mhip_crosslinkers_t h, const int32_t* row_ptr, const int32_t* col,
                                      size_t num_entries, const int64_t* ids, mhip_stream_t stream) {
-  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "crosslinkers handle is null");
-  MHIP_REQUIRE(row_ptr != nullptr, MHIP_ERR_INVALID_ARGUMENT, "row_ptr is null");
-  MHIP_REQUIRE(num_entries == 0 || col, MHIP_ERR_INVALID_ARGUMENT, "col is null");
-  MHIP_REQUIRE(num_entries < (1ull << 31), MHIP_ERR_INVALID_ARGUMENT, "too many candidates for a 32-bit row_ptr");
-  hipStream_t s = as_stream(stream);
-  h->has_candidates = false;
-  if (int e = h->cptr.reserve((h->n + 1) * sizeof(int32_t))) return e;
-  if (int e = h->ccol.reserve(num_entries * sizeof(int32_t) + 8)) return e;
-  if (int e = h->ckey.reserve(num_entries * sizeof(int64_t) + 8)) return e;
-  MHIP_HIP(hipMemcpyAsync(h->cptr.ptr, row_ptr, (h->n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-  if (num_entries > 0) {
-    MHIP_HIP(hipMemcpyAsync(h->ccol.ptr, col, num_entries * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    k_xl_entry_keys<<<grid_for(num_entries), kBlock, 0, s>>>(num_entries, h->ccol.as<int32_t>(), ids,
-                                                            h->ckey.as<int64_t>());
-    MHIP_LAUNCH_CHECK();
-    k_xl_row_sort<<<grid_for(h->n), kBlock, 0, s>>>(h->n, h->cptr.as<int32_t>(), h->ckey.as<int64_t>(),
-                                                   h->ccol.as<int32_t>());
-    MHIP_LAUNCH_CHECK();
-  }
-  h->cand_entries = num_entries;
-  h->has_candidates = true;
-  return MHIP_SUCCESS;
+  return set_candidates(h, false, row_ptr, col, num_entries, ids, 0, stream);
 }
 
 int mhip_crosslinkers_kmc_step(mhip_crosslinkers_t h, const double* center, double dt, const uint64_t* keys,
@@ -549,16 +505,9 @@ int mhip_crosslinkers_set_periphery_sites(mhip_crosslinkers_t h, size_t P, const
   // what needs no handle first, so that every refusal can be checked without a device
   MHIP_REQUIRE(P > 0, MHIP_ERR_INVALID_ARGUMENT, "periphery sites: P must be > 0");
   MHIP_REQUIRE(P < (1ull << 31), MHIP_ERR_INVALID_ARGUMENT, "too many periphery sites for a 32-bit right head");
-  MHIP_REQUIRE(std::isfinite(bind_rate) && bind_rate >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
-               "periphery bind_rate must be finite and >= 0, got %g", bind_rate);
-  MHIP_REQUIRE(std::isfinite(unbind_rate) && unbind_rate >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
-               "periphery unbind_rate must be finite and >= 0, got %g", unbind_rate);
-  MHIP_REQUIRE(std::isfinite(k) && k >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
-               "periphery spring constant k must be finite and >= 0, got %g", k);
-  MHIP_REQUIRE(std::isfinite(r) && r >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
-               "periphery rest length / r_max must be finite and >= 0, got %g", r);
-  MHIP_REQUIRE(std::isfinite(capture_radius) && capture_radius > 0.0, MHIP_ERR_INVALID_ARGUMENT,
-               "periphery capture_radius must be finite and > 0, got %g", capture_radius);
+  if (int e = check_constants("periphery ", "periphery ", "rest length / r_max", false, k, r, bind_rate, unbind_rate,
+                              capture_radius))
+    return e;
   MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "crosslinkers handle is null");
   MHIP_REQUIRE(site_center != nullptr, MHIP_ERR_INVALID_ARGUMENT, "site_center is null");
   MHIP_REQUIRE(h->type != MHIP_SPRING_FENE || r > 0.0, MHIP_ERR_INVALID_ARGUMENT,
@@ -566,7 +515,7 @@ int mhip_crosslinkers_set_periphery_sites(mhip_crosslinkers_t h, size_t P, const
   MHIP_REQUIRE(!h->has_sites || P == h->num_sites, MHIP_ERR_INVALID_ARGUMENT,
                "periphery sites: P = %zu, but an earlier call set %zu sites", P, h->num_sites);
   hipStream_t s = as_stream(stream);
-  h->has_site_candidates = false;
+  h->sites.valid = false;
   if (int e = h->site.reserve(P * 3 * sizeof(double))) return e;
   MHIP_HIP(hipMemcpyAsync(h->site.ptr, site_center, P * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
   h->num_sites = P;
@@ -577,27 +526,7 @@ int mhip_crosslinkers_set_periphery_sites(mhip_crosslinkers_t h, size_t P, const
 
 int mhip_crosslinkers_set_periphery_candidates(mhip_crosslinkers_t h, const int32_t* row_ptr, const int32_t* col,
                                                size_t num_entries, int32_t col_offset, mhip_stream_t stream) {
-  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "crosslinkers handle is null");
-  MHIP_REQUIRE(row_ptr != nullptr, MHIP_ERR_INVALID_ARGUMENT, "row_ptr is null");
-  MHIP_REQUIRE(num_entries == 0 || col, MHIP_ERR_INVALID_ARGUMENT, "col is null");
-  MHIP_REQUIRE(num_entries < (1ull << 31), MHIP_ERR_INVALID_ARGUMENT, "too many candidates for a 32-bit row_ptr");
-  MHIP_REQUIRE(h->has_sites, MHIP_ERR_RUNTIME, "mhip_crosslinkers_set_periphery_sites has not been called");
-  hipStream_t s = as_stream(stream);
-  h->has_site_candidates = false;
-  if (int e = h->pptr.reserve((h->n + 1) * sizeof(int32_t))) return e;
-  if (int e = h->pcol.reserve(num_entries * sizeof(int32_t) + 8)) return e;
-  if (int e = h->pkey.reserve(num_entries * sizeof(int64_t) + 8)) return e;
-  MHIP_HIP(hipMemcpyAsync(h->pptr.ptr, row_ptr, (h->n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-  if (num_entries > 0) {
-    k_xl_site_cols<<<grid_for(num_entries), kBlock, 0, s>>>(num_entries, col, col_offset, h->pcol.as<int32_t>(),
-                                                           h->pkey.as<int64_t>());
-    MHIP_LAUNCH_CHECK();
-    k_xl_row_sort<<<grid_for(h->n), kBlock, 0, s>>>(h->n, h->pptr.as<int32_t>(), h->pkey.as<int64_t>(),
-                                                   h->pcol.as<int32_t>());
-    MHIP_LAUNCH_CHECK();
-  }
-  h->has_site_candidates = true;
-  return MHIP_SUCCESS;
+  return set_candidates(h, true, row_ptr, col, num_entries, nullptr, col_offset, stream);
 }
 
 int mhip_crosslinkers_force(mhip_crosslinkers_t h, const double* center, double* force, int accumulate,
@@ -656,14 +585,13 @@ int mhip_crosslinkers_renumber(mhip_crosslinkers_t h, const int32_t* new_of_old,
   MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "crosslinkers handle is null");
   MHIP_REQUIRE(h->n == 0 || new_of_old, MHIP_ERR_INVALID_ARGUMENT, "new_of_old is null");
   hipStream_t s = as_stream(stream);
-  h->has_candidates = false;  // the candidate rows are in the old numbering
-  h->has_site_candidates = false;
+  h->beads.valid = false;  // the candidate rows are in the old numbering
+  h->sites.valid = false;
   if (h->m > 0) {
-    if (h->has_sites)
-      k_xl_renumber_periphery<<<grid_for(h->m), kBlock, 0, s>>>(h->m, new_of_old, h->left.as<int32_t>(),
-                                                               h->right.as<int32_t>());
-    else
-      k_xl_renumber<<<grid_for(h->m), kBlock, 0, s>>>(h->m, new_of_old, h->left.as<int32_t>(), h->right.as<int32_t>());
+    dispatch<true, false>(h->has_sites, [&](auto sites) {
+      k_xl_renumber<decltype(sites)::value><<<grid_for(h->m), kBlock, 0, s>>>(h->m, new_of_old, h->left.as<int32_t>(),
+                                                                             h->right.as<int32_t>());
+    });
     MHIP_LAUNCH_CHECK();
   }
   if (int e = build_left(h, s)) return e;

@@ -30,6 +30,7 @@ void dispatch_bools(bool a, bool b, F&& f) {  // f(std::bool_constant<a>{}, std:
 // A source lists item i of m at bodies: src(i, f) calls f(body, entry) for each.  build_incidence: count -> exclusive
 // scan -> fill -> per-body sort into ptr[0 .. n], ent, every body's list ascending (the fill order depends on atomic
 // arrival).  deg: n + 1 ints of scratch; ws: scan_workspace_bytes(n).  m == 0: ptr all zero, no launches.
+// Every source of the library is one of the three below, and chain.hip instantiates the build for each.
 struct PairEnds {  // entry (s << 1) | side of pair s at body pairs[s][side]
   const int2* pairs;
   template <class F>
@@ -46,6 +47,15 @@ struct ListedAt {  // entry c at body at[c]; with `other`, only where at[c] != o
   __device__ void operator()(size_t c, F&& f) const {
     const int32_t b = at[c];
     if (!other || other[c] != b) f(b, static_cast<int32_t>(c));
+  }
+};
+struct ListedAtBody {  // entry c at body at[c] where that is a body (>= 0: a negative head sits on none) and != other[c]
+  const int32_t* at;
+  const int32_t* other;
+  template <class F>
+  __device__ void operator()(size_t c, F&& f) const {
+    const int32_t b = at[c];
+    if (b >= 0 && other[c] != b) f(b, static_cast<int32_t>(c));
   }
 };
 template <class SRC>

@@ -570,18 +570,15 @@ class ContactStepper:
     def _new_crosslinker_search(self):
         """the candidate search: bounding spheres of radius capture_radius / 2 (+ skin), sources the beads that carry a
         crosslinker, targets the bind sites; a fresh builder, since the masks follow the body numbering"""
-        if self.xl_links is not None:
-            self.xl_links.close()
-        self.xl_links = (ops.GenNeighborLinks().set_search_buffer(self.crosslinker_skin)
-                         .set_search_kind(ops.SEARCH_SPHERES).set_enforce_source_target_symmetry(True)
-                         .acts_on(self.xl_sources, self.xl_sites).concretize())
+        def search(old, sources, targets):
+            if old is not None:
+                old.close()
+            return (ops.GenNeighborLinks().set_search_buffer(self.crosslinker_skin).set_search_kind(ops.SEARCH_SPHERES)
+                    .set_enforce_source_target_symmetry(True).acts_on(sources, targets).concretize())
+        self.xl_links = search(self.xl_links, self.xl_sources, self.xl_sites)
         if self.xl_site_points is not None:  # periphery_sites=: sources the same beads, targets the sites
-            if self.xl_site_links is not None:
-                self.xl_site_links.close()
             src = torch.cat([self.xl_sources, torch.zeros_like(self._xl_site_targets[self.xl_sources.shape[0]:])])
-            self.xl_site_links = (ops.GenNeighborLinks().set_search_buffer(self.crosslinker_skin)
-                                  .set_search_kind(ops.SEARCH_SPHERES).set_enforce_source_target_symmetry(True)
-                                  .acts_on(src, self._xl_site_targets).concretize())
+            self.xl_site_links = search(self.xl_site_links, src, self._xl_site_targets)
 
     def crosslinker_kmc(self):
         """candidate list (rebuilt by the displacement rule, rows sorted by id once per build) -> one KMC step at the

@@ -355,6 +355,82 @@ def test_every_crosslinker_site_bound_then_renumber(which):
     xl.close()
 
 
+def _shared_right_case(m, n=130):
+    """every second crosslinker doubly bound, to one of 11 beads that none has as its left: the right lists hold many
+    crosslinkers each, so the per-body sort after the fill decides their order"""
+    rng = np.random.default_rng(54 + m)
+    c = np.arange(m)
+    left = (c * 7) % 97
+    right = np.where(c % 2 == 0, 100 + (c * 37) % 11, left)
+    return rng.uniform(0.0, 4.0, (n, 3)), rng.uniform(0.0, 4.0, (37, 3)), left, right
+
+
+# neither kind of site is ever bound to and nothing unbinds: a KMC step changes no head and rebuilds the right lists
+QUIET_P = dict(kind="hookean", k=5.0, r=0.5, bind_rate=0.0, unbind_rate=0.0, kt=1.0, capture_radius=1.0)
+QUIET_PER = dict(A=0.0, k=4.0, r=0.4, capture_radius=1.2)
+
+
+@pytest.mark.parametrize("m", [1, 65, 257])
+def test_right_incidence_is_the_same_with_and_without_sites(m):
+    from mundy_amd import ops
+    n = 130
+    c, pts, left, right = _shared_right_case(m, n)
+    if m > 1:
+        assert np.bincount(right[right != left]).max() >= 3
+    ones, p = np.ones(n, np.uint8), QUIET_P
+    center = dev(c)
+    with_sites = _handle(n, left, None, ones, p, pts, QUIET_PER)
+    without = ops.Crosslinkers(n, left, left, ones, p["kind"], p["k"], p["r"], p["bind_rate"], p["unbind_rate"], p["kt"],
+                               p["capture_radius"])
+
+    def same(what, heads, pos):
+        for xl in (with_sites, without):
+            le, ri = _state(xl)
+            assert (le == heads[0]).all() and (ri == heads[1]).all(), what
+        fa, fb = with_sites.force(pos), without.force(pos)
+        assert_bits_equal(host(fa[0]), host(fb[0]), what)
+        assert int(fa[1].item()) == int(fb[1].item()) and float(fa[2].item()) == float(fb[2].item()), what
+        return host(fa[0])
+
+    for xl in (with_sites, without):
+        xl.set_state(None, dev(right.astype(np.int32)))
+    f0 = same("after set_state", (left, right), center)
+    assert_bits_equal(f0, pm.crosslinker_force(n, left, right, "hookean", p["k"], p["r"], c, pts)[0], "model")
+    links, src = _search(center, left, ones, p["capture_radius"], 0.1)
+    plinks, _, _ = _site_search(center, src, dev(pts), QUIET_PER["capture_radius"], 0.1)
+    with_sites.set_periphery_candidates(plinks.row_ptr, plinks.col, col_offset=n)
+    for xl in (with_sites, without):
+        xl.set_candidates(links.row_ptr, links.col, None)
+        ev = host(xl.kmc_step(center, 0.05, _i64(np.arange(m)), torch.zeros(m, dtype=torch.int64, device="cuda")))
+        assert (ev == 0).all()
+    assert_bits_equal(same("after a KMC step", (left, right), center), f0, "the step moved no head")
+    new_of_old = renumberings(np.random.default_rng(0), n)["reversed"]
+    for xl in (with_sites, without):
+        xl.renumber(dev(new_of_old))
+    c2 = np.empty_like(c)
+    c2[new_of_old] = c
+    f2 = same("after renumber", (new_of_old[left], new_of_old[right]), dev(c2))
+    assert_bits_equal(f2[new_of_old], f0, "force after renumber")
+    with_sites.close()
+    without.close()
+
+
+@pytest.mark.parametrize("m", [1, 65, 257])
+def test_right_incidence_leaves_out_the_periphery_bound_among_the_bead_bound(m):
+    n = 130
+    c, pts, left, right = _shared_right_case(m, n)
+    bound = np.flatnonzero(right != left)
+    right[bound[::2]] = -((bound[::2] % pts.shape[0]) + 1)   # every second doubly bound one sits on a site instead
+    xl = _handle(n, left, right, np.ones(n, np.uint8), QUIET_P, pts, QUIET_PER)
+    le, ri = _state(xl)
+    assert (le == left).all() and (ri == right).all() and (ri < 0).any()
+    f, over, mx = xl.force(dev(c))
+    want, wover, wmx, _ = pm.crosslinker_force(n, left, right, "hookean", QUIET_P["k"], QUIET_P["r"], c, pts)
+    assert_bits_equal(host(f), want, "force")
+    assert int(over.item()) == wover and float(mx.item()) == wmx
+    xl.close()
+
+
 def test_refusals_that_need_a_handle():
     from mundy_amd import ops
     n = 8
