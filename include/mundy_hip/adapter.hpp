@@ -13,6 +13,8 @@
 //   mundy_hip::ContactOperator   the matrix-free LinearOp with `void apply(x, y) const` (convex.hpp:133-136); its body
 //                       sweep alone is linker_potential_force_reduction / compute_generalized_velocity (soft contact)
 //   mundy_hip::linkers  evaluate_linker_potentials: the Hertzian contact force per linker (Bacteria.cpp:755-804)
+//   mundy_hip::mech     owners of the chromatin step's library handles: Springs, Crosslinkers, ActiveSprings,
+//                       Hydrodynamics, HydroPeriphery (the HP1 app's force and velocity stages, HP1.cpp:4728-4803)
 //
 // Functors cannot cross a C ABI, so the convex spaces and residual policies are tag types that map to enums; a
 // user-defined LinearOp only needs `void apply(const DeviceVector&, DeviceVector&) const` on device vectors.
@@ -31,6 +33,8 @@
 
 #include "../mundy_hip.h"
 #include "../mundy_hip_contact_force.h"
+#include "../mundy_hip_hydro_periphery.h"
+#include "../mundy_hip_periphery_binding.h"
 
 namespace mundy_hip {
 
@@ -742,6 +746,14 @@ class GenNeighborLinks {  // mundy_mesh/GenNeighborLinkers.hpp:294-866 (builder 
     check(mhip_broadphase_get_pairs(h_, out.data(), nullptr, nullptr, stream));
     return out.data();
   }
+  /// the list's CSR rows (row_ptr [n + 1], col [num_links()]) into caller-owned buffers that only grow; returns the
+  /// entry count
+  size_t rows_into(DeviceArray<int32_t>& row_ptr, DeviceArray<int32_t>& col, mhip_stream_t stream = nullptr) const {
+    if (row_ptr.size() < n_ + 1) row_ptr = DeviceArray<int32_t>(n_ + 1);
+    if (col.size() < num_pairs_ || col.size() == 0) col = DeviceArray<int32_t>(num_pairs_ + num_pairs_ / 4 + 16);
+    check(mhip_broadphase_get_pairs(h_, nullptr, row_ptr.data(), col.data(), stream));
+    return num_pairs_;
+  }
 
  private:
   void guard(const char* what) const {
@@ -1234,6 +1246,175 @@ inline void compute_brownian_velocity(size_t n, const uint64_t* keys, uint64_t* 
                                       const double* mob_trans, double* velocity, mhip_stream_t stream = nullptr) {
   check(mhip_brownian_velocity(n, keys, counters, kt, dt, mob_trans, velocity, stream));
 }
+
+/// Crosslinkers that bind and unbind (mhip_crosslinkers_*; HP1.cpp:4728-4739): host arrays left [m] and is_site [n]
+/// bytes (empty = every body is a bind site); every crosslinker starts singly bound.  With periphery sites
+/// (mundy_hip_periphery_binding.h) the KMC step walks both candidate rows.
+class Crosslinkers {
+ public:
+  Crosslinkers(size_t num_bodies, const std::vector<int32_t>& left, const std::vector<unsigned char>& is_site, int type,
+               double k, double r, double bind_rate, double unbind_rate, double kt, double capture_radius,
+               mhip_stream_t stream = nullptr)
+      : m_(left.size()) {
+    check(mhip_crosslinkers_create(&h_, num_bodies, m_, left.data(), nullptr, is_site.empty() ? nullptr : is_site.data(),
+                                   type, k, r, bind_rate, unbind_rate, kt, capture_radius, stream));
+  }
+  ~Crosslinkers() { mhip_crosslinkers_destroy(h_); }
+  Crosslinkers(const Crosslinkers&) = delete;
+  Crosslinkers& operator=(const Crosslinkers&) = delete;
+  /// site_center [P][3] (device; copied)
+  void set_periphery_sites(size_t num_sites, const double* site_center, double bind_rate, double k, double r,
+                           double unbind_rate, double capture_radius, mhip_stream_t stream = nullptr) {
+    check(mhip_crosslinkers_set_periphery_sites(h_, num_sites, site_center, bind_rate, k, r, unbind_rate, capture_radius,
+                                                stream));
+    has_sites_ = true;
+  }
+  /// the CSR rows of a neighbour search (GenNeighborLinks::rows_into); ids [n] int64 order every row, null = by col
+  void set_candidates(const int32_t* row_ptr, const int32_t* col, size_t num_entries, const int64_t* ids,
+                      mhip_stream_t stream = nullptr) {
+    check(mhip_crosslinkers_set_candidates(h_, row_ptr, col, num_entries, ids, stream));
+  }
+  /// the first n rows of a search over the beads followed by the sites: col_offset = n
+  void set_periphery_candidates(const int32_t* row_ptr, const int32_t* col, size_t num_entries, int32_t col_offset,
+                                mhip_stream_t stream = nullptr) {
+    check(mhip_crosslinkers_set_periphery_candidates(h_, row_ptr, col, num_entries, col_offset, stream));
+  }
+  /// one KMC step; events [device, 2 ints] = (binds, unbinds); with periphery sites the number of periphery-bound
+  /// crosslinkers after the step is added to periphery_bound [device, 1 int, or null]
+  void kmc_step(const double* center, double dt, const uint64_t* keys, uint64_t* counters, int* events,
+                int* periphery_bound = nullptr, mhip_stream_t stream = nullptr) {
+    if (has_sites_)
+      check(mhip_crosslinkers_kmc_step_periphery(h_, center, dt, keys, counters, events, periphery_bound, nullptr,
+                                                 stream));
+    else
+      check(mhip_crosslinkers_kmc_step(h_, center, dt, keys, counters, events, nullptr, stream));
+  }
+  /// the doubly bound crosslinkers as springs into force [n][3]; the statistics [device] as Springs::compute_forces
+  void force(const double* center, double* force, bool accumulate, int* overstretched, double* max_length,
+             mhip_stream_t stream = nullptr) {
+    check(mhip_crosslinkers_force(h_, center, force, accumulate ? 1 : 0, overstretched, max_length, stream));
+  }
+  /// right [m] on the host: left[c] = singly bound, -(s + 1) = bound to periphery site s
+  std::vector<int32_t> right_heads() const {
+    DeviceArray<int32_t> right(m_ ? m_ : 1);
+    check(mhip_crosslinkers_get_state(h_, nullptr, right.data(), nullptr));
+    std::vector<int32_t> host = right.download();
+    host.resize(m_);
+    return host;
+  }
+  size_t size() const { return m_; }
+  bool has_periphery_sites() const { return has_sites_; }
+  mhip_crosslinkers_t handle() const { return h_; }
+
+ private:
+  mhip_crosslinkers_t h_ = nullptr;
+  size_t m_;
+  bool has_sites_ = false;
+};
+
+/// Active euchromatin force dipoles (mhip_active_springs_*; HP1.cpp:3770-3853, :4286-4354): host pairs [m][2]; rng keys
+/// are the spring indices, counters start at 0
+class ActiveSprings {
+ public:
+  ActiveSprings(size_t num_bodies, const std::vector<int32_t>& pairs, double sigma, double kon, double koff,
+                mhip_stream_t stream = nullptr)
+      : m_(pairs.size() / 2) {
+    check(mhip_active_springs_create(&h_, num_bodies, m_, pairs.data(), sigma, kon, koff, nullptr, nullptr, stream));
+  }
+  ~ActiveSprings() { mhip_active_springs_destroy(h_); }
+  ActiveSprings(const ActiveSprings&) = delete;
+  ActiveSprings& operator=(const ActiveSprings&) = delete;
+  /// switches [device, 2 ints] = (switched on, switched off)
+  void sample(int* switches, mhip_stream_t stream = nullptr) { check(mhip_active_springs_sample(h_, switches, stream)); }
+  /// active [device, 1 int, or null] = springs in state 1
+  void force(const double* center, double* force, bool accumulate, int* active, mhip_stream_t stream = nullptr) {
+    check(mhip_active_springs_force(h_, center, force, accumulate ? 1 : 0, active, stream));
+  }
+  void advance(double dt, mhip_stream_t stream = nullptr) { check(mhip_active_springs_advance(h_, dt, stream)); }
+  /// state [m] (0 inactive, 1 active) and next_time [m] on the host
+  std::vector<int32_t> states() const {
+    DeviceArray<int32_t> state(m_ ? m_ : 1);
+    check(mhip_active_springs_get_state(h_, state.data(), nullptr, nullptr, nullptr, nullptr));
+    std::vector<int32_t> host = state.download();
+    host.resize(m_);
+    return host;
+  }
+  std::vector<double> next_times() const {
+    DeviceVector next_time(m_ ? m_ : 1);
+    check(mhip_active_springs_get_state(h_, nullptr, next_time.data(), nullptr, nullptr, nullptr));
+    std::vector<double> host = next_time.download();
+    host.resize(m_);
+    return host;
+  }
+  size_t size() const { return m_; }
+  mhip_active_springs_t handle() const { return h_; }
+
+ private:
+  mhip_active_springs_t h_ = nullptr;
+  size_t m_;
+};
+
+/// The workspace of the n-body hydrodynamic sums (mhip_hydro_t; HP1.cpp:3942-4059): one call at a time per object
+class Hydrodynamics {
+ public:
+  Hydrodynamics() { check(mhip_hydro_create(&h_)); }
+  ~Hydrodynamics() { mhip_hydro_destroy(h_); }
+  Hydrodynamics(const Hydrodynamics&) = delete;
+  Hydrodynamics& operator=(const Hydrodynamics&) = delete;
+  /// velocity rows (stride 3 or 6) of n beads in each other's flow: kind MHIP_HYDRO_*, radius the hydrodynamic radii
+  void velocity(int kind, double viscosity, size_t n, const double* center, const double* radius, const double* force,
+                double* velocity, int velocity_stride = 3, bool accumulate = false, mhip_stream_t stream = nullptr) {
+    check(mhip_hydro_velocity(h_, kind, viscosity, n, center, radius, force, n, center, radius, velocity,
+                              velocity_stride, accumulate ? 1 : 0, stream));
+  }
+  /// velocity[b][0..2] += u_hydro[b][0..2]: a stored hydrodynamic velocity [n][3] into the rows of U_ext
+  static void add_velocity(size_t n, const double* u_hydro, double* velocity, int velocity_stride,
+                           mhip_stream_t stream = nullptr) {
+    check(mhip_hydro_add_velocity(n, u_hydro, velocity, velocity_stride, stream));
+  }
+  mhip_hydro_t handle() const { return h_; }
+
+ private:
+  mhip_hydro_t h_ = nullptr;
+};
+
+/// The no-slip periphery of the hydrodynamics (mhip_hydro_periphery_*; HP1.cpp:4005-4037): host quadrature arrays
+/// points [S][3], weights [S], normals [S][3] (copied).  fill_matrix, invert, then correct on every update.
+class HydroPeriphery {
+ public:
+  HydroPeriphery(const std::vector<double>& points, const std::vector<double>& weights,
+                 const std::vector<double>& normals, double viscosity, mhip_stream_t stream = nullptr) {
+    DeviceVector p(points), w(weights), nrm(normals);
+    check(mhip_hydro_periphery_create(&h_, weights.size(), p.data(), w.data(), nrm.data(), viscosity, stream));
+    try {
+      check(mhip_stream_synchronize(stream));  // the three uploads go out of scope here
+    } catch (...) {
+      mhip_hydro_periphery_destroy(h_);
+      throw;
+    }
+  }
+  ~HydroPeriphery() { mhip_hydro_periphery_destroy(h_); }
+  HydroPeriphery(const HydroPeriphery&) = delete;
+  HydroPeriphery& operator=(const HydroPeriphery&) = delete;
+  void fill_matrix(mhip_stream_t stream = nullptr) { check(mhip_hydro_periphery_fill_matrix(h_, stream)); }
+  /// the matrix becomes its inverse; returns the smallest pivot
+  double invert(mhip_stream_t stream = nullptr) {
+    double min_pivot = 0.0;
+    check(mhip_hydro_periphery_invert(h_, &min_pivot, stream));
+    return min_pivot;
+  }
+  /// the correction of the beads' velocity (kind, arrays and stride as Hydrodynamics::velocity) added to velocity
+  void correct(Hydrodynamics& workspace, int kind, size_t n, const double* center, const double* radius,
+               const double* force, double* velocity, int velocity_stride, bool skip_same_index,
+               mhip_stream_t stream = nullptr) {
+    check(mhip_hydro_periphery_correct(h_, workspace.handle(), kind, n, center, radius, force, velocity, velocity_stride,
+                                       skip_same_index ? 1 : 0, stream));
+  }
+  mhip_hydro_periphery_t handle() const { return h_; }
+
+ private:
+  mhip_hydro_periphery_t h_ = nullptr;
+};
 
 }  // namespace mech
 

@@ -18,6 +18,9 @@
 // SphereChainStepper is the bead-spring chain step of the chromatin apps (NgpHP1.cpp:3802-3990) on spheres, in four
 // stages a host program puts its own force and velocity terms between:
 //   neighbour list -> spring forces -> U_ext = M F + U_brown -> contacts, LCP on sep + dt D^T U_ext, U_ext + M D lambda
+// Its opt-in stages are the rest of the HP1 step (HP1.cpp:4728-4803): crosslinker KMC and springs, periphery bind sites,
+// the nuclear wall and active dipoles in the force stage, n-body hydrodynamics with the periphery's no-slip correction
+// in the velocity stage.
 #pragma once
 #include <chrono>
 #include <cmath>
@@ -53,6 +56,14 @@ struct StepStats {
   double max_curvature_deviation = 0.0;  // FilamentStepper: the largest component of |kappa - kappa_rest|
   double max_spring_length = 0.0;        // SphereChainStepper: the longest spring at the start of the step
   int springs_overstretched = 0;         // SphereChainStepper: springs past their limit (FENE: L >= r_max)
+  // SphereChainStepper with crosslinkers, a periphery or active springs: the step's statistics array
+  int crosslinker_binds = 0, crosslinker_unbinds = 0;  // this step's KMC events
+  int crosslinker_periphery_bound = 0;                 // crosslinkers bound to a periphery site after the KMC step
+  int crosslinkers_overstretched = 0;
+  double max_crosslinker_length = 0.0;
+  int periphery_colliding = 0;  // beads that touch the wall
+  double max_periphery_overlap = 0.0;
+  int active_springs = 0, active_switches_on = 0, active_switches_off = 0;
 };
 
 /// the LCP of a contact operator with right-hand side q: fused BBPGD from lambda = 0 (NgpLcp.cpp:890-891); x receives
@@ -693,6 +704,11 @@ class DistributedSpherocylinderStepper {
 /// step() is the stages in a row.  The only host reads of a step are the neighbour list's rebuild test, the solver's
 /// convergence polls and, at the end of every resolve(), two small blocking downloads: the longest spring and the
 /// overstretched count, whether the caller looks at them or not.  They are what resolve() waits for the step with.
+/// The HP1 stages are options, each a setter called before the first step:
+///   set_crosslinkers [+ set_periphery_sites], set_periphery, set_active_springs     terms of forces(), in the
+///     reference's order (HP1.cpp:4733-4741): KMC -> active sampling -> springs -> crosslinker springs -> periphery
+///     -> active dipoles; their statistics share one device array that resolve() downloads once
+///   set_hydrodynamics [+ set_hydro_periphery]     u_hydro of force(), added to U_ext after the noise (:4744-4803)
 class SphereChainStepper {
  public:
   /// host arrays: center [n][3], radius [n], mob_trans [n]; spring_pairs [m][2] with one stiffness and one rest length
@@ -752,22 +768,109 @@ class SphereChainStepper {
     have_contact_force_ = true;
     return force_.data();
   }
-  /// the spring force into force() [n][3] (Hertz mode: added to the contact force that contact_forces() left there);
-  /// returns it for the caller to accumulate further terms into
-  double* forces() {
-    if (hertz_) {  // (the spring kernel overwrites: its term goes through a buffer of its own)
-      if (!have_contact_force_) throw std::logic_error("SphereChainStepper: forces() before contact_forces()");
-      springs_.compute_forces(center_.data(), spring_term_.data());
-      check(mhip_axpby(3 * n_, 1.0, spring_term_.data(), 1.0, force_.data(), nullptr));
-      return force_.data();
-    }
-    springs_.compute_forces(center_.data(), force_.data());
-    return force_.data();
+  /// Crosslinkers that bind and unbind (mech::Crosslinkers; host arrays left [mx], is_site [n] bytes): their KMC step
+  /// opens forces(), the doubly bound ones follow the backbone as springs of `type`.  Every crosslinker starts singly
+  /// bound; rng keys are the crosslinker indices, counters start at 0, candidate rows are walked by body index.  The
+  /// candidate list is a search of its own (reach capture_radius / 2, buffer skin) under the displacement rule.
+  void set_crosslinkers(const std::vector<int32_t>& left, const std::vector<unsigned char>& is_site, int type, double k,
+                        double r, double bind_rate, double unbind_rate, double kt, double capture_radius, double skin) {
+    xl_.reset(new Crosslinkers(n_, left, is_site, type, k, r, bind_rate, unbind_rate, kt, capture_radius));
+    std::vector<std::uint64_t> key(left.size());
+    for (size_t c = 0; c < key.size(); ++c) key[c] = c;
+    xl_keys_ = DeviceArray<std::uint64_t>(key);
+    xl_counters_ = DeviceArray<std::uint64_t>(std::vector<std::uint64_t>(left.size(), 0));
+    std::vector<std::int64_t> id(n_);
+    for (size_t i = 0; i < n_; ++i) id[i] = static_cast<std::int64_t>(i);
+    ids_ = DeviceArray<std::int64_t>(id);
+    xl_sources_.assign(n_, 0);
+    for (int32_t l : left) xl_sources_[static_cast<size_t>(l)] = 1;
+    xl_skin_ = skin;
+    xl_search_.reset(new CandidateSearch(xl_sources_, is_site, 0.5 * capture_radius, skin));
+    use_stats();
   }
-  /// U_ext = M F + U_brown into u_ext() [n][6] (the counters advance); returns it for the caller to add to
+  /// Immobile bind sites on the periphery (points [P][3], host), after set_crosslinkers: a second candidate list over
+  /// the beads followed by the sites, sources the same beads, targets the sites
+  void set_periphery_sites(const std::vector<double>& points, double bind_rate, double k, double r, double unbind_rate,
+                           double capture_radius) {
+    if (!xl_) throw std::logic_error("SphereChainStepper: set_periphery_sites needs set_crosslinkers first");
+    const size_t P = points.size() / 3;
+    std::vector<double> all = center_.download();
+    all.insert(all.end(), points.begin(), points.end());
+    site_all_ = DeviceVector(all);
+    xl_->set_periphery_sites(P, site_all_.data() + 3 * n_, bind_rate, k, r, unbind_rate, capture_radius);
+    std::vector<unsigned char> sources(xl_sources_), targets(n_, 0);
+    sources.resize(n_ + P, 0);
+    targets.resize(n_ + P, 1);
+    site_search_.reset(new CandidateSearch(sources, targets, 0.5 * capture_radius, xl_skin_));
+  }
+  /// The nuclear wall (mhip_periphery_force): one term of forces()
+  void set_periphery(const mhip_periphery& wall) {
+    wall_ = wall;
+    have_wall_ = true;
+    use_stats();
+  }
+  /// Active force dipoles (mech::ActiveSprings; host pairs [ma][2]): sampled in forces() before the springs, their
+  /// force its last term, their timers advanced by resolve()
+  void set_active_springs(const std::vector<int32_t>& pairs, double sigma, double kon, double koff) {
+    active_.reset(new ActiveSprings(n_, pairs, sigma, kon, koff));
+    use_stats();
+  }
+  /// N-body hydrodynamics (kind MHIP_HYDRO_*, the beads' own radii): external_velocity() adds the stored u_hydro of
+  /// force() to U_ext on every step and recomputes it when step_index() % update_every == 0
+  void set_hydrodynamics(int kind, double viscosity, int update_every) {
+    if (update_every < 1) throw std::invalid_argument("SphereChainStepper: update_every must be >= 1");
+    hydro_.reset(new Hydrodynamics());
+    hydro_kind_ = kind;
+    viscosity_ = viscosity;
+    update_every_ = static_cast<size_t>(update_every);
+    u_hydro_ = DeviceVector(3 * n_);
+  }
+  /// The no-slip periphery of the hydrodynamics (host quadrature arrays), after set_hydrodynamics: its matrix is filled
+  /// and inverted here (min_pivot()), its correction goes into u_hydro at every update
+  void set_hydro_periphery(const std::vector<double>& points, const std::vector<double>& weights,
+                           const std::vector<double>& normals, bool skip_same_index) {
+    if (!hydro_) throw std::logic_error("SphereChainStepper: set_hydro_periphery needs set_hydrodynamics first");
+    hydro_periphery_.reset(new HydroPeriphery(points, weights, normals, viscosity_));
+    hydro_periphery_->fill_matrix();
+    min_pivot_ = hydro_periphery_->invert();
+    skip_same_index_ = skip_same_index;
+  }
+  /// The force stage in the reference's order (HP1.cpp:4733-4741) into force() [n][3]: crosslinker KMC, active sampling,
+  /// springs (Hertz mode: added to the contact force that contact_forces() left there), crosslinker springs, periphery,
+  /// active dipoles, every term after the springs added to them.  Returns force() for the caller to accumulate further
+  /// terms into.
+  double* forces() {
+    if (hertz_ && !have_contact_force_) throw std::logic_error("SphereChainStepper: forces() before contact_forces()");
+    const double* x = center_.data();
+    double* f = force_.data();
+    if (stats_.size()) check(mhip_fill(stats_.size(), stats_.data(), 0.0, nullptr));
+    if (xl_) crosslinker_kmc();
+    if (active_) active_->sample(stat_int(8, 0));
+    if (hertz_) {  // (the spring kernel overwrites: its term goes through a buffer of its own)
+      springs_.compute_forces(x, spring_term_.data());
+      check(mhip_axpby(3 * n_, 1.0, spring_term_.data(), 1.0, f, nullptr));
+    } else {
+      springs_.compute_forces(x, f);
+    }
+    if (xl_) xl_->force(x, f, true, stat_int(5, 0), stat_double(4));
+    if (have_wall_)
+      check(mhip_periphery_force(&wall_, n_, x, radius_.data(), f, 1, stat_int(7, 0), stat_double(6), nullptr));
+    if (active_) active_->force(x, f, true, stat_int(7, 1));
+    return f;
+  }
+  /// U_ext = M F + U_brown (+ u_hydro) into u_ext() [n][6] (the counters advance); returns it for the caller to add to
   double* external_velocity() {
     check(mhip_drag_velocity(n_, mob_t_.data(), force_.data(), u_ext_.data(), nullptr));
     compute_brownian_velocity(n_, keys_.data(), counters_.data(), kt_, dt_, mob_t_.data(), u_ext_.data());
+    if (hydro_) {
+      if (step_index_ % update_every_ == 0) {
+        const double *x = center_.data(), *a = radius_.data();
+        hydro_->velocity(hydro_kind_, viscosity_, n_, x, a, force_.data(), u_hydro_.data());
+        if (hydro_periphery_)
+          hydro_periphery_->correct(*hydro_, hydro_kind_, n_, x, a, force_.data(), u_hydro_.data(), 3, skip_same_index_);
+      }
+      Hydrodynamics::add_velocity(n_, u_hydro_.data(), u_ext_.data(), 6);
+    }
     return u_ext_.data();
   }
   /// contacts -> operator (built after a rebuild, otherwise refreshed) -> q = sep + dt D^T U_ext (NgpHP1.cpp:1488-1531)
@@ -783,11 +886,8 @@ class SphereChainStepper {
       st.num_contacts = num_lambda_;
       st.converged = true;
       check(mhip_deep_copy(6 * n_, vel_.data(), u_ext_.data(), nullptr));
-      if (integrate) check(mhip_integrate_euler(n_, dt_, vel_.data(), center_.data(), nullptr, nullptr));
+      integrate_and_read(integrate, st);
       st.max_overlap = max_overlap_.download()[0];
-      st.max_spring_length = springs_.max_length();  // these reads wait for the step
-      st.springs_overstretched = springs_.overstretched();
-      ++step_index_;
       return st;
     }
     const size_t C = links_.num_links(), cap = C ? C : 1;  // no workspace is null without contacts
@@ -811,10 +911,7 @@ class SphereChainStepper {
     st.converged = res.converged != 0;
     check(mhip_deep_copy(6 * n_, vel_.data(), op_->compute_generalized_velocity(), nullptr));
     check(mhip_axpby(6 * n_, 1.0, u_ext_.data(), 1.0, vel_.data(), nullptr));
-    if (integrate) check(mhip_integrate_euler(n_, dt_, vel_.data(), center_.data(), nullptr, nullptr));
-    st.max_spring_length = springs_.max_length();  // these two reads wait for the step
-    st.springs_overstretched = springs_.overstretched();
-    ++step_index_;
+    integrate_and_read(integrate, st);
     return st;
   }
   /// the plain chain step
@@ -839,8 +936,81 @@ class SphereChainStepper {
   const DeviceArray<int32_t>& pairs() const { return pairs_; }
   const Springs& springs() const { return springs_; }
   size_t step_index() const { return step_index_; }
+  /// the optional stages' handles (null before their setter)
+  const Crosslinkers* crosslinkers() const { return xl_.get(); }
+  const ActiveSprings* active_springs() const { return active_.get(); }
+  /// the smallest pivot of set_hydro_periphery's inversion
+  double min_pivot() const { return min_pivot_; }
 
  private:
+  /// A candidate list of the crosslinkers: bounding spheres of one reach, both orientations, sources and targets as
+  /// byte masks over the searched points, rebuilt by the displacement rule (buffer = skin); the rows as a CSR
+  struct CandidateSearch {
+    CandidateSearch(const std::vector<unsigned char>& sources, const std::vector<unsigned char>& targets, double r,
+                    double skin)
+        : n(sources.size()), reach(std::vector<double>(n, r)) {
+      DeviceArray<unsigned char> s(sources), t(targets);
+      links.set_search_kind(MHIP_SEARCH_SPHERES).set_enforce_source_target_symmetry(true).set_search_buffer(skin);
+      links.acts_on(n, s.data(), targets.empty() ? nullptr : t.data()).concretize();
+      check(mhip_stream_synchronize(nullptr));  // the masks are copied; the two uploads go out of scope here
+    }
+    /// true when the list was rebuilt: row_ptr / col / entries are new
+    bool update(const double* points) {
+      if (!links.generate(n, nullptr, points, reach.data())) return false;
+      entries = links.rows_into(row_ptr, col);
+      return true;
+    }
+    size_t n, entries = 0;
+    DeviceVector reach;
+    DeviceArray<int32_t> row_ptr, col;
+    mesh::GenNeighborLinks links;
+  };
+  /// candidate lists (the beads' own; with periphery sites the one over beads followed by sites, the beads' rows copied
+  /// in every step, the sites' columns offset by n) -> one KMC step at the positions of the start of the step
+  void crosslinker_kmc() {
+    const double* x = center_.data();
+    if (xl_search_->update(x))
+      xl_->set_candidates(xl_search_->row_ptr.data(), xl_search_->col.data(), xl_search_->entries, ids_.data());
+    if (site_search_) {
+      check(mhip_deep_copy(3 * n_, site_all_.data(), x, nullptr));
+      if (site_search_->update(site_all_.data()))
+        xl_->set_periphery_candidates(site_search_->row_ptr.data(), site_search_->col.data(), site_search_->entries,
+                                      static_cast<int32_t>(n_));
+    }
+    xl_->kmc_step(x, dt_, xl_keys_.data(), xl_counters_.data(), stat_int(3, 0), stat_int(5, 1));
+  }
+  /// the statistics array of the optional force terms, in the layout of DESIGN.md 5h: 9 doubles, the int32 entries two
+  /// to a slot; zeroed by forces(), downloaded once by resolve()
+  void use_stats() {
+    if (stats_.size() == 0) stats_ = DeviceVector(9);
+  }
+  double* stat_double(size_t slot) { return stats_.data() + slot; }
+  int* stat_int(size_t slot, size_t lane) { return reinterpret_cast<int*>(stats_.data()) + 2 * slot + lane; }
+  /// the end of resolve(): Euler update, the active timers, and the step's blocking reads
+  void integrate_and_read(bool integrate, StepStats& st) {
+    if (integrate) {
+      check(mhip_integrate_euler(n_, dt_, vel_.data(), center_.data(), nullptr, nullptr));
+      if (active_) active_->advance(dt_);
+    }
+    st.max_spring_length = springs_.max_length();  // these reads wait for the step
+    st.springs_overstretched = springs_.overstretched();
+    if (stats_.size()) {
+      const std::vector<double> d = stats_.download();
+      int i[18];
+      std::memcpy(i, d.data(), sizeof i);
+      st.crosslinker_binds = i[6];
+      st.crosslinker_unbinds = i[7];
+      st.max_crosslinker_length = d[4];
+      st.crosslinkers_overstretched = i[10];
+      st.crosslinker_periphery_bound = i[11];
+      st.max_periphery_overlap = d[6];
+      st.periphery_colliding = i[14];
+      st.active_springs = i[15];
+      st.active_switches_on = i[16];
+      st.active_switches_off = i[17];
+    }
+    ++step_index_;
+  }
   size_t n_;
   double dt_, kt_;
   convex::PGDConfig<double> cfg_;
@@ -857,6 +1027,25 @@ class SphereChainStepper {
   DeviceArray<int32_t> pairs_;
   mesh::GenNeighborLinks links_;
   std::unique_ptr<ContactOperator> op_;
+  // the optional stages (their setters)
+  DeviceVector stats_;  // the statistics array of crosslinkers, periphery and active springs
+  std::unique_ptr<Crosslinkers> xl_;
+  std::unique_ptr<CandidateSearch> xl_search_, site_search_;
+  DeviceArray<std::uint64_t> xl_keys_, xl_counters_;
+  DeviceArray<std::int64_t> ids_;
+  std::vector<unsigned char> xl_sources_;  // bytes [n]: the beads that carry a crosslinker
+  double xl_skin_ = 0.0;
+  DeviceVector site_all_;  // [n + P][3]: the beads' centres followed by the periphery sites
+  bool have_wall_ = false;
+  mhip_periphery wall_{};
+  std::unique_ptr<ActiveSprings> active_;
+  std::unique_ptr<Hydrodynamics> hydro_;
+  std::unique_ptr<HydroPeriphery> hydro_periphery_;
+  int hydro_kind_ = MHIP_HYDRO_RPYC;
+  double viscosity_ = 0.0, min_pivot_ = 0.0;
+  size_t update_every_ = 1;
+  bool skip_same_index_ = false;
+  DeviceVector u_hydro_;  // [n][3]: the stored hydrodynamic velocity
 };
 
 /// Centerline-twist elastic filaments (mhip_filaments_*), stepped in the reference's order: the state lives in the

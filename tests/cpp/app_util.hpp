@@ -20,6 +20,34 @@ inline std::vector<T> read_array(std::FILE* f, size_t count) {
   return v;
 }
 
+/// What the input file of every chain step app opens with: uint64 counts[header_words] = (n, m springs, the app's own
+/// counts ...), then doubles center[3n] radius[n] mob_trans[n], then int32 pairs[2m].  `file` stays open behind the
+/// pairs for what the app reads next.
+struct ChainInput {
+  std::FILE* file;
+  std::vector<std::uint64_t> counts;
+  size_t n, m;
+  std::vector<double> center, radius, mob_trans;
+  std::vector<int32_t> pairs;
+};
+/// a file that does not open ends the program (status 2), as a short one does
+inline ChainInput read_chain_input(const char* path, size_t header_words = 2) {
+  ChainInput in;
+  in.file = std::fopen(path, "rb");
+  if (!in.file) {
+    std::perror(path);
+    std::exit(2);
+  }
+  in.counts = read_array<std::uint64_t>(in.file, header_words);
+  in.n = in.counts[0];
+  in.m = in.counts[1];
+  in.center = read_array<double>(in.file, 3 * in.n);
+  in.radius = read_array<double>(in.file, in.n);
+  in.mob_trans = read_array<double>(in.file, in.n);
+  in.pairs = read_array<int32_t>(in.file, 2 * in.m);
+  return in;
+}
+
 /// order-sensitive FNV-1a over the bit patterns of a host range (items of at most 8 bytes, zero-extended)
 template <class T>
 inline unsigned long long fnv1a(const T* v, size_t count) {

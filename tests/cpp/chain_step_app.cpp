@@ -19,23 +19,14 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "Usage: %s <input.bin> <steps> <dt> <search_buffer> <k> <r0> <kt>\n", argv[0]);
     return 1;
   }
-  std::FILE* f = std::fopen(argv[1], "rb");
-  if (!f) {
-    std::perror(argv[1]);
-    return 2;
-  }
-  const auto nm = read_array<std::uint64_t>(f, 2);
-  const size_t n = nm[0], m = nm[1];
-  const auto center_h = read_array<double>(f, 3 * n), radius_h = read_array<double>(f, n),
-             mob_h = read_array<double>(f, n);
-  const auto pairs_h = read_array<int32_t>(f, 2 * m);
-  std::fclose(f);
+  const ChainInput in = read_chain_input(argv[1]);
+  std::fclose(in.file);
   const int steps = std::atoi(argv[2]);
   const double dt = std::atof(argv[3]), buffer = std::atof(argv[4]), k = std::atof(argv[5]), r0 = std::atof(argv[6]),
                kt = std::atof(argv[7]);
 
-  mech::SphereChainStepper st(center_h, radius_h, mob_h, dt, buffer, {10000, 1e-5} /* NgpLcp.cpp:851-852 */, pairs_h,
-                              MHIP_SPRING_HOOKEAN, k, r0, kt);
+  mech::SphereChainStepper st(in.center, in.radius, in.mob_trans, dt, buffer, {10000, 1e-5} /* NgpLcp.cpp:851-852 */,
+                              in.pairs, MHIP_SPRING_HOOKEAN, k, r0, kt);
   for (int s = 0; s < steps; ++s) {
     const auto t0 = std::chrono::steady_clock::now();
     const mech::StepStats r = st.step();

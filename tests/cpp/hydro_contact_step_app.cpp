@@ -1,7 +1,8 @@
 // hydro_contact_step_app.cpp -- the chromatin step with n-body hydrodynamics and Hertzian contacts in the order of the
 // reference's HP1 app (HP1.cpp:4728-4803; compute_rpy_hydro :3942-4059): the Hertz force is the first term of the force
-// field, so the hydrodynamic velocity sees it.  On spheres, driven from a C++ host program through the stages of
-// mech::SphereChainStepper (mundy_hip/stepper.hpp) and the C ABI, with no Python and no torch in the process:
+// field, so the hydrodynamic velocity sees it.  On spheres, driven from a C++ host program through
+// mech::SphereChainStepper (mundy_hip/stepper.hpp) and its set_hertz_contact + set_hydrodynamics, with no Python and no
+// torch in the process:
 //   neighbour list -> contacts -> Hertz force per linker -> F = D f (mhip_contact_op_body_force) -> += Hookean spring
 //   forces -> U_ext = M F + U_brown -> every update_every-th step u_hydro = hydro(F) -> U_ext += u_hydro -> U = U_ext
 //   -> Euler
@@ -26,17 +27,8 @@ int main(int argc, char** argv) {
                  argv[0]);
     return 1;
   }
-  std::FILE* f = std::fopen(argv[1], "rb");
-  if (!f) {
-    std::perror(argv[1]);
-    return 2;
-  }
-  const auto nm = read_array<std::uint64_t>(f, 2);
-  const size_t n = nm[0], m = nm[1];
-  const auto center_h = read_array<double>(f, 3 * n), radius_h = read_array<double>(f, n),
-             mob_h = read_array<double>(f, n);
-  const auto pairs_h = read_array<int32_t>(f, 2 * m);
-  std::fclose(f);
+  const ChainInput in = read_chain_input(argv[1]);
+  std::fclose(in.file);
   const int steps = std::atoi(argv[2]);
   const double dt = std::atof(argv[3]), buffer = std::atof(argv[4]), k = std::atof(argv[5]), r0 = std::atof(argv[6]),
                kt = std::atof(argv[7]), viscosity = std::atof(argv[8]);
@@ -47,24 +39,13 @@ int main(int argc, char** argv) {
     return 1;
   }
 
-  mech::SphereChainStepper st(center_h, radius_h, mob_h, dt, buffer, {10000, 1e-5} /* NgpLcp.cpp:851-852 */, pairs_h,
-                              MHIP_SPRING_HOOKEAN, k, r0, kt);
+  mech::SphereChainStepper st(in.center, in.radius, in.mob_trans, dt, buffer, {10000, 1e-5} /* NgpLcp.cpp:851-852 */,
+                              in.pairs, MHIP_SPRING_HOOKEAN, k, r0, kt);
   st.set_hertz_contact(youngs_modulus, poisson_ratio, /*contact_forces_in_force_stage=*/true);
-  DeviceVector u_hydro(3 * n);
-  mhip_hydro_t hydro = nullptr;
-  check(mhip_hydro_create(&hydro));
+  st.set_hydrodynamics(kind, viscosity, update_every);
   for (int s = 0; s < steps; ++s) {
     const auto t0 = std::chrono::steady_clock::now();
-    st.neighbors();
-    st.contact_forces();
-    st.forces();
-    double* u_ext = st.external_velocity();
-    // the stored hydrodynamic velocity of F: recomputed every update_every-th step, added on every step
-    const double *x = st.center().data(), *a = st.radius().data();
-    if (s % update_every == 0)
-      check(mhip_hydro_velocity(hydro, kind, viscosity, n, x, a, st.force(), n, x, a, u_hydro.data(), 3, 0, nullptr));
-    check(mhip_hydro_add_velocity(n, u_hydro.data(), u_ext, 6, nullptr));
-    const mech::StepStats r = st.resolve();
+    const mech::StepStats r = st.step();
     const double ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::printf("STEP %d contacts %zu max_overlap %.17g max_spring_length %.17g rebuilt %d ms %.3f\n", s,
                 r.num_contacts, r.max_overlap, r.max_spring_length, r.rebuilt ? 1 : 0, ms);
@@ -73,7 +54,6 @@ int main(int argc, char** argv) {
       return 3;
     }
   }
-  check(mhip_hydro_destroy(hydro));
   std::printf("CHECKSUM center %016llx\n", checksum(st.center().download()));
   return 0;
 }

@@ -1,8 +1,9 @@
 // hydro_periphery_step_app.cpp -- the chromatin step with n-body hydrodynamics inside a no-slip periphery, as the
 // reference's HP1 app runs it by default (HP1.cpp:4744-4803; compute_rpy_hydro :3942-4059 with
 // enable_periphery_hydrodynamics, :4005-4037): the step of hydro_step_app.cpp plus the composite call of
-// mundy_hip_hydro_periphery.h, driven from a C++ host program with no Python and no torch in the process:
-//   start-up: the surface's matrix is filled and inverted (mhip_hydro_periphery_fill_matrix, _invert)
+// mundy_hip_hydro_periphery.h, driven from a C++ host program through mech::SphereChainStepper (mundy_hip/stepper.hpp)
+// and its set_hydrodynamics + set_hydro_periphery, with no Python and no torch in the process:
+//   start-up: the surface's matrix is filled and inverted (set_hydro_periphery)
 //   neighbour list -> Hookean spring forces F -> U_ext = M F + U_brown -> every update_every-th step
 //   u_hydro = hydro(F) + correction(F) -> U_ext += u_hydro -> contacts -> BBPGD -> U = U_ext + M D lambda -> Euler
 // Usage: hydro_periphery_step_app <input.bin> <steps> <dt> <search_buffer> <k> <r0> <kt> <viscosity> <kind> <update_every>
@@ -16,7 +17,6 @@
 
 #include "app_util.hpp"
 #include "mundy_hip/stepper.hpp"
-#include "mundy_hip_hydro_periphery.h"
 
 using namespace mundy_hip;
 
@@ -27,22 +27,13 @@ int main(int argc, char** argv) {
                  argv[0]);
     return 1;
   }
-  std::FILE* f = std::fopen(argv[1], "rb");
-  if (!f) {
-    std::perror(argv[1]);
-    return 2;
-  }
-  const auto nm = read_array<std::uint64_t>(f, 2);
-  const size_t n = nm[0], m = nm[1];
-  const auto center_h = read_array<double>(f, 3 * n), radius_h = read_array<double>(f, n),
-             mob_h = read_array<double>(f, n);
-  const auto pairs_h = read_array<int32_t>(f, 2 * m);
-  const auto surf = read_array<std::uint64_t>(f, 2);
+  const ChainInput in = read_chain_input(argv[1]);
+  const auto surf = read_array<std::uint64_t>(in.file, 2);
   const size_t S = surf[0];
-  const int skip_same_index = surf[1] != 0 ? 1 : 0;
-  const auto points_h = read_array<double>(f, 3 * S), weights_h = read_array<double>(f, S),
-             normals_h = read_array<double>(f, 3 * S);
-  std::fclose(f);
+  const bool skip_same_index = surf[1] != 0;
+  const auto points = read_array<double>(in.file, 3 * S), weights = read_array<double>(in.file, S),
+             normals = read_array<double>(in.file, 3 * S);
+  std::fclose(in.file);
   const int steps = std::atoi(argv[2]);
   const double dt = std::atof(argv[3]), buffer = std::atof(argv[4]), k = std::atof(argv[5]), r0 = std::atof(argv[6]),
                kt = std::atof(argv[7]), viscosity = std::atof(argv[8]);
@@ -52,35 +43,14 @@ int main(int argc, char** argv) {
     return 1;
   }
 
-  mech::SphereChainStepper st(center_h, radius_h, mob_h, dt, buffer, {10000, 1e-5} /* NgpLcp.cpp:851-852 */, pairs_h,
-                              MHIP_SPRING_HOOKEAN, k, r0, kt);
-  DeviceVector u_hydro(3 * n);
-  mhip_hydro_t hydro = nullptr;
-  check(mhip_hydro_create(&hydro));
-  mhip_hydro_periphery_t periphery = nullptr;
-  {
-    DeviceVector points(points_h), weights(weights_h), normals(normals_h);
-    check(mhip_hydro_periphery_create(&periphery, S, points.data(), weights.data(), normals.data(), viscosity, nullptr));
-    check(mhip_stream_synchronize(nullptr));  // the handle has copied the quadrature
-  }
-  double min_pivot = 0.0;
-  check(mhip_hydro_periphery_fill_matrix(periphery, nullptr));
-  check(mhip_hydro_periphery_invert(periphery, &min_pivot, nullptr));
-  std::printf("PERIPHERY nodes %zu min_pivot %.17g\n", S, min_pivot);
+  mech::SphereChainStepper st(in.center, in.radius, in.mob_trans, dt, buffer, {10000, 1e-5} /* NgpLcp.cpp:851-852 */,
+                              in.pairs, MHIP_SPRING_HOOKEAN, k, r0, kt);
+  st.set_hydrodynamics(kind, viscosity, update_every);
+  st.set_hydro_periphery(points, weights, normals, skip_same_index);
+  std::printf("PERIPHERY nodes %zu min_pivot %.17g\n", S, st.min_pivot());
   for (int s = 0; s < steps; ++s) {
     const auto t0 = std::chrono::steady_clock::now();
-    st.neighbors();
-    st.forces();
-    double* u_ext = st.external_velocity();
-    // the stored hydrodynamic velocity of F: recomputed every update_every-th step, added on every step
-    const double *x = st.center().data(), *a = st.radius().data();
-    if (s % update_every == 0) {
-      check(mhip_hydro_velocity(hydro, kind, viscosity, n, x, a, st.force(), n, x, a, u_hydro.data(), 3, 0, nullptr));
-      check(mhip_hydro_periphery_correct(periphery, hydro, kind, n, x, a, st.force(), u_hydro.data(), 3, skip_same_index,
-                                         nullptr));
-    }
-    check(mhip_hydro_add_velocity(n, u_hydro.data(), u_ext, 6, nullptr));
-    const mech::StepStats r = st.resolve();
+    const mech::StepStats r = st.step();
     const double ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::printf("STEP %d contacts %zu iterations %u max_spring_length %.17g rebuilt %d converged %d ms %.3f\n", s,
                 r.num_contacts, r.num_iters, r.max_spring_length, r.rebuilt ? 1 : 0, r.converged ? 1 : 0, ms);
@@ -89,8 +59,6 @@ int main(int argc, char** argv) {
       return 3;
     }
   }
-  check(mhip_hydro_periphery_destroy(periphery));
-  check(mhip_hydro_destroy(hydro));
   std::printf("CHECKSUM center %016llx\n", checksum(st.center().download()));
   return 0;
 }

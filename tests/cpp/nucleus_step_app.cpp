@@ -1,7 +1,7 @@
 // nucleus_step_app.cpp -- the chromatin step of the reference's HP1 app inside its nucleus: bead-spring chains with
 // thermal noise, confined by the periphery (HP1.cpp:4063-4284) and driven by the active euchromatin force dipoles
-// (:3770-3853, :4286-4354), from a C++ host program through the stages of mech::SphereChainStepper
-// (mundy_hip/stepper.hpp) and the C ABI, with no Python and no torch in the process.  The force stage in the
+// (:3770-3853, :4286-4354), from a C++ host program through mech::SphereChainStepper (mundy_hip/stepper.hpp) and its
+// set_periphery + set_active_springs, with no Python and no torch in the process.  The force stage in the
 // reference's order (:4733-4741):
 //   neighbour list -> active sampling -> Hookean backbone forces -> periphery force -> active force dipoles
 //   -> U_ext = M F + U_brown -> contacts, q = sep + dt D^T U_ext -> BBPGD from lambda = 0 -> U = U_ext + M D lambda
@@ -26,18 +26,9 @@ int main(int argc, char** argv) {
                  argv[0]);
     return 1;
   }
-  std::FILE* f = std::fopen(argv[1], "rb");
-  if (!f) {
-    std::perror(argv[1]);
-    return 2;
-  }
-  const auto nm = read_array<std::uint64_t>(f, 3);
-  const size_t n = nm[0], m = nm[1], ma = nm[2];
-  const auto center_h = read_array<double>(f, 3 * n), radius_h = read_array<double>(f, n),
-             mob_h = read_array<double>(f, n);
-  const auto pairs_h = read_array<int32_t>(f, 2 * m);
-  const auto active_h = read_array<int32_t>(f, 2 * ma);
-  std::fclose(f);
+  const ChainInput in = read_chain_input(argv[1], 3);
+  const auto active_pairs = read_array<int32_t>(in.file, 2 * in.counts[2]);
+  std::fclose(in.file);
   const int steps = std::atoi(argv[2]);
   const double dt = std::atof(argv[3]), buffer = std::atof(argv[4]), k = std::atof(argv[5]), r0 = std::atof(argv[6]),
                kt = std::atof(argv[7]);
@@ -49,39 +40,22 @@ int main(int argc, char** argv) {
   for (int a = 0; a < 4; ++a) wall.quat[a] = std::atof(argv[16 + a]);
   const double sigma = std::atof(argv[20]), kon = std::atof(argv[21]), koff = std::atof(argv[22]);
 
-  mech::SphereChainStepper st(center_h, radius_h, mob_h, dt, buffer, {10000, 1e-5} /* NgpLcp.cpp:851-852 */, pairs_h,
-                              MHIP_SPRING_HOOKEAN, k, r0, kt);
-  const double *center = st.center().data(), *radius = st.radius().data();
-  mhip_active_springs_t act = nullptr;
-  check(mhip_active_springs_create(&act, n, ma, active_h.data(), sigma, kon, koff, nullptr, nullptr, nullptr));
-  DeviceArray<int> switches(2), num_active(1), colliding(1);
-  DeviceVector deepest(1);
-
+  mech::SphereChainStepper st(in.center, in.radius, in.mob_trans, dt, buffer, {10000, 1e-5} /* NgpLcp.cpp:851-852 */,
+                              in.pairs, MHIP_SPRING_HOOKEAN, k, r0, kt);
+  st.set_periphery(wall);
+  st.set_active_springs(active_pairs, sigma, kon, koff);
   for (int s = 0; s < steps; ++s) {
-    st.neighbors();
-    // F = F_spring + F_periphery + F_active, after the sampling (HP1.cpp:4733-4741)
-    check(mhip_active_springs_sample(act, switches.data(), nullptr));
-    double* force = st.forces();
-    check(mhip_periphery_force(&wall, n, center, radius, force, 1, colliding.data(), deepest.data(), nullptr));
-    check(mhip_active_springs_force(act, center, force, 1, num_active.data(), nullptr));
-    st.external_velocity();
-    const mech::StepStats r = st.resolve();
-    check(mhip_active_springs_advance(act, dt, nullptr));  // the timers
-    const auto sw = switches.download();
+    const mech::StepStats r = st.step();
     std::printf("STEP %d contacts %zu iterations %u colliding %d active %d on %d off %d rebuilt %d converged %d\n", s,
-                r.num_contacts, r.num_iters, colliding.download()[0], num_active.download()[0], sw[0], sw[1],
-                r.rebuilt ? 1 : 0, r.converged ? 1 : 0);
+                r.num_contacts, r.num_iters, r.periphery_colliding, r.active_springs, r.active_switches_on,
+                r.active_switches_off, r.rebuilt ? 1 : 0, r.converged ? 1 : 0);
     if (r.springs_overstretched != 0) {
       std::fprintf(stderr, "overstretched spring\n");
       return 3;
     }
   }
-  DeviceArray<int32_t> state(ma ? ma : 1);
-  DeviceVector next_time(ma ? ma : 1);
-  check(mhip_active_springs_get_state(act, state.data(), next_time.data(), nullptr, nullptr, nullptr));
   std::printf("CHECKSUM center %016llx\n", checksum(st.center().download()));
-  std::printf("CHECKSUM state %016llx\n", checksum(state.download(), ma));
-  std::printf("CHECKSUM next_time %016llx\n", checksum(next_time.download(), ma));
-  check(mhip_active_springs_destroy(act));
+  std::printf("CHECKSUM state %016llx\n", checksum(st.active_springs()->states()));
+  std::printf("CHECKSUM next_time %016llx\n", checksum(st.active_springs()->next_times()));
   return 0;
 }

@@ -4,13 +4,16 @@
 //                                                            RandomLCP{3,7,200}: x0 = 99.99, max_iters 1000, tol 1e-6)
 //   mundy/geom/tests/unit_tests/UnitTestComputeAABB.cpp:167-232, UnitTestSegmentSegment.cpp:417-472
 //   mundy/mesh/tests/unit_tests/UnitTestGenNeighborLinks.cpp:73-152 (two coincident spheres -> one link)
+// and three cases of this project's own on the optional stages of mech::SphereChainStepper (mundy_hip/stepper.hpp).
 // Needs a GPU; built and run by tests/test_adapter_cpp.py.  Exit code = number of failed checks.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 
 #include "mundy_hip/adapter.hpp"
+#include "mundy_hip/stepper.hpp"
 
 using namespace mundy_hip;
 namespace cx = mundy_hip::convex;
@@ -434,6 +437,82 @@ static void test_periodic_metrics() {  // UnitTestPeriodicity.cpp:623-660 (MinIm
   EXPECT_TRUE(metric.inverse()[0] == 0.01 && metric.inverse()[4] == 0.01 && metric.inverse()[1] == 0.0);
 }
 
+// ---- SphereChainStepper's optional stages (include/mundy_hip/stepper.hpp) ---------------------------------------------------
+// 2 chains of 8 beads of radius 0.5 along x, 1.1 apart, the chains 3 apart in y; Hookean backbone k = 10, r0 = 0.9
+struct SmallChains {
+  std::vector<double> center, radius, mob;
+  std::vector<int32_t> pairs;
+  SmallChains() : radius(16, 0.5), mob(16, 1.0) {
+    for (int c = 0; c < 2; ++c)
+      for (int b = 0; b < 8; ++b) {
+        center.insert(center.end(), {1.1 * b, 3.0 * c, 0.0});
+        if (b) pairs.insert(pairs.end(), {8 * c + b - 1, 8 * c + b});
+      }
+  }
+  std::unique_ptr<mech::SphereChainStepper> stepper() const {
+    return std::make_unique<mech::SphereChainStepper>(center, radius, mob, 1e-3, 0.2, cx::PGDConfig<double>{10000, 1e-5},
+                                                      pairs, MHIP_SPRING_HOOKEAN, 10.0, 0.9, 0.1);
+  }
+};
+static bool same_bits(const std::vector<double>& a, const std::vector<double>& b) {
+  return a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0;
+}
+
+static void test_stepper_periphery_setter() {
+  const SmallChains in;
+  const size_t n = in.radius.size();
+  // a spherical wall about the middle of the beads: the chain ends, 4.1 from the centre, lie outside R = 3
+  mhip_periphery wall{};
+  wall.shape = MHIP_PERIPHERY_SPHERE;
+  wall.radii[0] = wall.radii[1] = wall.radii[2] = 3.0;
+  wall.k = 5.0;
+  wall.center[0] = 3.85;
+  wall.center[1] = 1.5;
+  wall.quat[0] = 1.0;
+  auto st = in.stepper();
+  st->set_periphery(wall);
+  st->neighbors();
+  const double* f = st->forces();
+  std::vector<double> got(3 * n);
+  check(mhip_memcpy_d2h(got.data(), f, got.size() * sizeof(double), nullptr));
+  // the same two calls by hand
+  mech::Springs springs(n, in.pairs, MHIP_SPRING_HOOKEAN, {}, 10.0, {}, 0.9);
+  DeviceVector want(3 * n), springs_only(3 * n);
+  springs.compute_forces(st->center().data(), want.data());
+  springs.compute_forces(st->center().data(), springs_only.data());
+  check(mhip_periphery_force(&wall, n, st->center().data(), st->radius().data(), want.data(), 1, nullptr, nullptr,
+                             nullptr));
+  EXPECT_TRUE(same_bits(got, want.download()));
+  EXPECT_TRUE(!same_bits(got, springs_only.download()));  // the wall acts
+  st->external_velocity();
+  const mech::StepStats r = st->resolve();
+  EXPECT_TRUE(r.periphery_colliding >= 1);
+  EXPECT_TRUE(r.max_periphery_overlap > 0.0);
+}
+
+static void test_stepper_crosslinker_setter() {
+  const SmallChains in;
+  auto plain = in.stepper(), with = in.stepper();
+  // one crosslinker per chain, every bead a bind site, and a binding rate of 0: nothing ever binds, no force
+  with->set_crosslinkers({0, 8}, std::vector<unsigned char>(in.radius.size(), 1), MHIP_SPRING_HOOKEAN, 5.0, 1.0,
+                         /*bind_rate=*/0.0, /*unbind_rate=*/1.0, /*kt=*/1.0, /*capture_radius=*/2.0, /*skin=*/0.5);
+  for (int s = 0; s < 3; ++s) {
+    plain->step();
+    const mech::StepStats r = with->step();
+    EXPECT_TRUE(r.crosslinker_binds == 0 && r.crosslinker_unbinds == 0 && r.crosslinkers_overstretched == 0);
+  }
+  EXPECT_TRUE(same_bits(with->center().download(), plain->center().download()));
+  EXPECT_TRUE(!same_bits(plain->center().download(), in.center));  // the beads have moved
+  EXPECT_TRUE(with->crosslinkers()->right_heads() == (std::vector<int32_t>{0, 8}));
+}
+
+static void test_stepper_setter_order() {
+  const SmallChains in;
+  auto st = in.stepper();
+  EXPECT_THROW(st->set_periphery_sites({0.0, 0.0, 5.0}, 1.0, 1.0, 1.0, 1.0, 1.0), std::logic_error);
+  EXPECT_THROW(st->set_hydro_periphery({0.0, 0.0, 5.0}, {1.0}, {0.0, 0.0, -1.0}, true), std::logic_error);
+}
+
 int main() {
   int count = 0;
   char arch[128];
@@ -449,6 +528,9 @@ int main() {
   test_gen_neighbor_links_reference_usage();
   test_periodic_metrics();
   test_ellipsoid_sphere_cases();
+  test_stepper_periphery_setter();
+  test_stepper_crosslinker_setter();
+  test_stepper_setter_order();
   std::printf("%s (%d failed checks)\n", g_failures ? "FAILED" : "ALL PASSED", g_failures);
   return g_failures;
 }
