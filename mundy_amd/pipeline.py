@@ -710,6 +710,9 @@ class ContactStepper:
         self.u_hydro = torch.zeros((n, 3), dtype=torch.float64, device=dev)  # the stored velocity, added every step
         self.hydro_step = 0  # the reference's timestep_index_ of `% hydro_update_frequency_ == 0`
         self._hydro_ws = ops.HydroWorkspace()
+        # after reorder_bodies: (the row of every bead of the constructor's numbering, that number of every row), int32.
+        # The hydrodynamics are evaluated in the constructor's numbering (_hydro_velocity)
+        self._hydro_rows = self._hydro_numbers = None
         self.hydro_periphery = None
         if periphery is not None:  # the surface, its matrix and the inverse: built once, here
             to = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)  # noqa: E731
@@ -727,34 +730,52 @@ class ContactStepper:
             self.hydro["skip_same_index"] = periphery["skip_same_index"]
 
     def _snapshot_hydro(self):
-        """the stored velocity, the step counter and the hydrodynamic radii"""
-        return (self.u_hydro.clone(), self.hydro_step, None if self.hydro_radius is None else self.hydro_radius.clone())
+        """the stored velocity, the step counter, the hydrodynamic radii and the numbering the rows are in"""
+        return (self.u_hydro.clone(), self.hydro_step, None if self.hydro_radius is None else self.hydro_radius.clone(),
+                self._hydro_rows, self._hydro_numbers)  # (the two maps are replaced, never written: no copies)
 
     def _restore_hydro(self, saved):
-        u, self.hydro_step, radius = saved
+        u, self.hydro_step, radius, self._hydro_rows, self._hydro_numbers = saved
         self.u_hydro.copy_(u)
         if radius is not None:
             self.hydro_radius.copy_(radius)
 
     def _renumber_hydro(self, perm, inv):
-        """the stored velocity and the radii move with their rows"""
+        """the stored velocity and the radii move with their rows; the two maps to and from the constructor's numbering
+        compose with the permutation"""
         self.u_hydro = ops.gather_rows(perm, self.u_hydro)
         if self.hydro_radius is not None:
             self.hydro_radius = ops.gather_rows(perm, self.hydro_radius)
+        if self._hydro_rows is None:
+            self._hydro_rows, self._hydro_numbers = inv, perm
+        else:
+            self._hydro_rows = inv[self._hydro_rows.long()]
+            self._hydro_numbers = self._hydro_numbers[perm.long()]
 
     def _hydro_velocity(self, force):
-        """every update_every-th step u_hydro = hydro(F) of the force stage's F; every step u_ext[:, :3] += u_hydro"""
+        """every update_every-th step u_hydro = hydro(F) of the force stage's F; every step u_ext[:, :3] += u_hydro.
+
+        hydro(F) is evaluated in the constructor's numbering, whatever reorder_bodies has done since: the all-pairs sums
+        walk the sources in index order and skip_same_index pairs surface node i with bead i (as the reference does, which
+        never renumbers), so u_hydro of a bead is the same in bits in any order of the rows.  After a reorder this costs
+        three row gathers before and one after the O(n^2) sums; before one, nothing."""
         if self.hydro_step % self.hydro["update_every"] == 0:
             if force is None:
                 self.u_hydro.zero_()
             else:
-                radius = self.radius if self.hydro_radius is None else self.hydro_radius
-                ops.hydro_velocity(self.hydro["kind"], self.viscosity, self.center, radius, force, out=self.u_hydro,
+                center, radius = self.center, self.radius if self.hydro_radius is None else self.hydro_radius
+                rows, u = self._hydro_rows, self.u_hydro
+                if rows is not None:
+                    center, radius, force = (ops.gather_rows(rows, t) for t in (center, radius, force))
+                    u = torch.empty_like(self.u_hydro)
+                ops.hydro_velocity(self.hydro["kind"], self.viscosity, center, radius, force, out=u,
                                    workspace=self._hydro_ws)
                 if self.hydro_periphery is not None:  # the no-slip correction of the periphery, into the same u_hydro
-                    self.hydro_periphery.correct(self.hydro["kind"], self.center, radius, force, self.u_hydro,
+                    self.hydro_periphery.correct(self.hydro["kind"], center, radius, force, u,
                                                  skip_same_index=self.hydro["skip_same_index"],
                                                  workspace=self._hydro_ws)
+                if rows is not None:
+                    self.u_hydro = ops.gather_rows(self._hydro_numbers, u)
         self.hydro_step += 1
         ops.hydro_add_velocity(self.u_hydro, self.u_ext)
 

@@ -4,7 +4,7 @@
 //                                                            RandomLCP{3,7,200}: x0 = 99.99, max_iters 1000, tol 1e-6)
 //   mundy/geom/tests/unit_tests/UnitTestComputeAABB.cpp:167-232, UnitTestSegmentSegment.cpp:417-472
 //   mundy/mesh/tests/unit_tests/UnitTestGenNeighborLinks.cpp:73-152 (two coincident spheres -> one link)
-// and three cases of this project's own on the optional stages of mech::SphereChainStepper (mundy_hip/stepper.hpp).
+// and four cases of this project's own on the optional stages of mech::SphereChainStepper (mundy_hip/stepper.hpp).
 // Needs a GPU; built and run by tests/test_adapter_cpp.py.  Exit code = number of failed checks.
 #include <cmath>
 #include <cstdio>
@@ -513,6 +513,53 @@ static void test_stepper_setter_order() {
   EXPECT_THROW(st->set_hydro_periphery({0.0, 0.0, 5.0}, {1.0}, {0.0, 0.0, -1.0}, true), std::logic_error);
 }
 
+static void test_stepper_setters_commute() {
+  // the optional stages in two valid orders -- the wall, the active dipoles and the hydrodynamics before the
+  // crosslinkers, and after them -- are one stepper: the same statistics every step, bit-identical centres after five
+  const SmallChains in;
+  const size_t n = in.radius.size();
+  mhip_periphery wall{};
+  wall.shape = MHIP_PERIPHERY_SPHERE;
+  wall.radii[0] = wall.radii[1] = wall.radii[2] = 3.0;
+  wall.k = 5.0;
+  wall.center[0] = 3.85;
+  wall.center[1] = 1.5;
+  wall.quat[0] = 1.0;
+  const std::vector<int32_t> left{0, 2, 4, 6, 8, 10, 12, 14};
+  const std::vector<int32_t> active{0, 1, 2, 3, 8, 9, 10, 11};  // four of the backbone springs
+  const auto others = [&](mech::SphereChainStepper& st) {
+    st.set_periphery(wall);
+    st.set_active_springs(active, 2.0, 300.0, 200.0);
+    st.set_hydrodynamics(MHIP_HYDRO_RPYC, 1.0, 2);
+  };
+  const auto crosslinkers = [&](mech::SphereChainStepper& st) {
+    st.set_crosslinkers(left, std::vector<unsigned char>(n, 1), MHIP_SPRING_HOOKEAN, 5.0, 1.0, /*bind_rate=*/300.0,
+                        /*unbind_rate=*/150.0, /*kt=*/0.1, /*capture_radius=*/1.5, /*skin=*/0.3);
+  };
+  auto before = in.stepper(), after = in.stepper(), plain = in.stepper();
+  others(*before);
+  crosslinkers(*before);
+  crosslinkers(*after);
+  others(*after);
+  int binds = 0, colliding = 0;
+  for (int s = 0; s < 5; ++s) {
+    const mech::StepStats a = before->step(), b = after->step();
+    plain->step();
+    EXPECT_TRUE(a.crosslinker_binds == b.crosslinker_binds && a.crosslinker_unbinds == b.crosslinker_unbinds);
+    EXPECT_TRUE(a.periphery_colliding == b.periphery_colliding && a.max_periphery_overlap == b.max_periphery_overlap);
+    EXPECT_TRUE(a.active_springs == b.active_springs && a.active_switches_on == b.active_switches_on &&
+                a.active_switches_off == b.active_switches_off);
+    EXPECT_TRUE(a.max_crosslinker_length == b.max_crosslinker_length && a.num_contacts == b.num_contacts);
+    binds += a.crosslinker_binds;
+    colliding += a.periphery_colliding;
+  }
+  EXPECT_TRUE(binds > 0 && colliding > 0);  // the stages act
+  EXPECT_TRUE(same_bits(before->center().download(), after->center().download()));
+  EXPECT_TRUE(!same_bits(before->center().download(), plain->center().download()));
+  EXPECT_TRUE(before->crosslinkers()->right_heads() == after->crosslinkers()->right_heads());
+  EXPECT_TRUE(before->active_springs()->states() == after->active_springs()->states());
+}
+
 int main() {
   int count = 0;
   char arch[128];
@@ -531,6 +578,7 @@ int main() {
   test_stepper_periphery_setter();
   test_stepper_crosslinker_setter();
   test_stepper_setter_order();
+  test_stepper_setters_commute();
   std::printf("%s (%d failed checks)\n", g_failures ? "FAILED" : "ALL PASSED", g_failures);
   return g_failures;
 }

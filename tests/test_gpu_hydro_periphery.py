@@ -473,7 +473,35 @@ def test_stepper_reorder_bodies(surface4):
     ua, ub = host(a.u_hydro)[perm], host(b.u_hydro)
     print("reorder: max |du| %.3g, smallest bound %.3g" % (np.abs(ub - ua).max(), bound.min()))
     assert (np.abs(ub - ua) <= bound).all()
-    assert (ua.view(np.uint64) != ub.view(np.uint64)).any()
+    # the stepper evaluates the sums in the constructor's numbering: the bound holds with nothing to spare
+    assert np.abs(ub).max() > 0.0
+    assert_bits_equal(ub, ua, "u_hydro of every bead, whatever its row")
+
+
+def test_stepper_reorder_bodies_keeps_the_skipped_pairs():
+    """skip_same_index=True (the default) drops the term of surface node i onto bead i of the constructor's numbering,
+    before and after reorder_bodies: the corrected u_hydro of every bead keeps its bits"""
+    d = _chains()
+    n = d["center"].shape[0]
+    hy = dict(kind="rpyc", periphery=_pe())
+    a, b, c = _stepper(d, hy), _stepper(d, hy), _stepper(d, dict(kind="rpyc", periphery=_pe(skip_same_index=False)))
+    assert a.hydro["skip_same_index"] and not c.hydro["skip_same_index"]
+    for s in (a, b, c):
+        s.step()
+    # the skip acts: from the same centres it changes the first S beads and no other
+    S = a.hydro_periphery.num_nodes
+    differ = (host(a.u_hydro).view(np.uint64) != host(c.u_hydro).view(np.uint64)).any(axis=1)
+    assert S < n and differ[:S].any() and not differ[S:].any()
+    perm = host(b.reorder_bodies()).astype(np.int64)
+    assert (perm[:S] >= S).any() and (perm[S:] < S).any()   # beads cross the boundary between the two kinds of row
+    for s in (a, b):
+        s.compute_aabb()
+        s.generate_neighbor_links()
+        s.external_velocity()
+    assert_bits_equal(host(b.center), host(a.center)[perm], "centres")
+    ua = host(a.u_hydro)
+    assert np.abs(ua).max() > 0.0
+    assert_bits_equal(host(b.u_hydro), ua[perm], "u_hydro of every bead, whatever its row")
 
 
 def test_stepper_precomputed_inverse(surface4):
