@@ -20,7 +20,9 @@
 //   neighbour list -> spring forces -> U_ext = M F + U_brown -> contacts, LCP on sep + dt D^T U_ext, U_ext + M D lambda
 // Its opt-in stages are the rest of the HP1 step (HP1.cpp:4728-4803): crosslinker KMC and springs, periphery bind sites,
 // the nuclear wall and active dipoles in the force stage, n-body hydrodynamics with the periphery's no-slip correction
-// in the velocity stage.
+// in the velocity stage; set_backbone_collision adds that app's excluded volume, frictionless contacts between the
+// backbone segments (HP1.cpp:4356-4496), as the term at the head of the force stage, and set_sphere_contacts(false)
+// then leaves the sphere contact out, the reference's own configuration.
 #pragma once
 #include <chrono>
 #include <cmath>
@@ -31,6 +33,8 @@
 #include <string>
 
 #include "mundy_hip/adapter.hpp"
+
+#include "../mundy_hip_segment_contact.h"
 
 namespace mundy_hip {
 namespace mech {
@@ -64,6 +68,53 @@ struct StepStats {
   int periphery_colliding = 0;  // beads that touch the wall
   double max_periphery_overlap = 0.0;
   int active_springs = 0, active_switches_on = 0, active_switches_off = 0;
+  // SphereChainStepper with set_backbone_collision: the segment contacts' own statistics
+  double max_segment_overlap = 0.0;    // max(0, -sep) over the force branch, corrected end segments included
+  size_t segment_contacts = 0;         // segment pairs in the force branch
+  size_t num_segment_pairs = 0;        // segment pairs in the neighbour list
+  bool segment_list_rebuilt = false;   // whether this step rebuilt that list
+};
+
+/// Frictionless Hertzian or WCA contacts between segments given by an end-index list over n bodies
+/// (mhip_segment_contacts_*, include/mundy_hip_segment_contact.h): RAII over the handle.  Host arrays ends [m][2],
+/// radius [m] or empty (then radius_scalar), end_correction [m] bytes or empty (none corrected).
+class SegmentContacts {
+ public:
+  SegmentContacts(size_t num_bodies, const std::vector<int32_t>& ends, const std::vector<double>& radius,
+                  double radius_scalar, const std::vector<unsigned char>& end_correction,
+                  const mhip_segment_contact_params& params, mhip_stream_t stream = nullptr)
+      : m_(ends.size() / 2) {
+    if (!radius.empty() && radius.size() != m_) throw std::invalid_argument("SegmentContacts: one radius per segment");
+    if (!end_correction.empty() && end_correction.size() != m_)
+      throw std::invalid_argument("SegmentContacts: one end_correction byte per segment");
+    check(mhip_segment_contacts_create(&h_, num_bodies, m_, ends.data(), radius.empty() ? nullptr : radius.data(),
+                                       radius_scalar, end_correction.empty() ? nullptr : end_correction.data(), &params,
+                                       stream));
+  }
+  ~SegmentContacts() { mhip_segment_contacts_destroy(h_); }
+  SegmentContacts(const SegmentContacts&) = delete;
+  SegmentContacts& operator=(const SegmentContacts&) = delete;
+  /// the segment view at center [n][3] and, when due, the list; returns whether it was rebuilt
+  bool update(const double* center, bool force_rebuild = false, mhip_stream_t stream = nullptr) {
+    int rebuilt = 0;
+    check(mhip_segment_contacts_update(h_, center, force_rebuild ? 1 : 0, &rebuilt, stream));
+    return rebuilt != 0;
+  }
+  /// force [n][3] written or added to; stats [device, 16 bytes] = (bits of the max overlap, linkers in the force branch)
+  void force(const double* center, double* force, bool accumulate, void* stats, mhip_stream_t stream = nullptr) {
+    check(mhip_segment_contacts_force(h_, center, force, accumulate ? 1 : 0, stats, stream));
+  }
+  mhip_segment_contact_fields fields() const {
+    mhip_segment_contact_fields f{};
+    check(mhip_segment_contacts_get(h_, &f));
+    return f;
+  }
+  size_t size() const { return m_; }
+  mhip_segment_contacts_t handle() const { return h_; }
+
+ private:
+  mhip_segment_contacts_t h_ = nullptr;
+  size_t m_;
 };
 
 /// the LCP of a contact operator with right-hand side q: fused BBPGD from lambda = 0 (NgpLcp.cpp:890-891); x receives
@@ -731,6 +782,7 @@ class SphereChainStepper {
 
   /// the neighbour list by the rebuild rule; returns whether it was rebuilt (pairs() changes only then)
   bool neighbors() {
+    if (!sphere_contacts_) return false;
     check(mhip_compute_aabb_spheres(n_, center_.data(), radius_.data(), aabb_.data(), nullptr));
     rebuilt_ = links_.generate(n_, aabb_.data(), center_.data(), radius_.data(), nullptr, false);
     if (rebuilt_) links_.links_into(pairs_);
@@ -753,6 +805,7 @@ class SphereChainStepper {
   /// Hertz mode, between neighbors() and forces(): contacts -> Hertz force per linker -> operator (built after a rebuild,
   /// otherwise refreshed) -> the contact force of every body F = D f into force() [n][3]; returns it
   double* contact_forces() {
+    if (!sphere_contacts_) return force_.data();
     if (!hertz_) throw std::logic_error("SphereChainStepper: contact_forces() needs set_hertz_contact");
     const size_t C = links_.num_links(), cap = C ? C : 1;  // no workspace is null without contacts
     double *sep = workspace(w_sep_, cap), *normal = workspace(w_normal_, 3 * cap), *f = workspace(lambda_, cap);
@@ -767,6 +820,24 @@ class SphereChainStepper {
     op_->body_force(f, force_.data(), 3);
     have_contact_force_ = true;
     return force_.data();
+  }
+  /// The backbone excluded volume (mech::SegmentContacts; host arrays ends [m][2], radius [m] or empty with
+  /// radius_scalar, end_correction [m] bytes or empty): the term at the head of forces() after the sampling, added to the
+  /// contact force in Hertz mode, written first otherwise; the springs then go through a buffer of their own.  Its list is
+  /// brought up to date at the start of forces().
+  void set_backbone_collision(const mhip_segment_contact_params& params, const std::vector<int32_t>& ends,
+                              const std::vector<double>& radius, double radius_scalar,
+                              const std::vector<unsigned char>& end_correction) {
+    backbone_.reset(new SegmentContacts(n_, ends, radius, radius_scalar, end_correction, params));
+    backbone_stats_ = DeviceArray<std::uint64_t>(std::vector<std::uint64_t>(2, 0));
+    if (spring_term_.size() == 0) spring_term_ = DeviceVector(3 * n_);
+  }
+  /// false: no sphere contact at all -- neighbors() and contact_forces() do nothing and resolve() is U = U_ext, the
+  /// reference's own configuration.  Needs set_backbone_collision first: something has to keep the chains apart.
+  void set_sphere_contacts(bool on) {
+    if (!on && !backbone_)
+      throw std::logic_error("SphereChainStepper: set_sphere_contacts(false) needs set_backbone_collision first");
+    sphere_contacts_ = on;
   }
   /// Crosslinkers that bind and unbind (mech::Crosslinkers; host arrays left [mx], is_site [n] bytes): their KMC step
   /// opens forces(), the doubly bound ones follow the backbone as springs of `type`.  Every crosslinker starts singly
@@ -836,17 +907,21 @@ class SphereChainStepper {
     skip_same_index_ = skip_same_index;
   }
   /// The force stage in the reference's order (HP1.cpp:4733-4741) into force() [n][3]: crosslinker KMC, active sampling,
-  /// springs (Hertz mode: added to the contact force that contact_forces() left there), crosslinker springs, periphery,
-  /// active dipoles, every term after the springs added to them.  Returns force() for the caller to accumulate further
+  /// backbone segment contacts (Hertz mode: added to the contact force that contact_forces() left there), springs (added
+  /// to what is there in Hertz mode or after the segment contacts), crosslinker springs, periphery, active dipoles, every
+  /// term after the springs added to them.  Returns force() for the caller to accumulate further
   /// terms into.
   double* forces() {
-    if (hertz_ && !have_contact_force_) throw std::logic_error("SphereChainStepper: forces() before contact_forces()");
+    const bool first_term = hertz_ && sphere_contacts_;  // force() holds D f
+    if (first_term && !have_contact_force_) throw std::logic_error("SphereChainStepper: forces() before contact_forces()");
     const double* x = center_.data();
     double* f = force_.data();
     if (stats_.size()) check(mhip_fill(stats_.size(), stats_.data(), 0.0, nullptr));
+    if (backbone_) segment_list_rebuilt_ = backbone_->update(x);
     if (xl_) crosslinker_kmc();
     if (active_) active_->sample(stat_int(8, 0));
-    if (hertz_) {  // (the spring kernel overwrites: its term goes through a buffer of its own)
+    if (backbone_) backbone_->force(x, f, first_term, backbone_stats_.data());
+    if (first_term || backbone_) {  // (the spring kernel overwrites: its term goes through a buffer of its own)
       springs_.compute_forces(x, spring_term_.data());
       check(mhip_axpby(3 * n_, 1.0, spring_term_.data(), 1.0, f, nullptr));
     } else {
@@ -879,6 +954,12 @@ class SphereChainStepper {
   StepStats resolve(bool integrate = true) {
     StepStats st;
     st.rebuilt = rebuilt_;
+    if (!sphere_contacts_) {  // U = U_ext: the segment contacts are inside it
+      st.converged = true;
+      check(mhip_deep_copy(6 * n_, vel_.data(), u_ext_.data(), nullptr));
+      integrate_and_read(integrate, st);
+      return st;
+    }
     if (hertz_) {
       if (!have_contact_force_) throw std::logic_error("SphereChainStepper: resolve() before contact_forces()");
       have_contact_force_ = false;
@@ -1009,6 +1090,13 @@ class SphereChainStepper {
       st.active_switches_on = i[16];
       st.active_switches_off = i[17];
     }
+    if (backbone_) {
+      const std::vector<std::uint64_t> b = backbone_stats_.download();
+      std::memcpy(&st.max_segment_overlap, &b[0], sizeof(double));
+      st.segment_contacts = static_cast<size_t>(b[1]);
+      st.num_segment_pairs = backbone_->fields().num_pairs;
+      st.segment_list_rebuilt = segment_list_rebuilt_;
+    }
     ++step_index_;
   }
   size_t n_;
@@ -1046,6 +1134,10 @@ class SphereChainStepper {
   size_t update_every_ = 1;
   bool skip_same_index_ = false;
   DeviceVector u_hydro_;  // [n][3]: the stored hydrodynamic velocity
+  // the backbone segment contacts (set_backbone_collision) and whether the spheres collide at all (set_sphere_contacts)
+  std::unique_ptr<SegmentContacts> backbone_;
+  DeviceArray<std::uint64_t> backbone_stats_;  // (bits of the max overlap, linkers in the force branch)
+  bool segment_list_rebuilt_ = false, sphere_contacts_ = true;
 };
 
 /// Centerline-twist elastic filaments (mhip_filaments_*), stepped in the reference's order: the state lives in the

@@ -82,6 +82,20 @@ class FilamentContactFields(C.Structure):
                                                                          for f in FILAMENT_CONTACT_FIELDS]
 
 
+class SegmentContactParams(C.Structure):
+    _fields_ = [("kind", C.c_int), ("skin", C.c_double), ("youngs_modulus", C.c_double), ("poisson_ratio", C.c_double),
+                ("epsilon", C.c_double), ("sigma", C.c_double), ("cutoff", C.c_double)]
+
+
+# mhip_segment_contact_fields: name -> columns; pairs (int32) .. share have num_pairs rows, seg and aabb num_segments
+SEGMENT_CONTACT_FIELDS = {"pairs": 2, "sep": 1, "force": 3, "share": 6, "seg": 8, "aabb": 6}
+
+
+class SegmentContactFields(C.Structure):
+    _fields_ = [("num_bodies", C.c_size_t), ("num_segments", C.c_size_t),
+                ("num_pairs", C.c_size_t)] + [(f, C.c_void_p) for f in SEGMENT_CONTACT_FIELDS]
+
+
 class VelocityHalo(C.Structure):
     """mhip_velocity_halo: the per-iteration ghost-velocity exchange of one rank (host lists + one device index list)"""
     _fields_ = [("velocity", C.c_void_p), ("num_send_peers", C.c_int), ("send_peer", C.POINTER(C.c_int)),
@@ -346,6 +360,18 @@ PERIPHERY_BINDING_SIGNATURES = {
     "mhip_crosslinkers_set_periphery_candidates": [_vp, _vp, _vp, _sz, C.c_int32, _vp],
     "mhip_crosslinkers_kmc_step_periphery": [_vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp],
 }
+# include/mundy_hip_segment_contact.h, a header of its own for the same reason: name -> argtypes, every function returns
+# int status.  tests/test_segment_contact_host.py checks this table against that header and the library.
+SEGMENT_CONTACT_HERTZ, SEGMENT_CONTACT_WCA = 0, 1
+SEGMENT_CONTACT_SIGNATURES = {
+    "mhip_segment_contacts_create": [C.POINTER(_vp), _sz, _sz, _vp, _vp, _d, _vp, C.POINTER(SegmentContactParams), _vp],
+    "mhip_segment_contacts_destroy": [_vp],
+    "mhip_segment_contacts_update": [_vp, _vp, _i, C.POINTER(_i), _vp],
+    "mhip_segment_contacts_force": [_vp, _vp, _vp, _i, _vp, _vp],
+    "mhip_segment_contacts_linker_pass": [_vp, _vp, _vp],
+    "mhip_segment_contacts_reduce": [_vp, _vp, _i, _vp, _vp],
+    "mhip_segment_contacts_get": [_vp, C.POINTER(SegmentContactFields)],
+}
 OTHER_SYMBOLS = {"mhip_last_error": ([], C.c_char_p), "mhip_version": ([], C.c_int),
                  "mhip_release_cached_workspaces": ([], C.c_int)}
 
@@ -365,7 +391,8 @@ def load():
         import torch  # noqa: F401
         lib = C.CDLL(LIB_PATH)
         for name, argtypes in (list(SIGNATURES.items()) + list(PERIPHERY_SIGNATURES.items()) +
-                               list(CONTACT_FORCE_SIGNATURES.items()) + list(PERIPHERY_BINDING_SIGNATURES.items())):
+                               list(CONTACT_FORCE_SIGNATURES.items()) + list(PERIPHERY_BINDING_SIGNATURES.items()) +
+                               list(SEGMENT_CONTACT_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = C.c_int

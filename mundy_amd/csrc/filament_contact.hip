@@ -23,16 +23,7 @@ namespace mhip {
 
 constexpr int kTile = kBlock;
 
-struct SegmentRow {
-  V3 p0, p1;
-  double r;
-};
-__device__ inline SegmentRow load_segment(const double* __restrict__ seg, size_t i) {
-  const double2* q = reinterpret_cast<const double2*>(seg + 8 * i);  // a 64-byte line
-  const double2 a = q[0], b = q[1], c = q[2], d = q[3];
-  return {{a.x, a.y, b.x}, {b.y, c.x, c.y}, d.x};
-}
-
+// (SegmentRow, load_segment, segment_share and the row writers: force_device.hpp, shared with segment_contact.hip)
 // seg[i] = (x_i, x_{i+1}, r_i, 0) and the reference's buffered box; a filament's last node: (x_i, x_i, r_i, 0)
 __global__ void __launch_bounds__(kBlock)
     k_segment_view(size_t n, const uint8_t* __restrict__ has_right, const double* __restrict__ x,
@@ -73,25 +64,6 @@ __device__ inline V3 segment_point_velocity(V3 x0, V3 x1, V3 v0, V3 v1, V3 cp) {
   const V3 term2 = (dot(lc, t) * (rv - dot(t, rv) * t)) * iL;
   return (v0 + term1) + term2;
 }
-// what the right end node receives of the linker force Fs acting at cp; the left one receives Fs - this (RED :206-221).
-// The `+` inside term2 is the reference's (the velocity map has `-`): DESIGN.md 5k.
-__device__ inline V3 segment_share(V3 x0, V3 x1, V3 cp, V3 Fs) {
-  const V3 lc = cp - x0, lr = x1 - x0;
-  const double iL = 1.0 / norm(lr);
-  const V3 t = lr * iL;
-  const V3 term1 = (dot(t, Fs) * lc) * iL;
-  const V3 term2 = (dot(lc, t) * (Fs + dot(t, Fs) * t)) * iL;
-  return term2 - term1;
-}
-
-__device__ inline void store_row_nan(double* p, size_t c) {
-  const double q = __builtin_nan("");
-  store3(p, c, V3{q, q, q});
-}
-__device__ inline void reset_row(double* p, size_t c) {  // +0.0, written only where it is not +0.0 already
-  if (!row_is_pos_zero(p, c)) store3(p, c, V3{0.0, 0.0, 0.0});
-}
-
 // One linker per lane and pass, grid-stride.  stats[0]: bits of max(0, -sep) over the contact branch; stats[1]: number of
 // contacts whose tangential force was capped.  One atomic per workgroup for each.
 __global__ void __launch_bounds__(kBlock)

@@ -26,7 +26,7 @@ __global__ void __launch_bounds__(kBlock)
       f = __builtin_nan("");  // a pair outside [0, N) is never dereferenced
     } else if (s < 0.0) {
       const HertzPair h = hertz_pair<E_ARRAY, NU_ARRAY>(p, radius, E, E0, nu, nu0);
-      f = (4.0 / 3.0) * h.Es * sqrt(h.Rs) * pow(-s, 1.5);
+      f = hertz_force_magnitude(h.Es, h.Rs, s);
       dmax = -s > dmax ? -s : dmax;
     }
     force[c] = f;

@@ -2201,3 +2201,169 @@ class FilamentContacts(_Handle):
             raise ValueError("%s: expected %d float64 values" % (name, rows * w))
         if rows:
             capi.check(capi.load().mhip_deep_copy(rows * w, C.c_void_p(ptr), _ptr(value, name=name), _stream()))
+
+
+# ---- frictionless contacts between backbone segments (mhip_segment_contacts_*, include/mundy_hip_segment_contact.h) -----
+SEGMENT_CONTACT_KINDS = {"hertz": capi.SEGMENT_CONTACT_HERTZ, "wca": capi.SEGMENT_CONTACT_WCA}
+SEGMENT_CONTACT_KEYS = ("kind", "radius", "skin", "youngs_modulus", "poisson_ratio", "epsilon", "sigma", "cutoff",
+                        "segments", "end_correction")
+SEGMENT_CONTACT_DEFAULTS = dict(youngs_modulus=1000.0, poisson_ratio=0.3, epsilon=1.0, sigma=1.0, cutoff=1.12246204831,
+                                segments=None, end_correction=None)
+
+
+def chain_end_segments(n, ends):
+    """the reference's "first or last element in chain": segments with an end node that belongs to no other segment ->
+    uint8 [m]"""
+    ends = np.asarray(ends).reshape(-1, 2)
+    deg = np.bincount(ends.reshape(-1), minlength=n)
+    return (deg[ends] == 1).any(axis=1).astype(np.uint8) if ends.size else np.zeros(0, np.uint8)
+
+
+def check_segment_contacts(n, spec):
+    """host-side validation of a segment contact term over n bodies (no library call): the refusals of
+    mhip_segment_contacts_create.  spec: kind, radius, skin, segments ([m, 2] ends) and optionally the material / WCA
+    parameters and end_correction (None: chain_end_segments; False: none; or a mask [m])
+    -> (ends int32 [m, 2], radius array [m] / None, radius scalar, end_correction uint8 [m], capi.SegmentContactParams)"""
+    check_dict_spec(spec, "segment contacts", SEGMENT_CONTACT_KEYS, optional=tuple(SEGMENT_CONTACT_DEFAULTS))
+    spec = dict(SEGMENT_CONTACT_DEFAULTS, **spec)
+    if spec["kind"] not in SEGMENT_CONTACT_KINDS:
+        raise ValueError("segment contact kind must be 'hertz' or 'wca', got %r" % (spec["kind"],))
+    if spec["segments"] is None:
+        raise ValueError("segment contacts: segments is missing")
+    seg = spec["segments"]
+    p = seg.detach().cpu().numpy() if isinstance(seg, torch.Tensor) else np.asarray(seg)
+    if p.size == 0:
+        p = p.reshape(0, 2)
+    if p.ndim != 2 or p.shape[1] != 2 or not (p.dtype.kind in "iu" or p.size == 0):
+        raise ValueError("segments must be integers of shape [m, 2], got %s %s" % (p.dtype, p.shape))
+    if p.size and (p.min() < 0 or p.max() >= n):
+        raise ValueError("segments: an index outside [0, %d)" % n)
+    if p.size and (p[:, 0] == p[:, 1]).any():
+        raise ValueError("segments: a segment from a body to itself (segment %d)" % int(np.argmax(p[:, 0] == p[:, 1])))
+    m = p.shape[0]
+    ra, r0 = _spring_param(spec["radius"], m, "segment radius", True)
+
+    def number(name, ok, what):
+        v = float(spec[name])
+        if not (math.isfinite(v) and ok(v)):
+            raise ValueError("%s must be finite and %s, got %r" % (name, what, v))
+        return v
+    skin = number("skin", lambda v: v >= 0.0, ">= 0")
+    hertz = spec["kind"] == "hertz"
+    # (the parameters of the other law are carried, not checked: the library reads only its own kind's)
+    E = number("youngs_modulus", lambda v: v > 0.0, "> 0") if hertz else float(spec["youngs_modulus"])
+    nu = number("poisson_ratio", lambda v: 0.0 < v < 1.0, "in (0, 1)") if hertz else float(spec["poisson_ratio"])
+    eps = float(spec["epsilon"]) if hertz else number("epsilon", lambda v: v >= 0.0, ">= 0")
+    sigma = float(spec["sigma"]) if hertz else number("sigma", lambda v: v > 0.0, "> 0")
+    cutoff = float(spec["cutoff"]) if hertz else number("cutoff", lambda v: v > 0.0, "> 0")
+    ec = spec["end_correction"]
+    if ec is None:
+        corr = chain_end_segments(n, p)
+    elif ec is False:
+        corr = np.zeros(m, np.uint8)
+    else:
+        corr = ec.detach().cpu().numpy() if isinstance(ec, torch.Tensor) else np.asarray(ec)
+        if corr.shape != (m,) or corr.dtype.kind not in "biu":
+            raise ValueError("end_correction must be None, False or a mask of shape [%d], got %s %s" %
+                             (m, corr.dtype, corr.shape))
+        corr = (corr != 0).astype(np.uint8)
+    prm = capi.SegmentContactParams(SEGMENT_CONTACT_KINDS[spec["kind"]], skin, E, nu, eps, sigma, cutoff)
+    return np.ascontiguousarray(p, dtype=np.int32), ra, r0, np.ascontiguousarray(corr), prm
+
+
+class SegmentContacts(_Handle):
+    """Frictionless Hertzian or WCA contacts between the segments `segments` [m, 2] over n bodies
+    (mhip_segment_contacts_*): the backbone excluded volume of the HP1 app.  Per step: update(center) ->
+    force(center, out, accumulate).  spec: the dict of check_segment_contacts."""
+    _destroy = "mhip_segment_contacts_destroy"
+
+    def __init__(self, n, **spec):
+        ends, ra, r0, corr, prm = check_segment_contacts(n, spec)
+        self.n, self.num_segments, self.kind = int(n), ends.shape[0], spec["kind"]
+        self.ends, self.radius, self.end_correction, self.params = ends, (ra if ra is not None else r0), corr, prm
+        h = C.c_void_p()
+        cp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        capi.check(capi.load().mhip_segment_contacts_create(C.byref(h), self.n, ends.shape[0], cp(ends), cp(ra), r0,
+                                                            cp(corr), C.byref(prm), _stream()))
+        self._h = h
+        self.stats = torch.zeros(2, dtype=torch.int64, device="cuda")
+
+    def _center(self, center):
+        if tuple(center.shape) != (self.n, 3):
+            raise ValueError("center must have shape [%d, 3], got %s" % (self.n, tuple(center.shape)))
+        return _ptr(center, cols=3, name="center")
+
+    def update(self, center, force_rebuild=False):
+        """the segment view and boxes at `center` and, on the first call, when forced or when a box corner has moved by
+        skin / 2, the list -> rebuilt"""
+        rebuilt = C.c_int(0)
+        capi.check(capi.load().mhip_segment_contacts_update(self._h, self._center(center), int(bool(force_rebuild)),
+                                                            C.byref(rebuilt), _stream()))
+        return bool(rebuilt.value)
+
+    def _out(self, out, accumulate):
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate needs an `out` to add to")
+            out = torch.empty((self.n, 3), dtype=torch.float64, device="cuda")
+        if tuple(out.shape) != (self.n, 3):
+            raise ValueError("out must have shape [%d, 3], got %s" % (self.n, tuple(out.shape)))
+        return out
+
+    def force(self, center, out=None, accumulate=False, stats=None):
+        """segment view at `center`, linker pass, reduction -> (force [n, 3], stats int64 [2] on the device: the bits of
+        the double max overlap, the number of linkers in the force branch)"""
+        out = self._out(out, accumulate)
+        stats = self.stats if stats is None else stats
+        capi.check(capi.load().mhip_segment_contacts_force(self._h, self._center(center), _ptr(out, name="out"),
+                                                           int(bool(accumulate)),
+                                                           _ptr(stats, dtype=torch.int64, name="stats"), _stream()))
+        return out, stats
+
+    def linker_pass(self, stats=None):
+        """the first half of force() over the segment view as it stands: sep, force, share of every linker"""
+        stats = self.stats if stats is None else stats
+        capi.check(capi.load().mhip_segment_contacts_linker_pass(self._h, _ptr(stats, dtype=torch.int64, name="stats"),
+                                                                 _stream()))
+        return stats
+
+    def reduce(self, out=None, accumulate=False, stats=None):
+        """the second half of force(): the node forces from the linker rows as they stand; stats[0] is only raised"""
+        out = self._out(out, accumulate)
+        capi.check(capi.load().mhip_segment_contacts_reduce(
+            self._h, _ptr(out, name="out"), int(bool(accumulate)),
+            _ptr(stats, dtype=torch.int64, name="stats", allow_none=True), _stream()))
+        return out
+
+    @staticmethod
+    def read_stats(stats):
+        """stats tensor -> (max overlap, linkers in the force branch); synchronises"""
+        s = stats.cpu().numpy()
+        return float(s[:1].view(np.float64)[0]), int(s[1])
+
+    def fields(self):
+        f = capi.SegmentContactFields()
+        capi.check(capi.load().mhip_segment_contacts_get(self._h, C.byref(f)))
+        return f
+
+    @property
+    def num_pairs(self):
+        return int(self.fields().num_pairs)
+
+    def field(self, name):
+        """a copy of one field (capi.SEGMENT_CONTACT_FIELDS) as a device tensor; pairs int32 [c, 2], share [c, 2, 3]"""
+        if name not in capi.SEGMENT_CONTACT_FIELDS:
+            raise ValueError("unknown segment contact field %r" % (name,))
+        f = self.fields()
+        rows = self.num_segments if name in ("seg", "aabb") else int(f.num_pairs)
+        w = capi.SEGMENT_CONTACT_FIELDS[name]
+        if name == "pairs":
+            out = torch.empty((rows, 2), dtype=torch.int32, device="cuda")
+            words = rows  # one 8-byte word per pair
+        else:
+            out = torch.empty((rows, w) if w > 1 else (rows,), dtype=torch.float64, device="cuda")
+            words = rows * w
+        if words:
+            capi.check(capi.load().mhip_deep_copy(words, C.c_void_p(out.data_ptr()), C.c_void_p(getattr(f, name)),
+                                                  _stream()))
+        return out.view(rows, 2, 3) if name == "share" else out

@@ -55,6 +55,14 @@ velocity and the periphery's no-slip correction all see it, and no body sweep fo
         -> every update_every-th step u_hydro = hydro(F) (+ the periphery's correction of F) -> U_ext += u_hydro
         -> U = U_ext -> Euler update
 
+backbone_collision= adds the excluded volume of that app, which acts between the backbone segments that join consecutive
+beads, not between the bead spheres (compute_hertzian_contact_forces, HP1.cpp:4356-4496: the first term of its force
+field, :4737); contact_model="none" then leaves the sphere contact out altogether, the reference's own configuration:
+
+    ... -> segment list (rebuilt when a segment box has moved by skin / 2) -> crosslinker KMC -> active sampling
+        -> backbone segment contacts (Hertz or WCA; after D f, where that is the first term) -> spring forces -> ...
+        -> U_ext as above [-> contacts -> solve or Hertz sweep, unless contact_model="none": U = U_ext] -> Euler update
+
 hertz_friction= replaces the frictionless Hertz force by the reference's frictional rod contact with a per-pair
 tangential history (SpherocylinderSegmentSpherocylinderSegmentFrictionalHertzianContact.cpp:384-518, run every step by
 CollidingOverdampedFrictionalSperm.cpp:1553-1731):
@@ -141,6 +149,10 @@ class StepStats:
     max_stretch: float = 0.0               # FilamentStepper: the largest |l - l0| / l0 over the edges at the force evaluation
     max_curvature_deviation: float = 0.0   # ... the largest component of |kappa - kappa_rest| over the elements
     num_pairs: int = 0  # FilamentStepper(contacts=): segment pairs in the neighbour list (max_overlap, num_sliding, rebuilt too)
+    max_segment_overlap: float = 0.0   # backbone_collision=: max(0, -sep) over the force branch, corrected end segments included
+    segment_contacts: int = 0          # ... segment pairs in the force branch at this step's force evaluation
+    num_segment_pairs: int = 0         # ... segment pairs in the neighbour list
+    segment_list_rebuilt: bool = False  # ... whether this step rebuilt that list
 
 
 class ContactStepper:
@@ -152,7 +164,8 @@ class ContactStepper:
                  conservative_ellipsoid_box=False, friction_method="apgd", contact_model="lcp", youngs_modulus=1000.0,
                  poisson_ratio=0.3, growth_rate=None, division_length=None, capacity=None, ids=None, springs=None,
                  brownian_kt=None, rng_keys=None, rng_counter=None, hertz_friction=None, hertz_damping=(0.0, 0.0),
-                 hertz_density=1.0, crosslinkers=None, periphery=None, active_forces=None, hydrodynamics=None):
+                 hertz_density=1.0, crosslinkers=None, periphery=None, active_forces=None, hydrodynamics=None,
+                 backbone_collision=None):
         """kind = "sphere" | "spherocylinder" | "mixed".  Mixed systems (BASELINE configs[4]) pass kinds [n] int32
         (0 sphere, 1 spherocylinder, 2 ellipsoid) and shape [n, 3] = (r,-,-) / (r,L,-) / (r1,r2,r3) instead of
         radius / length.
@@ -211,11 +224,22 @@ class ContactStepper:
         (contact_model="hertz" only; default False: the step above, unchanged) makes the Hertz contact force the first
         term of F, as the reference has it: contacts are evaluated before the forces, F = D f + springs + ..., the
         hydrodynamics and the periphery's correction see the contact forces, and U = U_ext with no body sweep (DESIGN.md
-        5p).  With "lcp" it is refused: the multipliers do not exist when U_ext is formed."""
+        5p).  With "lcp" it is refused: the multipliers do not exist when U_ext is formed.
+        backbone_collision = dict(kind="hertz" | "wca", radius=, skin=, youngs_modulus=1000.0, poisson_ratio=0.3,
+        epsilon=1.0, sigma=1.0, cutoff=1.12246204831, segments=None, end_correction=None): frictionless contacts between
+        the backbone segments (ops.SegmentContacts), a force term after the crosslinker KMC and the active
+        sampling and before the springs; the chain step (spheres, free space).  segments [m, 2] defaults to the springs=
+        pairs; radius a number or [m]; skin >= 0 the buffer of the segment list; end_correction None marks every segment
+        with an end node that belongs to no other segment (the reference's "first or last element in chain"), a byte mask
+        [m] or False overrides it.  contact_model = "none" (only with backbone_collision): no sphere list, narrow phase,
+        solve or sweep; U = U_ext, num_contacts = 0 and body_contact_force() raises -- the reference's configuration.
+        With "lcp" and "hertz" the segment term is one more force of the force stage."""
         if kind not in ("sphere", "spherocylinder", "mixed"):
             raise ValueError("kind must be 'sphere', 'spherocylinder' or 'mixed'")
-        if contact_model not in ("lcp", "hertz"):
-            raise ValueError("contact_model must be 'lcp' or 'hertz'")
+        if contact_model not in ("lcp", "hertz", "none"):
+            raise ValueError("contact_model must be 'lcp', 'hertz' or 'none'")
+        if contact_model == "none" and backbone_collision is None:
+            raise ValueError("contact_model='none' leaves no excluded volume: it needs backbone_collision=")
         self.contact_model = contact_model
         if contact_model == "hertz":  # (checked before anything reaches the device)
             for what, v in (("friction", friction), ("contact_cutoff", contact_cutoff)):
@@ -235,10 +259,13 @@ class ContactStepper:
         nucleus_spec = None
         if periphery is not None or active_forces is not None:  # (checked before anything reaches the device)
             nucleus_spec = self._check_nucleus(chain_only, center.shape[0], radius, springs, periphery, active_forces)
+        backbone_spec = None
+        if backbone_collision is not None:  # (checked before anything reaches the device)
+            backbone_spec = self._check_backbone(chain_only, center.shape[0], springs, backbone_collision)
         hydro_spec = None
         if hydrodynamics is not None:  # (checked before anything reaches the device)
             if (springs is None and brownian_kt is None and crosslinkers is None and periphery is None and
-                    active_forces is None):
+                    active_forces is None and backbone_collision is None):
                 raise ValueError("hydrodynamics belongs to the chain step: pass springs= or brownian_kt= (0.0: no noise)")
             self._check_chain_only("hydrodynamics", "the kernels are free-space", *chain_only)
             hydro_spec = ops.check_hydrodynamics(hydrodynamics, center.shape[0])
@@ -266,7 +293,7 @@ class ContactStepper:
         elif division_length is not None or capacity is not None or ids is not None:
             raise ValueError("division_length, capacity and ids belong to growth mode: pass growth_rate")
         self.chain = (springs is not None or brownian_kt is not None or crosslinkers is not None or
-                      nucleus_spec is not None)
+                      nucleus_spec is not None or backbone_spec is not None)
         if self.chain:  # (checked before anything reaches the device)
             chain_spec = self._check_chain(kind, center.shape[0], periodic_box, friction, contact_cutoff, springs,
                                            brownian_kt, rng_keys, rng_counter)
@@ -331,7 +358,7 @@ class ContactStepper:
         self.contact_cutoff = None if contact_cutoff is None else float(contact_cutoff)
         self.cutoff_fallbacks = 0
         self.ids = self.springs = self.rng_keys = self.rng_counter = self.crosslinkers = None
-        self.xl_sources = self.xl_sites = self.periphery = self.active = self.hydro = None
+        self.xl_sources = self.xl_sites = self.periphery = self.active = self.hydro = self.backbone = None
         if self.growth:
             self._init_growth(growth_rate, division_length, capacity, ids, search_buffer)
         if self.chain:
@@ -344,13 +371,16 @@ class ContactStepper:
             self._init_nucleus(*nucleus_spec)
         if hydro_spec is not None:
             self._init_hydro(*hydro_spec)
-        if self.hydro_contact_forces and self.springs is not None:  # the springs' own term, added to F = D f
+        if backbone_spec is not None:
+            self._init_backbone(backbone_spec)
+        # the springs' own term, added to F = D f or to the segment contacts' force (the spring kernel overwrites)
+        if (self.hydro_contact_forces or self.backbone is not None) and self.springs is not None:
             self._spring_term = torch.zeros((n, 3), dtype=torch.float64, device=center.device)
         # the optional modes that carry state of their own: snapshot, restore and reorder_bodies call their
         # _snapshot_<mode>() / _restore_<mode>(saved) / _renumber_<mode>(perm, inv) hooks in this order
         on = dict(growth=self.growth, friction=self.hertz_friction is not None, springs=self.springs is not None,
                   crosslinkers=self.crosslinkers is not None, periphery=self.periphery is not None,
-                  active=self.active is not None, hydro=self.hydro is not None)
+                  active=self.active is not None, hydro=self.hydro is not None, backbone=self.backbone is not None)
         self._modes = [m for m, v in on.items() if v]
 
     @staticmethod
@@ -702,6 +732,46 @@ class ContactStepper:
     def _renumber_active(self, perm, inv):
         self.active.renumber(inv)  # endpoints; states and timers stay
 
+    # -- contacts between backbone segments (HP1.cpp:4356-4496) -------------------------------------------------------------
+    @staticmethod
+    def _check_backbone(chain_only, n, springs, spec):
+        ContactStepper._check_chain_only("backbone_collision segments", "no minimum-image segments", *chain_only)
+        ops.check_dict_spec(spec, "backbone_collision", ops.SEGMENT_CONTACT_KEYS,
+                            optional=tuple(ops.SEGMENT_CONTACT_DEFAULTS))
+        spec = dict(spec)
+        if spec.get("segments") is None:
+            if springs is None:
+                raise ValueError("backbone_collision needs segments= or springs=: its segments default to the spring pairs")
+            if not isinstance(springs, (tuple, list)) or len(springs) != 4:
+                raise ValueError("springs must be (pairs, 'hookean' | 'fene', k, r)")
+            spec["segments"] = springs[0]
+        ends, ra, r0, corr, _ = ops.check_segment_contacts(n, spec)
+        # host copies: what _renumber_backbone makes the next handle from
+        spec.update(segments=ends, radius=ra if ra is not None else r0, end_correction=corr)
+        return spec
+
+    def _init_backbone(self, spec):
+        self._backbone_spec = spec
+        self.backbone = ops.SegmentContacts(self.center.shape[0], **spec)
+        # (bits of the double max overlap, linkers in the force branch): read once, at the end of the step
+        self._backbone_stats = torch.zeros(2, dtype=torch.int64, device=self.center.device)
+        self._backbone_stale = False   # restore(): the next update rebuilds the list whatever has moved
+        self._backbone_rebuilt = False
+
+    def _snapshot_backbone(self):
+        return None  # (the forces do not depend on when the list was built: nothing to save)
+
+    def _restore_backbone(self, saved):
+        self._backbone_stale = True
+
+    def _renumber_backbone(self, perm, inv):
+        """segment ends through the inverse permutation (segment order kept): a new handle from the host copy of the
+        ends, whose first update builds its list"""
+        spec = self._backbone_spec
+        spec["segments"] = np.ascontiguousarray(inv.cpu().numpy()[spec["segments"]], dtype=np.int32)
+        self.backbone.close()
+        self.backbone = ops.SegmentContacts(self.center.shape[0], **spec)
+
     # -- n-body hydrodynamics as a velocity stage (HP1.cpp:3942-4059, :4744-4803) -----------------------------------------
     def _init_hydro(self, kind, radius, every, periphery=None):
         n, dev = self.center.shape[0], self.center.device
@@ -780,17 +850,25 @@ class ContactStepper:
         ops.hydro_add_velocity(self.u_hydro, self.u_ext)
 
     def _force_stage(self, external_force):
-        """the force stage in the reference's order (HP1.cpp:4733-4741): crosslinker KMC, active sampling, springs,
-        crosslinker springs, periphery, active force dipoles, external force; every term after the first that writes is
-        added into self.spring_force.  With no such term the caller's external_force (or None: no force at all) is
+        """the force stage in the reference's order (HP1.cpp:4733-4741): crosslinker KMC, active sampling, backbone
+        segment contacts, springs, crosslinker springs, periphery, active force dipoles, external force; every term after
+        the first that writes is added into self.spring_force.  The segment list is brought up to date first, on the
+        positions of the start of the step.  With no such term the caller's external_force (or None: no force at all) is
         returned as it is, not copied.  With hydrodynamics contact_forces the buffer already holds the contact force
         F = D f (contact_forces()), the first term as in the reference, and every term here is added to it:
-        F = ((((D f + F_spring) + F_crosslinker) + F_periphery) + F_active) + F_ext, each + one rounding."""
+        F = (((((D f + F_backbone) + F_spring) + F_crosslinker) + F_periphery) + F_active) + F_ext, each + one rounding,
+        a term that is off left out."""
         st, force, written = self._chain_stats, self.spring_force, self.hydro_contact_forces
+        if self.backbone is not None:
+            self._backbone_rebuilt = self.backbone.update(self.center, force_rebuild=self._backbone_stale)
+            self._backbone_stale = False
         if self.crosslinkers is not None:
             self.crosslinker_kmc()
         if self.active is not None:
             self.active.sample(switches=stat(st, "active_switches"))
+        if self.backbone is not None:
+            self.backbone.force(self.center, out=force, accumulate=written, stats=self._backbone_stats)
+            written = True
         if self.springs is not None and written:  # (the spring kernel overwrites: its term goes through a buffer of its own)
             self.springs.force(self.center, out=self._spring_term,
                                stats=(stat(st, "springs_overstretched"), stat(st, "max_spring_length")))
@@ -1198,7 +1276,7 @@ class ContactStepper:
         return self.op.body_force(self.lam)
 
     def integrate(self):
-        if self.hydro_contact_forces:  # U = U_ext: the contact force is inside it
+        if self.hydro_contact_forces or self.contact_model == "none":  # U = U_ext: every contact force is inside it
             vel = self.velocity = self.u_ext.clone()
             ops.integrate_euler(self.dt, vel, self.center, self.quat)
             return
@@ -1235,6 +1313,16 @@ class ContactStepper:
                 ev.append((name, e))
 
         mark("start")
+        if self.contact_model == "none":  # no sphere contact at all: the force stage, then U = U_ext
+            self.external_velocity(external_force, mark)
+            if integrate:
+                self.integrate()
+                if self.active is not None:
+                    self.active.advance(self.dt)
+            mark("integrate")
+            st.converged = True  # (as the Hertz path reports: nothing to solve)
+            self._read_chain_stats(st)
+            return self._timings(st, ev, timed)
         if self.growth:
             st.num_born = self.grow_and_divide()
             st.num_bodies = self.n
@@ -1271,34 +1359,45 @@ class ContactStepper:
         st.num_contacts = self.contact_pairs.shape[0]
         st.num_iters, st.residual, st.converged = res.num_iters, res.residual, res.converged
         if self.chain:
-            got = read_stats(self._chain_stats)  # the one read of the step
-            st.max_overlap, st.max_spring_length = got["max_overlap"], got["max_spring_length"]
-            if got["springs_overstretched"]:
-                raise RuntimeError("%d FENE spring(s) stretched to L >= r_max: no force (reduce dt)"
-                                   % got["springs_overstretched"])
-            if self.crosslinkers is not None:
-                st.crosslinker_binds, st.crosslinker_unbinds = got["crosslinker_binds"], got["crosslinker_unbinds"]
-                self.crosslinker_bound += st.crosslinker_binds - st.crosslinker_unbinds
-                st.crosslinker_bound = self.crosslinker_bound
-                st.max_crosslinker_length = got["max_crosslinker_length"]
-                st.crosslinker_periphery_bound = got["crosslinker_periphery_bound"]
-                if got["crosslinkers_overstretched"]:
-                    raise RuntimeError("%d FENE crosslinker(s) stretched to L >= r_max: no force (reduce dt)"
-                                       % got["crosslinkers_overstretched"])
-            if self.periphery is not None or self.active is not None:
-                st.periphery_colliding, st.max_periphery_overlap = got["periphery_colliding"], got["max_periphery_overlap"]
-                st.active_springs = got["active_springs"]
-                st.active_switches = (got["active_switches_on"], got["active_switches_off"])
+            self._read_chain_stats(st)
         elif self.hertz_friction is not None:  # the one read of the step: (max_overlap, num_sliding)
             h = self._fr_stats.cpu()
             st.max_overlap, st.num_sliding = float(h[0]), int(h.view(torch.int64)[1])
         elif self.contact_model == "hertz":
             st.max_overlap = float(self.max_overlap.item())
+        return self._timings(st, ev, timed)
+
+    @staticmethod
+    def _timings(st, ev, timed):
         if timed:
             torch.cuda.synchronize()
             for (_, a), (name, b) in zip(ev[:-1], ev[1:]):
                 st.timings_ms[name] = a.elapsed_time(b)
         return st
+
+    def _read_chain_stats(self, st):
+        """the chain step's statistics into st: one read of the statistics array, and one of the segment contacts' own"""
+        got = read_stats(self._chain_stats)  # the one read of the step
+        st.max_overlap, st.max_spring_length = got["max_overlap"], got["max_spring_length"]
+        if got["springs_overstretched"]:
+            raise RuntimeError("%d FENE spring(s) stretched to L >= r_max: no force (reduce dt)"
+                               % got["springs_overstretched"])
+        if self.crosslinkers is not None:
+            st.crosslinker_binds, st.crosslinker_unbinds = got["crosslinker_binds"], got["crosslinker_unbinds"]
+            self.crosslinker_bound += st.crosslinker_binds - st.crosslinker_unbinds
+            st.crosslinker_bound = self.crosslinker_bound
+            st.max_crosslinker_length = got["max_crosslinker_length"]
+            st.crosslinker_periphery_bound = got["crosslinker_periphery_bound"]
+            if got["crosslinkers_overstretched"]:
+                raise RuntimeError("%d FENE crosslinker(s) stretched to L >= r_max: no force (reduce dt)"
+                                   % got["crosslinkers_overstretched"])
+        if self.periphery is not None or self.active is not None:
+            st.periphery_colliding, st.max_periphery_overlap = got["periphery_colliding"], got["max_periphery_overlap"]
+            st.active_springs = got["active_springs"]
+            st.active_switches = (got["active_switches_on"], got["active_switches_off"])
+        if self.backbone is not None:
+            st.max_segment_overlap, st.segment_contacts = ops.SegmentContacts.read_stats(self._backbone_stats)
+            st.num_segment_pairs, st.segment_list_rebuilt = self.backbone.num_pairs, self._backbone_rebuilt
 
 
 class FilamentStepper:

@@ -305,3 +305,13 @@ def periphery_bind_sites(shape, radii, count, seed=1234):
         kept.append(np.stack([a * x[keep], b * y[keep], c * z[keep]], axis=1))
         have += int(keep.sum())
     return np.ascontiguousarray(np.concatenate(kept)[:count])
+
+
+def backbone_segments(node_ptr):
+    """the backbone segments of contiguous chains: chain c holds the beads node_ptr[c] .. node_ptr[c + 1] - 1, and a
+    segment joins every two consecutive beads of a chain -> ends int32 [m, 2], in bead order"""
+    ptr = np.asarray(node_ptr, dtype=np.int64)
+    if ptr.ndim != 1 or ptr.size < 1 or (np.diff(ptr) < 0).any():
+        raise ValueError("node_ptr must be a non-decreasing 1-d array, got %r" % (node_ptr,))
+    first = np.concatenate([np.arange(a, b - 1) for a, b in zip(ptr[:-1], ptr[1:])] or [np.zeros(0, np.int64)])
+    return np.ascontiguousarray(np.stack([first, first + 1], axis=1).astype(np.int32))
