@@ -34,6 +34,7 @@
 #include "../mundy_hip.h"
 #include "../mundy_hip_contact_force.h"
 #include "../mundy_hip_hydro_periphery.h"
+#include "../mundy_hip_hydro_solve.h"
 #include "../mundy_hip_periphery_binding.h"
 
 namespace mundy_hip {
@@ -1372,6 +1373,8 @@ class Hydrodynamics {
                            mhip_stream_t stream = nullptr) {
     check(mhip_hydro_add_velocity(n, u_hydro, velocity, velocity_stride, stream));
   }
+  /// time only: velocity() skips sources whose force is (+-0, +-0, +-0) inside every staged tile (the same bits)
+  void set_sparse_sources(bool on) { check(mhip_hydro_set_sparse_sources(h_, on ? 1 : 0)); }
   mhip_hydro_t handle() const { return h_; }
 
  private:
@@ -1416,6 +1419,23 @@ class HydroPeriphery {
   mhip_hydro_periphery_t h_ = nullptr;
 };
 
+/// The long-range part of the hydrodynamic mobility M_h = m_t + hydro_kind (+ the periphery's no-slip correction) of
+/// an LCP (mhip_hydro_mobility, mundy_hip_hydro_solve.h; the reference's SphereRpyMobilityOp and
+/// SphereConfinedRpyMobilityOp, NgpHP1.cpp:677-766): kind MHIP_HYDRO_RPYC or MHIP_HYDRO_RPY, centres [n][3] and
+/// hydrodynamic radii [n] (device arrays the caller keeps alive and the library reads at every call), the workspace,
+/// and optionally a periphery that holds its inverse.  Holds pointers, owns nothing.
+class HydroMobility {
+ public:
+  HydroMobility(Hydrodynamics& workspace, int kind, double viscosity, size_t n, const double* center,
+                const double* radius, const HydroPeriphery* periphery = nullptr, bool skip_same_index = true)
+      : m_{workspace.handle(), kind, viscosity, n, center, radius, periphery ? periphery->handle() : nullptr,
+           skip_same_index ? 1 : 0} {}
+  const mhip_hydro_mobility* c_mobility() const { return &m_; }
+
+ private:
+  mhip_hydro_mobility m_;
+};
+
 }  // namespace mech
 
 /// solve_lcp (convex.hpp:839-845)
@@ -1424,6 +1444,25 @@ auto solve_lcp(const Problem& prob, const Strategy& strat, typename Strategy::st
     typename Strategy::result_t {
   auto cqpp_prob = convex::to_cqpp(prob);
   return solve_cqpp(cqpp_prob, strat, state);
+}
+
+/// solve_lcp against a hydrodynamic mobility (NgpHP1.cpp:1487-1645; mhip_bbpgd_solve_contact_hydro): the LCP of a
+/// sphere ContactOperator with A = dt D^T M_h D, the fused driver; the operator's rows then hold M_h D x
+template <class Problem, class Strategy>
+auto solve_lcp(const Problem& prob, const Strategy& strat, typename Strategy::state_t& state,
+               const mech::HydroMobility& mobility) -> typename Strategy::result_t {
+  static_assert(std::is_same_v<std::decay_t<decltype(prob.A())>, ContactOperator>,
+                "a hydrodynamic mobility needs a ContactOperator");
+  const mhip_space sp = convex::space::LowerBound<double>{0.0}.c_space();
+  const mhip_pgd_config cfg{strat.config().max_iters, strat.config().tol, Strategy::residual_policy_t::kind};
+  mhip_solve_result r{};
+  check(mhip_bbpgd_solve_contact_hydro(prob.A().handle(), mobility.c_mobility(), prob.q().data(), &sp, &cfg,
+                                       state.x().data(), state.grad().data(), state.x_tmp().data(),
+                                       state.grad_tmp().data(), &r, nullptr));
+  state.iter() = r.num_iters;
+  state.residual() = r.residual;
+  state.converged() = r.converged != 0;
+  return {r.num_iters, r.residual, r.converged != 0};
 }
 
 }  // namespace mundy_hip

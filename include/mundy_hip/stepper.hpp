@@ -118,15 +118,20 @@ class SegmentContacts {
 };
 
 /// the LCP of a contact operator with right-hand side q: fused BBPGD from lambda = 0 (NgpLcp.cpp:890-891); x receives
-/// the multipliers, g, x_tmp and g_tmp [C] are work vectors
+/// the multipliers, g, x_tmp and g_tmp [C] are work vectors.  mobility: the LCP against the hydrodynamic mobility
+/// (mhip_bbpgd_solve_contact_hydro); null: the operator's dry one
 inline mhip_solve_result solve_lcp_from_zero(ContactOperator& op, size_t C, const double* q,
                                              const convex::PGDConfig<double>& cfg, double* x, double* g, double* x_tmp,
-                                             double* g_tmp) {
+                                             double* g_tmp, const HydroMobility* mobility = nullptr) {
   check(mhip_fill(C, x, 0.0, nullptr));
   const mhip_space lcp{MHIP_SPACE_LOWER_BOUND, 0.0, 0.0};
   const mhip_pgd_config pc{cfg.max_iters, cfg.tol, MHIP_RESIDUAL_PROJECTED_DIFF};
   mhip_solve_result res{};
-  check(mhip_bbpgd_solve_contact(op.handle(), q, &lcp, &pc, x, g, x_tmp, g_tmp, &res, nullptr));
+  if (mobility)
+    check(mhip_bbpgd_solve_contact_hydro(op.handle(), mobility->c_mobility(), q, &lcp, &pc, x, g, x_tmp, g_tmp, &res,
+                                         nullptr));
+  else
+    check(mhip_bbpgd_solve_contact(op.handle(), q, &lcp, &pc, x, g, x_tmp, g_tmp, &res, nullptr));
   return res;
 }
 
@@ -796,6 +801,8 @@ class SphereChainStepper {
       throw std::invalid_argument("SphereChainStepper: youngs_modulus must be > 0 and 0 < poisson_ratio < 1");
     if (!contact_forces_in_force_stage)
       throw std::invalid_argument("SphereChainStepper: the Hertz contact runs with its force in the force stage only");
+    if (hydro_solve_)
+      throw std::invalid_argument("SphereChainStepper: the hydrodynamic solve is the LCP's: no Hertz contact with it");
     material_.youngs_modulus = youngs_modulus;
     material_.poisson_ratio = poisson_ratio;
     hertz_ = true;
@@ -837,6 +844,8 @@ class SphereChainStepper {
   void set_sphere_contacts(bool on) {
     if (!on && !backbone_)
       throw std::logic_error("SphereChainStepper: set_sphere_contacts(false) needs set_backbone_collision first");
+    if (!on && hydro_solve_)
+      throw std::invalid_argument("SphereChainStepper: the hydrodynamic solve needs the sphere contacts");
     sphere_contacts_ = on;
   }
   /// Crosslinkers that bind and unbind (mech::Crosslinkers; host arrays left [mx], is_site [n] bytes): their KMC step
@@ -890,11 +899,27 @@ class SphereChainStepper {
   /// force() to U_ext on every step and recomputes it when step_index() % update_every == 0
   void set_hydrodynamics(int kind, double viscosity, int update_every) {
     if (update_every < 1) throw std::invalid_argument("SphereChainStepper: update_every must be >= 1");
+    if (hydro_solve_ && kind != MHIP_HYDRO_RPYC && kind != MHIP_HYDRO_RPY)
+      throw std::invalid_argument("SphereChainStepper: the hydrodynamic solve needs MHIP_HYDRO_RPYC or MHIP_HYDRO_RPY");
     hydro_.reset(new Hydrodynamics());
     hydro_kind_ = kind;
     viscosity_ = viscosity;
     update_every_ = static_cast<size_t>(update_every);
     u_hydro_ = DeviceVector(3 * n_);
+  }
+  /// true: resolve() solves the LCP against M_h = m_t + hydro_kind (+ the periphery's correction, where one is set) at
+  /// the current positions, as the reference's newer chromatin app does (NgpHP1.cpp:1487-1645), so U = U_ext + M_h D
+  /// lambda; U_ext and q are unchanged.  Needs set_hydrodynamics (RPYC or RPY: the Stokeslet is not positive
+  /// semi-definite at bead separations) and the LCP model with sphere contacts.  false: the dry solve, the default.
+  void set_hydrodynamic_solve(bool on) {
+    if (on) {
+      if (!hydro_) throw std::logic_error("SphereChainStepper: set_hydrodynamic_solve needs set_hydrodynamics first");
+      if (hertz_ || !sphere_contacts_)
+        throw std::invalid_argument("SphereChainStepper: the hydrodynamic solve needs the LCP contact model");
+      if (hydro_kind_ != MHIP_HYDRO_RPYC && hydro_kind_ != MHIP_HYDRO_RPY)
+        throw std::invalid_argument("SphereChainStepper: the hydrodynamic solve needs MHIP_HYDRO_RPYC or MHIP_HYDRO_RPY");
+    }
+    hydro_solve_ = on;
   }
   /// The no-slip periphery of the hydrodynamics (host quadrature arrays), after set_hydrodynamics: its matrix is filled
   /// and inverted here (min_pivot()), its correction goes into u_hydro at every update
@@ -986,7 +1011,15 @@ class SphereChainStepper {
     check(mhip_contact_op_constraint_rate(op_->handle(), u_ext_.data(), q, nullptr));
     check(mhip_axpby(C, 1.0, sep, dt_, q, nullptr));
     num_lambda_ = C;
-    const mhip_solve_result res = solve_lcp_from_zero(*op_, C, q, cfg_, x, g, x_tmp, g_tmp);
+    // (the hydrodynamic solve: M_h at the current positions; the rows then hold M_h D lambda)
+    mhip_solve_result res{};
+    if (hydro_solve_) {
+      const HydroMobility mobility(*hydro_, hydro_kind_, viscosity_, n_, center_.data(), radius_.data(),
+                                   hydro_periphery_.get(), skip_same_index_);
+      res = solve_lcp_from_zero(*op_, C, q, cfg_, x, g, x_tmp, g_tmp, &mobility);
+    } else {
+      res = solve_lcp_from_zero(*op_, C, q, cfg_, x, g, x_tmp, g_tmp);
+    }
     st.num_iters = res.num_iters;
     st.residual = res.residual;
     st.converged = res.converged != 0;
@@ -1133,6 +1166,7 @@ class SphereChainStepper {
   double viscosity_ = 0.0, min_pivot_ = 0.0;
   size_t update_every_ = 1;
   bool skip_same_index_ = false;
+  bool hydro_solve_ = false;  // set_hydrodynamic_solve
   DeviceVector u_hydro_;  // [n][3]: the stored hydrodynamic velocity
   // the backbone segment contacts (set_backbone_collision) and whether the spheres collide at all (set_sphere_contacts)
   std::unique_ptr<SegmentContacts> backbone_;

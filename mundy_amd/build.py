@@ -13,7 +13,8 @@ FLAG_OVERRIDES = {"mixed_fma.hip": {"-ffp-contract=off": "-ffp-contract=fast"}}
 HEADERS = ["mhip_internal.hpp", "geom_device.hpp", "ellipsoid_device.hpp", "ellipsoid_lockstep.hpp", "segment_ellipsoid.hpp", "force_device.hpp", "scratch_owner.hpp", os.path.join("..", "..", "include", "mundy_hip.h"), os.path.join("..", "..", "include", "mundy_hip_hydro_periphery.h"),
            os.path.join("..", "..", "include", "mundy_hip_contact_force.h"),
            os.path.join("..", "..", "include", "mundy_hip_periphery_binding.h"),
-           os.path.join("..", "..", "include", "mundy_hip_segment_contact.h")]
+           os.path.join("..", "..", "include", "mundy_hip_segment_contact.h"),
+           os.path.join("..", "..", "include", "mundy_hip_hydro_solve.h")]
 # -ffp-contract=off: a*b+c stays two roundings so per-element results are bit-identical to the scalar reference order
 FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

@@ -372,6 +372,20 @@ SEGMENT_CONTACT_SIGNATURES = {
     "mhip_segment_contacts_reduce": [_vp, _vp, _i, _vp, _vp],
     "mhip_segment_contacts_get": [_vp, C.POINTER(SegmentContactFields)],
 }
+# include/mundy_hip_hydro_solve.h, a header of its own for the same reason: name -> argtypes, every function returns int
+# status.  tests/test_hydro_solve_host.py checks this table against that header and the library.
+class HydroMobility(C.Structure):
+    """mhip_hydro_mobility: M_h without its dry part (workspace, kind, viscosity, n, center, radius, periphery, skip)"""
+    _fields_ = [("workspace", C.c_void_p), ("kind", C.c_int), ("viscosity", C.c_double), ("n", C.c_size_t),
+                ("center", C.c_void_p), ("radius", C.c_void_p), ("periphery", C.c_void_p), ("skip_same_index", C.c_int)]
+
+
+HYDRO_SOLVE_SIGNATURES = {
+    "mhip_hydro_set_sparse_sources": [_vp, _i],
+    "mhip_contact_op_apply_hydro": [_vp, C.POINTER(HydroMobility), _vp, _vp, _vp],
+    "mhip_bbpgd_solve_contact_hydro": [_vp, C.POINTER(HydroMobility), _vp, C.POINTER(Space), C.POINTER(PgdConfig), _vp,
+                                       _vp, _vp, _vp, C.POINTER(SolveResult), _vp],
+}
 OTHER_SYMBOLS = {"mhip_last_error": ([], C.c_char_p), "mhip_version": ([], C.c_int),
                  "mhip_release_cached_workspaces": ([], C.c_int)}
 
@@ -392,7 +406,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, argtypes in (list(SIGNATURES.items()) + list(PERIPHERY_SIGNATURES.items()) +
                                list(CONTACT_FORCE_SIGNATURES.items()) + list(PERIPHERY_BINDING_SIGNATURES.items()) +
-                               list(SEGMENT_CONTACT_SIGNATURES.items())):
+                               list(SEGMENT_CONTACT_SIGNATURES.items()) + list(HYDRO_SOLVE_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = C.c_int

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/mundy_hip_contact_force.h"
+#include "../../include/mundy_hip_hydro_solve.h"
 #include "mhip_internal.hpp"
 
 namespace mhip {
@@ -487,6 +488,9 @@ struct OpView {
   const double* fire_at;
   int32_t* fired;
   unsigned long long* tier_counters;
+  // hydrodynamic solve (mundy_hip_hydro_solve.h): the body sweep also leaves F_b, the rounded force sum it multiplies by
+  // m_t, as [N][3] -- the sources of the pair kernel that follows it.  null = not kept.
+  double* force_rows;
 };
 
 // XCD-aware work mapping (MI355X: 8 XCDs, each with a private 4 MiB L2; workgroups are dealt round-robin over the XCDs,
@@ -955,6 +959,7 @@ __global__ void __launch_bounds__(kBlock, MHIP_KBODY_WAVES)
     W = cross(w, axis);  // the row carries Z = W x u: the contact-point velocity is U + coef Z
   }
   const V3 Ub{mt * F.x, mt * F.y, mt * F.z};  // U = F / (6 pi r mu)  (NgpLcp.cpp:484-486)
+  if (op.force_rows != nullptr) store3(op.force_rows, b, F);  // (uniform: the bits of mhip_contact_op_body_force)
   v[0] = make_double2(Ub.x, Ub.y);
   v[1] = make_double2(Ub.z, W.x);
   v[2] = make_double2(W.y, W.z);
@@ -2411,6 +2416,7 @@ struct ProfilingEvents {  // 3 per enqueued iteration: before body, between, aft
 };
 struct OpWorkspaces {
   HandleBuffer inc_ptr, inc, cursor, vel, partials, state, scanws, half, axis, omega, vel_out;
+  HandleBuffer force_rows;  // F = D x [N][3] of the hydrodynamic solve's body sweeps (see OpView)
   HandleBuffer iterate;  // packed (x, g) ping-pong pair of the fused / staged solvers: 2 x C x 16 bytes
   HandleBuffer rate_rows;  // (U, W x u) rows of a caller's velocity (mhip_contact_op_constraint_rate, rods)
   HandleBuffer body_mask, pos;  // activity masks of the packed LCP solves (see OpView)
@@ -3997,6 +4003,190 @@ int mhip_bbpgd_solve_contact(mhip_contact_op_t op, const double* q, const mhip_s
   // rods: the angular velocities of the final iterate (the iterations' sweeps keep only the (U, Z) rows)
   if (op->kin == KIN_ROD)
     if (int e = op_launch_body(op, X_APPLY, x, nullptr, nullptr, nullptr, sp, s)) return e;
+  return solve_result(op, s, result);
+}
+
+}  // extern "C"
+
+// ---- the LCP against a hydrodynamic mobility (include/mundy_hip_hydro_solve.h) ------------------------------------------
+namespace mhip {  // hydro_periphery.hip
+int hydro_periphery_correct(mhip_hydro_periphery* h, mhip_hydro* ws, int kind, size_t n, const double* center,
+                            const double* radius, const double* force, double* velocity, int velocity_stride,
+                            int skip_same_index, const HydroLaunchOptions* opt, mhip_stream_t stream);
+}
+
+namespace {
+
+// what apply_hydro and the hydrodynamic solve refuse of their operator and mobility, before any HIP call
+int check_hydro_mobility(const mhip_contact_op* op, const mhip_hydro_mobility* m) {
+  MHIP_REQUIRE(op != nullptr, MHIP_ERR_INVALID_ARGUMENT, "operator handle is null");
+  MHIP_REQUIRE(m != nullptr, MHIP_ERR_INVALID_ARGUMENT, "mobility is null");
+  MHIP_REQUIRE(m->workspace != nullptr, MHIP_ERR_INVALID_ARGUMENT, "hydro handle is null");
+  MHIP_REQUIRE(m->kind != MHIP_HYDRO_STOKES, MHIP_ERR_INVALID_ARGUMENT,
+               "the Stokeslet is not positive semi-definite at bead separations: the mobility is rpyc or rpy");
+  MHIP_REQUIRE(m->kind == MHIP_HYDRO_RPY || m->kind == MHIP_HYDRO_RPYC, MHIP_ERR_INVALID_ARGUMENT,
+               "unknown hydrodynamic kernel kind %d", m->kind);
+  MHIP_REQUIRE(std::isfinite(m->viscosity) && m->viscosity > 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "viscosity must be finite and > 0, got %g", m->viscosity);
+  MHIP_REQUIRE(op->kin == KIN_TRANS, MHIP_ERR_INVALID_ARGUMENT,
+               "the hydrodynamic mobility needs a sphere operator: no lever arms, rods or mob_rot");
+  MHIP_REQUIRE(m->n == op->view.N, MHIP_ERR_INVALID_ARGUMENT, "the mobility has %zu bodies, the operator %zu", m->n,
+               op->view.N);
+  MHIP_REQUIRE(m->n == 0 || (m->center && m->radius), MHIP_ERR_INVALID_ARGUMENT, "mobility center / radius is null");
+  MHIP_REQUIRE(!op->stage.active, MHIP_ERR_RUNTIME, "a staged solve is in progress");
+  MHIP_REQUIRE(op->view.body_first == 0 && op->view.body_count == op->view.N && op->view.counted == nullptr,
+               MHIP_ERR_LOGIC, "the hydrodynamic mobility of a partitioned operator is not supported");
+  if (m->periphery != nullptr) {
+    const double* matrix = nullptr;
+    int state = MHIP_HYDRO_PERIPHERY_EMPTY;
+    if (int e = mhip_hydro_periphery_matrix(m->periphery, &matrix, &state)) return e;
+    MHIP_REQUIRE(state == MHIP_HYDRO_PERIPHERY_INVERSE, MHIP_ERR_LOGIC,
+                 "the mobility's periphery needs its inverse: call invert or set_inverse first");
+  }
+  return MHIP_SUCCESS;
+}
+
+// While one of the two entry points runs the body sweeps leave F beside the rows; the pointer is taken off again when
+// the entry point returns, however it does.  The caller's workspace is never changed: what the solve asks of its pair
+// sums travels with every launch (HydroLaunchOptions).
+struct HydroSession {
+  mhip_contact_op* op;
+  explicit HydroSession(mhip_contact_op* o) : op(o) {}
+  int begin() {
+    if (int e = op->force_rows.reserve((3 * op->view.N + 2) * sizeof(double))) return e;
+    op->view.force_rows = op->force_rows.as<double>();
+    return MHIP_SUCCESS;
+  }
+  ~HydroSession() { op->view.force_rows = nullptr; }
+};
+
+// U += hydro_kind(F) (+ the periphery's correction) onto the rows U_b = m_t F_b the body sweep has just written, from
+// the F it left beside them: the bodies of the public calls, in the header's order, with compacted source tiles (most
+// beads carry no contact force) and -- the solve's iterations -- behind `gate`, the solver's `done`
+int hydro_rows(mhip_contact_op* op, const mhip_hydro_mobility* m, const int* gate, mhip_stream_t stream) {
+  const size_t N = op->view.N;
+  const double* F = op->view.force_rows;
+  const HydroLaunchOptions opt{true, gate};
+  if (int e = hydro_velocity(m->workspace, m->kind, m->viscosity, N, m->center, m->radius, F, N, m->center, m->radius,
+                             op->view.vel, 6, 1, &opt, stream))
+    return e;
+  if (m->periphery == nullptr) return MHIP_SUCCESS;
+  return hydro_periphery_correct(m->periphery, m->workspace, m->kind, N, m->center, m->radius, F, op->view.vel, 6,
+                                 m->skip_same_index, &opt, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mhip_contact_op_apply_hydro(mhip_contact_op_t op, const mhip_hydro_mobility* mobility, const double* x, double* y,
+                                mhip_stream_t stream) {
+  if (int e = check_hydro_mobility(op, mobility)) return e;
+  MHIP_REQUIRE(op->view.C == 0 || (x && y), MHIP_ERR_INVALID_ARGUMENT, "x / y must not be null");
+  const size_t N = op->view.N;
+  if (N == 0) return MHIP_SUCCESS;
+  hipStream_t s = as_stream(stream);
+  op->last_stream = s;
+  if (op->view.C == 0) {  // no contact, no force: +0.0 rows
+    MHIP_HIP(hipMemsetAsync(op->view.vel, 0, 6 * N * sizeof(double), s));
+    return MHIP_SUCCESS;
+  }
+  HydroSession session(op);
+  if (int e = session.begin()) return e;
+  const Space none{MHIP_SPACE_UNCONSTRAINED, 0, 0};
+  if (int e = op_launch_body(op, X_APPLY, x, x, nullptr, nullptr, none, s)) return e;
+  if (int e = hydro_rows(op, mobility, nullptr, stream)) return e;
+  return op_launch_constraint(op, X_APPLY, const_cast<double*>(x), nullptr, nullptr, y, nullptr, none, 0,
+                              grid_for(op->view.C), s);
+}
+
+// mhip_bbpgd_solve_contact's driver without its cold tier and profiling, and with M_h's long-range part between the two
+// sweeps of every iteration
+int mhip_bbpgd_solve_contact_hydro(mhip_contact_op_t op, const mhip_hydro_mobility* mobility, const double* q,
+                                   const mhip_space* space, const mhip_pgd_config* config, double* x, double* g,
+                                   double* x_tmp, double* g_tmp, mhip_solve_result* result, mhip_stream_t stream) {
+  TraceRange trace_range("solve_cqpp (fused BBPGD, hydrodynamic mobility)");
+  MHIP_REQUIRE(result != nullptr, MHIP_ERR_INVALID_ARGUMENT, "null handle / result");
+  if (int e = check_hydro_mobility(op, mobility)) return e;
+  if (int e = check_config(config)) return e;
+  Space sp;
+  if (int e = to_space(space, &sp)) return e;
+  MHIP_REQUIRE(sp.kind == MHIP_SPACE_LOWER_BOUND && sp.lo == 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "the hydrodynamic solve is an LCP: the space must be LowerBound{0}");
+  const size_t C = op->view.C, N = op->view.N;
+  hipStream_t s = as_stream(stream);
+  if (C == 0) {  // as the dry solve; the rows of no force are +0.0
+    result->num_iters = 0;
+    result->residual = config->residual_kind == MHIP_RESIDUAL_PROJECTED_DIFF ? kLowest / kSmallStep : kLowest;
+    result->converged = 1;
+    if (N > 0) {
+      op->last_stream = s;
+      MHIP_HIP(hipMemsetAsync(op->view.vel, 0, 6 * N * sizeof(double), s));
+    }
+    return MHIP_SUCCESS;
+  }
+  MHIP_REQUIRE(q && x && g && x_tmp && g_tmp, MHIP_ERR_INVALID_ARGUMENT, "solver vectors must not be null");
+  MHIP_REQUIRE(x != x_tmp && g != g_tmp && x != g, MHIP_ERR_INVALID_ARGUMENT, "solver vectors must not alias");
+  HydroSession session(op);
+  if (int e = session.begin()) return e;
+  SolverState* st = op->state.as<SolverState>();
+  double* parts = op->partials.as<double>();
+  const unsigned cgrid = constraint_grid(C);
+  const int rk = config->residual_kind;
+  if (int e = op->iterate.reserve(2 * (C + 1) * sizeof(double2))) return e;
+  double* P0 = op->iterate.as<double>();
+  double* P1 = P0 + 2 * C;
+  if (op->view.body_mask) MHIP_HIP(hipMemsetAsync(op->view.body_mask, 0x00, N * sizeof(unsigned long long), s));
+  op->view.aptr = nullptr;  // no snapshot of the active entries yet (the init sweep writes the masks)
+  // tiering mode 0, whatever the operator's setting (see the header): nothing tracks, nothing sleeps
+  mhip_contact_op::Tier& tier = op->tier;
+  tier.disabled = true;
+  tier.tiered_iterations = tier.retiers = tier.wakeups = 0;
+  tier.hot_sum = 0.0;
+  // initialize: x_tmp = x ; g_tmp = A x_tmp + q ; residual ; step = 1/res   (the pair lands packed in P0)
+  if (int e = op_launch_body(op, X_INIT, x, x, nullptr, nullptr, sp, s)) return e;
+  if (int e = hydro_rows(op, mobility, nullptr, stream)) return e;  // (`done` may be left over from an earlier solve)
+  if (int e = op_launch_constraint(op, X_INIT, P0, P1, x, nullptr, q, sp, rk, cgrid, s, true)) return e;
+  finalize_sweep<X_INIT>(op, cgrid, config, s);
+  MHIP_LAUNCH_CHECK();
+  // the iterations' pair sums stop where the body sweep does: at the solver's `done`
+  unsigned enqueued = 0, chunk = 8;
+  PollPlan plan;
+  for (;;) {
+    MHIP_HIP(hipMemcpyAsync(op->host_state, st, sizeof(SolverState), hipMemcpyDeviceToHost, s));
+    MHIP_HIP(hipStreamSynchronize(s));
+    if (op->host_state->done || enqueued >= config->max_iters) break;
+    // the compact active lists of the body sweep, at the fused driver's polls (see mhip_bbpgd_solve_contact)
+    if (enqueued == 0)
+      if (int e = op_snapshot_active(op, s)) return e;
+    if (!plan.light_poll()) {
+      if (enqueued >= kSnapshotAfter)
+        if (int e = op_snapshot_active(op, s)) return e;
+      plan.full_poll_done(enqueued, *reinterpret_cast<const int32_t*>(op->host_state + 1), false, false);
+    }
+    const unsigned stretch = plan.stretch(chunk, op->host_state->iter, op->host_state->residual, config->tol, C);
+    const unsigned todo = (config->max_iters - enqueued < stretch) ? config->max_iters - enqueued : stretch;
+    for (unsigned k = 0; k < todo; ++k) {
+      if (int e = op_launch_body(op, X_SOLVE, P0, P1, nullptr, nullptr, sp, s, true)) return e;
+      if (int e = hydro_rows(op, mobility, &st->done, stream)) return e;
+      if (int e = op_launch_constraint(op, X_SOLVE, P0, P1, nullptr, nullptr, q, sp, rk, cgrid, s, true)) return e;
+      if (cgrid > MHIP_FOLD_ABOVE) {  // (as the fused driver folds and finalizes)
+        k_fold_finalize<X_SOLVE><<<kFoldGroups, MHIP_FOLD_BLOCK, 0, s>>>(
+            (int)cgrid, (size_t)cgrid, parts, parts + kRed * (size_t)cgrid,
+            reinterpret_cast<unsigned*>(op->state.as<char>() + sizeof(SolverState) + 16), st, rk, config->tol,
+            config->max_iters, 0, nullptr);
+      } else {
+        k_finalize<X_SOLVE><<<1, final_block(cgrid), 0, s>>>((int)cgrid, parts, 1, cgrid, st, rk, config->tol,
+                                                             config->max_iters, 0, nullptr);
+      }
+      MHIP_LAUNCH_CHECK();
+    }
+    enqueued += todo;
+    if (chunk < 64) chunk *= 2;
+  }
+  k_finish_packed<<<grid_for(C), kBlock, 0, s>>>(C, st, reinterpret_cast<const double2*>(P0),
+                                                 reinterpret_cast<const double2*>(P1), x, g, x_tmp, g_tmp);
+  MHIP_LAUNCH_CHECK();
   return solve_result(op, s, result);
 }
 

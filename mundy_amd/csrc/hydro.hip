@@ -237,6 +237,9 @@ struct HydroArgs {
   double* out;       // in-lane: velocity (stride, accumulate); partial: partial[chunk][target][3]
   int stride, accumulate;
   HydroConst k;
+  // (the hydrodynamic solve, mundy_hip_hydro_solve.h) a device word of the solver: non-zero = the solve is over and this
+  // launch, enqueued behind its last iteration, leaves everything as it is.  null: no such word.
+  const int* gate;
 };
 
 // source s as the kernel stages it in LDS
@@ -272,9 +275,14 @@ __device__ inline typename HydroSourceOf<KIND>::type hydro_stage(const HydroArgs
   }
 }
 
-template <int KIND, bool PARTIAL>
+// SPARSE (mhip_hydro_set_sparse_sources; never the double layer): a staged tile is compacted, in order, to the sources
+// with a non-zero force component.  A source with f = (+-0, +-0, +-0) adds +-0.0 to every target (finite inputs), and a
+// sum started from +0.0 is unchanged by +-0.0 terms: the same bits.  The count is uniform over the workgroup.
+template <int KIND, bool PARTIAL, bool SPARSE>
 __global__ void __launch_bounds__(kBlock) k_hydro(HydroArgs p) {
   __shared__ typename HydroSourceOf<KIND>::type tile[kBlock];
+  __shared__ int kept[SPARSE ? kBlock / 64 : 1];  // per wave: sources of the tile that stay
+  if (p.gate != nullptr && *p.gate != 0) return;
   const size_t t = blockIdx.x * (size_t)kBlock + threadIdx.x;
   const bool valid = t < p.nt;
   double tx = 0.0, ty = 0.0, tz = 0.0, b = 0.0;
@@ -295,9 +303,30 @@ __global__ void __launch_bounds__(kBlock) k_hydro(HydroArgs p) {
     for (size_t s0 = s_begin; s0 < s_end; s0 += kBlock) {
       __syncthreads();  // the previous tile has been read by every wave
       const size_t s = s0 + threadIdx.x;
-      if (s < s_end) tile[threadIdx.x] = hydro_stage<KIND>(p, s);
+      int cnt = s_end - s0 < (size_t)kBlock ? static_cast<int>(s_end - s0) : kBlock;
+      if constexpr (SPARSE) {
+        typename HydroSourceOf<KIND>::type src{};
+        bool keep = false;
+        if (s < s_end) {
+          src = hydro_stage<KIND>(p, s);
+          keep = src.fx != 0.0 || src.fy != 0.0 || src.fz != 0.0;  // (-0.0 != 0.0 is false; a NaN stays)
+        }
+        const unsigned long long votes = __ballot(keep);
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if (lane == 0) kept[wave] = __popcll(votes);
+        __syncthreads();
+        int slot = __popcll(votes & ((1ull << lane) - 1ull));  // kept sources before this one: in its wave ...
+        cnt = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) {
+          if (w < wave) slot += kept[w];  // ... and in the waves before it
+          cnt += kept[w];
+        }
+        if (keep) tile[slot] = src;  // slot <= threadIdx.x < kBlock
+      } else {
+        if (s < s_end) tile[threadIdx.x] = hydro_stage<KIND>(p, s);
+      }
       __syncthreads();
-      const int cnt = s_end - s0 < (size_t)kBlock ? static_cast<int>(s_end - s0) : kBlock;
       int skip_j = -1;
       if (KIND == kHydroDoubleLayer && p.skip_same && t >= s0 && t - s0 < (size_t)cnt) skip_j = static_cast<int>(t - s0);
       hydro_add_tile<KIND>(tile, cnt, tx, ty, tz, b, p.k, skip_j, acc);
@@ -324,9 +353,11 @@ __global__ void __launch_bounds__(kBlock) k_hydro(HydroArgs p) {
 
 // the ordered second pass of the partial shape: chunk sums in ascending chunk index from +0.0, the old value last
 __global__ void __launch_bounds__(kBlock) k_hydro_reduce(size_t nt, size_t nchunks, const double* __restrict__ partial,
-                                                        double* __restrict__ out, int stride, int accumulate) {
+                                                        double* __restrict__ out, int stride, int accumulate,
+                                                        const int* __restrict__ gate) {
   const size_t t = blockIdx.x * (size_t)kBlock + threadIdx.x;
   if (t >= nt) return;
+  if (gate != nullptr && *gate != 0) return;
   V3 total{0.0, 0.0, 0.0};
   for (size_t c = 0; c < nchunks; ++c) total = total + load3(partial, c * nt + t);
   double* o = out + t * (size_t)stride;
@@ -353,11 +384,20 @@ __global__ void __launch_bounds__(kBlock) k_hydro_add(size_t n, const double* __
 }
 
 template <int KIND>
-static void launch_hydro(bool partial, dim3 grid, const HydroArgs& a, hipStream_t s) {
+static void launch_hydro(bool partial, bool sparse, dim3 grid, const HydroArgs& a, hipStream_t s) {
+  if constexpr (KIND != kHydroDoubleLayer) {  // (surface densities are dense: the double layer has no sparse form)
+    if (sparse) {
+      if (partial)
+        k_hydro<KIND, true, true><<<grid, kBlock, 0, s>>>(a);
+      else
+        k_hydro<KIND, false, true><<<grid, kBlock, 0, s>>>(a);
+      return;
+    }
+  }
   if (partial)
-    k_hydro<KIND, true><<<grid, kBlock, 0, s>>>(a);
+    k_hydro<KIND, true, false><<<grid, kBlock, 0, s>>>(a);
   else
-    k_hydro<KIND, false><<<grid, kBlock, 0, s>>>(a);
+    k_hydro<KIND, false, false><<<grid, kBlock, 0, s>>>(a);
 }
 
 }  // namespace mhip
@@ -365,13 +405,14 @@ static void launch_hydro(bool partial, dim3 grid, const HydroArgs& a, hipStream_
 using namespace mhip;
 
 namespace mhip {
-int hydro_launch(mhip_hydro* h, int kind, HydroArgs a, double* velocity, hipStream_t s);
+int hydro_launch(mhip_hydro* h, int kind, HydroArgs a, double* velocity, bool sparse, hipStream_t s);
 }
 
 struct mhip_hydro {
   HandleBuffer partial;  // grow-only: [chunk][target][3] of the largest partial-shape call so far
   int path = MHIP_HYDRO_PATH_AUTO;
   int last_path = MHIP_HYDRO_PATH_AUTO;
+  bool sparse = false;  // mhip_hydro_set_sparse_sources
 };
 
 extern "C" {
@@ -395,6 +436,13 @@ int mhip_hydro_set_path(mhip_hydro_t h, int path) {
   return MHIP_SUCCESS;
 }
 
+int mhip_hydro_set_sparse_sources(mhip_hydro_t h, int on) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "hydro handle is null");
+  MHIP_REQUIRE(on == 0 || on == 1, MHIP_ERR_INVALID_ARGUMENT, "sparse sources must be 0 or 1, got %d", on);
+  h->sparse = on != 0;
+  return MHIP_SUCCESS;
+}
+
 int mhip_hydro_last_path(mhip_hydro_t h, int* path) {
   MHIP_REQUIRE(h != nullptr && path != nullptr, MHIP_ERR_INVALID_ARGUMENT, "hydro handle / path is null");
   *path = h->last_path;
@@ -405,6 +453,16 @@ int mhip_hydro_velocity(mhip_hydro_t h, int kind, double viscosity, size_t ns, c
                         const double* source_radius, const double* source_force, size_t nt,
                         const double* target_center, const double* target_radius, double* velocity,
                         int velocity_stride, int accumulate, mhip_stream_t stream) {
+  return hydro_velocity(h, kind, viscosity, ns, source_center, source_radius, source_force, nt, target_center,
+                        target_radius, velocity, velocity_stride, accumulate, nullptr, stream);
+}
+
+}  // extern "C"
+
+int mhip::hydro_velocity(mhip_hydro* h, int kind, double viscosity, size_t ns, const double* source_center,
+                         const double* source_radius, const double* source_force, size_t nt,
+                         const double* target_center, const double* target_radius, double* velocity,
+                         int velocity_stride, int accumulate, const HydroLaunchOptions* opt, mhip_stream_t stream) {
   MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "hydro handle is null");
   MHIP_REQUIRE(kind == MHIP_HYDRO_STOKES || kind == MHIP_HYDRO_RPY || kind == MHIP_HYDRO_RPYC,
                MHIP_ERR_INVALID_ARGUMENT, "unknown hydrodynamic kernel kind %d", kind);
@@ -438,13 +496,12 @@ int mhip_hydro_velocity(mhip_hydro_t h, int kind, double viscosity, size_t ns, c
   a.k.scale = 1.0 / (8.0 * M_PI * viscosity);
   a.k.c8 = one_over_eight * inv_pi * inv_viscosity;
   a.k.c6 = one_over_six * inv_pi * inv_viscosity;
-  return hydro_launch(h, kind, a, velocity, as_stream(stream));
+  a.gate = opt ? opt->gate : nullptr;
+  return hydro_launch(h, kind, a, velocity, opt ? opt->sparse : h->sparse, as_stream(stream));
 }
 
-}  // extern "C"
-
 // the launch both entry points share: the launch rule, the grow-only buffer and the ordered second pass
-int mhip::hydro_launch(mhip_hydro* h, int kind, HydroArgs a, double* velocity, hipStream_t s) {
+int mhip::hydro_launch(mhip_hydro* h, int kind, HydroArgs a, double* velocity, bool sparse, hipStream_t s) {
   const size_t nt = a.nt;
   const int velocity_stride = a.stride;
   a.nchunks = (a.ns + kHydroChunk - 1) / kHydroChunk;
@@ -466,15 +523,15 @@ int mhip::hydro_launch(mhip_hydro* h, int kind, HydroArgs a, double* velocity, h
     a.out = velocity;
   }
   switch (kind) {
-    case MHIP_HYDRO_STOKES: launch_hydro<MHIP_HYDRO_STOKES>(partial, grid, a, s); break;
-    case MHIP_HYDRO_RPY: launch_hydro<MHIP_HYDRO_RPY>(partial, grid, a, s); break;
-    case MHIP_HYDRO_RPYC: launch_hydro<MHIP_HYDRO_RPYC>(partial, grid, a, s); break;
-    default: launch_hydro<kHydroDoubleLayer>(partial, grid, a, s); break;
+    case MHIP_HYDRO_STOKES: launch_hydro<MHIP_HYDRO_STOKES>(partial, sparse, grid, a, s); break;
+    case MHIP_HYDRO_RPY: launch_hydro<MHIP_HYDRO_RPY>(partial, sparse, grid, a, s); break;
+    case MHIP_HYDRO_RPYC: launch_hydro<MHIP_HYDRO_RPYC>(partial, sparse, grid, a, s); break;
+    default: launch_hydro<kHydroDoubleLayer>(partial, false, grid, a, s); break;
   }
   MHIP_LAUNCH_CHECK();
   if (partial) {
     k_hydro_reduce<<<grid_exact(nt), kBlock, 0, s>>>(nt, a.nchunks, h->partial.as<double>(), velocity, velocity_stride,
-                                                     a.accumulate);
+                                                     a.accumulate, a.gate);
     MHIP_LAUNCH_CHECK();
   }
   return MHIP_SUCCESS;
@@ -486,6 +543,16 @@ int mhip_hydro_double_layer(mhip_hydro_t h, double viscosity, size_t ns, const d
                             const double* weight, const double* force, size_t nt, const double* target_center,
                             double* velocity, int velocity_stride, int accumulate, int skip_same_index,
                             mhip_stream_t stream) {
+  return hydro_double_layer(h, viscosity, ns, center, normal, weight, force, nt, target_center, velocity, velocity_stride,
+                            accumulate, skip_same_index, nullptr, stream);
+}
+
+}  // extern "C"
+
+int mhip::hydro_double_layer(mhip_hydro* h, double viscosity, size_t ns, const double* center, const double* normal,
+                             const double* weight, const double* force, size_t nt, const double* target_center,
+                             double* velocity, int velocity_stride, int accumulate, int skip_same_index,
+                             const HydroLaunchOptions* opt, mhip_stream_t stream) {
   MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "hydro handle is null");
   MHIP_REQUIRE(std::isfinite(viscosity) && viscosity > 0.0, MHIP_ERR_INVALID_ARGUMENT,
                "viscosity must be finite and > 0, got %g", viscosity);
@@ -511,8 +578,11 @@ int mhip_hydro_double_layer(mhip_hydro_t h, double viscosity, size_t ns, const d
   a.accumulate = accumulate ? 1 : 0;
   const double scale_dl = 3.0 / (4.0 * M_PI * viscosity);
   a.k.scale = -scale_dl;
-  return hydro_launch(h, kHydroDoubleLayer, a, velocity, as_stream(stream));
+  a.gate = opt ? opt->gate : nullptr;
+  return hydro_launch(h, kHydroDoubleLayer, a, velocity, false, as_stream(stream));  // (surface densities are dense)
 }
+
+extern "C" {
 
 int mhip_hydro_add_velocity(size_t n, const double* u_hydro, double* velocity, int velocity_stride,
                             mhip_stream_t stream) {

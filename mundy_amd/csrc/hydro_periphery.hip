@@ -238,6 +238,12 @@ __global__ void __launch_bounds__(kBlock) k_periphery_matvec(size_t N, const dou
 
 using namespace mhip;
 
+namespace mhip {
+int hydro_periphery_correct(mhip_hydro_periphery* h, mhip_hydro* ws, int kind, size_t n, const double* center,
+                            const double* radius, const double* force, double* velocity, int velocity_stride,
+                            int skip_same_index, const HydroLaunchOptions* opt, mhip_stream_t stream);
+}
+
 struct mhip_hydro_periphery {
   size_t S = 0;
   double viscosity = 0.0;
@@ -398,6 +404,16 @@ int mhip_hydro_periphery_surface_forces(mhip_hydro_periphery_t h, const double* 
 int mhip_hydro_periphery_correct(mhip_hydro_periphery_t h, mhip_hydro_t ws, int kind, size_t n, const double* center,
                                  const double* radius, const double* force, double* velocity, int velocity_stride,
                                  int skip_same_index, mhip_stream_t stream) {
+  return hydro_periphery_correct(h, ws, kind, n, center, radius, force, velocity, velocity_stride, skip_same_index,
+                                 nullptr, stream);
+}
+
+}  // extern "C"
+
+// the composite call with the launch options of its two pair sums (mhip_internal.hpp; the hydrodynamic solve gates them)
+int mhip::hydro_periphery_correct(mhip_hydro_periphery* h, mhip_hydro* ws, int kind, size_t n, const double* center,
+                                  const double* radius, const double* force, double* velocity, int velocity_stride,
+                                  int skip_same_index, const HydroLaunchOptions* opt, mhip_stream_t stream) {
   MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "periphery handle is null");
   MHIP_REQUIRE(ws != nullptr, MHIP_ERR_INVALID_ARGUMENT, "hydro handle is null");
   MHIP_REQUIRE(kind == MHIP_HYDRO_STOKES || kind == MHIP_HYDRO_RPY || kind == MHIP_HYDRO_RPYC,
@@ -412,12 +428,10 @@ int mhip_hydro_periphery_correct(mhip_hydro_periphery_t h, mhip_hydro_t ws, int 
   const size_t S = h->S;
   double *u = h->u_surf.as<double>(), *f = h->f_surf.as<double>();
   const double* y = h->points.as<double>();
-  if (int e = mhip_hydro_velocity(ws, kind, h->viscosity, n, center, radius, force, S, y, h->zero_radius.as<double>(), u,
-                                  3, 0, stream))
+  if (int e = hydro_velocity(ws, kind, h->viscosity, n, center, radius, force, S, y, h->zero_radius.as<double>(), u, 3, 0,
+                             opt, stream))
     return e;
   if (int e = periphery_surface_forces(h, u, f, as_stream(stream))) return e;
-  return mhip_hydro_double_layer(ws, h->viscosity, S, y, h->normals.as<double>(), h->weights.as<double>(), f, n, center,
-                                 velocity, velocity_stride, 1, skip_same_index, stream);
+  return hydro_double_layer(ws, h->viscosity, S, y, h->normals.as<double>(), h->weights.as<double>(), f, n, center,
+                            velocity, velocity_stride, 1, skip_same_index, opt, stream);
 }
-
-}  // extern "C"

@@ -509,6 +509,26 @@ struct PollPlan {
   }
 };
 
+// hydro.hip / hydro_periphery.hip, for the hydrodynamic solve (convex.hip; mundy_hip_hydro_solve.h): the bodies of
+// mhip_hydro_velocity, mhip_hydro_double_layer and mhip_hydro_periphery_correct with what the solve asks of its own
+// launches, handed over per call so that the caller's workspace is never changed --
+//   sparse  the staged tiles are compacted to the sources that carry a force, whatever the workspace's switch says
+//   gate    a device word that turns the launches into no-ops once it is non-zero (the solver's `done`: iterations
+//           enqueued behind the converging one must not add to the rows again); null: none
+// opt == nullptr is the public entry point: the workspace's own switch, no gate.
+struct HydroLaunchOptions {
+  bool sparse;
+  const int* gate;
+};
+int hydro_velocity(mhip_hydro* h, int kind, double viscosity, size_t ns, const double* source_center,
+                   const double* source_radius, const double* source_force, size_t nt, const double* target_center,
+                   const double* target_radius, double* velocity, int velocity_stride, int accumulate,
+                   const HydroLaunchOptions* opt, mhip_stream_t stream);
+int hydro_double_layer(mhip_hydro* h, double viscosity, size_t ns, const double* center, const double* normal,
+                       const double* weight, const double* force, size_t nt, const double* target_center,
+                       double* velocity, int velocity_stride, int accumulate, int skip_same_index,
+                       const HydroLaunchOptions* opt, mhip_stream_t stream);
+
 // sort.hip: stable LSD radix sort of (u64 key, u32 value) records over the key bits [0, 8 * passes), passes even (the
 // result is back in keys / vals); segment sorts (ascending, unsigned) -- see sort.hip
 constexpr int kShortSegment = 32;  // segments up to this length are sorted by one thread

@@ -738,6 +738,22 @@ class ContactOperator(_Handle):
         capi.check(capi.load().mhip_contact_op_apply(self._h, _ptr(x), _ptr(y), _stream()))
         return y
 
+    def apply_hydro(self, mobility, x, y=None):
+        """y = dt D^T M_h D x with the hydrodynamic mobility M_h = m_t + hydro_kind (+ the periphery's correction) of a
+        HydroMobility (mhip_contact_op_apply_hydro; include/mundy_hip_hydro_solve.h); body_velocity() then reads the
+        rows M_h D x.  Bit for bit the composition body_force -> m_t F -> hydro_velocity -> correct -> dt constraint_rate."""
+        if not isinstance(mobility, HydroMobility):
+            raise ValueError("mobility must be a HydroMobility, got %r" % (mobility,))
+        if tuple(x.shape) != (self.num_constraints,):
+            raise ValueError("x must have shape [%d], got %s" % (self.num_constraints, tuple(x.shape)))
+        mobility.check_operator(self)
+        y = torch.empty_like(x) if y is None else y
+        if tuple(y.shape) != (self.num_constraints,):
+            raise ValueError("y must have shape [%d], got %s" % (self.num_constraints, tuple(y.shape)))
+        capi.check(capi.load().mhip_contact_op_apply_hydro(self._h, C.byref(mobility.struct), _ptr(x, name="x"),
+                                                           _ptr(y, name="y"), _stream()))
+        return y
+
     def body_sweep(self, x):
         """the velocity rows (U, W) = M D x of per-contact force magnitudes x [C] (body i gets -x n, body j +x n): the
         body sweep alone, no constraint sweep (LinkerPotentialForceReduction + compute_generalized_velocity,
@@ -854,10 +870,28 @@ def _state(x0, state):
     return x, torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
 
 
-def solve_cqpp(A, q, space, x0, cfg=None, state=None, fused=True):
+def solve_cqpp(A, q, space, x0, cfg=None, state=None, fused=True, mobility=None):
     """solve_cqpp (convex.hpp:789-797).  A is a ContactOperator (matrix free) or a dense [n, n] tensor.
-    Returns (x, grad, SolveResult); `state` = caller-owned (x, grad, x_tmp, grad_tmp) as PGDState holds them."""
+    Returns (x, grad, SolveResult); `state` = caller-owned (x, grad, x_tmp, grad_tmp) as PGDState holds them.
+    mobility: a HydroMobility -- the LCP of a sphere ContactOperator against A = dt D^T M_h D
+    (mhip_bbpgd_solve_contact_hydro; A.body_velocity() then holds M_h D x); None: the dry mobility of the operator."""
     cfg = cfg or PGDConfig()
+    if mobility is not None:
+        if not isinstance(mobility, HydroMobility):
+            raise ValueError("mobility must be a HydroMobility, got %r" % (mobility,))
+        if not isinstance(A, ContactOperator):
+            raise ValueError("a hydrodynamic mobility needs a ContactOperator, not a dense matrix")
+        if not fused:
+            raise ValueError("a hydrodynamic mobility has the fused driver only")
+        if int(space[0]) != SPACE_LOWER_BOUND or float(space[1]) != 0.0:
+            raise ValueError("the hydrodynamic solve is an LCP: the space must be LowerBound{0}, got %r" % (space,))
+        mobility.check_operator(A)
+        x, g, x_tmp, g_tmp = _state(x0, state)
+        res, sp, pc = capi.SolveResult(), _space(space), _cfg(cfg)
+        capi.check(capi.load().mhip_bbpgd_solve_contact_hydro(
+            A._h, C.byref(mobility.struct), _ptr(q), C.byref(sp), C.byref(pc), _ptr(x), _ptr(g), _ptr(x_tmp),
+            _ptr(g_tmp), C.byref(res), _stream()))
+        return x, g, SolveResult(int(res.num_iters), float(res.residual), bool(res.converged))
     x, g, x_tmp, g_tmp = _state(x0, state)
     res, sp, pc = capi.SolveResult(), _space(space), _cfg(cfg)
     lib = capi.load()
@@ -937,9 +971,9 @@ def resolve_collisions(op, sep, lam, dt, max_allowable_overlap=1e-5, max_col_ite
     return lam, g, CollisionResult(float(res.residual), int(res.num_iters), float(spd.value) * float(dt))
 
 
-def solve_lcp(A, q, x0, cfg=None, state=None, fused=True):
-    """solve_lcp (convex.hpp:839-845): 0 <= A x + q  _|_  x >= 0."""
-    return solve_cqpp(A, q, LCP_SPACE, x0, cfg, state, fused)
+def solve_lcp(A, q, x0, cfg=None, state=None, fused=True, mobility=None):
+    """solve_lcp (convex.hpp:839-845): 0 <= A x + q  _|_  x >= 0.  mobility: see solve_cqpp."""
+    return solve_cqpp(A, q, LCP_SPACE, x0, cfg, state, fused, mobility)
 
 
 # ---- reordering / integration -----------------------------------------------------------------------------------------
@@ -1241,13 +1275,15 @@ def _hydro_kind(kind):
 
 
 def check_hydrodynamics(spec, n):
-    """hydrodynamics=dict(kind=, radius=None, update_every=1, periphery=None, contact_forces=False) of the stepper ->
-    (kind, radius, update_every); radius None (the beads' own), a number or [n] numbers, finite and >= 0 -> None or a
-    host array [n]; periphery: checked by check_hydro_periphery; contact_forces: a bool, which the stepper reads"""
-    check_dict_spec(spec, "hydrodynamics", ("kind", "radius", "update_every", "periphery", "contact_forces"),
-                    optional=("radius", "update_every", "periphery", "contact_forces"))
-    if not isinstance(spec.get("contact_forces", False), bool):
-        raise ValueError("hydrodynamics contact_forces must be a bool, got %r" % (spec["contact_forces"],))
+    """hydrodynamics=dict(kind=, radius=None, update_every=1, periphery=None, contact_forces=False, in_solve=False) of
+    the stepper -> (kind, radius, update_every); radius None (the beads' own), a number or [n] numbers, finite and >= 0
+    -> None or a host array [n]; periphery: checked by check_hydro_periphery; contact_forces and in_solve: bools, which
+    the stepper reads"""
+    check_dict_spec(spec, "hydrodynamics", ("kind", "radius", "update_every", "periphery", "contact_forces", "in_solve"),
+                    optional=("radius", "update_every", "periphery", "contact_forces", "in_solve"))
+    for key in ("contact_forces", "in_solve"):
+        if not isinstance(spec.get(key, False), bool):
+            raise ValueError("hydrodynamics %s must be a bool, got %r" % (key, spec[key]))
     _hydro_kind(spec["kind"])
     if spec.get("periphery") is not None:  # (the stepper takes its checked form from check_hydro_periphery)
         check_hydro_periphery(spec["periphery"])
@@ -1286,6 +1322,14 @@ class HydroWorkspace(_Handle):
         p = C.c_int()
         capi.check(capi.load().mhip_hydro_last_path(self._h, C.byref(p)))
         return {v: k for k, v in HYDRO_PATHS.items()}[p.value]
+
+    def set_sparse_sources(self, on=True):
+        """hydro_velocity on this workspace skips the sources whose force is (+-0, +-0, +-0) inside every staged tile
+        (mhip_hydro_set_sparse_sources): time only, the bits are the same.  Off by default; the hydrodynamic solve's
+        own launches use it whatever this switch says, and leave it alone."""
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError("on must be a bool, got %r" % (on,))
+        capi.check(capi.load().mhip_hydro_set_sparse_sources(self._h, 1 if on else 0))
 
 
 _hydro_default = None
@@ -1512,6 +1556,56 @@ class HydroPeriphery(_Handle):
             _ptr(force, name="force"), _ptr(velocity, name="velocity"), int(velocity.shape[1]),
             1 if skip_same_index else 0, _stream()))
         return velocity
+
+
+class HydroMobility:
+    """mhip_hydro_mobility (include/mundy_hip_hydro_solve.h): the long-range part of M_h = m_t + hydro_kind (+ the
+    periphery's no-slip correction) for ContactOperator.apply_hydro and solve_lcp(..., mobility=).  kind "rpyc" | "rpy"
+    (the Stokeslet is not positive semi-definite at bead separations); center [n, 3] and the hydrodynamic radius [n] are
+    device tensors this object keeps alive and the library reads at every call (update them in place, or build a new
+    one); periphery: a HydroPeriphery holding its inverse, built with the same viscosity; workspace: a HydroWorkspace
+    (default: the module's; one call at a time, as for hydro_velocity)."""
+
+    def __init__(self, kind, viscosity, center, radius, periphery=None, skip_same_index=True, workspace=None):
+        global _hydro_default
+        k = _hydro_kind(kind)
+        if k == capi.HYDRO_STOKES:
+            raise ValueError("the Stokeslet is not positive semi-definite at bead separations: kind must be 'rpyc' or "
+                             "'rpy'")
+        mu = float(viscosity)
+        if not (mu > 0.0 and mu < float("inf")):
+            raise ValueError("viscosity must be finite and > 0, got %r" % (viscosity,))
+        if center.dim() != 2 or center.shape[1] != 3:
+            raise ValueError("center must have shape [n, 3], got %s" % (tuple(center.shape),))
+        n = center.shape[0]
+        if tuple(radius.shape) != (n,):
+            raise ValueError("radius must have shape [%d], got %s" % (n, tuple(radius.shape)))
+        if periphery is not None and not isinstance(periphery, HydroPeriphery):
+            raise ValueError("periphery must be a HydroPeriphery, got %r" % (periphery,))
+        if periphery is not None and periphery.viscosity != mu:  # (its correction uses the handle's own)
+            raise ValueError("the periphery was built with viscosity %r, the mobility has %r" % (periphery.viscosity, mu))
+        if not isinstance(skip_same_index, (bool, np.bool_)):
+            raise ValueError("skip_same_index must be a bool, got %r" % (skip_same_index,))
+        if workspace is not None and not isinstance(workspace, HydroWorkspace):
+            raise ValueError("workspace must be a HydroWorkspace, got %r" % (workspace,))
+        cp, rp = _ptr(center, name="center"), _ptr(radius, name="radius")
+        if workspace is None:
+            if _hydro_default is None:
+                _hydro_default = HydroWorkspace()
+            workspace = _hydro_default
+        self.kind, self.viscosity, self.num_bodies = kind, mu, n
+        self.center, self.radius, self.periphery, self.workspace = center, radius, periphery, workspace
+        self.skip_same_index = bool(skip_same_index)
+        self.struct = capi.HydroMobility(workspace._h, k, mu, n, cp, rp, periphery._h if periphery is not None else None,
+                                         1 if skip_same_index else 0)
+
+    def check_operator(self, op):
+        """what the library refuses of the pair (operator, mobility), refused here before it is called"""
+        _, _, ra, rb, _, mob_rot, rod, _ = op._keep
+        if ra is not None or rb is not None or mob_rot is not None or rod is not None:
+            raise ValueError("the hydrodynamic mobility needs a sphere operator: no lever arms, rods or mob_rot")
+        if op.num_bodies != self.num_bodies:
+            raise ValueError("the mobility has %d bodies, the operator %d" % (self.num_bodies, op.num_bodies))
 
 
 def hydro_double_layer(viscosity, center, normal, weight, force, tgt_center, out=None, accumulate=False,

@@ -55,6 +55,14 @@ velocity and the periphery's no-slip correction all see it, and no body sweep fo
         -> every update_every-th step u_hydro = hydro(F) (+ the periphery's correction of F) -> U_ext += u_hydro
         -> U = U_ext -> Euler update
 
+hydrodynamics=dict(..., in_solve=True) with contact_model="lcp" solves the LCP against the hydrodynamic mobility, as the
+reference's newer chromatin app does (resolve_collisions over an ApplyMobilityOp, NgpHP1.cpp:1487-1645: every BBPGD
+iteration is F = D lambda -> U = M F -> sdot = D^T U with M = RPY + local drag, :833-925, or with the no-slip periphery as
+well, :927-1023): the force stage, U_ext and q = sep + dt D^T U_ext are the step's above, and
+
+    ... -> solve 0 <= lambda _|_ dt D^T M_h D lambda + q >= 0, M_h = m_t + hydro_kind (+ the periphery's correction) at
+        the current positions (ops.solve_lcp(mobility=)) -> U = U_ext + M_h D lambda -> Euler update
+
 backbone_collision= adds the excluded volume of that app, which acts between the backbone segments that join consecutive
 beads, not between the bead spheres (compute_hertzian_contact_forces, HP1.cpp:4356-4496: the first term of its force
 field, :4737); contact_model="none" then leaves the sphere contact out altogether, the reference's own configuration:
@@ -224,7 +232,11 @@ class ContactStepper:
         (contact_model="hertz" only; default False: the step above, unchanged) makes the Hertz contact force the first
         term of F, as the reference has it: contacts are evaluated before the forces, F = D f + springs + ..., the
         hydrodynamics and the periphery's correction see the contact forces, and U = U_ext with no body sweep (DESIGN.md
-        5p).  With "lcp" it is refused: the multipliers do not exist when U_ext is formed.
+        5p).  With "lcp" it is refused: the multipliers do not exist when U_ext is formed.  Its optional key
+        in_solve=True (contact_model="lcp" only, kind "rpyc" or "rpy", not with contact_forces; default False: the step
+        above, unchanged) solves the LCP against M_h = m_t + hydro_kind (+ the periphery's correction) at the current
+        positions instead of the dry m_t, so U = U_ext + M_h D lambda and every bead feels every contact (DESIGN.md 5u);
+        body_contact_force() stays D lambda, warm_start works as before, reorder_bodies is refused.
         backbone_collision = dict(kind="hertz" | "wca", radius=, skin=, youngs_modulus=1000.0, poisson_ratio=0.3,
         epsilon=1.0, sigma=1.0, cutoff=1.12246204831, segments=None, end_correction=None): frictionless contacts between
         the backbone segments (ops.SegmentContacts), a force term after the crosslinker KMC and the active
@@ -272,11 +284,20 @@ class ContactStepper:
             if hydrodynamics.get("contact_forces", False) and contact_model != "hertz":
                 raise ValueError("hydrodynamics contact_forces needs contact_model='hertz': the LCP's multipliers do not "
                                  "exist when U_ext is formed")
+            if hydrodynamics.get("in_solve", False):
+                # (with contact_forces=True as well: refused above under "lcp", here under any other model)
+                if contact_model != "lcp":
+                    raise ValueError("hydrodynamics in_solve needs contact_model='lcp': it is the mobility of the LCP")
+                if hydro_spec[0] == "stokes":
+                    raise ValueError("hydrodynamics in_solve needs kind 'rpyc' or 'rpy': the Stokeslet is not positive "
+                                     "semi-definite at bead separations")
             if hydrodynamics.get("periphery") is not None:
                 hydro_spec += (ops.check_hydro_periphery(hydrodynamics["periphery"]),)
         # the Hertz force as the first term of the chain step's force field (HP1.cpp:4737-4741) instead of a body sweep
         # after U_ext
         self.hydro_contact_forces = hydrodynamics is not None and bool(hydrodynamics.get("contact_forces", False))
+        # the LCP solved against the hydrodynamic mobility (NgpHP1.cpp:1487-1645; mundy_hip_hydro_solve.h), not the dry one
+        self.hydro_in_solve = hydrodynamics is not None and bool(hydrodynamics.get("in_solve", False))
         self.hertz_friction = None
         if hertz_friction is not None:  # (checked before anything reaches the device)
             self._check_hertz_friction(contact_model, kind, rod_kinematics, growth_rate, springs, brownian_kt,
@@ -1062,7 +1083,11 @@ class ContactStepper:
         contact sweeps hits nearby lines.  curve = "morton" (lattice of edge cell_size anchored at lo) or "hilbert"
         (the hilbert_3d order of a (2^level)^3 lattice over [lo, hi]; both give the same sweep times).  Every per-body
         tensor is permuted in place, the caller's center and radius and, in the Hertz model where they are tensors, its
-        youngs_modulus and poisson_ratio among them.  Returns the permutation (new position k holds old body perm[k])."""
+        youngs_modulus and poisson_ratio among them.  Returns the permutation (new position k holds old body perm[k]).
+        Refused with hydrodynamics in_solve: a renumbering changes the association of the solve's all-pairs sums."""
+        if self.hydro_in_solve:
+            raise ValueError("reorder_bodies is not supported with hydrodynamics in_solve: the all-pairs sums inside the "
+                             "solve are taken in the rows' order")
         if lo is None:
             lo = self.center.min(dim=0).values.tolist() if self.box is None else [0.0, 0.0, 0.0]
         if curve == "hilbert":
@@ -1220,9 +1245,17 @@ class ContactStepper:
             q = self.op.constraint_rate(self.u_ext)
             ops.axpby(1.0, c["sep"], self.dt, q)
             self.q = q
-        x, g, res = ops.solve_lcp(self.op, q, self.lam, self.cfg)
+        x, g, res = ops.solve_lcp(self.op, q, self.lam, self.cfg, mobility=self._hydro_mobility())
         self.lam, self.grad = x, g
         return res
+
+    def _hydro_mobility(self):
+        """hydrodynamics in_solve: M_h at the current positions (the rows then hold M_h D lambda); otherwise None"""
+        if not self.hydro_in_solve:
+            return None
+        radius = self.radius if self.hydro_radius is None else self.hydro_radius
+        return ops.HydroMobility(self.hydro["kind"], self.viscosity, self.center, radius, periphery=self.hydro_periphery,
+                                 skip_same_index=self.hydro.get("skip_same_index", True), workspace=self._hydro_ws)
 
     def _contact_radius(self):
         """the radius the Hertz model takes: the sphere / rod radius, not the bounding radius"""
