@@ -536,13 +536,14 @@ def _unshared_pairs(ends):
     return i[~share], j[~share]
 
 
-def grow_segments(seed, kind):
+def grow_segments(seed, kind, branch=True):
     """chains grown bead by bead in a box: a new segment is kept only if, against every earlier segment that shares no
     node with it, it stays min_dist apart (Hertz: MIN_DIST; WCA: 0.8 sigma) and MIN_SIN from parallel whenever it is
     within reach, and 2 MARGIN from the law's branch boundary.  Step lengths 0.85 .. 1.25 (on both sides of the WCA
     cutoff and of 2 r), per-segment radii 0.4 .. 0.55.  Five chains of four segments; a sixth of two starts from an
     inner node of the first (a node with three segments); then twelve single segments, each laid across an existing
     one so that both closest points are interior (second neighbours along a chain supply the end - end pairs).
+    branch=False leaves the sixth chain out: every chain is then a run of consecutive nodes (a filament).
     -> (grown, x [n, 3], ends int32 [m, 2], radius [m])"""
     rng = np.random.default_rng(seed)
     x, ends, radius = [], [], []
@@ -625,7 +626,7 @@ def grow_segments(seed, kind):
             return True
         return False
 
-    good = all(chain(None, 4, max_dot) for _ in range(5)) and chain(2, 2, 0.2)
+    good = all(chain(None, 4, max_dot) for _ in range(5)) and (not branch or chain(2, 2, 0.2))
     good = good and all(crossing() for _ in range(12))
     return good, np.array(x), np.array(ends, dtype=np.int32), np.array(radius)
 
@@ -860,7 +861,8 @@ def mp_energies(case):
 # ---- the tolerances (measured and asserted by tests/test_potentials_host.py, whose docstring holds the table) --------------------------
 TOLERANCE_K = {"springs": 16.0, "crosslinkers": 16.0, "active": 4.0, "sphere wall": 64.0, "ellipsoid wall": 512.0,
                "ellipsoid wall, fast": 8.0, "sphere Hertz": 256.0, "segment Hertz": 32.0, "segment WCA": 256.0,
-               "rpyc": 16.0}
+               "rpyc": 16.0, "filament force": 64.0, "filament force, wave": 128.0, "filament torque": 128.0,
+               "filament Hertz": 16.0}
 FAST_RSQRT_DELTA = 1.752e-3
 
 

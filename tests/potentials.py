@@ -18,6 +18,8 @@ imported from a *_model.py, from the oracle or from the package.
     segment - segment Hertz                                 the same, delta = r_i + r_j - dist(seg_i, seg_j)
     segment - segment WCA                                   4 eps [(sigma / d)^12 - (sigma / d)^6] + const,  d < cutoff
     end-segment correction                                  the same two laws at d = L of the segment (Hertz: delta = 2 r - L)
+    rod element (bend and twist), rod edge (stretch)        see "the discrete rod" below: frames carried by parallel transport
+    filament segment - segment Hertz                        the segment Hertz law with the radii of the segments' left nodes
 
     1 / E* = (1 - nu_i^2) / E_i + (1 - nu_j^2) / E_j        1 / R* = 1 / r_i + 1 / r_j          (contact mechanics)
 
@@ -271,6 +273,112 @@ def to_float(F):
     return np.array([[float(v) for v in row] for row in F], dtype=np.float64).reshape(len(F), -1)
 
 
+# ---- the discrete rod: frames, curvature, energy ------------------------------------------------------------------------------
+# An edge carries a frame as a unit quaternion q = (w, x, y, z), body -> lab.  Between two evaluations the frame follows the
+# edge by parallel transport in time: with T and D the edge's tangent and frame at the last evaluation (held fixed), t(x)
+# its tangent now and theta its twist,
+#       q(x, theta) = PT(T -> t(x)) [cos theta/2, sin theta/2 T] D
+# PT(T -> t) = [w, (T x t) / (2 w)], w = sqrt((1 + T.t) / 2), is the rotation about T x t that takes T to t.  The
+# curvature of an interior node, in the frame of its left edge, is twice the vector part of conj(q_left) q_right (for a
+# rotation by the angle phi about the body-frame axis n: 2 sin(phi / 2) n), and the energy of the element around a node
+# of radius r
+#       (1 / (2 l0)) dk^T diag(E I, E I, 2 G I) dk,    dk = kappa - rest,  I = pi r^4 / 4,  G = E / (2 (1 + nu))
+# An edge of length l stores (1/2) (E pi r^2 / l0) (l - l0)^2 with r the radius of its right node.
+def cross(a, b):
+    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+
+def qmul(p, q):
+    return [p[0] * q[0] - p[1] * q[1] - p[2] * q[2] - p[3] * q[3],
+            p[0] * q[1] + p[1] * q[0] + p[2] * q[3] - p[3] * q[2],
+            p[0] * q[2] - p[1] * q[3] + p[2] * q[0] + p[3] * q[1],
+            p[0] * q[3] + p[1] * q[2] - p[2] * q[1] + p[3] * q[0]]
+
+
+def qconj(q):
+    return [q[0], -q[1], -q[2], -q[3]]
+
+
+def unit_tangent(x0, x1):
+    d = sub(x1, x0)
+    L = norm(d)
+    return [d[0] / L, d[1] / L, d[2] / L]
+
+
+def transport(T, t):
+    """the quaternion of the parallel transport of the unit vector T onto the unit vector t (T.t > -1)"""
+    w = mp.sqrt((1 + dot(T, t)) / 2)
+    c = cross(T, t)
+    return [w, c[0] / (2 * w), c[1] / (2 * w), c[2] / (2 * w)]
+
+
+def twist_rotation(theta, T):
+    """the rotation by theta about the unit vector T"""
+    s = mp.sin(theta / 2)
+    return [mp.cos(theta / 2), s * T[0], s * T[1], s * T[2]]
+
+
+def edge_frame(T, t, theta, D):
+    return qmul(qmul(transport(T, t), twist_rotation(theta, T)), D)
+
+
+def curvature(q_left, q_right):
+    g = qmul(qconj(q_left), q_right)
+    return [2 * g[1], 2 * g[2], 2 * g[3]]
+
+
+def wave_rest_curvature(rest, amplitude, wave_number, s, frequency, time, phase):
+    """the travelling wave replaces component 0 of the rest curvature of the node at arclength s"""
+    return [amplitude * mp.sin(wave_number * s + frequency * time + phase), rest[1], rest[2]]
+
+
+def rod_bend_twist(kappa, rest, r, E, nu, l0):
+    I = mp.pi * r ** 4 / 4
+    G = E / (2 * (1 + nu))
+    dk = sub(kappa, rest)
+    return (E * I * (dk[0] * dk[0] + dk[1] * dk[1]) + 2 * G * I * dk[2] * dk[2]) / (2 * l0)
+
+
+def rod_stretch(L, r_right, E, l0):
+    return E * mp.pi * r_right * r_right / l0 * (L - l0) ** 2 / 2
+
+
+def rod_element(p, theta, T, D, rest, r, E, nu, l0):
+    """the energy of the element around p[1]: p = its three nodes, theta, T, D = (left edge, right edge)"""
+    ql = edge_frame(T[0], unit_tangent(p[0], p[1]), theta[0], D[0])
+    qr = edge_frame(T[1], unit_tangent(p[1], p[2]), theta[1], D[1])
+    return rod_bend_twist(curvature(ql, qr), rest, r, E, nu, l0)
+
+
+def rod_edge(p, r_right, E, l0):
+    return rod_stretch(norm(sub(p[1], p[0])), r_right, E, l0)
+
+
+def rod_gradient(energy, pos, theta, h=None):
+    """energy(pos, theta) -> U, pos a list of mpf triples and theta a list of mpf: -(dU/dpos [len(pos)] triples, dU/dtheta
+    [len(theta)]) by central differences, as gradient() takes them"""
+    h = mp.mpf(10) ** -15 if h is None else h
+    gx, gt = [], []
+    for b in range(len(pos)):
+        g = []
+        for k in range(3):
+            hi, lo = [list(p) for p in pos], [list(p) for p in pos]
+            hi[b][k], lo[b][k] = hi[b][k] + h, lo[b][k] - h
+            g.append(-(energy(hi, theta) - energy(lo, theta)) / (2 * h))
+        gx.append(g)
+    for b in range(len(theta)):
+        hi, lo = list(theta), list(theta)
+        hi[b], lo[b] = hi[b] + h, lo[b] - h
+        gt.append(-(energy(pos, hi) - energy(pos, lo)) / (2 * h))
+    return gx, gt
+
+
+def filament_pair_hertz(a0, a1, b0, b1, ri, rj, E, nu):
+    """the frictionless Hertz energy of two filament segments of one material: delta = r_i + r_j less the distance of
+    the centrelines; k_n = 4/3 E* of the frictional law is this energy's d^2 U / d delta^2 / sqrt(R* delta)"""
+    return hertz(ri + rj - segment_segment(a0, a1, b0, b1)[0], effective_modulus(E, nu, E, nu), effective_radius(ri, rj))
+
+
 # ---- the mobility ---------------------------------------------------------------------------------------------------------------
 def rpyc_branch(r, a, b):
     return "far" if r > a + b else ("overlap" if r > abs(a - b) else "nested")
@@ -488,3 +596,88 @@ def ld_backbone_energy(x, ends, kind, radius, end_correction, E=1000.0, nu=0.3, 
         else:
             U = U + ld_wca(L, epsilon, sigma, cutoff).sum()
     return U
+
+
+# ---- the discrete rod in longdouble, one row per edge or element ----------------------------------------------------------------
+def ld_cross(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
+
+
+def ld_dot(a, b):
+    return a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1] + a[..., 2] * b[..., 2]
+
+
+def ld_qmul(p, q):
+    return np.stack([p[..., 0] * q[..., 0] - p[..., 1] * q[..., 1] - p[..., 2] * q[..., 2] - p[..., 3] * q[..., 3],
+                     p[..., 0] * q[..., 1] + p[..., 1] * q[..., 0] + p[..., 2] * q[..., 3] - p[..., 3] * q[..., 2],
+                     p[..., 0] * q[..., 2] - p[..., 1] * q[..., 3] + p[..., 2] * q[..., 0] + p[..., 3] * q[..., 1],
+                     p[..., 0] * q[..., 3] + p[..., 1] * q[..., 2] - p[..., 2] * q[..., 1] + p[..., 3] * q[..., 0]], axis=-1)
+
+
+def ld_qconj(q):
+    return q * np.array([1, -1, -1, -1], dtype=LD)
+
+
+def ld_unit_tangent(x0, x1):
+    d = _ld(x1) - _ld(x0)
+    return d / ld_norm(d)[..., None]
+
+
+def ld_transport(T, t):
+    T, t = _ld(T), _ld(t)
+    w = np.sqrt((LD(1) + ld_dot(T, t)) / LD(2))
+    return np.concatenate([w[..., None], ld_cross(T, t) / (LD(2) * w)[..., None]], axis=-1)
+
+
+def ld_twist_rotation(theta, T):
+    half = _ld(theta) / LD(2)
+    return np.concatenate([np.cos(half)[..., None], np.sin(half)[..., None] * _ld(T)], axis=-1)
+
+
+def ld_edge_frame(T, t, theta, D):
+    return ld_qmul(ld_qmul(ld_transport(T, t), ld_twist_rotation(theta, T)), _ld(D))
+
+
+def ld_curvature(q_left, q_right):
+    return LD(2) * ld_qmul(ld_qconj(_ld(q_left)), _ld(q_right))[..., 1:]
+
+
+def ld_wave_rest_curvature(rest, amplitude, wave_number, s, frequency, time, phase):
+    out = _ld(rest).copy()
+    out[..., 0] = _ld(amplitude) * np.sin(_ld(wave_number) * _ld(s) + _ld(frequency) * _ld(time) + _ld(phase))
+    return out
+
+
+def ld_rod_bend_twist(kappa, rest, r, E, nu, l0):
+    r, E, nu, l0 = _ld(r), _ld(E), _ld(nu), _ld(l0)
+    I = np.arctan(LD(1)) * r ** 4   # pi / 4 = atan(1), in longdouble
+    G = E / (LD(2) * (LD(1) + nu))
+    dk = _ld(kappa) - _ld(rest)
+    return (E * I * (dk[..., 0] * dk[..., 0] + dk[..., 1] * dk[..., 1]) + LD(2) * G * I * dk[..., 2] * dk[..., 2]) / (LD(2) * l0)
+
+
+def ld_rod_stretch(L, r_right, E, l0):
+    r, l0 = _ld(r_right), _ld(l0)
+    return _ld(E) * (LD(4) * np.arctan(LD(1))) * r * r / l0 * (_ld(L) - l0) ** 2 / LD(2)
+
+
+def ld_filament_pair_hertz(a0, a1, b0, b1, ri, rj, E, nu):
+    d = ld_segment_segment(a0, a1, b0, b1)
+    return ld_hertz(_ld(ri) + _ld(rj) - d, ld_effective_modulus(E, nu, E, nu), ld_effective_radius(ri, rj))
+
+
+def ld_rod_energy(node_ptr, x, q, radius, rest, E, nu, l0):
+    """the energy of filaments from their centres x [n, 3] and edge frames q [n, 4] (row e: the edge e -> e + 1; the row
+    of a filament's last node is not read) -> (per interior node [n], per edge [n]), zero in the rows that have neither"""
+    node_ptr = np.asarray(node_ptr)
+    n = int(node_ptr[-1])
+    x, q = _ld(x), _ld(q)
+    has_r, has_l = np.ones(n, bool), np.ones(n, bool)
+    has_r[node_ptr[1:] - 1], has_l[node_ptr[:-1]] = False, False
+    inner = np.flatnonzero(has_r & has_l)
+    edge = np.flatnonzero(has_r)
+    bend, stretch = np.zeros(n, dtype=LD), np.zeros(n, dtype=LD)
+    bend[inner] = ld_rod_bend_twist(ld_curvature(q[inner - 1], q[inner]), _ld(rest)[inner], _ld(radius)[inner], E, nu, l0)
+    stretch[edge] = ld_rod_stretch(ld_norm(x[edge + 1] - x[edge]), _ld(radius)[edge + 1], E, l0)
+    return bend, stretch

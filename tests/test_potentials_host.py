@@ -21,18 +21,29 @@ that the model stays under K / 4.
     segment Hertz                    5.94                  32
     segment WCA                     35.7                  256
     rpyc (per block)                 2.88                  16
+    filament force                  13.9                   64
+    filament force, wave            30.9                  128
+    filament torque                 26.6                  128
+    filament Hertz                   2.63                  16
 
     delta = 1.752e-3 (measured 1.75118e-3): the largest relative error of the one-step fast inverse square root over
     the r^2 of far_cloud(), against 1 / sqrt in longdouble
 
 (The walls' and the sphere Hertz deviations are those of the overlap, a difference of O(1) numbers, over overlaps down
-to 0.02 and 0.005.)"""
+to 0.02 and 0.005.)
+
+The filament rows are tests/filament_cases.py's: filament_model.py against the gradient of the discrete rod energy, plus
+the stray term R where the binormal acts (the "moved" states), over every state in its own frame and run from a rotated
+and translated layout; the torque row in units of eps S_tau.  The wave has a row of its own: its phase k s + omega t +
+phi is rounded at |phase| up to 190 on the 259-node filament, which costs A eps |phase|.  filament Hertz is
+filament_contact_model.py without friction against the pair Hertz energy."""
 import math
 
 import mpmath as mp
 import numpy as np
 import pytest
 
+import filament_cases as fc
 import gradient_cases as gc
 import potentials as P
 
@@ -66,6 +77,159 @@ def test_mpmath_and_longdouble_forms_agree(name):
 def test_inputs_meet_their_conditions():
     for case in gc.cases().values():
         case.check()
+    for name in fc.NAMES:
+        fc.state(name).check()
+        fc.moved_exact(name)[1].check()
+    fc.contact_case().check()
+
+
+def _ld_minus_mp(v, u):
+    """the longdouble v less the mpf u, exactly"""
+    return mp.mpf(float(v)) + mp.mpf(float(v - np.longdouble(float(v)))) - u
+
+
+@pytest.mark.parametrize("name", fc.NAMES)
+def test_filament_forms_agree(name):
+    """every element's and every edge's energy on the inputs of the device tests, to 1e-15 of itself"""
+    st = fc.state(name)
+    el, ed = fc.ld_energies(st)
+    worst, count = 0.0, 0
+    with P.hp():
+        mel, med = fc.mp_energies(st, st.nodes)
+        for b, u_el, u_ed in zip(st.nodes, mel, med):
+            for u, v in ((u_el, el[b]), (u_ed, ed[b])):
+                if u is None:
+                    assert v == 0
+                    continue
+                assert u > 0
+                worst, count = max(worst, float(abs(_ld_minus_mp(v, u)) / u)), count + 1
+    print("%s: worst relative difference %.3g over %d terms" % (name, worst, count))
+    assert worst <= 1e-15 and count >= 20
+
+
+def test_filament_contact_forms_agree():
+    case = fc.contact_case()
+    ld = case.ld_energies()
+    with P.hp():
+        X = [P.vec(p) for p in case.x]
+        exact = [t.energy([X[b] for b in t.bodies]) for t in case.terms()]
+        worst = 0.0
+        for u, v in zip(exact, ld):
+            if u == 0:
+                assert v == 0
+            else:
+                worst = max(worst, float(abs(_ld_minus_mp(v, u)) / u))
+    print("worst relative difference %.3g" % worst)
+    assert worst <= 1e-15 and sum(u != 0 for u in exact) >= 16 and sum(u == 0 for u in exact) >= 8
+
+
+# ---- the discrete rod by hand -----------------------------------------------------------------------------------------------
+def _frames_both(T, x, theta, D):
+    """the frames of the edges of the polyline x from old tangents T, twists and old frames, in both forms -> ([edges, 4]
+    float64 from mpmath, [edges, 4] longdouble)"""
+    x = np.asarray(x, dtype=np.float64)
+    with P.hp():
+        q = [P.edge_frame(P.vec(T[e]), P.unit_tangent(P.vec(x[e]), P.vec(x[e + 1])), gc.M(theta[e]),
+                          [gc.M(v) for v in D[e]]) for e in range(len(x) - 1)]
+        q = np.array([[float(v) for v in row] for row in q])
+    ql = P.ld_edge_frame(np.asarray(T), P.ld_unit_tangent(x[:-1], x[1:]), np.asarray(theta), np.asarray(D))
+    assert np.abs(np.asarray(ql, dtype=np.float64) - q).max() <= 2e-16
+    return q, ql
+
+
+def _curvature_both(q, ql):
+    with P.hp():
+        k = np.array([[float(v) for v in P.curvature([gc.M(v) for v in q[i]], [gc.M(v) for v in q[i + 1]])]
+                      for i in range(len(q) - 1)])
+    kl = np.asarray(P.ld_curvature(ql[:-1], ql[1:]), dtype=np.float64)
+    assert np.abs(kl - k).max() <= 4e-16
+    return k
+
+
+IDENTITY4 = (1.0, 0.0, 0.0, 0.0)
+
+
+def test_rod_by_hand():
+    z = (0.0, 0.0, 1.0)
+    n = 6
+    straight = np.stack([np.zeros(n), np.zeros(n), np.arange(n) * 1.0], axis=1)
+    # a straight rod at rest, dyadic inputs: every frame the identity, E = 0 exactly, in both forms
+    q, ql = _frames_both([z] * (n - 1), straight, [0.0] * (n - 1), [IDENTITY4] * (n - 1))
+    assert (q == np.array(IDENTITY4)).all() and (ql == np.array(IDENTITY4, dtype=P.LD)).all()
+    ptr = np.array([0, n])
+    qn = np.concatenate([ql, [IDENTITY4]])
+    bend, stretch = P.ld_rod_energy(ptr, straight, qn, np.full(n, 0.75), np.zeros((n, 3)), 10.0, 0.3, 1.0)
+    assert (bend == 0).all() and (stretch == 0).all()
+    with P.hp():
+        X = [P.vec(p) for p in straight]
+        for i in range(1, n - 1):
+            assert P.rod_element(X[i - 1:i + 2], [mp.mpf(0)] * 2, [P.vec(z)] * 2, [P.vec(IDENTITY4)] * 2, [mp.mpf(0)] * 3,
+                                 gc.M(0.75), gc.M(10.0), gc.M(0.3), gc.M(1.0)) == 0
+            assert P.rod_edge(X[i:i + 2], gc.M(0.75), gc.M(10.0), gc.M(1.0)) == 0
+    # a planar polygonal arc, turning angle phi per node, reached from the straight rod by transport alone: the curvature
+    # is 2 sin(phi / 2) about the normal of the plane, here -x (z turns towards +y)
+    phi = 0.3
+    a = np.arange(n - 1) * phi
+    arc = np.concatenate([np.zeros((1, 3)), np.cumsum(np.stack([np.zeros(n - 1), np.sin(a), np.cos(a)], axis=1) * 1.1, axis=0)])
+    q, ql = _frames_both([z] * (n - 1), arc, [0.0] * (n - 1), [IDENTITY4] * (n - 1))
+    k = _curvature_both(q, ql)
+    assert np.abs(k[1:] - np.array([-2.0 * math.sin(phi / 2.0), 0.0, 0.0])).max() <= 1e-15
+    assert np.abs(k[0] - np.array([-2.0 * math.sin(phi / 2.0), 0.0, 0.0])).max() <= 1e-15
+    # its element energy by hand: (1 / (2 l0)) E (pi r^4 / 4) (2 sin(phi / 2) - rest_0)^2
+    r, E, l0, rest0 = 0.75, 10.0, 0.8, -0.1
+    want = 0.5 / l0 * E * (math.pi * r ** 4 / 4.0) * (-2.0 * math.sin(phi / 2.0) - rest0) ** 2
+    qn = np.concatenate([ql, [IDENTITY4]])
+    bend, _ = P.ld_rod_energy(ptr, arc, qn, np.full(n, r), np.tile([rest0, 0.0, 0.0], (n, 1)), E, 0.3, l0)
+    assert np.abs(np.asarray(bend[1:-1], dtype=np.float64) - want).max() <= 1e-14 * want and bend[0] == 0 and bend[-1] == 0
+    # a straight rod with the twist difference dtheta between neighbouring edges: kappa_3 = 2 sin(dtheta / 2)
+    dth = 0.4
+    q, ql = _frames_both([z] * (n - 1), straight, np.arange(n - 1) * dth, [IDENTITY4] * (n - 1))
+    k = _curvature_both(q, ql)
+    assert np.abs(k - np.array([0.0, 0.0, 2.0 * math.sin(dth / 2.0)])).max() <= 1e-15
+    # ... stored with 2 G I = E I / (1 + nu): the twist energy by hand
+    nu = 0.25
+    want = 0.5 / l0 * (E / (1.0 + nu)) * (math.pi * r ** 4 / 4.0) * (2.0 * math.sin(dth / 2.0)) ** 2
+    qn = np.concatenate([ql, [IDENTITY4]])
+    bend, _ = P.ld_rod_energy(ptr, straight, qn, np.full(n, r), np.zeros((n, 3)), E, nu, l0)
+    assert np.abs(np.asarray(bend[1:-1], dtype=np.float64) - want).max() <= 1e-14 * want
+    # one edge stretched by 0.5 (the third), the right node's radius 0.5 among radii of 1: 1/2 (E pi r^2 / l0) 0.25
+    long = straight.copy()
+    long[3:, 2] += 0.5
+    radius = np.ones(n)
+    radius[3] = 0.5
+    _, stretch = P.ld_rod_energy(ptr, long, np.tile(IDENTITY4, (n, 1)), radius, np.zeros((n, 3)), 8.0, 0.3, 1.0)
+    want = 0.5 * 8.0 * math.pi * 0.25 * 0.25
+    assert abs(float(stretch[2]) - want) <= 1e-15 * want and stretch[2] == stretch.sum()
+    with P.hp():
+        assert abs(P.rod_edge([P.vec(long[2]), P.vec(long[3])], gc.M(0.5), gc.M(8.0), gc.M(1.0)) - mp.pi / 4) <= mp.mpf(10) ** -45
+
+
+def test_wave_rest_curvature_by_hand():
+    rest = np.array([[0.05, -0.02, 0.07]])
+    with P.hp():
+        got = P.wave_rest_curvature(P.vec(rest[0]), gc.M(0.2), gc.M(0.5), gc.M(3.0), gc.M(2.0), gc.M(0.25), gc.M(-2.0))
+        assert got[0] == 0 and got[1:] == P.vec(rest[0])[1:]   # A sin(1.5 + 0.5 - 2)
+        got = P.wave_rest_curvature(P.vec(rest[0]), gc.M(0.2), gc.M(0.5), gc.M(3.0), gc.M(2.0), gc.M(0.25), gc.M(0.0))
+        assert abs(got[0] - mp.mpf("0.2") * mp.sin(2)) <= mp.mpf(10) ** -16
+    ld = P.ld_wave_rest_curvature(rest, 0.2, 0.5, 3.0, 2.0, 0.25, 0.0)
+    assert abs(float(ld[0, 0]) - 0.2 * math.sin(2.0)) <= 1e-16 and (ld[0, 1:] == rest[0, 1:]).all()
+
+
+def test_the_stray_term_is_the_whole_departure_from_the_gradient():
+    """On the "moved" states filament_model.py is -grad E + R within K (test_calibration); without R it is not, by the
+    size of R, which is at least 100 K eps S_F on some node: the device test cannot pass with R dropped."""
+    K = gc.TOLERANCE_K["filament force"]
+    for name in fc.NAMES:
+        if fc.split(name)[0] != "moved":
+            continue
+        st, ex = fc.state(name), fc.exact_of(name)
+        Fm, _ = st.model_rows()
+        with_r = fc.deviation(Fm, ex["F"], ex["S_F"])
+        without = fc.deviation(Fm, ex["F"] - ex["R"], ex["S_F"])
+        size = np.abs(ex["R"]).max(axis=1) / (EPS * ex["S_F"])
+        print("%s: max |R| = %.3g = %.3g eps S_F; model - exact: %.3g with R, %.3g without" % (
+            name, np.abs(ex["R"]).max(), size.max(), with_r.max(), without.max()))
+        assert with_r.max() <= K / 4.0 and size.max() >= 100.0 * K and without.max() >= 100.0 * K
 
 
 # ---- geometry -------------------------------------------------------------------------------------------------------------------
@@ -149,6 +313,7 @@ def test_calibration():
         worst[case.group] = max(worst.get(case.group, 0.0), float(dev.max()), float(dev2.max()))
         print("%-34s worst deviation of the model %8.3g eps S_b, rotated %8.3g" % (name, dev.max(), dev2.max()))
     worst["rpyc"] = _rpyc_model_deviation()
+    worst.update(_filament_model_deviation())
     print("\n    %-26s %-28s %s   (4 x worst, rounded up)" % ("term", "worst deviation [eps S_b]", "K"))
     for group, k in gc.TOLERANCE_K.items():
         print("    %-26s %-28.3g %-5g %g" % (group, worst[group], k, _pow2_at_least(4.0 * worst[group])))
@@ -156,6 +321,29 @@ def test_calibration():
     for group, k in gc.TOLERANCE_K.items():
         assert worst[group] <= k / 4.0, (group, worst[group], k)
         assert k == 2.0 ** round(math.log2(k))
+
+
+def _filament_model_deviation():
+    """filament_model.py against -grad E (+ R) and -dE/dtheta, every state in its own frame and run from the rotated
+    layout; filament_contact_model.py without friction against the pair Hertz energy"""
+    worst = {"filament force": 0.0, "filament force, wave": 0.0, "filament torque": 0.0}
+    for name in fc.NAMES:
+        group = "filament force, wave" if fc.split(name)[0] == "wave" else "filament force"
+        for tag, st, ex in (("", fc.state(name), fc.exact_of(name)), (", rotated",) + fc.moved_exact(name)[1:]):
+            Fm, Tm = st.model_rows()
+            dF, dT = fc.deviation(Fm, ex["F"], ex["S_F"]), fc.deviation(Tm, ex["tau"], ex["S_tau"])
+            assert np.isfinite(dF).all() and np.isfinite(dT).all(), name
+            print("%-34s worst deviation of the model: force %8.3g eps S_F, torque %8.3g eps S_tau" % (
+                name + tag, dF.max(), dT.max()))
+            worst[group] = max(worst[group], float(dF.max()))
+            worst["filament torque"] = max(worst["filament torque"], float(dT.max()))
+    case = fc.contact_case()
+    F, S = fc.contact_exact()
+    d = gc.deviation(case.model(), F, S)
+    assert np.isfinite(d).all()
+    print("%-34s worst deviation of the model %8.3g eps S_b" % ("filament contacts", d.max()))
+    worst["filament Hertz"] = float(d.max())
+    return worst
 
 
 def _rpyc_model_deviation():
