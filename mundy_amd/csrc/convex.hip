@@ -417,6 +417,10 @@ struct SolverState {  // device resident
   unsigned iter;   // reported iteration count
   unsigned flips;  // completed non-terminal iterations = parity of the x/x_tmp ping-pong
   int converged, done, converged_at_init;
+  // mobilities of the solve's body range (k_mob_uniform, at the start of a fused solve): non-zero = the array holds
+  // more than one bit pattern; else its one value.  They reach the host with the first poll's copy of this record.
+  int mt_mixed, mr_mixed;
+  double mt_one, mr_one;
 };
 
 enum XMode { X_APPLY = 0, X_INIT = 1, X_SOLVE = 2 };
@@ -476,6 +480,19 @@ struct OpView {
   const double* arec;
   size_t arec_stride;
   const unsigned long long* snap_mask;  // [N] the masks the snapshot was taken from
+  // Clean-wave bytes: one byte per 32 bodies counted from body_first -- the bodies of one wave of the two-lane sweep.
+  // 0 promises that for every body of the group mask & ~snap_mask == 0 and the list has at most 64 entries, i.e. that
+  // the flat stream over the compact lists is ALL the sweep has to walk: the wave then loads neither the bodies' row
+  // pointers nor their two mask words.  The snapshot writes the bytes ("has a list longer than 64"), whoever sets a
+  // mask bit afterwards (constraint sweep, the tail's wake path) stores 1 to the two bodies' groups -- plain stores,
+  // read by the NEXT launch.  null = every wave is dirty.
+  unsigned char* wave_dirty;
+  // Uniform mobilities (monodisperse systems: every body has the same two numbers).  Bit 0 / bit 1 set: mt / mr is
+  // bitwise mt_one / mr_one for every body of the range -- found on the device at the start of the solve, set by the
+  // host from the first poll on and cleared when the solve ends; the body sweep then takes the value from its
+  // arguments instead of loading a word per body (the same double: the same products).
+  int mob_uniform;
+  double mt_one, mr_one;
   // Tiered solves (see "Cold tier" below): the body rows ping-pong between vel (even parity) and vel_alt like the
   // iterate does, so that the rows of the last TWO iterates exist when the solve ends; drift [N] accumulates, per body,
   // an upper bound of how far any of its contact-point velocities has moved (times dt) since the bookkeeping began.
@@ -612,6 +629,14 @@ __global__ void __launch_bounds__(kBlock, MHIP_KBODY_WAVES)
       E1 = op.aptr[op.body_first + tb1];
     }
   }
+  // two lanes per body: a wave's 32 bodies share one clean-wave byte (OpView::wave_dirty), a tile's four waves one
+  // aligned word of them -- one more scalar load beside E0 / E1 and the solver state, no round trip of its own
+  constexpr bool kCleanWaves = FLAT && G == 2;
+  static_assert(kBlock == 256, "a tile's clean-wave bytes are read as one 32-bit word");
+  unsigned dirty_word = ~0u;
+  if constexpr (kCleanWaves) {
+    if (op.aptr != nullptr && op.wave_dirty != nullptr) dirty_word = reinterpret_cast<const unsigned*>(op.wave_dirty)[tile];
+  }
   const double* xt = X0;
   const double* gt = G0;
   double step = 0.0;
@@ -631,7 +656,29 @@ __global__ void __launch_bounds__(kBlock, MHIP_KBODY_WAVES)
   constexpr int HW = (KIN == KIN_RIGID) ? 6 : (KIN == KIN_ROD ? 4 : 3);
   // force and torque sums in double-double: their rounded values do not depend on the order of the list, on G or on U
   DD3 Fdd{{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}}, Tdd{{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
-  const int32_t beg = op.inc_ptr[b], end = op.inc_ptr[b + 1];
+  // activity masks apply when Proj(0 - step g) == 0 is guaranteed for g >= 0: LCP space, finite non-negative step
+  const bool masked = PACKED && MODE == X_SOLVE && op.body_mask != nullptr && sp.kind == MHIP_SPACE_LOWER_BOUND &&
+                      sp.lo == 0.0 && step >= 0.0 && step <= 1.7976931348623157e308;
+  // a clean wave of a masked sweep walks the compact lists and nothing else: no row pointers, no mask words (uniform
+  // over the wave: a scalar branch)
+  bool clean = false;
+  if constexpr (kCleanWaves) {
+    const unsigned wave = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)));
+    clean = masked && ((dirty_word >> (8u * wave)) & 0xffu) == 0u;
+  }
+  // (beg, end and the two early mask words are SET ONLY in waves that are not clean and read only there: given a value
+  // on the clean side too, the compiler merged the two by a copy of the loaded word -- and waited for it on the spot,
+  // a memory round trip in front of every other load of a dirty wave)
+  // INVARIANT: no member of `own` may be read where `clean` is true (enforced by control flow alone: every read below
+  // sits under `!clean`, or under `!masked`, which implies it)
+  struct {
+    int32_t beg, end;
+    unsigned long long snap_early, mask_early;
+  } own;
+  if (!clean) {
+    own.beg = op.inc_ptr[b];
+    own.end = op.inc_ptr[b + 1];
+  }
   // the body's own constants, needed only after the sums: fetched now, by the lane that will use them, so that they are
   // not one more dependent memory level at the end of the chain
   double mt = 0.0, mr = 0.0;
@@ -653,27 +700,30 @@ __global__ void __launch_bounds__(kBlock, MHIP_KBODY_WAVES)
   constexpr bool kEarlyTail = FLAT && FLATP >= MHIP_KBODY_EARLY_FROM && track;
   constexpr bool kEarlySnap = FLAT && FLATP >= MHIP_KBODY_EARLY_FROM;
   double drift_old = 0.0, fire_thr = 0.0;
-  unsigned long long snap_early = 0ull;
-  if (kEarlySnap) {
+  if (kEarlySnap && !clean) {
     // (an UNCONDITIONAL load from a pointer chosen on the scalar side: inside a branch the compiler complemented the
     // word on the spot, i.e. waited for it -- a full memory round trip in front of everything else.  Without a
-    // snapshot the word read is never used; the body rows are always there to be read.)
+    // snapshot the word read is never used; the body rows are always there to be read.  The clean-wave branch around
+    // it is a scalar one and holds nothing but the loads.)
     const unsigned long long* src = (op.aptr != nullptr && op.body_mask != nullptr)
                                         ? op.snap_mask
                                         : reinterpret_cast<const unsigned long long*>(op.vel);
-    snap_early = src[b];
+    own.snap_early = src[b];
   }
-  unsigned long long mask_early = 0ull;  // (the body's activity mask: used after the flat stream, asked for now)
-  if (kEarlySnap) {
+  // (the body's activity mask: used after the flat stream, asked for now)
+  if (kEarlySnap && !clean) {
     const unsigned long long* src = (op.body_mask != nullptr) ? op.body_mask
                                                               : reinterpret_cast<const unsigned long long*>(op.vel);
-    mask_early = src[b];
+    own.mask_early = src[b];
   }
   // tracked sweeps: the row of the previous iterate (the drift is the difference of the two rows), with the early words
   double2 o0 = make_double2(0.0, 0.0), o1 = o0, o2 = o0;
   if (sub == 0) {
-    mt = op.mt[b];
-    if (KIN != KIN_TRANS) mr = op.mr[b];
+    mt = op.mt_one;
+    mr = op.mr_one;
+    if (!(op.mob_uniform & 1)) mt = op.mt[b];
+    if (KIN != KIN_TRANS && !(op.mob_uniform & 2)) mr = op.mr[b];
+    if (KIN == KIN_TRANS) mr = 0.0;
     if (KIN == KIN_ROD) axis = load3(op.axis, b);
     if (kEarlyTail) {
       drift_old = op.drift[b];
@@ -763,11 +813,11 @@ __global__ void __launch_bounds__(kBlock, MHIP_KBODY_WAVES)
       if (KIN == KIN_ROD) dd_add(Tdd, h1[u].y * f);  // S = sum coef f; the torque is u x S, formed once per body below
     }
   };
-  // activity masks apply when Proj(0 - step g) == 0 is guaranteed for g >= 0: LCP space, finite non-negative step
-  const bool masked = PACKED && MODE == X_SOLVE && op.body_mask != nullptr && sp.kind == MHIP_SPACE_LOWER_BOUND &&
-                      sp.lo == 0.0 && step >= 0.0 && step <= 1.7976931348623157e308;
-  int32_t full_from = beg;  // incidence slots from here on are walked unconditionally
-  if (masked) {
+  int32_t full_from = 0, full_end = 0;  // incidence slots [full_from, full_end) are walked unconditionally
+  if (!masked) {  // (never a clean wave)
+    full_from = own.beg;
+    full_end = own.end;
+  } else {
     // (the compact lists first: nothing in there waits for the body's own rows -- masks, row pointers -- loaded above)
     if (op.aptr != nullptr) {  // the snapshot's active entries, streamed; what became active since stays in mm
       const int32_t ab = op.aptr[b], ae = op.aptr[b + 1];
@@ -886,37 +936,49 @@ __global__ void __launch_bounds__(kBlock, MHIP_KBODY_WAVES)
         }
       }
     }
-    const int32_t head = (end - beg < 64) ? end - beg : 64;
-    unsigned long long mm = kEarlySnap ? mask_early : op.body_mask[b];
-    if (head < 64) mm &= (1ull << head) - 1ull;
-    if (op.aptr != nullptr) mm &= ~(kEarlySnap ? snap_early : op.snap_mask[b]);
-    if (FLAT && !has_body) mm = 0ull;
-    int32_t kk[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) kk[u] = -1;
-    int rank = 0, nm = 0;
-    while (mm) {  // the lane takes every G-th set bit (in slot order), U at a time
-      const int bit = __ffsll(static_cast<long long>(mm)) - 1;
-      mm &= mm - 1ull;
-      if ((rank++ & (G - 1)) != sub) continue;
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (nm == u) kk[u] = beg + bit;
-      if (++nm == U) {
-        process(op.inc, op.half, kk, true);
-        nm = 0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) kk[u] = -1;
+    if (!clean) {  // (a clean wave has nothing left to walk: the compact lists were all)
+      const int32_t beg = own.beg, end = own.end;
+      const int32_t head = (end - beg < 64) ? end - beg : 64;
+      unsigned long long mm, snap = 0ull;
+      if (kEarlySnap) {
+        mm = own.mask_early;
+        snap = own.snap_early;
+        asm volatile("" : "+v"(snap));  // (the word is complemented HERE, not -- behind a wait -- where it was asked for)
+      } else {
+        mm = op.body_mask[b];
+        if (op.aptr != nullptr) snap = op.snap_mask[b];
       }
+      if (head < 64) mm &= (1ull << head) - 1ull;
+      if (op.aptr != nullptr) mm &= ~snap;
+      if (FLAT && !has_body) mm = 0ull;
+      int32_t kk[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) kk[u] = -1;
+      int rank = 0, nm = 0;
+      while (mm) {  // the lane takes every G-th set bit (in slot order), U at a time
+        const int bit = __ffsll(static_cast<long long>(mm)) - 1;
+        mm &= mm - 1ull;
+        if ((rank++ & (G - 1)) != sub) continue;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          if (nm == u) kk[u] = beg + bit;
+        if (++nm == U) {
+          process(op.inc, op.half, kk, true);
+          nm = 0;
+#pragma unroll
+          for (int u = 0; u < U; ++u) kk[u] = -1;
+        }
+      }
+      if (nm) process(op.inc, op.half, kk, true);
+      full_from = beg + head;
+      full_end = end;
     }
-    if (nm) process(op.inc, op.half, kk, true);
-    full_from = beg + head;
   }
   if (FLAT && !has_body) return;  // (no barrier follows; whole groups leave together)
-  for (int32_t k0 = full_from + sub; k0 < end; k0 += G * U) {
+  for (int32_t k0 = full_from + sub; k0 < full_end; k0 += G * U) {
     int32_t kk[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) kk[u] = (k0 + u * G < end) ? k0 + u * G : -1;
+    for (int u = 0; u < U; ++u) kk[u] = (k0 + u * G < full_end) ? k0 + u * G : -1;
     process(op.inc, op.half, kk, false);
   }
 #pragma unroll
@@ -1033,6 +1095,13 @@ __device__ inline double contact_dt_sdot(const OpView& op, const double* __restr
   return op.dt * sdot;
 }
 
+// the clean-wave byte of a body's group (OpView::wave_dirty, not null here): an idempotent plain store; ghost bodies,
+// which this rank does not sweep, have none
+__device__ inline void mark_wave_dirty(const OpView& op, int32_t body) {
+  const size_t rel = static_cast<size_t>(body) - op.body_first;  // (wraps past body_count below body_first)
+  if (rel < op.body_count) op.wave_dirty[rel >> 5] = 1;
+}
+
 // Cold tail of a tiered solve ("Cold tier" below).  A sleeping contact (i, j) holds two thresholds, thr[0] for drift[i]
 // and thr[1] for drift[j] (each body gets half the contact's slack); fire_at[b] is the smallest threshold among b's
 // sleeping contacts.  The body sweep lists the bodies whose drift has reached fire_at.  The first `blocks` workgroups
@@ -1072,6 +1141,10 @@ __device__ __forceinline__ void tier_evaluate(const OpView& op, const double* __
       const unsigned pi = op.pos[2 * c], pj = op.pos[2 * c + 1];
       if (pi < 64u) atomicXor(&op.body_mask[ij.x], 1ull << pi);
       if (pj < 64u) atomicXor(&op.body_mask[ij.y], 1ull << pj);
+      if (now && op.wave_dirty != nullptr) {  // a woken contact's force must appear in the very next body sweep
+        if (pi < 64u) mark_wave_dirty(op, ij.x);
+        if (pj < 64u) mark_wave_dirty(op, ij.y);
+      }
     }
   }
   if (op.counted == nullptr || op.counted[c]) {
@@ -1274,6 +1347,11 @@ __global__ void __launch_bounds__(kBlock, (KIN == KIN_RIGID ? 6 : 7))
             const unsigned pi = op.pos[2 * c], pj = op.pos[2 * c + 1];
             if (pi < 64u) atomicXor(&op.body_mask[ij.x], 1ull << pi);
             if (pj < 64u) atomicXor(&op.body_mask[ij.y], 1ull << pj);
+            // a bit was SET: the waves of the two bodies leave the clean path until the next snapshot
+            if (MODE == X_SOLVE && now && op.wave_dirty != nullptr) {
+              if (pi < 64u) mark_wave_dirty(op, ij.x);
+              if (pj < 64u) mark_wave_dirty(op, ij.y);
+            }
           }
         }
       } else {
@@ -1822,6 +1900,25 @@ __global__ void __launch_bounds__(kBlock) k_pos_build(size_t N, const int32_t* _
     }
   }
 }
+// Is mt (and mr, where the kinematics have one) bitwise one value over the bodies [first, first + count)?  Run at the
+// start of a solve, on st->mt_mixed = st->mr_mixed = 0: 16 bytes per body once per solve.  (See OpView::mob_uniform.)
+__global__ void __launch_bounds__(kBlock)
+    k_mob_uniform(size_t first, size_t count, const double* __restrict__ mt, const double* __restrict__ mr,
+                  SolverState* __restrict__ st) {
+  const long long t0 = __double_as_longlong(mt[first]);
+  const long long r0 = mr != nullptr ? __double_as_longlong(mr[first]) : 0ll;
+  bool tm = false, rm = false;
+  for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < count; t += (size_t)gridDim.x * blockDim.x) {
+    tm = tm || __double_as_longlong(mt[first + t]) != t0;
+    if (mr != nullptr) rm = rm || __double_as_longlong(mr[first + t]) != r0;
+  }
+  if (tm) st->mt_mixed = 1;  // (plain stores of the same value)
+  if (rm) st->mr_mixed = 1;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    st->mt_one = __longlong_as_double(t0);
+    st->mr_one = __longlong_as_double(r0);
+  }
+}
 // ---- active lists: snapshot of the flagged entries (see OpView) -----------------------------------------------------------
 __global__ void __launch_bounds__(kBlock)
     k_active_count(size_t first, size_t count, const int32_t* __restrict__ inc_ptr,
@@ -1846,7 +1943,8 @@ __global__ void __launch_bounds__(kBlock)
     k_active_fill_flat(size_t first, size_t count, const int32_t* __restrict__ inc_ptr, const int32_t* __restrict__ inc,
                        const double* __restrict__ half, const unsigned long long* __restrict__ body_mask,
                        const int32_t* __restrict__ aptr_local, int32_t* __restrict__ aptr, int32_t* __restrict__ aent,
-                       double* __restrict__ arec, size_t stride, unsigned long long* __restrict__ snap_mask) {
+                       double* __restrict__ arec, size_t stride, unsigned long long* __restrict__ snap_mask,
+                       unsigned char* __restrict__ wave_dirty) {
   __shared__ unsigned long long tmask[kBlock];
   __shared__ int32_t tbeg[kBlock];
   __shared__ int32_t tptr[kBlock + 1];
@@ -1854,9 +1952,11 @@ __global__ void __launch_bounds__(kBlock)
   if (t0 >= count) return;
   const int nb = static_cast<int>(count - t0 < (size_t)kBlock ? count - t0 : (size_t)kBlock);
   const int tid = static_cast<int>(threadIdx.x);
+  bool long_list = false;
   if (tid < nb) {
     const size_t t = t0 + tid, b = first + t;
     const int32_t beg = inc_ptr[b], deg = inc_ptr[b + 1] - beg;
+    long_list = deg > 64;
     unsigned long long m = body_mask[b];
     if (deg < 64) m &= (1ull << deg) - 1ull;
     snap_mask[b] = m;
@@ -1868,6 +1968,10 @@ __global__ void __launch_bounds__(kBlock)
     tptr[tid] = out;
   }
   if (tid == 0) tptr[nb] = aptr_local[t0 + nb];
+  // the clean-wave bytes start from "a list of this group is longer than 64 entries" (a half wave here = 32 bodies = one
+  // group); mask & ~snap_mask is zero everywhere as of now
+  const unsigned long long longs = __ballot(long_list);
+  if ((tid & 31) == 0 && tid < nb) wave_dirty[(t0 + tid) >> 5] = ((longs >> (tid & 32)) & 0xffffffffull) != 0ull;
   __syncthreads();
   const int32_t E0 = tptr[0], E1 = tptr[nb];
   for (int32_t o = E0 + tid; o < E1; o += kBlock) {
@@ -2421,7 +2525,7 @@ struct OpWorkspaces {
   HandleBuffer rate_rows;  // (U, W x u) rows of a caller's velocity (mhip_contact_op_constraint_rate, rods)
   HandleBuffer body_mask, pos;  // activity masks of the packed LCP solves (see OpView)
   HandleBuffer sort_tmp, sort_list;  // workspaces of the incidence-list sort
-  HandleBuffer aptr, aent, arec, snap_mask, acnt;  // active lists (see OpView)
+  HandleBuffer aptr, aent, arec, snap_mask, acnt, wave_dirty;  // active lists, clean-wave bytes (see OpView)
   // cold tier (its other state is mhip_contact_op::Tier)
   HandleBuffer tier_geo[2], tier_iter[2], tier_misc, tier_vel2, tier_drift, tier_arm, tier_xprev;
   PinnedBlock<SolverState> host_state;  // + 64 spare bytes: the length of the compact active lists
@@ -2626,6 +2730,16 @@ int op_snapshot_active(mhip_contact_op* op, hipStream_t s) {
   const size_t stride = 2 * C + 2;  // entries between two planes of the records
   if (int e = op->arec.reserve(stride * ((hw + 1) / 2) * sizeof(double2))) return e;
   if (int e = op->snap_mask.reserve((N + 2) * sizeof(unsigned long long))) return e;
+  // one word per tile of the two-lane body sweep, whose grid is rounded up to a multiple of 8 tiles.  Sized from N,
+  // indexed from body_first over body_count bodies: the bytes of groups past the last body (the rest of the last tile's
+  // word, the tiles of the rounded-up grid) are never written by anyone and are read by waves without a body, for which
+  // either path is safe -- zeroed once, when the buffer is made, so that no branch depends on memory nobody wrote
+  {
+    const void* const before = op->wave_dirty.ptr;
+    const size_t bytes = ((N + 127) / 128 + 8) * sizeof(unsigned);
+    if (int e = op->wave_dirty.reserve(bytes)) return e;
+    if (op->wave_dirty.ptr != before) MHIP_HIP(hipMemsetAsync(op->wave_dirty.ptr, 0, bytes, s));
+  }
   int32_t* local = op->cursor.as<int32_t>();  // free since the incidence build
   k_active_count<<<grid_for(cnt), kBlock, 0, s>>>(v.body_first, cnt, v.inc_ptr, v.body_mask, op->acnt.as<int32_t>());
   MHIP_LAUNCH_CHECK();
@@ -2633,7 +2747,7 @@ int op_snapshot_active(mhip_contact_op* op, hipStream_t s) {
   pick<6, 4, 3>(hw, [&](auto h) {
     k_active_fill_flat<decltype(h)::value><<<grid_exact(cnt), kBlock, 0, s>>>(
         v.body_first, cnt, v.inc_ptr, v.inc, v.half, v.body_mask, local, op->aptr.as<int32_t>(), op->aent.as<int32_t>(),
-        op->arec.as<double>(), stride, op->snap_mask.as<unsigned long long>());
+        op->arec.as<double>(), stride, op->snap_mask.as<unsigned long long>(), op->wave_dirty.as<unsigned char>());
   });
   MHIP_LAUNCH_CHECK();
   // the length of the compact lists travels to the host with the next poll (it picks the flat sweep's chunk; see
@@ -2646,6 +2760,7 @@ int op_snapshot_active(mhip_contact_op* op, hipStream_t s) {
   v.arec = op->arec.as<double>();
   v.arec_stride = stride;
   v.snap_mask = op->snap_mask.as<unsigned long long>();
+  v.wave_dirty = op->wave_dirty.as<unsigned char>();
   return MHIP_SUCCESS;
 }
 // from this many completed iterations on the masks have settled enough for a snapshot to pay
@@ -3859,6 +3974,15 @@ int mhip_bbpgd_solve_contact(mhip_contact_op_t op, const double* q, const mhip_s
   double* P1 = P0 + 2 * C;
   if (op->view.body_mask) MHIP_HIP(hipMemsetAsync(op->view.body_mask, 0x00, op->view.N * sizeof(unsigned long long), s));
   op->view.aptr = nullptr;  // no snapshot of the active entries yet (the init sweep writes the masks)
+  // are the mobilities one value for every body?  Asked anew in every solve (the caller's arrays may have changed in
+  // place); the answer comes back with the first poll
+  op->view.mob_uniform = 0;
+  if (op->view.body_count > 0) {
+    MHIP_HIP(hipMemsetAsync(&st->mt_mixed, 0, 2 * sizeof(int), s));
+    k_mob_uniform<<<grid_for(op->view.body_count), kBlock, 0, s>>>(op->view.body_first, op->view.body_count, op->view.mt,
+                                                                  op->kin != KIN_TRANS ? op->view.mr : nullptr, st);
+    MHIP_LAUNCH_CHECK();
+  }
   // initialize: x_tmp = x ; g_tmp = A x_tmp + q ; residual ; step = 1/res   (the pair lands packed in P0)
   if (int e = op_launch_body(op, X_INIT, x, x, nullptr, nullptr, sp, s)) return e;
   if (int e = op_launch_constraint(op, X_INIT, P0, P1, x, nullptr, q, sp, rk, cgrid, s, true)) return e;
@@ -3880,6 +4004,10 @@ int mhip_bbpgd_solve_contact(mhip_contact_op_t op, const double* q, const mhip_s
   struct TierGuard {
     mhip_contact_op* op;
     ~TierGuard() {
+      struct ForgetMobilities {  // (last: after the view has been restored) the verdict holds for this solve only
+        mhip_contact_op* op;
+        ~ForgetMobilities() { op->view.mob_uniform = 0; }
+      } forget{op};
       if (!op->tier.active) {
         op->view.vel_alt = nullptr;
         op->view.drift = nullptr;
@@ -3935,8 +4063,15 @@ int mhip_bbpgd_solve_contact(mhip_contact_op_t op, const double* q, const mhip_s
     // first poll -- unless the problem was solved already -- so that iterations 1 ... 8 stream compact lists too instead
     // of walking every body's mask (round 3: k_body at 130-196 us in those iterations against 110 with a snapshot); what
     // becomes active since takes the per-body path
-    if (enqueued == 0)
+    if (enqueued == 0) {
       if (int e = op_snapshot_active(op, s)) return e;
+      if (op->view.body_count > 0) {  // the mobilities' verdict arrived with this poll's state
+        const SolverState& hs = *op->host_state;
+        op->view.mob_uniform = (hs.mt_mixed ? 0 : 1) | ((op->kin != KIN_TRANS && !hs.mr_mixed) ? 2 : 0);
+        op->view.mt_one = hs.mt_one;
+        op->view.mr_one = hs.mr_one;
+      }
+    }
     // cold tier: the drift bookkeeping starts with the first iteration, the first classification comes with the first
     // snapshot (short solves -- a relaxed packing needs ~100 iterations -- get their tiers early)
     const bool light = plan.light_poll();
