@@ -549,8 +549,9 @@ int mhip_active_springs_destroy(mhip_active_springs_t handle);
  *   twist_velocity = ((1 / (8 pi eta)) ir ir ir) twist_torque, ir = 1 / r.
  * get  device pointers to every field; those of the edge state change places at every advance, so ask again after it.
  * force / edge_pass / node_pass / velocity / advance before set_state: MHIP_ERR_RUNTIME.  Contacts between filament segments:
- * mhip_filament_contacts_* below, whose node forces enter through external_force.  Not built: the
- * inertial variants (CollidingFrictionalSperm.cpp:1571-1675), clamp_edge1 (:1813-1830), several GPUs. */
+ * mhip_filament_contacts_* below, whose node forces enter through external_force.  The inertial variants
+ * (CollidingFrictionalSperm.cpp:1571-1675, CollidingSperm.cpp): mundy_hip_filament_inertial.h.  Not built: clamp_edge1
+ * (:1813-1830), several GPUs. */
 typedef struct mhip_filament_params {
   double youngs_modulus, poisson_ratio, rest_length, viscosity;
   double wave_amplitude, wave_number, wave_frequency; /* A, k = 2 pi / wavelength, omega = 2 pi / period (:1110-1111) */
@@ -627,7 +628,8 @@ int mhip_filaments_destroy(mhip_filaments_t handle);
  *   current list; before the first update it is kept and carried into the first list (a restart).
  * get  device pointers (they move at a rebuild: ask again after an update that rebuilt) and counts.
  * force before save_velocity or update: MHIP_ERR_RUNTIME, the message names the missing call.
- * Not built: periodic cells, several GPUs, a renumbering of nodes, the frictionless ...HertzianContact and WCA kernels. */
+ * The frictionless ...HertzianContact kernel: mhip_filament_contacts_set_law of mundy_hip_filament_inertial.h.
+ * Not built: periodic cells, several GPUs, a renumbering of nodes, the WCA kernel. */
 typedef struct mhip_filament_contact_params {
   double skin, youngs_modulus, poisson_ratio;
   double mu, normal_damping, tangential_damping, density;

@@ -35,6 +35,7 @@
 #include "mundy_hip/adapter.hpp"
 
 #include "../mundy_hip_segment_contact.h"
+#include "../mundy_hip_filament_inertial.h"
 
 namespace mundy_hip {
 namespace mech {
@@ -58,6 +59,7 @@ struct StepStats {
   size_t num_carried = 0;    // frictional Hertz mode: history rows carried to a rebuilt list this step
   double max_stretch = 0.0;              // FilamentStepper: the largest |l - l0| / l0 over the edges
   double max_curvature_deviation = 0.0;  // FilamentStepper: the largest component of |kappa - kappa_rest|
+  double kinetic_energy = 0.0;           // FilamentStepper::set_inertial: of the velocities the corrector wrote
   double max_spring_length = 0.0;        // SphereChainStepper: the longest spring at the start of the step
   int springs_overstretched = 0;         // SphereChainStepper: springs past their limit (FENE: L >= r_max)
   // SphereChainStepper with crosslinkers, a periphery or active springs: the step's statistics array
@@ -1176,7 +1178,9 @@ class SphereChainStepper {
 
 /// Centerline-twist elastic filaments (mhip_filaments_*), stepped in the reference's order: the state lives in the
 /// library handle, fields() hands out its device pointers (those of the edge state change places at every step).
-/// set_contacts adds the frictional Hertzian contacts between their segments (mhip_filament_contacts_*).
+/// set_contacts adds the frictional Hertzian contacts between their segments (mhip_filament_contacts_*);
+/// set_inertial gives the nodes mass (mundy_hip_filament_inertial.h: the Newmark step of CollidingSperm.cpp and
+/// CollidingFrictionalSperm.cpp), set_contact_law chooses the frictionless Hertz law, equilibrate is the stiffness ramp.
 class FilamentStepper {
  public:
   /// host arrays: node_ptr [F + 1]; center [N][3], twist [N], edge_orientation [N][4] (w, x, y, z; by left node: the
@@ -1186,7 +1190,7 @@ class FilamentStepper {
                   const std::vector<double>& radius, const std::vector<double>& rest_curvature,
                   const std::vector<double>& arclength, const std::vector<double>& phase,
                   const mhip_filament_params& params)
-      : node_ptr_(node_ptr), monolayer_(params.monolayer), stats_(4) {
+      : node_ptr_(node_ptr), monolayer_(params.monolayer), youngs_modulus_(params.youngs_modulus), stats_(5) {
     if (node_ptr.empty()) throw std::invalid_argument("FilamentStepper: node_ptr is empty");
     const size_t f = node_ptr.size() - 1, n = static_cast<size_t>(node_ptr.back() < 0 ? 0 : node_ptr.back());
     if (center.size() != 3 * n || twist.size() != n || edge_orientation.size() != 4 * n || radius.size() != n ||
@@ -1223,13 +1227,67 @@ class FilamentStepper {
     contacts_ = c;
   }
 
+  /// nodes with mass from the next step on (call before the first step: mhip_filaments_set_state has zeroed the
+  /// accelerations only if the handle was inertial then, and this call zeroes them too); fixed_filament [F] or empty
+  void set_inertial(const mhip_filament_inertial_params& params, const std::vector<unsigned char>& fixed_filament = {}) {
+    if (!fixed_filament.empty() && fixed_filament.size() + 1 != node_ptr_.size())
+      throw std::invalid_argument("FilamentStepper: fixed_filament does not have one entry per filament");
+    check(mhip_filaments_set_inertial(h_, &params, fixed_filament.empty() ? nullptr : fixed_filament.data()));
+    inertial_ = true;
+  }
+  /// MHIP_FILAMENT_CONTACT_FRICTIONAL (the default) or MHIP_FILAMENT_CONTACT_HERTZ; after set_contacts
+  void set_contact_law(int law) {
+    if (!contacts_) throw std::logic_error("FilamentStepper: set_contact_law before set_contacts");
+    check(mhip_filament_contacts_set_law(contacts_, law));
+    law_ = law;
+  }
+
+  /// The stiffness ramp of CollidingFrictionalSperm.cpp:1781-1865: E = relaxed; while E < the stepper's modulus:
+  /// inertial steps without contacts until the kinetic energy is <= threshold (at least one per level), then
+  /// E *= growth.  The step index is not advanced (a wave stays frozen).  poll_every: the kinetic energy is read once
+  /// per poll_every steps (1: the reference's loop).  More than max_steps steps in all: std::runtime_error.  On return
+  /// the modulus is the stepper's own again.  -> the steps per level
+  std::vector<size_t> equilibrate(double dt, double relaxed_youngs_modulus, double threshold = 1e-6, double growth = 1.1,
+                                  size_t poll_every = 1, size_t max_steps = 1000000) {
+    if (!inertial_) throw std::logic_error("FilamentStepper: equilibrate before set_inertial");
+    if (!(relaxed_youngs_modulus > 0.0) || !(growth > 1.0) || poll_every < 1)
+      throw std::invalid_argument("FilamentStepper: equilibrate needs relaxed_youngs_modulus > 0, growth > 1, poll_every >= 1");
+    struct Restore {
+      FilamentStepper* s;
+      ~Restore() { mhip_filaments_set_youngs_modulus(s->h_, s->youngs_modulus_); }
+    } restore{this};
+    const double time = static_cast<double>(step_index_) * dt;
+    std::vector<size_t> levels;
+    size_t total = 0;
+    for (double E = relaxed_youngs_modulus; E < youngs_modulus_; E *= growth) {
+      check(mhip_filaments_set_youngs_modulus(h_, E));
+      size_t count = 0;
+      double energy = std::numeric_limits<double>::infinity();
+      while (energy > threshold) {
+        if (total + poll_every > max_steps) throw std::runtime_error("FilamentStepper: equilibrate exceeded max_steps");
+        for (size_t k = 0; k < poll_every; ++k) {
+          check(mhip_filaments_predict(h_, dt));
+          check(mhip_filaments_force(h_, time, nullptr, stats_.data()));
+          check(mhip_filaments_correct(h_, dt, stats_.data() + 4));
+        }
+        count += poll_every;
+        total += poll_every;
+        energy = stats_.download()[4];
+      }
+      levels.push_back(count);
+    }
+    return levels;
+  }
+
   /// advance -> forces at x(t + dt), time = step index * dt as the reference counts it (:1115) -> velocities;
   /// external_force [device, N x 3, or null] is added first.  With contacts (:2013-2021): save_velocity -> advance ->
   /// update -> contact force with external_force -> forces with the contacts' node forces -> velocities.
+  /// After set_inertial: save_velocity (frictional law only) -> predict -> update -> contact force -> forces -> correct.
   StepStats step(double dt, const double* external_force = nullptr) {
     StepStats st;
-    if (contacts_) check(mhip_filament_contacts_save_velocity(contacts_));
-    check(mhip_filaments_advance(h_, dt));
+    if (contacts_ && law_ == MHIP_FILAMENT_CONTACT_FRICTIONAL) check(mhip_filament_contacts_save_velocity(contacts_));
+    if (inertial_) check(mhip_filaments_predict(h_, dt));
+    else check(mhip_filaments_advance(h_, dt));
     if (contacts_) {
       int rebuilt = 0;
       check(mhip_filament_contacts_update(contacts_, &rebuilt));
@@ -1240,11 +1298,13 @@ class FilamentStepper {
       st.num_contacts = cf.num_pairs;
     }
     check(mhip_filaments_force(h_, static_cast<double>(step_index_) * dt, external_force, stats_.data()));
-    check(mhip_filaments_velocity(h_));
+    if (inertial_) check(mhip_filaments_correct(h_, dt, stats_.data() + 4));
+    else check(mhip_filaments_velocity(h_));
     ++step_index_;
     const auto s = stats_.download();  // the one host read of the step
     st.max_stretch = s[0];
     st.max_curvature_deviation = s[1];
+    if (inertial_) st.kinetic_energy = s[4];
     if (contacts_) {
       st.max_overlap = s[2];
       unsigned long long sliding = 0;
@@ -1263,14 +1323,21 @@ class FilamentStepper {
     check(mhip_filaments_get(h_, &f));
     return f;
   }
+  mhip_filament_inertial_fields inertial_fields() const {
+    mhip_filament_inertial_fields f{};
+    check(mhip_filaments_get_inertial(h_, &f));
+    return f;
+  }
   size_t step_index() const { return step_index_; }
 
  private:
   mhip_filaments_t h_ = nullptr;
   mhip_filament_contacts_t contacts_ = nullptr;
   std::vector<int32_t> node_ptr_;
-  int monolayer_ = 0;
-  DeviceVector stats_;  // (max_stretch, max_curvature_deviation, max_overlap, the bits of num_sliding)
+  int monolayer_ = 0, law_ = MHIP_FILAMENT_CONTACT_FRICTIONAL;
+  bool inertial_ = false;
+  double youngs_modulus_ = 0.0;
+  DeviceVector stats_;  // (max_stretch, max_curvature_deviation, max_overlap, the bits of num_sliding, kinetic energy)
   size_t step_index_ = 0;
 };
 

@@ -66,6 +66,16 @@ class FilamentFields(C.Structure):
     _fields_ = [("num_nodes", C.c_size_t), ("num_filaments", C.c_size_t)] + [(f, C.c_void_p) for f in FILAMENT_FIELDS]
 
 
+class FilamentInertialParams(C.Structure):
+    """mhip_filament_inertial_params (include/mundy_hip_filament_inertial.h)"""
+    _fields_ = [("density", C.c_double), ("damping_kind", C.c_int), ("translational_damping", C.c_double),
+                ("twist_damping", C.c_double)]
+
+
+class FilamentInertialFields(C.Structure):
+    _fields_ = [("acceleration", C.c_void_p), ("twist_acceleration", C.c_void_p)]
+
+
 class FilamentContactParams(C.Structure):
     _fields_ = [("skin", C.c_double), ("youngs_modulus", C.c_double), ("poisson_ratio", C.c_double), ("mu", C.c_double),
                 ("normal_damping", C.c_double), ("tangential_damping", C.c_double), ("density", C.c_double),
@@ -386,6 +396,20 @@ HYDRO_SOLVE_SIGNATURES = {
     "mhip_bbpgd_solve_contact_hydro": [_vp, C.POINTER(HydroMobility), _vp, C.POINTER(Space), C.POINTER(PgdConfig), _vp,
                                        _vp, _vp, _vp, C.POINTER(SolveResult), _vp],
 }
+# include/mundy_hip_filament_inertial.h, a header of its own for the same reason: name -> argtypes, every function returns
+# int status.  tests/test_filament_inertial_host.py checks this table against that header and the library.
+FILAMENT_DAMPING_CONSTANT, FILAMENT_DAMPING_CRITICAL = 0, 1
+FILAMENT_CONTACT_FRICTIONAL, FILAMENT_CONTACT_HERTZ = 0, 1
+FILAMENT_INERTIAL_SIGNATURES = {
+    "mhip_filaments_set_inertial": [_vp, C.POINTER(FilamentInertialParams), _vp],
+    "mhip_filaments_set_motion": [_vp, _vp, _vp, _vp, _vp],
+    "mhip_filaments_predict": [_vp, _d],
+    "mhip_filaments_correct": [_vp, _d, _vp],
+    "mhip_filaments_kinetic_energy": [_vp, _vp],
+    "mhip_filaments_set_youngs_modulus": [_vp, _d],
+    "mhip_filaments_get_inertial": [_vp, C.POINTER(FilamentInertialFields)],
+    "mhip_filament_contacts_set_law": [_vp, _i],
+}
 OTHER_SYMBOLS = {"mhip_last_error": ([], C.c_char_p), "mhip_version": ([], C.c_int),
                  "mhip_release_cached_workspaces": ([], C.c_int)}
 
@@ -406,7 +430,8 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, argtypes in (list(SIGNATURES.items()) + list(PERIPHERY_SIGNATURES.items()) +
                                list(CONTACT_FORCE_SIGNATURES.items()) + list(PERIPHERY_BINDING_SIGNATURES.items()) +
-                               list(SEGMENT_CONTACT_SIGNATURES.items()) + list(HYDRO_SOLVE_SIGNATURES.items())):
+                               list(SEGMENT_CONTACT_SIGNATURES.items()) + list(HYDRO_SOLVE_SIGNATURES.items()) +
+                               list(FILAMENT_INERTIAL_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = C.c_int

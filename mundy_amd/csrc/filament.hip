@@ -20,6 +20,7 @@
 #include "mhip_internal.hpp"
 #include "force_device.hpp"
 #include "geom_device.hpp"
+#include "../../include/mundy_hip_filament_inertial.h"
 
 #include <cmath>
 #include <vector>
@@ -275,6 +276,132 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
+// ---- inertial nodes: the Newmark step of CollidingSperm.cpp and CollidingFrictionalSperm.cpp ---------------------------
+// (include/mundy_hip_filament_inertial.h restates both kernels operation for operation.)
+//   predict   disable_twist :1699-1706 / apply_monolayer :1708-1737 / rotate_field_states / update_generalized_position
+//             :968-1018, in the order of the loop :1902-1921                                       one node per lane
+//   correct   update_generalized_position_velocity_and_acceleration :1616-1672 and, fused, the node's term of
+//             global_kinetic_energy :1739-1779                                                     one node per lane
+// zero_out_transient_node_fields (:955-966) is not restated: the node pass writes force and torque from +0.0 or the
+// external force and the corrector overwrites velocity and acceleration, so no zeroed value is ever read.  The
+// reference's StateN / StateNP1 copies of velocity and acceleration collapse into one: both kernels are node-local and
+// read a node's old values before they overwrite them.  All streaming (byte counts: DESIGN.md 5v).
+struct NewmarkD {  // formed once on the host: the same IEEE operations, the same bits
+  double c1;      // (1.0 - gamma) dt, :1647
+  double c2;      // (dt dt) beta, :1665
+  double c3;      // dt gamma, :1669
+  double density, E, ct, cr;
+};
+
+template <bool NO_TWIST, bool MONOLAYER>
+__global__ void __launch_bounds__(kBlock)
+    k_filament_predict(size_t n, double dt, double coeff, double* __restrict__ x, double* __restrict__ twist,
+                       double* __restrict__ vel, double* __restrict__ twist_vel, double* __restrict__ acc,
+                       double* __restrict__ twist_acc) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    V3 c = load3(x, i), v = load3(vel, i), a = load3(acc, i);
+    double tw = 0.0, tv = 0.0, ta = 0.0;
+    if (NO_TWIST) {  // :1703-1705: the corrector reads the two zeroed fields
+      twist_vel[i] = 0.0;
+      twist_acc[i] = 0.0;
+    } else {
+      tw = twist[i], tv = twist_vel[i], ta = twist_acc[i];
+    }
+    if (MONOLAYER) {  // :1733-1735
+      c.x = 0.0, v.x = 0.0, a.x = 0.0;
+      vel[3 * i] = 0.0;
+      acc[3 * i] = 0.0;
+    }
+    store3(x, i, (c + dt * v) + coeff * a);  // :1014
+    twist[i] = (tw + dt * tv) + coeff * ta;  // :1015-1016
+  }
+}
+
+// mass and moment of inertia of the sphere lumped at a node (:1633-1636)
+__device__ inline void node_mass(double r, double rho, double& m, double& I) {
+  const double r2 = r * r;
+  const double r3 = r2 * r;
+  m = 4.0 / 3.0 * M_PI * r3 * rho;
+  I = 2.0 / 5.0 * m * r2;
+}
+// :1767-1769
+__device__ inline double node_kinetic_energy(double m, double I, V3 v, double w) {
+  return 0.5 * m * dot(v, v) + 0.5 * I * w * w;
+}
+// the lanes' double-double sums -> one pair per workgroup, partials[2 b], partials[2 b + 1]
+__device__ inline void store_energy_partial(DD acc, double* __restrict__ partials) {
+  __shared__ double scratch[2 * (kBlock / 64)];
+  const DD r = block_sum(acc, scratch);
+  if (threadIdx.x == 0) {
+    partials[2 * blockIdx.x] = r.hi;
+    partials[2 * blockIdx.x + 1] = r.lo;
+  }
+}
+
+template <bool CRITICAL, bool FIXED, bool ENERGY>
+__global__ void __launch_bounds__(kBlock)
+    k_filament_correct(size_t n, NewmarkD P, const double* __restrict__ radius, const uint8_t* __restrict__ fixed,
+                       const double* __restrict__ force, const double* __restrict__ torque, double* __restrict__ x,
+                       double* __restrict__ twist, double* __restrict__ vel, double* __restrict__ twist_vel,
+                       double* __restrict__ acc, double* __restrict__ twist_acc, double* __restrict__ partials) {
+  DD sum{0.0, 0.0};
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    if (FIXED && fixed[i]) {  // :1652-1656; its term of the energy is +0.0
+      store3(vel, i, V3{0.0, 0.0, 0.0});
+      store3(acc, i, V3{0.0, 0.0, 0.0});
+      twist_vel[i] = 0.0;
+      twist_acc[i] = 0.0;
+      continue;
+    }
+    double m, I;
+    node_mass(radius[i], P.density, m, I);
+    const double ct = CRITICAL ? sqrt(m * P.E) : P.ct;  // :1645-1646; CollidingSperm.cpp:1576-1577
+    const double cr = CRITICAL ? ct : P.cr;
+    const V3 v = load3(vel, i), a = load3(acc, i);
+    const double tv = twist_vel[i], ta = twist_acc[i];
+    const V3 pv = v + P.c1 * a;                                     // :1648
+    const double ptv = tv + P.c1 * ta;                              // :1649
+    const V3 an = (1.0 / m) * (load3(force, i) - ct * v);           // :1658
+    const double tan_ = 1.0 / I * (torque[i] - cr * tv);            // :1659-1660
+    store3(x, i, load3(x, i) + P.c2 * an);                          // :1666
+    twist[i] = twist[i] + P.c2 * tan_;                              // :1667
+    const V3 vn = pv + P.c3 * an;                                   // :1670
+    const double tvn = ptv + P.c3 * tan_;                           // :1671
+    store3(acc, i, an);
+    twist_acc[i] = tan_;
+    store3(vel, i, vn);
+    twist_vel[i] = tvn;
+    if (ENERGY) dd_add(sum, node_kinetic_energy(m, I, vn, tvn));
+  }
+  if (ENERGY) store_energy_partial(sum, partials);
+}
+
+// global_kinetic_energy (:1739-1779) from the velocities as they stand: the lanes, the grid and so the partial sums of
+// k_filament_correct<.., true>
+__global__ void __launch_bounds__(kBlock)
+    k_filament_energy(size_t n, double density, const double* __restrict__ radius, const double* __restrict__ vel,
+                      const double* __restrict__ twist_vel, double* __restrict__ partials) {
+  DD sum{0.0, 0.0};
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    double m, I;
+    node_mass(radius[i], density, m, I);
+    dd_add(sum, node_kinetic_energy(m, I, load3(vel, i), twist_vel[i]));
+  }
+  store_energy_partial(sum, partials);
+}
+
+// One workgroup: lane t adds the pairs t, t + kBlock, .. in ascending order, the lanes' sums are added as block_sum adds
+// them, one rounding.  kBlock pairs per pass: a grid of more than kBlock workgroups (n > kBlock * kBlock nodes) takes
+// the loop's second pass.
+__global__ void __launch_bounds__(kBlock)
+    k_filament_energy_fold(unsigned parts, const double* __restrict__ partials, double* __restrict__ out) {
+  __shared__ double scratch[2 * (kBlock / 64)];
+  DD sum{0.0, 0.0};
+  for (unsigned k = threadIdx.x; k < parts; k += kBlock) dd_add(sum, DD{partials[2 * k], partials[2 * k + 1]});
+  const DD r = block_sum(sum, scratch);
+  if (threadIdx.x == 0) out[0] = dd_value(r);
+}
+
 }  // namespace mhip
 
 using namespace mhip;
@@ -288,6 +415,11 @@ struct mhip_filaments {
   HandleBuffer flag, fid, node_ptr, phase, radius, rest, arclength;
   HandleBuffer center, twist, vel, twist_vel, force, torque, curvature;
   HandleBuffer tangent[2], orient[2], length[2], binormal[2];
+  // mundy_hip_filament_inertial.h
+  bool inertial = false, any_fixed = false;
+  mhip_filament_inertial_params iprm{};
+  HandleBuffer acc, twist_acc, fixed, energy_partials;
+  std::vector<int32_t> host_node_ptr;  // the per-node flag of the fixed filaments is built from it
 };
 
 extern "C" {
@@ -350,6 +482,7 @@ int mhip_filaments_create(mhip_filaments_t* handle, size_t num_filaments, const 
   h->n = n;
   h->f = num_filaments;
   h->prm = p;
+  h->host_node_ptr.assign(node_ptr, node_ptr + num_filaments + 1);
   hipStream_t s = as_stream(stream);
   h->stream = s;
   const size_t d = sizeof(double);
@@ -407,6 +540,10 @@ int mhip_filaments_set_state(mhip_filaments_t h, const double* center, const dou
   }
   for (HandleBuffer* b : {&h->vel, &h->force, &h->curvature}) MHIP_HIP(hipMemsetAsync(b->ptr, 0, 3 * n * d, s));
   for (HandleBuffer* b : {&h->twist_vel, &h->torque}) MHIP_HIP(hipMemsetAsync(b->ptr, 0, n * d, s));
+  if (h->inertial) {
+    MHIP_HIP(hipMemsetAsync(h->acc.ptr, 0, 3 * n * d, s));
+    MHIP_HIP(hipMemsetAsync(h->twist_acc.ptr, 0, n * d, s));
+  }
   k_filament_init_edges<<<grid_for(n), kBlock, 0, s>>>(n, h->flag.as<uint8_t>(), h->center.as<double>(),
                                                        h->tangent[0].as<double>(), h->length[0].as<double>(),
                                                        h->tangent[1].as<double>(), h->length[1].as<double>());
@@ -515,6 +652,161 @@ int mhip_filaments_get(mhip_filaments_t h, mhip_filament_fields* out) {
   out->edge_orientation_old = h->orient[old].as<double>();
   out->edge_length_old = h->length[old].as<double>();
   out->edge_binormal_old = h->binormal[old].as<double>();
+  return MHIP_SUCCESS;
+}
+
+// ---- mundy_hip_filament_inertial.h ------------------------------------------------------------------------------------
+int mhip_filaments_set_inertial(mhip_filaments_t h, const mhip_filament_inertial_params* params,
+                                const unsigned char* fixed_filament) {
+  // the arguments that need no handle first, so that every refusal can be had without a device
+  MHIP_REQUIRE(params != nullptr, MHIP_ERR_INVALID_ARGUMENT, "params is null");
+  const mhip_filament_inertial_params& p = *params;
+  MHIP_REQUIRE(std::isfinite(p.density) && p.density > 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "density must be finite and > 0, got %g", p.density);
+  MHIP_REQUIRE(p.damping_kind == MHIP_FILAMENT_DAMPING_CONSTANT || p.damping_kind == MHIP_FILAMENT_DAMPING_CRITICAL,
+               MHIP_ERR_INVALID_ARGUMENT, "unknown damping kind %d", p.damping_kind);
+  if (p.damping_kind == MHIP_FILAMENT_DAMPING_CONSTANT)
+    MHIP_REQUIRE(std::isfinite(p.translational_damping) && p.translational_damping >= 0.0 &&
+                     std::isfinite(p.twist_damping) && p.twist_damping >= 0.0,
+                 MHIP_ERR_INVALID_ARGUMENT, "damping coefficients must be finite and >= 0, got %g, %g",
+                 p.translational_damping, p.twist_damping);
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "filaments handle is null");
+  const size_t n = h->n, d = sizeof(double);
+  hipStream_t s = h->stream;
+  std::vector<uint8_t> fixed;
+  bool any = false;
+  if (fixed_filament) {
+    fixed.assign(n, 0);
+    const std::vector<int32_t>& ptr = h->host_node_ptr;
+    for (size_t f = 0; f < h->f; ++f)
+      if (fixed_filament[f]) {
+        any = true;
+        for (int32_t i = ptr[f]; i < ptr[f + 1]; ++i) fixed[i] = 1;
+      }
+  }
+  int e = MHIP_SUCCESS;
+  if ((e = h->acc.reserve(3 * n * d + 8)) || (e = h->twist_acc.reserve(n * d + 8)) || (e = h->fixed.reserve(n + 8)) ||
+      (e = h->energy_partials.reserve(2 * kMaxGrid * d)))
+    return e;
+  if (n > 0) {
+    MHIP_HIP(hipMemsetAsync(h->acc.ptr, 0, 3 * n * d, s));
+    MHIP_HIP(hipMemsetAsync(h->twist_acc.ptr, 0, n * d, s));
+    if (any) {
+      if ((e = upload(__func__, h->fixed, fixed.data(), n, s))) return e;
+      if ((e = hip_status(__func__, hipStreamSynchronize(s)))) return e;  // `fixed` goes when this returns
+    }
+  }
+  h->iprm = p;
+  h->any_fixed = any;
+  h->inertial = true;
+  return MHIP_SUCCESS;
+}
+
+int mhip_filaments_set_motion(mhip_filaments_t h, const double* velocity, const double* twist_velocity,
+                              const double* acceleration, const double* twist_acceleration) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "filaments handle is null");
+  MHIP_REQUIRE(h->inertial, MHIP_ERR_RUNTIME, "mhip_filaments_set_motion before mhip_filaments_set_inertial");
+  MHIP_REQUIRE(h->has_state, MHIP_ERR_RUNTIME, "mhip_filaments_set_motion before mhip_filaments_set_state");
+  const size_t n = h->n, d = sizeof(double);
+  if (n == 0) return MHIP_SUCCESS;
+  hipStream_t s = h->stream;
+  const struct {
+    HandleBuffer* dst;
+    const double* src;
+    size_t bytes;
+  } rows[] = {{&h->vel, velocity, 3 * n * d},
+              {&h->twist_vel, twist_velocity, n * d},
+              {&h->acc, acceleration, 3 * n * d},
+              {&h->twist_acc, twist_acceleration, n * d}};
+  for (const auto& r : rows) {
+    if (r.src) MHIP_HIP(hipMemcpyAsync(r.dst->ptr, r.src, r.bytes, hipMemcpyDeviceToDevice, s));
+    else MHIP_HIP(hipMemsetAsync(r.dst->ptr, 0, r.bytes, s));
+  }
+  return MHIP_SUCCESS;
+}
+
+int mhip_filaments_predict(mhip_filaments_t h, double dt) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "filaments handle is null");
+  MHIP_REQUIRE(std::isfinite(dt) && dt >= 0.0, MHIP_ERR_INVALID_ARGUMENT, "dt must be finite and >= 0, got %g", dt);
+  MHIP_REQUIRE(h->inertial, MHIP_ERR_RUNTIME, "mhip_filaments_predict before mhip_filaments_set_inertial");
+  MHIP_REQUIRE(h->has_state, MHIP_ERR_RUNTIME, "mhip_filaments_predict before mhip_filaments_set_state");
+  h->cur ^= 1;  // rotate_field_states: what was new is old
+  if (h->n == 0) return MHIP_SUCCESS;
+  const double beta = 0.25;
+  const double coeff = 0.5 * dt * dt * (1.0 - 2.0 * beta);  // :1012-1013
+  dispatch_bools(h->prm.disable_twist != 0, h->prm.monolayer != 0, [&](auto nt, auto ml) {
+    k_filament_predict<decltype(nt)::value, decltype(ml)::value><<<grid_for(h->n), kBlock, 0, h->stream>>>(
+        h->n, dt, coeff, h->center.as<double>(), h->twist.as<double>(), h->vel.as<double>(), h->twist_vel.as<double>(),
+        h->acc.as<double>(), h->twist_acc.as<double>());
+  });
+  MHIP_LAUNCH_CHECK();
+  return MHIP_SUCCESS;
+}
+
+static int filament_energy_fold(mhip_filaments_t h, double* out) {
+  k_filament_energy_fold<<<1, kBlock, 0, h->stream>>>(grid_for(h->n), h->energy_partials.as<double>(), out);
+  MHIP_LAUNCH_CHECK();
+  return MHIP_SUCCESS;
+}
+
+int mhip_filaments_correct(mhip_filaments_t h, double dt, double* kinetic_energy) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "filaments handle is null");
+  MHIP_REQUIRE(std::isfinite(dt) && dt >= 0.0, MHIP_ERR_INVALID_ARGUMENT, "dt must be finite and >= 0, got %g", dt);
+  MHIP_REQUIRE(h->inertial, MHIP_ERR_RUNTIME, "mhip_filaments_correct before mhip_filaments_set_inertial");
+  MHIP_REQUIRE(h->has_state, MHIP_ERR_RUNTIME, "mhip_filaments_correct before mhip_filaments_set_state");
+  hipStream_t s = h->stream;
+  if (h->n == 0) {
+    if (kinetic_energy) MHIP_HIP(hipMemsetAsync(kinetic_energy, 0, sizeof(double), s));
+    return MHIP_SUCCESS;
+  }
+  const double gamma = 0.5, beta = 0.25;
+  const mhip_filament_inertial_params& p = h->iprm;
+  const NewmarkD P{(1.0 - gamma) * dt, dt * dt * beta, dt * gamma, p.density, h->prm.youngs_modulus,
+                   p.translational_damping, p.twist_damping};
+  dispatch_bools(p.damping_kind == MHIP_FILAMENT_DAMPING_CRITICAL, h->any_fixed, [&](auto cr, auto fx) {
+    dispatch<true, false>(kinetic_energy != nullptr, [&](auto en) {
+      k_filament_correct<decltype(cr)::value, decltype(fx)::value, decltype(en)::value>
+          <<<grid_for(h->n), kBlock, 0, s>>>(h->n, P, h->radius.as<double>(), h->fixed.as<uint8_t>(),
+                                             h->force.as<double>(), h->torque.as<double>(), h->center.as<double>(),
+                                             h->twist.as<double>(), h->vel.as<double>(), h->twist_vel.as<double>(),
+                                             h->acc.as<double>(), h->twist_acc.as<double>(),
+                                             h->energy_partials.as<double>());
+    });
+  });
+  MHIP_LAUNCH_CHECK();
+  return kinetic_energy ? filament_energy_fold(h, kinetic_energy) : MHIP_SUCCESS;
+}
+
+int mhip_filaments_kinetic_energy(mhip_filaments_t h, double* out) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "filaments handle is null");
+  MHIP_REQUIRE(out != nullptr, MHIP_ERR_INVALID_ARGUMENT, "out is null");
+  MHIP_REQUIRE(h->inertial, MHIP_ERR_RUNTIME, "mhip_filaments_kinetic_energy before mhip_filaments_set_inertial");
+  MHIP_REQUIRE(h->has_state, MHIP_ERR_RUNTIME, "mhip_filaments_kinetic_energy before mhip_filaments_set_state");
+  hipStream_t s = h->stream;
+  if (h->n == 0) {
+    MHIP_HIP(hipMemsetAsync(out, 0, sizeof(double), s));
+    return MHIP_SUCCESS;
+  }
+  k_filament_energy<<<grid_for(h->n), kBlock, 0, s>>>(h->n, h->iprm.density, h->radius.as<double>(),
+                                                      h->vel.as<double>(), h->twist_vel.as<double>(),
+                                                      h->energy_partials.as<double>());
+  MHIP_LAUNCH_CHECK();
+  return filament_energy_fold(h, out);
+}
+
+int mhip_filaments_set_youngs_modulus(mhip_filaments_t h, double youngs_modulus) {
+  MHIP_REQUIRE(std::isfinite(youngs_modulus) && youngs_modulus >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
+               "youngs_modulus must be finite and >= 0, got %g", youngs_modulus);
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "filaments handle is null");
+  h->prm.youngs_modulus = youngs_modulus;  // the node pass forms the shear modulus from it at every call
+  return MHIP_SUCCESS;
+}
+
+int mhip_filaments_get_inertial(mhip_filaments_t h, mhip_filament_inertial_fields* out) {
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "filaments handle is null");
+  MHIP_REQUIRE(out != nullptr, MHIP_ERR_INVALID_ARGUMENT, "fields is null");
+  out->acceleration = h->acc.as<double>();
+  out->twist_acceleration = h->twist_acc.as<double>();
   return MHIP_SUCCESS;
 }
 

@@ -14,6 +14,7 @@
 #include "mhip_internal.hpp"
 #include "force_device.hpp"
 #include "geom_device.hpp"
+#include "../../include/mundy_hip_filament_inertial.h"
 
 #include <algorithm>
 #include <cmath>
@@ -66,6 +67,10 @@ __device__ inline V3 segment_point_velocity(V3 x0, V3 x1, V3 v0, V3 v1, V3 cp) {
 }
 // One linker per lane and pass, grid-stride.  stats[0]: bits of max(0, -sep) over the contact branch; stats[1]: number of
 // contacts whose tangential force was capped.  One atomic per workgroup for each.
+// FRICTION = false: the frictionless law of ...SpherocylinderSegmentSpherocylinderSegmentHertzianContact.cpp:208-225
+// (mundy_hip_filament_inertial.h): the branch is sep < 0, the force on the left segment (-F) n with hertz_force_magnitude,
+// no velocity is read, tang_disp stays +0.0 and nothing is counted.
+template <bool FRICTION>
 __global__ void __launch_bounds__(kBlock)
     k_filament_linkers(size_t C, size_t N, const int* __restrict__ pairs, const double* __restrict__ seg,
                        const double* __restrict__ vel_prev, double E0, double nu0, mhip_hertz_friction_params prm,
@@ -89,7 +94,8 @@ __global__ void __launch_bounds__(kBlock)
     const SegSeg r = dist_segment_segment(a.p0, a.p1, b.p0, b.p1);
     const double s = r.dist - (a.r + b.r);
     sep[c] = s;
-    if (s > 0.0) {  // no contact: the history is reset (FHC :433-435), force and shares are +0.0
+    // no contact: the history is reset (FHC :433-435), force and shares are +0.0
+    if (FRICTION ? s > 0.0 : !(s < 0.0)) {
       reset_row(tang_disp, c);
       reset_row(force, c);
       reset_row(share, 2 * c);
@@ -97,6 +103,17 @@ __global__ void __launch_bounds__(kBlock)
       continue;
     }
     const V3 n = (r.cp2 - r.cp1) * (1.0 / r.dist);  // left to right (linker kernel :226)
+    if (!FRICTION) {
+      const double Rs = (a.r * b.r) / (a.r + b.r);
+      const double Es = (E0 * E0) / (E0 - E0 * nu0 * nu0 + E0 - E0 * nu0 * nu0);
+      const V3 F = (-hertz_force_magnitude(Es, Rs, s)) * n;  // :225
+      reset_row(tang_disp, c);
+      store3(force, c, F);
+      store3(share, 2 * c, segment_share(a.p0, a.p1, r.cp1, F));
+      store3(share, 2 * c + 1, segment_share(b.p0, b.p1, r.cp2, V3{-F.x, -F.y, -F.z}));
+      dmax = -s > dmax ? -s : dmax;
+      continue;
+    }
     const V3 vi = segment_point_velocity(a.p0, a.p1, load3(vel_prev, p.x), load3(vel_prev, (size_t)p.x + 1), r.cp1);
     const V3 vj = segment_point_velocity(b.p0, b.p1, load3(vel_prev, p.y), load3(vel_prev, (size_t)p.y + 1), r.cp2);
     HertzPair h;  // hertz_pair's expressions, the radii being the segments' and the material one scalar pair
@@ -177,6 +194,7 @@ struct mhip_filament_contacts {
   hipStream_t stream = nullptr;
   mhip_broadphase_t bp = nullptr;
   bool saved = false, has_list = false;
+  int law = MHIP_FILAMENT_CONTACT_FRICTIONAL;  // mundy_hip_filament_inertial.h
   int cur = 0;           // which copy of (pairs, hist) is the current list
   size_t c = 0;          // its length (before the first update: the length of a planted list)
   HandleBuffer has_right, radius, ex_ptr, ex_idx;
@@ -369,7 +387,7 @@ int mhip_filament_contacts_linker_pass(mhip_filament_contacts_t h, double dt, vo
   MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "filament contacts handle is null");
   MHIP_REQUIRE(stats != nullptr, MHIP_ERR_INVALID_ARGUMENT, "stats is null");
   MHIP_REQUIRE(std::isfinite(dt) && dt >= 0.0, MHIP_ERR_INVALID_ARGUMENT, "dt must be finite and >= 0, got %g", dt);
-  MHIP_REQUIRE(h->saved, MHIP_ERR_RUNTIME,
+  MHIP_REQUIRE(h->saved || h->law == MHIP_FILAMENT_CONTACT_HERTZ, MHIP_ERR_RUNTIME,
                "mhip_filament_contacts_linker_pass before mhip_filament_contacts_save_velocity");
   MHIP_REQUIRE(h->has_list, MHIP_ERR_RUNTIME, "mhip_filament_contacts_linker_pass before mhip_filament_contacts_update");
   hipStream_t s = h->stream;
@@ -379,10 +397,12 @@ int mhip_filament_contacts_linker_pass(mhip_filament_contacts_t h, double dt, vo
   const mhip_filament_contact_params& p = h->prm;
   const mhip_hertz_friction_params law{p.mu, p.normal_damping, p.tangential_damping, p.density,
                                        p.history_dt < 0.0 ? dt : p.history_dt};
-  k_filament_linkers<<<grid_for(c), kBlock, 0, s>>>(
-      c, n, h->pairs[h->cur].as<int>(), h->seg.as<double>(), h->vel_prev.as<double>(), p.youngs_modulus, p.poisson_ratio,
-      law, h->sep.as<double>(), h->hist[h->cur].as<double>(), h->force.as<double>(), h->share.as<double>(),
-      static_cast<unsigned long long*>(stats));
+  dispatch<true, false>(h->law == MHIP_FILAMENT_CONTACT_FRICTIONAL, [&](auto fr) {
+    k_filament_linkers<decltype(fr)::value><<<grid_for(c), kBlock, 0, s>>>(
+        c, n, h->pairs[h->cur].as<int>(), h->seg.as<double>(), h->vel_prev.as<double>(), p.youngs_modulus,
+        p.poisson_ratio, law, h->sep.as<double>(), h->hist[h->cur].as<double>(), h->force.as<double>(),
+        h->share.as<double>(), static_cast<unsigned long long*>(stats));
+  });
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
 }
@@ -405,7 +425,8 @@ int mhip_filament_contacts_reduce(mhip_filament_contacts_t h, const double* exte
 int mhip_filament_contacts_force(mhip_filament_contacts_t h, double dt, const double* external_force, void* stats) {
   // every refusal comes before the first launch
   MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "filament contacts handle is null");
-  MHIP_REQUIRE(h->saved, MHIP_ERR_RUNTIME, "mhip_filament_contacts_force before mhip_filament_contacts_save_velocity");
+  MHIP_REQUIRE(h->saved || h->law == MHIP_FILAMENT_CONTACT_HERTZ, MHIP_ERR_RUNTIME,
+               "mhip_filament_contacts_force before mhip_filament_contacts_save_velocity");
   MHIP_REQUIRE(h->has_list, MHIP_ERR_RUNTIME, "mhip_filament_contacts_force before mhip_filament_contacts_update");
   if (int e = mhip_filament_contacts_linker_pass(h, dt, stats)) return e;
   return mhip_filament_contacts_reduce(h, external_force);
@@ -453,6 +474,14 @@ int mhip_filament_contacts_get(mhip_filament_contacts_t h, mhip_filament_contact
   out->seg = h->seg.as<double>();
   out->aabb = h->aabb.as<double>();
   out->velocity_prev = h->vel_prev.as<double>();
+  return MHIP_SUCCESS;
+}
+
+int mhip_filament_contacts_set_law(mhip_filament_contacts_t h, int law) {
+  MHIP_REQUIRE(law == MHIP_FILAMENT_CONTACT_FRICTIONAL || law == MHIP_FILAMENT_CONTACT_HERTZ, MHIP_ERR_INVALID_ARGUMENT,
+               "unknown filament contact law %d", law);
+  MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "filament contacts handle is null");
+  h->law = law;
   return MHIP_SUCCESS;
 }
 

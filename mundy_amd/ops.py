@@ -2080,6 +2080,32 @@ def check_filaments(node_ptr, radius, rest_curvature, arclength, phase, youngs_m
     return np.ascontiguousarray(ptr, dtype=np.int32), r, kr, s, ph, prm
 
 
+def check_filament_inertial(num_filaments, density, damping="critical", fixed_filaments=None):
+    """host-side validation of Filaments.set_inertial (no library call) -> (capi.FilamentInertialParams, the mask as
+    uint8 [F] / None)"""
+    rho = float(density)
+    if not (math.isfinite(rho) and rho > 0.0):
+        raise ValueError("density must be finite and > 0, got %r" % (density,))
+    if isinstance(damping, str):
+        if damping != "critical":
+            raise ValueError('damping must be "critical" or (translational, twist), got %r' % (damping,))
+        prm = capi.FilamentInertialParams(rho, capi.FILAMENT_DAMPING_CRITICAL, 0.0, 0.0)
+    else:
+        if not (isinstance(damping, (tuple, list)) and len(damping) == 2):
+            raise ValueError('damping must be "critical" or (translational, twist), got %r' % (damping,))
+        ct, cr = _finite_nonneg(damping[0], "damping[0]"), _finite_nonneg(damping[1], "damping[1]")
+        prm = capi.FilamentInertialParams(rho, capi.FILAMENT_DAMPING_CONSTANT, ct, cr)
+    fixed = None
+    if fixed_filaments is not None:
+        fixed = fixed_filaments.detach().cpu().numpy() if isinstance(fixed_filaments, torch.Tensor) else fixed_filaments
+        fixed = np.asarray(fixed)
+        if fixed.shape != (num_filaments,) or fixed.dtype.kind not in "biu":
+            raise ValueError("fixed_filaments must be a mask of shape [%d], got %s %s"
+                             % (num_filaments, fixed.dtype, fixed.shape))
+        fixed = np.ascontiguousarray(fixed != 0, dtype=np.uint8)
+    return prm, fixed
+
+
 class Filaments(_Handle):
     """F centerline-twist filaments over N nodes (mhip_filaments_*): the state lives in the handle.  wave: None, or
     dict(amplitude, wave_number, frequency) of the travelling rest-curvature wave (phase [F] keys it per filament).
@@ -2147,8 +2173,60 @@ class Filaments(_Handle):
     def velocity(self):
         capi.check(capi.load().mhip_filaments_velocity(self._h))
 
+    # ---- inertial nodes (include/mundy_hip_filament_inertial.h) -------------------------------------------------------
+    def set_inertial(self, density, damping="critical", fixed_filaments=None):
+        """nodes with mass: per step predict(dt) -> force(time, external) -> correct(dt).  damping: "critical"
+        (c_t = c_r = sqrt(m E), CollidingFrictionalSperm.cpp) or the constants (c_t, c_r) (CollidingSperm.cpp);
+        fixed_filaments: None or a mask [F] of the filaments that do not move"""
+        prm, fixed = check_filament_inertial(self.num_filaments, density, damping, fixed_filaments)
+        capi.check(capi.load().mhip_filaments_set_inertial(
+            self._h, C.byref(prm), None if fixed is None else fixed.ctypes.data_as(C.c_void_p)))
+        self.inertial = prm
+
+    def set_motion(self, velocity=None, twist_velocity=None, acceleration=None, twist_acceleration=None):
+        """device tensors [N, 3], [N], [N, 3], [N]; None: zeros"""
+        n = self.n
+        for name, t, shape in (("velocity", velocity, (n, 3)), ("twist_velocity", twist_velocity, (n,)),
+                               ("acceleration", acceleration, (n, 3)), ("twist_acceleration", twist_acceleration, (n,))):
+            if t is not None and tuple(t.shape) != shape:
+                raise ValueError("%s must have shape %s, got %s" % (name, list(shape), tuple(t.shape)))
+        capi.check(capi.load().mhip_filaments_set_motion(
+            self._h, _ptr(velocity, allow_none=True, name="velocity"),
+            _ptr(twist_velocity, allow_none=True, name="twist_velocity"),
+            _ptr(acceleration, allow_none=True, name="acceleration"),
+            _ptr(twist_acceleration, allow_none=True, name="twist_acceleration")))
+
+    def predict(self, dt):
+        capi.check(capi.load().mhip_filaments_predict(self._h, float(dt)))
+
+    def correct(self, dt, kinetic_energy=None):
+        """kinetic_energy: None, or a float64 device tensor whose first element receives the sum"""
+        capi.check(capi.load().mhip_filaments_correct(self._h, float(dt), _ptr(kinetic_energy, allow_none=True,
+                                                                               name="kinetic_energy")))
+
+    def kinetic_energy(self, out=None):
+        """the kinetic energy of the current velocities -> float64 [1] on the device"""
+        if out is None:
+            out = torch.empty(1, dtype=torch.float64, device="cuda")
+        capi.check(capi.load().mhip_filaments_kinetic_energy(self._h, _ptr(out, name="out")))
+        return out
+
+    def set_youngs_modulus(self, youngs_modulus):
+        capi.check(capi.load().mhip_filaments_set_youngs_modulus(self._h, float(youngs_modulus)))
+        self.params.youngs_modulus = float(youngs_modulus)
+
     def field(self, name):
-        """a copy of one field (capi.FILAMENT_FIELDS) as a device tensor"""
+        """a copy of one field (capi.FILAMENT_FIELDS, "acceleration", "twist_acceleration") as a device tensor"""
+        if name in ("acceleration", "twist_acceleration"):
+            got = capi.FilamentInertialFields()
+            capi.check(capi.load().mhip_filaments_get_inertial(self._h, C.byref(got)))
+            if not getattr(got, name):
+                raise RuntimeError("%s before set_inertial" % name)
+            w = 3 if name == "acceleration" else 1
+            out = torch.empty((self.n, w) if w > 1 else (self.n,), dtype=torch.float64, device="cuda")
+            if self.n:
+                capi.check(capi.load().mhip_deep_copy(self.n * w, _ptr(out), C.c_void_p(getattr(got, name)), _stream()))
+            return out
         if name not in capi.FILAMENT_FIELDS:
             raise ValueError("unknown filament field %r" % (name,))
         fields = capi.FilamentFields()
@@ -2162,10 +2240,16 @@ class Filaments(_Handle):
 
 
 # ---- frictional Hertzian contacts between filament segments (mhip_filament_contacts_*) ---------------------------------
+FILAMENT_CONTACT_LAWS = {"frictional": capi.FILAMENT_CONTACT_FRICTIONAL, "hertz": capi.FILAMENT_CONTACT_HERTZ}
+
+
 def check_filament_contacts(n, skin, youngs_modulus, poisson_ratio, mu, damping=(0.0, 0.0), density=1.0,
-                            segment_radius=None, history_dt=None, bonded_exclusion=1):
+                            segment_radius=None, history_dt=None, bonded_exclusion=1, law="frictional"):
     """host-side validation of a contact stage over n nodes (no library call) -> (capi.FilamentContactParams without the
-    monolayer flag, segment_radius [n] / None)"""
+    monolayer flag, segment_radius [n] / None).  law: "frictional", or "hertz", the frictionless law
+    (mundy_hip_filament_inertial.h), which reads neither mu nor the dampings"""
+    if law not in FILAMENT_CONTACT_LAWS:
+        raise ValueError("law must be one of %s, got %r" % (", ".join(sorted(FILAMENT_CONTACT_LAWS)), law))
     def number(v, name, ok, what):
         v = float(v)
         if not (math.isfinite(v) and ok(v)):
@@ -2210,6 +2294,16 @@ class FilamentContacts(_Handle):
             None if r is None else r.ctypes.data_as(C.c_void_p), C.byref(prm), _stream()))
         self._h = h
         self.stats = torch.zeros(2, dtype=torch.float64, device="cuda")
+        self.law = "frictional"
+        if params.get("law", "frictional") != "frictional":
+            self.set_law(params["law"])
+
+    def set_law(self, law):
+        """"frictional" (the default) or "hertz": the frictionless law, which needs no save_velocity"""
+        if law not in FILAMENT_CONTACT_LAWS:
+            raise ValueError("law must be one of %s, got %r" % (", ".join(sorted(FILAMENT_CONTACT_LAWS)), law))
+        capi.check(capi.load().mhip_filament_contacts_set_law(self._h, FILAMENT_CONTACT_LAWS[law]))
+        self.law = law
 
     def save_velocity(self):
         capi.check(capi.load().mhip_filament_contacts_save_velocity(self._h))

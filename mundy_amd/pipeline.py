@@ -156,6 +156,7 @@ class StepStats:
     active_switches: tuple = (0, 0)      # ... springs that switched (on, off) this step
     max_stretch: float = 0.0               # FilamentStepper: the largest |l - l0| / l0 over the edges at the force evaluation
     max_curvature_deviation: float = 0.0   # ... the largest component of |kappa - kappa_rest| over the elements
+    kinetic_energy: float = 0.0            # ... dynamics=: the kinetic energy of the velocities the corrector wrote
     num_pairs: int = 0  # FilamentStepper(contacts=): segment pairs in the neighbour list (max_overlap, num_sliding, rebuilt too)
     max_segment_overlap: float = 0.0   # backbone_collision=: max(0, -sep) over the force branch, corrected end segments included
     segment_contacts: int = 0          # ... segment pairs in the force branch at this step's force evaluation
@@ -1439,30 +1440,49 @@ class FilamentStepper:
     [N, 4] (w, x, y, z; by left node: synth.filaments builds the reference's initial triad), arclength [N]; twist and
     rest_curvature default to 0; wave = dict(amplitude, wave_number, frequency) with phase [F].  Host arrays or tensors.
     contacts = None, or dict(skin, youngs_modulus, poisson_ratio, mu, damping=(0, 0), density=1.0, segment_radius=None,
-    history_dt=None, bonded_exclusion=1): frictional Hertzian contacts between the segments (ops.FilamentContacts), whose
-    node forces, added to the caller's external_force, enter the filament forces."""
+    history_dt=None, bonded_exclusion=1, law="frictional"): Hertzian contacts between the segments (ops.FilamentContacts),
+    frictional or, with law="hertz", frictionless, whose node forces, added to the caller's external_force, enter the
+    filament forces.
+    dynamics = None: the overdamped step.  dynamics = dict(density, damping="critical" | (c_t, c_r), fixed_filaments=None):
+    nodes with mass, stepped by the Newmark predictor / corrector of CollidingFrictionalSperm.cpp:1890-1948 and
+    CollidingSperm.cpp (ops.Filaments.set_inertial); equilibrate() is then the stiffness ramp of the former.  Frictional
+    contacts are accepted with dynamics: the seam (node_force as external_force) and the field the law reads (v(t), saved
+    before the predictor) are those of the overdamped app; the reference has that call commented out in its inertial
+    loop (CollidingFrictionalSperm.cpp:1927), so there is no reference run of that combination.
+    Left out: clamp_edge1 (commented out in every loop of the reference), the two-component rest curvature of
+    CollidingFrictionalSperm.cpp:1072-1082 (the wave is the library's), periodic cells, several GPUs."""
 
     def __init__(self, node_ptr, center, radius, edge_orientation, arclength, *, twist=None, rest_curvature=None,
                  phase=None, youngs_modulus, poisson_ratio=0.3, rest_length, viscosity, wave=None, disable_twist=False,
-                 monolayer=False, contacts=None):
+                 monolayer=False, contacts=None, dynamics=None):
         n = int(np.asarray(node_ptr.cpu() if isinstance(node_ptr, torch.Tensor) else node_ptr)[-1])
         if rest_curvature is None:
             rest_curvature = np.zeros((n, 3))
         if contacts is not None:  # refused before anything is built
             ops.check_dict_spec(contacts, "contacts", ("skin", "youngs_modulus", "poisson_ratio", "mu", "damping", "density",
-                                                       "segment_radius", "history_dt", "bonded_exclusion"),
-                                optional=("damping", "density", "segment_radius", "history_dt", "bonded_exclusion"))
+                                                       "segment_radius", "history_dt", "bonded_exclusion", "law"),
+                                optional=("damping", "density", "segment_radius", "history_dt", "bonded_exclusion", "law"))
             ops.check_filament_contacts(n, **contacts)
+        if dynamics is not None:
+            ops.check_dict_spec(dynamics, "dynamics", ("density", "damping", "fixed_filaments"),
+                                optional=("damping", "fixed_filaments"))
+            num_filaments = len(node_ptr) - 1
+            ops.check_filament_inertial(num_filaments, **dynamics)
         self.filaments = ops.Filaments(node_ptr, radius, rest_curvature, arclength, phase, youngs_modulus=youngs_modulus,
                                        poisson_ratio=poisson_ratio, rest_length=rest_length, viscosity=viscosity,
                                        wave=wave, disable_twist=disable_twist, monolayer=monolayer)
         dev = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(  # noqa: E731
             a, dtype=np.float64))).to(device="cuda", dtype=torch.float64).contiguous()
         self.n = n
+        self.youngs_modulus = float(youngs_modulus)
+        self.dynamics = dynamics
+        if dynamics is not None:
+            self.filaments.set_inertial(**dynamics)
         self.filaments.set_state(dev(center), dev(np.zeros(n) if twist is None else twist), dev(edge_orientation))
         self.step_index = 0
-        # (max_stretch, max_curvature_deviation, max_overlap, num_sliding as int64 bits): one host read per step
-        self._stats = torch.zeros(4, dtype=torch.float64, device="cuda")
+        # (max_stretch, max_curvature_deviation, max_overlap, num_sliding as int64 bits, kinetic_energy): one host read
+        # per step
+        self._stats = torch.zeros(5, dtype=torch.float64, device="cuda")
         self.contacts = None if contacts is None else ops.FilamentContacts(self.filaments, **contacts)
 
     def close(self):
@@ -1476,23 +1496,78 @@ class FilamentStepper:
     def step(self, dt, external_force=None, read_stats=True):
         """advance -> forces at x(t + dt), time = step_index * dt as the reference counts it -> velocities.  With
         contacts: save_velocity -> advance -> update -> contact force (with external_force) -> forces -> velocities.
+        With dynamics: save_velocity (frictional contacts only) -> predict -> update -> contact force -> forces ->
+        correct, which also sums the kinetic energy.
         read_stats=False skips the one host read of the step (the statistics then stay at their defaults)."""
         f, c = self.filaments, self.contacts
+        inertial = self.dynamics is not None
         st = StepStats(num_bodies=self.n)
-        if c is not None:
+        if c is not None and c.law == "frictional":
             c.save_velocity()
-        f.advance(dt)
+        if inertial:
+            f.predict(dt)
+        else:
+            f.advance(dt)
         if c is not None:
             st.rebuilt = c.update()
-            c.force(dt, external_force, self._stats[2:])
+            c.force(dt, external_force, self._stats[2:4])
             external_force = c.node_force_ptr()
         f.force(self.step_index * float(dt), external_force, self._stats[:2])
-        f.velocity()
+        if inertial:
+            f.correct(dt, self._stats[4:])
+        else:
+            f.velocity()
         self.step_index += 1
         if read_stats:
             got = self._stats.cpu()
             st.max_stretch, st.max_curvature_deviation = float(got[0]), float(got[1])
+            if inertial:
+                st.kinetic_energy = float(got[4])
             if c is not None:
                 st.max_overlap, st.num_sliding = float(got[2]), int(got.view(torch.int64)[3])
                 st.num_pairs = st.num_contacts = c.num_pairs
         return st
+
+    def equilibrate(self, dt, relaxed_youngs_modulus, threshold=1e-6, growth=1.1, poll_every=1, max_steps=1000000):
+        """The stiffness ramp of CollidingFrictionalSperm.cpp:1781-1865 (`equilibriate`): E = relaxed_youngs_modulus;
+        while E < the stepper's modulus: inertial steps without contacts until the kinetic energy is <= threshold (at
+        least one step per level), then E *= growth.  step_index is not advanced, so a wave stays frozen at its current
+        time (the reference does not propagate it there).  On return the modulus is the stepper's own again.
+        poll_every: the one liberty taken -- the kinetic energy (8 bytes) is read once per poll_every steps, so a level
+        ends at the first multiple of poll_every at which it is <= threshold; 1 is the reference's loop.  max_steps: the
+        most steps of the whole ramp; one more raises RuntimeError (the reference would spin).  -> the steps per level."""
+        if self.dynamics is None:
+            raise RuntimeError("equilibrate needs dynamics=")
+        E = float(relaxed_youngs_modulus)
+        if not (math.isfinite(E) and E > 0.0):
+            raise ValueError("relaxed_youngs_modulus must be finite and > 0, got %r" % (relaxed_youngs_modulus,))
+        if not (math.isfinite(float(growth)) and float(growth) > 1.0):
+            raise ValueError("growth must be finite and > 1, got %r" % (growth,))
+        if isinstance(poll_every, bool) or not isinstance(poll_every, (int, np.integer)) or poll_every < 1:
+            raise ValueError("poll_every must be an integer >= 1, got %r" % (poll_every,))
+        if isinstance(max_steps, bool) or not isinstance(max_steps, (int, np.integer)) or max_steps < 1:
+            raise ValueError("max_steps must be an integer >= 1, got %r" % (max_steps,))
+        f = self.filaments
+        time = self.step_index * float(dt)
+        levels, total = [], 0
+        try:
+            while E < self.youngs_modulus:
+                f.set_youngs_modulus(E)
+                count = 0
+                energy = float("inf")
+                while energy > float(threshold):
+                    if total + poll_every > max_steps:
+                        raise RuntimeError("equilibrate: the kinetic energy is %r > %r after %d steps (max_steps) at "
+                                           "E = %r" % (energy, threshold, total, E))
+                    for _ in range(int(poll_every)):
+                        f.predict(dt)
+                        f.force(time, None, self._stats[:2])
+                        f.correct(dt, self._stats[4:])
+                    count += int(poll_every)
+                    total += int(poll_every)
+                    energy = float(self._stats[4:].cpu()[0])
+                levels.append(count)
+                E *= float(growth)
+        finally:
+            f.set_youngs_modulus(self.youngs_modulus)
+        return levels
