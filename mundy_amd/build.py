@@ -10,7 +10,7 @@ LIB = os.path.join(HERE, "lib", "libmundy_hip.so")
 SOURCES = ["runtime.hip", "sort.hip", "geometry.hip", "broadphase.hip", "convex.hip", "reorder.hip", "halo.hip", "ellipsoid.hip", "mixed.hip", "mixed_fma.hip", "dist.hip", "hertz.hip", "hertz_friction.hip", "growth.hip", "chain.hip", "crosslink.hip", "periphery.hip", "active.hip", "filament.hip", "filament_contact.hip", "hydro.hip", "hydro_periphery.hip", "segment_contact.hip"]
 # per-source flag substitutions: the contracted build of the ellipsoid minimisation classes (see mixed_fma.hip)
 FLAG_OVERRIDES = {"mixed_fma.hip": {"-ffp-contract=off": "-ffp-contract=fast"}}
-HEADERS = ["mhip_internal.hpp", "geom_device.hpp", "ellipsoid_device.hpp", "ellipsoid_lockstep.hpp", "segment_ellipsoid.hpp", "force_device.hpp", "scratch_owner.hpp", os.path.join("..", "..", "include", "mundy_hip.h"), os.path.join("..", "..", "include", "mundy_hip_hydro_periphery.h"),
+HEADERS = ["mhip_internal.hpp", "geom_device.hpp", "ellipsoid_device.hpp", "ellipsoid_lockstep.hpp", "segment_ellipsoid.hpp", "force_device.hpp", "segment_linkers.hpp", "scratch_owner.hpp", os.path.join("..", "..", "include", "mundy_hip.h"), os.path.join("..", "..", "include", "mundy_hip_hydro_periphery.h"),
            os.path.join("..", "..", "include", "mundy_hip_contact_force.h"),
            os.path.join("..", "..", "include", "mundy_hip_periphery_binding.h"),
            os.path.join("..", "..", "include", "mundy_hip_segment_contact.h"),

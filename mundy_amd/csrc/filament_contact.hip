@@ -11,9 +11,7 @@
 //   reduction      .../linker_potential_force_reduction/kernels/SpherocylinderSegment.cpp:193-221: a gather, no atomic on
 //                  a force; a tile of nodes per workgroup with a one-segment halo in LDS
 // Byte counts and the accumulation order: DESIGN.md 5k.
-#include "mhip_internal.hpp"
-#include "force_device.hpp"
-#include "geom_device.hpp"
+#include "segment_linkers.hpp"
 #include "../../include/mundy_hip_filament_inertial.h"
 
 #include <algorithm>
@@ -24,8 +22,7 @@ namespace mhip {
 
 constexpr int kTile = kBlock;
 
-// (SegmentRow, load_segment, segment_share and the row writers: force_device.hpp, shared with segment_contact.hip)
-// seg[i] = (x_i, x_{i+1}, r_i, 0) and the reference's buffered box; a filament's last node: (x_i, x_i, r_i, 0)
+// seg[i] = (x_i, x_{i+1}, r_i, 0) and the box of reach r_i; a filament's last node: (x_i, x_i, r_i, 0)
 __global__ void __launch_bounds__(kBlock)
     k_segment_view(size_t n, const uint8_t* __restrict__ has_right, const double* __restrict__ x,
                    const double* __restrict__ radius, double skin, double* __restrict__ seg, double* __restrict__ aabb) {
@@ -33,15 +30,7 @@ __global__ void __launch_bounds__(kBlock)
     const V3 x0 = load3(x, i);
     const V3 x1 = has_right[i] ? load3(x, i + 1) : x0;  // has_right: i + 1 < n
     const double r = radius[i];
-    double2* q = reinterpret_cast<double2*>(seg + 8 * i);
-    q[0] = make_double2(x0.x, x0.y);
-    q[1] = make_double2(x0.z, x1.x);
-    q[2] = make_double2(x1.y, x1.z);
-    q[3] = make_double2(r, 0.0);
-    const Box b = aabb_segment(x0, x1, r);  // min - r, max + r; then the skin (:156-161)
-    double* o = aabb + 6 * i;
-    o[0] = b.lo.x - skin, o[1] = b.lo.y - skin, o[2] = b.lo.z - skin;
-    o[3] = b.hi.x + skin, o[4] = b.hi.y + skin, o[5] = b.hi.z + skin;
+    store_segment_view(seg, aabb, i, x0, x1, r, r, skin);
   }
 }
 
@@ -79,55 +68,40 @@ __global__ void __launch_bounds__(kBlock)
   double dmax = 0.0;
   unsigned capped = 0;
   for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < C; c += (size_t)gridDim.x * blockDim.x) {
-    // the list is read once per step
-    const int2 p{__builtin_nontemporal_load(pairs + 2 * c), __builtin_nontemporal_load(pairs + 2 * c + 1)};
+    const int2 p = load_pair_once(pairs, c);
     // a segment's right node is p + 1: row N - 1 is the last node of the last filament, never a segment
-    if (N < 2 || static_cast<unsigned>(p.x) >= N - 1 || static_cast<unsigned>(p.y) >= N - 1) {  // never dereferenced
-      sep[c] = __builtin_nan("");
+    if (N < 2 || static_cast<unsigned>(p.x) >= N - 1 || static_cast<unsigned>(p.y) >= N - 1) {
+      refuse_linker(sep, force, share, c);
       store_row_nan(tang_disp, c);
-      store_row_nan(force, c);
-      store_row_nan(share, 2 * c);
-      store_row_nan(share, 2 * c + 1);
       continue;
     }
-    const SegmentRow a = load_segment(seg, p.x), b = load_segment(seg, p.y);
-    const SegSeg r = dist_segment_segment(a.p0, a.p1, b.p0, b.p1);
-    const double s = r.dist - (a.r + b.r);
+    const SegmentLinker k = measure_linker(seg, p);
+    const double s = k.s;
     sep[c] = s;
     // no contact: the history is reset (FHC :433-435), force and shares are +0.0
     if (FRICTION ? s > 0.0 : !(s < 0.0)) {
       reset_row(tang_disp, c);
-      reset_row(force, c);
-      reset_row(share, 2 * c);
-      reset_row(share, 2 * c + 1);
+      reset_linker(force, share, c);
       continue;
     }
-    const V3 n = (r.cp2 - r.cp1) * (1.0 / r.dist);  // left to right (linker kernel :226)
+    const V3 n = k.normal();
     if (!FRICTION) {
-      const double Rs = (a.r * b.r) / (a.r + b.r);
-      const double Es = (E0 * E0) / (E0 - E0 * nu0 * nu0 + E0 - E0 * nu0 * nu0);
-      const V3 F = (-hertz_force_magnitude(Es, Rs, s)) * n;  // :225
       reset_row(tang_disp, c);
-      store3(force, c, F);
-      store3(share, 2 * c, segment_share(a.p0, a.p1, r.cp1, F));
-      store3(share, 2 * c + 1, segment_share(b.p0, b.p1, r.cp2, V3{-F.x, -F.y, -F.z}));
+      store_linker_force(force, share, c, k, (-segment_hertz(E0, nu0, k.a.r, k.b.r, s)) * n);  // :225
       dmax = -s > dmax ? -s : dmax;
       continue;
     }
-    const V3 vi = segment_point_velocity(a.p0, a.p1, load3(vel_prev, p.x), load3(vel_prev, (size_t)p.x + 1), r.cp1);
-    const V3 vj = segment_point_velocity(b.p0, b.p1, load3(vel_prev, p.y), load3(vel_prev, (size_t)p.y + 1), r.cp2);
+    const V3 vi = segment_point_velocity(k.a.p0, k.a.p1, load3(vel_prev, p.x), load3(vel_prev, (size_t)p.x + 1), k.r.cp1);
+    const V3 vj = segment_point_velocity(k.b.p0, k.b.p1, load3(vel_prev, p.y), load3(vel_prev, (size_t)p.y + 1), k.r.cp2);
     HertzPair h;  // hertz_pair's expressions, the radii being the segments' and the material one scalar pair
-    h.ri = a.r, h.rj = b.r;
+    h.ri = k.a.r, h.rj = k.b.r;
     h.Ei = E0, h.Ej = E0, h.vi = nu0, h.vj = nu0;
     h.Rs = (h.ri * h.rj) / (h.ri + h.rj);
     h.Es = (h.Ei * h.Ej) / (h.Ej - h.Ej * h.vi * h.vi + h.Ei - h.Ei * h.vj * h.vj);
-    const FrictionContact k = hertz_friction_law(vj - vi, n, s, h, prm, load3(tang_disp, c));
-    capped += k.capped ? 1u : 0u;
-    const V3 F = k.force;
-    store3(tang_disp, c, k.td);
-    store3(force, c, F);  // on the left segment; the right one receives the negative
-    store3(share, 2 * c, segment_share(a.p0, a.p1, r.cp1, F));
-    store3(share, 2 * c + 1, segment_share(b.p0, b.p1, r.cp2, V3{-F.x, -F.y, -F.z}));
+    const FrictionContact f = hertz_friction_law(vj - vi, n, s, h, prm, load3(tang_disp, c));
+    capped += f.capped ? 1u : 0u;
+    store3(tang_disp, c, f.td);
+    store_linker_force(force, share, c, k, f.force);
     dmax = -s > dmax ? -s : dmax;
   }
   block_stat_max(dmax, stats);
@@ -135,8 +109,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // Per tile of kTile nodes [s, s + kTile): the sums (a0, a1) of the segments s - 1 .. s + kTile - 1 are formed once each
-// into LDS -- a0[e] = +0.0 + sum of (Fs - share), a1[e] = +0.0 + sum of share over the segment's entries in ascending
-// order (entries of separated linkers, whose rows are +0.0, are passed over: the same bits) -- then node i adds
+// into LDS by sum_segment_entries (a separated linker, sep > 0, is passed over) -- then node i adds
 // ((external or +0.0) + a0[i]) + a1[i - 1], a term whose segment does not exist left out.
 // A segment's sums are one function of the same inputs in whichever tile they are formed.
 template <bool EXTERNAL>
@@ -152,24 +125,11 @@ __global__ void __launch_bounds__(kBlock)
     const long long s = tile * kTile;
     for (int k = tid; k < kTile + 1; k += kBlock) {
       const long long e = s - 1 + k;
-      V3 a0{0.0, 0.0, 0.0}, a1{0.0, 0.0, 0.0};
-      if (e >= 0 && e < n) {
-        const int32_t lo = ptr[e], hi = ptr[e + 1];
-        for (int32_t j = lo; j < hi; ++j) {
-          const int32_t en = ent[j];
-          const size_t c = static_cast<size_t>(en >> 1);
-          // A separated linker's rows are +0.0 (the linker pass of this step saw to it), and a sum that started from
-          // +0.0 is never -0.0: adding them changes no bit, so 8 bytes of sep stand for 48 bytes of rows.
-          if (sep[c] > 0.0) continue;
-          const V3 F = load3(force, c);
-          const V3 Fs = (en & 1) ? V3{-F.x, -F.y, -F.z} : F;
-          const V3 sm = load3(share, static_cast<size_t>(en));  // row 2 c + side
-          a0 = a0 + (Fs - sm);
-          a1 = a1 + sm;
-        }
-      }
-      A[0][k] = a0.x, A[1][k] = a0.y, A[2][k] = a0.z;
-      A[3][k] = a1.x, A[4][k] = a1.y, A[5][k] = a1.z;
+      SegmentSums q{{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+      if (e >= 0 && e < n)  // 8 bytes of sep stand for a separated linker's rows
+        q = sum_segment_entries(ptr, ent, static_cast<size_t>(e), force, share, [&](size_t c) { return sep[c] > 0.0; });
+      A[0][k] = q.a0.x, A[1][k] = q.a0.y, A[2][k] = q.a0.z;
+      A[3][k] = q.a1.x, A[4][k] = q.a1.y, A[5][k] = q.a1.z;
     }
     __syncthreads();
     const long long i = s + tid;
@@ -192,18 +152,12 @@ struct mhip_filament_contacts {
   size_t n = 0;
   mhip_filament_contact_params prm{};
   hipStream_t stream = nullptr;
-  mhip_broadphase_t bp = nullptr;
-  bool saved = false, has_list = false;
+  bool saved = false;
   int law = MHIP_FILAMENT_CONTACT_FRICTIONAL;  // mundy_hip_filament_inertial.h
-  int cur = 0;           // which copy of (pairs, hist) is the current list
-  size_t c = 0;          // its length (before the first update: the length of a planted list)
-  HandleBuffer has_right, radius, ex_ptr, ex_idx;
-  HandleBuffer seg, aabb, aabb_ref, vel_prev, node_force;
-  HandleBuffer pairs[2], hist[2], sep, force, share;
-  HandleBuffer inc_ptr, inc_ent, cursor, ws;
-  ~mhip_filament_contacts() {
-    if (bp) (void)mhip_broadphase_destroy(bp);
-  }
+  int cur = 0;                                 // which copy of (pairs, hist) is the current list, of length list.c
+  LinkerList list;
+  HandleBuffer has_right, radius, vel_prev, node_force;
+  HandleBuffer pairs[2], hist[2];
 };
 
 extern "C" {
@@ -215,12 +169,7 @@ int mhip_filament_contacts_create(mhip_filament_contacts_t* handle, mhip_filamen
   *handle = nullptr;
   MHIP_REQUIRE(params != nullptr, MHIP_ERR_INVALID_ARGUMENT, "params is null");
   const mhip_filament_contact_params& p = *params;
-  MHIP_REQUIRE(std::isfinite(p.skin) && p.skin >= 0.0, MHIP_ERR_INVALID_ARGUMENT, "skin must be finite and >= 0, got %g",
-               p.skin);
-  MHIP_REQUIRE(std::isfinite(p.youngs_modulus) && p.youngs_modulus > 0.0, MHIP_ERR_INVALID_ARGUMENT,
-               "youngs_modulus must be finite and > 0, got %g", p.youngs_modulus);
-  MHIP_REQUIRE(p.poisson_ratio > 0.0 && p.poisson_ratio < 1.0, MHIP_ERR_INVALID_ARGUMENT,
-               "poisson_ratio must lie in (0, 1), got %g", p.poisson_ratio);
+  if (int e = check_linker_params(p.skin, p.youngs_modulus, p.poisson_ratio, true)) return e;
   MHIP_REQUIRE(std::isfinite(p.mu) && p.mu >= 0.0, MHIP_ERR_INVALID_ARGUMENT, "mu must be finite and >= 0, got %g", p.mu);
   MHIP_REQUIRE(std::isfinite(p.normal_damping) && p.normal_damping >= 0.0 && std::isfinite(p.tangential_damping) &&
                    p.tangential_damping >= 0.0,
@@ -242,8 +191,7 @@ int mhip_filament_contacts_create(mhip_filament_contacts_t* handle, mhip_filamen
     MHIP_REQUIRE(node_ptr[f + 1] - node_ptr[f] >= 2, MHIP_ERR_INVALID_ARGUMENT, "filament %zu has fewer than 2 nodes", f);
   if (segment_radius)
     for (size_t i = 0; i < n; ++i)
-      MHIP_REQUIRE(std::isfinite(segment_radius[i]) && segment_radius[i] > 0.0, MHIP_ERR_INVALID_ARGUMENT,
-                   "segment %zu: radius must be finite and > 0, got %g", i, segment_radius[i]);
+      if (int e = check_segment_radius(i, segment_radius[i])) return e;
   // who may pair with whom: every real segment is source and target; segments at most bonded_exclusion apart along one
   // filament never pair (DestroyBoundNeighbors.cpp:150-170 for 1)
   std::vector<uint8_t> has_right(n, 0);
@@ -266,20 +214,14 @@ int mhip_filament_contacts_create(mhip_filament_contacts_t* handle, mhip_filamen
   h->prm = p;
   hipStream_t s = as_stream(stream);
   h->stream = s;
-  if (int e = mhip_broadphase_create(&h->bp)) return e;
   const size_t d = sizeof(double);
   int e = MHIP_SUCCESS;
+  if ((e = h->list.create(__func__, n, n, ex_ptr, ex_idx, s))) return e;
   if ((e = h->has_right.reserve(n + 8)) || (e = h->radius.reserve(n * d + 8)) ||
-      (e = h->ex_ptr.reserve((n + 1) * sizeof(int32_t))) || (e = h->ex_idx.reserve(ex_idx.size() * sizeof(int32_t) + 8)) ||
-      (e = h->seg.reserve(8 * n * d + 8)) || (e = h->aabb.reserve(6 * n * d + 8)) ||
-      (e = h->aabb_ref.reserve(6 * n * d + 8)) || (e = h->vel_prev.reserve(3 * n * d + 8)) ||
-      (e = h->node_force.reserve(3 * n * d + 8)) || (e = h->inc_ptr.reserve((n + 1) * sizeof(int32_t))) ||
-      (e = h->cursor.reserve((n + 1) * sizeof(int32_t))) || (e = h->ws.reserve(scan_workspace_bytes(n) + 8)))
+      (e = h->vel_prev.reserve(3 * n * d + 8)) || (e = h->node_force.reserve(3 * n * d + 8)))
     return e;
-  if ((e = upload(__func__, h->ex_ptr, ex_ptr.data(), (n + 1) * sizeof(int32_t), s))) return e;
   if (n > 0) {
     if ((e = upload(__func__, h->has_right, has_right.data(), n, s))) return e;
-    if (!ex_idx.empty() && (e = upload(__func__, h->ex_idx, ex_idx.data(), ex_idx.size() * sizeof(int32_t), s))) return e;
     if (segment_radius) {
       if ((e = upload(__func__, h->radius, segment_radius, n * d, s))) return e;
     } else {
@@ -288,10 +230,8 @@ int mhip_filament_contacts_create(mhip_filament_contacts_t* handle, mhip_filamen
     MHIP_HIP(hipMemsetAsync(h->vel_prev.ptr, 0, 3 * n * d, s));
     MHIP_HIP(hipMemsetAsync(h->node_force.ptr, 0, 3 * n * d, s));
   }
-  if ((e = mhip_broadphase_set_sets(h->bp, n, h->has_right.as<unsigned char>(), h->has_right.as<unsigned char>(), stream)))
-    return e;
-  if ((e = mhip_broadphase_set_exclusions(h->bp, n, h->ex_ptr.as<int32_t>(), h->ex_idx.as<int32_t>(), ex_idx.size(),
-                                          stream)))
+  if ((e = mhip_broadphase_set_sets(h->list.bp, n, h->has_right.as<unsigned char>(), h->has_right.as<unsigned char>(),
+                                    stream)))
     return e;
   // the host arrays built here may go as soon as this returns
   if ((e = hip_status(__func__, hipStreamSynchronize(s)))) return e;
@@ -324,8 +264,8 @@ int mhip_filament_contacts_segment_view(mhip_filament_contacts_t h) {
   if (int e = mhip_filaments_get(h->filaments, &fields)) return e;
   if (h->n == 0) return MHIP_SUCCESS;
   k_segment_view<<<grid_for(h->n), kBlock, 0, h->stream>>>(h->n, h->has_right.as<uint8_t>(), fields.center,
-                                                           h->radius.as<double>(), h->prm.skin, h->seg.as<double>(),
-                                                           h->aabb.as<double>());
+                                                           h->radius.as<double>(), h->prm.skin, h->list.seg.as<double>(),
+                                                           h->list.aabb.as<double>());
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
 }
@@ -337,48 +277,24 @@ int mhip_filament_contacts_update(mhip_filament_contacts_t h, int* rebuilt) {
   if (int e = mhip_filament_contacts_segment_view(h)) return e;
   mhip_filament_fields fields;
   if (int e = mhip_filaments_get(h->filaments, &fields)) return e;
-  const size_t n = h->n, d = sizeof(double);
+  const size_t n = h->n;
   hipStream_t s = h->stream;
-  mhip_stream_t ms = reinterpret_cast<mhip_stream_t>(s);
+  LinkerList& l = h->list;
   int moved = 1;  // the first call builds
-  if (h->has_list)
-    if (int e = mhip_aabb_moved(n, h->aabb.as<double>(), h->aabb_ref.as<double>(), 0.5 * h->prm.skin, &moved, ms))
-      return e;
+  if (l.has_list)
+    if (int e = l.moved(n, h->prm.skin, &moved, s)) return e;
   if (!moved) return MHIP_SUCCESS;
   // rebuild (:1612-1717): every pair of box-overlapping segments that are not neighbours along a filament
-  mhip_broadphase_config cfg{};
-  cfg.search_kind = MHIP_SEARCH_AABB;
-  cfg.symmetric = 0;
-  cfg.buffer = 0.0;  // the boxes carry the skin
-  size_t c_new = 0;
-  if (int e = mhip_broadphase_build(h->bp, &cfg, n, h->aabb.as<double>(), fields.center, nullptr, &c_new, ms)) return e;
-  MHIP_REQUIRE(c_new < (1ull << 30), MHIP_ERR_RUNTIME, "too many linkers for 32-bit incidence entries");
   const int old = h->cur, nw = old ^ 1;
-  int e = MHIP_SUCCESS;
-  if ((e = h->pairs[nw].reserve(c_new * sizeof(int2) + 8)) || (e = h->hist[nw].reserve(3 * c_new * d + 8)) ||
-      (e = h->inc_ent.reserve(2 * c_new * sizeof(int32_t) + 8)))
+  if (int e = l.rebuild(n, fields.center, h->pairs[nw], s, [&](size_t c_new) {
+        // surviving linkers keep their tang_disp, new ones start from +0.0
+        if (int e = h->hist[nw].reserve(3 * c_new * sizeof(double) + 8)) return e;
+        return mhip_contact_history_carry(l.c, h->pairs[old].as<int32_t>(), h->hist[old].as<double>(), nullptr, n, c_new,
+                                          h->pairs[nw].as<int32_t>(), h->hist[nw].as<double>(), nullptr,
+                                          reinterpret_cast<mhip_stream_t>(s));
+      }))
     return e;
-  if ((e = mhip_broadphase_get_pairs(h->bp, h->pairs[nw].as<int32_t>(), nullptr, nullptr, ms))) return e;
-  // surviving linkers keep their tang_disp, new ones start from +0.0
-  if ((e = mhip_contact_history_carry(h->c, h->pairs[old].as<int32_t>(), h->hist[old].as<double>(), nullptr, n, c_new,
-                                      h->pairs[nw].as<int32_t>(), h->hist[nw].as<double>(), nullptr, ms)))
-    return e;
-  // (after the carry: sep, force and share of the old list are dead, and reserve may move the buffers)
-  if ((e = h->sep.reserve(c_new * d + 8)) || (e = h->force.reserve(3 * c_new * d + 8)) ||
-      (e = h->share.reserve(6 * c_new * d + 8)))
-    return e;
-  if (c_new > 0) {
-    MHIP_HIP(hipMemsetAsync(h->sep.ptr, 0, c_new * d, s));
-    MHIP_HIP(hipMemsetAsync(h->force.ptr, 0, 3 * c_new * d, s));
-    MHIP_HIP(hipMemsetAsync(h->share.ptr, 0, 6 * c_new * d, s));
-  }
-  if ((e = build_incidence(n, c_new, PairEnds{h->pairs[nw].as<int2>()}, h->cursor.as<int32_t>(), h->inc_ptr.as<int32_t>(),
-                           h->inc_ent.as<int32_t>(), h->ws.ptr, s)))
-    return e;
-  if (n > 0) MHIP_HIP(hipMemcpyAsync(h->aabb_ref.ptr, h->aabb.ptr, 6 * n * d, hipMemcpyDeviceToDevice, s));
   h->cur = nw;
-  h->c = c_new;
-  h->has_list = true;
   *rebuilt = 1;
   return MHIP_SUCCESS;
 }
@@ -389,19 +305,20 @@ int mhip_filament_contacts_linker_pass(mhip_filament_contacts_t h, double dt, vo
   MHIP_REQUIRE(std::isfinite(dt) && dt >= 0.0, MHIP_ERR_INVALID_ARGUMENT, "dt must be finite and >= 0, got %g", dt);
   MHIP_REQUIRE(h->saved || h->law == MHIP_FILAMENT_CONTACT_HERTZ, MHIP_ERR_RUNTIME,
                "mhip_filament_contacts_linker_pass before mhip_filament_contacts_save_velocity");
-  MHIP_REQUIRE(h->has_list, MHIP_ERR_RUNTIME, "mhip_filament_contacts_linker_pass before mhip_filament_contacts_update");
+  const LinkerList& l = h->list;
+  MHIP_REQUIRE(l.has_list, MHIP_ERR_RUNTIME, "mhip_filament_contacts_linker_pass before mhip_filament_contacts_update");
   hipStream_t s = h->stream;
   MHIP_HIP(hipMemsetAsync(stats, 0, 2 * sizeof(unsigned long long), s));
-  const size_t n = h->n, c = h->c;
+  const size_t n = h->n, c = l.c;
   if (n == 0 || c == 0) return MHIP_SUCCESS;
   const mhip_filament_contact_params& p = h->prm;
   const mhip_hertz_friction_params law{p.mu, p.normal_damping, p.tangential_damping, p.density,
                                        p.history_dt < 0.0 ? dt : p.history_dt};
   dispatch<true, false>(h->law == MHIP_FILAMENT_CONTACT_FRICTIONAL, [&](auto fr) {
     k_filament_linkers<decltype(fr)::value><<<grid_for(c), kBlock, 0, s>>>(
-        c, n, h->pairs[h->cur].as<int>(), h->seg.as<double>(), h->vel_prev.as<double>(), p.youngs_modulus,
-        p.poisson_ratio, law, h->sep.as<double>(), h->hist[h->cur].as<double>(), h->force.as<double>(),
-        h->share.as<double>(), static_cast<unsigned long long*>(stats));
+        c, n, h->pairs[h->cur].as<int>(), l.seg.as<double>(), h->vel_prev.as<double>(), p.youngs_modulus,
+        p.poisson_ratio, law, l.sep.as<double>(), h->hist[h->cur].as<double>(), l.force.as<double>(),
+        l.share.as<double>(), static_cast<unsigned long long*>(stats));
   });
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
@@ -409,14 +326,15 @@ int mhip_filament_contacts_linker_pass(mhip_filament_contacts_t h, double dt, vo
 
 int mhip_filament_contacts_reduce(mhip_filament_contacts_t h, const double* external_force) {
   MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "filament contacts handle is null");
-  MHIP_REQUIRE(h->has_list, MHIP_ERR_RUNTIME, "mhip_filament_contacts_reduce before mhip_filament_contacts_update");
+  const LinkerList& l = h->list;
+  MHIP_REQUIRE(l.has_list, MHIP_ERR_RUNTIME, "mhip_filament_contacts_reduce before mhip_filament_contacts_update");
   const size_t n = h->n;
   if (n == 0) return MHIP_SUCCESS;
   const long long tiles = static_cast<long long>((n + kTile - 1) / kTile);
   dispatch<true, false>(external_force != nullptr, [&](auto ex) {
     k_filament_contact_reduce<decltype(ex)::value><<<grid_for(n), kBlock, 0, h->stream>>>(
-        static_cast<long long>(n), tiles, h->has_right.as<uint8_t>(), h->inc_ptr.as<int32_t>(), h->inc_ent.as<int32_t>(),
-        h->sep.as<double>(), h->force.as<double>(), h->share.as<double>(), external_force, h->node_force.as<double>());
+        static_cast<long long>(n), tiles, h->has_right.as<uint8_t>(), l.inc_ptr.as<int32_t>(), l.inc_ent.as<int32_t>(),
+        l.sep.as<double>(), l.force.as<double>(), l.share.as<double>(), external_force, h->node_force.as<double>());
   });
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
@@ -427,7 +345,7 @@ int mhip_filament_contacts_force(mhip_filament_contacts_t h, double dt, const do
   MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "filament contacts handle is null");
   MHIP_REQUIRE(h->saved || h->law == MHIP_FILAMENT_CONTACT_HERTZ, MHIP_ERR_RUNTIME,
                "mhip_filament_contacts_force before mhip_filament_contacts_save_velocity");
-  MHIP_REQUIRE(h->has_list, MHIP_ERR_RUNTIME, "mhip_filament_contacts_force before mhip_filament_contacts_update");
+  MHIP_REQUIRE(h->list.has_list, MHIP_ERR_RUNTIME, "mhip_filament_contacts_force before mhip_filament_contacts_update");
   if (int e = mhip_filament_contacts_linker_pass(h, dt, stats)) return e;
   return mhip_filament_contacts_reduce(h, external_force);
 }
@@ -441,22 +359,22 @@ int mhip_filament_contacts_set_history(mhip_filament_contacts_t h, size_t c, con
   mhip_stream_t ms = reinterpret_cast<mhip_stream_t>(s);
   const size_t d = sizeof(double);
   int e = MHIP_SUCCESS;
-  if (!h->has_list) {  // a restart: the first update carries these rows into its list
+  if (!h->list.has_list) {  // a restart: the first update carries these rows into its list
     if ((e = h->pairs[h->cur].reserve(c * sizeof(int2) + 8)) || (e = h->hist[h->cur].reserve(3 * c * d + 8))) return e;
     if (c > 0) {
       MHIP_HIP(hipMemcpyAsync(h->pairs[h->cur].ptr, pairs, c * sizeof(int2), hipMemcpyDeviceToDevice, s));
       MHIP_HIP(hipMemcpyAsync(h->hist[h->cur].ptr, tang_disp, 3 * c * d, hipMemcpyDeviceToDevice, s));
     }
-    h->c = c;
+    h->list.c = c;
     return MHIP_SUCCESS;
   }
-  if (h->c == 0) return MHIP_SUCCESS;
+  if (h->list.c == 0) return MHIP_SUCCESS;
   HandleBuffer& tmp = h->hist[h->cur ^ 1];
-  if ((e = tmp.reserve(3 * h->c * d + 8))) return e;
-  if ((e = mhip_contact_history_carry(c, pairs, tang_disp, nullptr, h->n, h->c, h->pairs[h->cur].as<int32_t>(),
+  if ((e = tmp.reserve(3 * h->list.c * d + 8))) return e;
+  if ((e = mhip_contact_history_carry(c, pairs, tang_disp, nullptr, h->n, h->list.c, h->pairs[h->cur].as<int32_t>(),
                                       tmp.as<double>(), nullptr, ms)))
     return e;
-  MHIP_HIP(hipMemcpyAsync(h->hist[h->cur].ptr, tmp.ptr, 3 * h->c * d, hipMemcpyDeviceToDevice, s));
+  MHIP_HIP(hipMemcpyAsync(h->hist[h->cur].ptr, tmp.ptr, 3 * h->list.c * d, hipMemcpyDeviceToDevice, s));
   return MHIP_SUCCESS;
 }
 
@@ -464,15 +382,15 @@ int mhip_filament_contacts_get(mhip_filament_contacts_t h, mhip_filament_contact
   MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "filament contacts handle is null");
   MHIP_REQUIRE(out != nullptr, MHIP_ERR_INVALID_ARGUMENT, "fields is null");
   out->num_nodes = h->n;
-  out->num_pairs = h->has_list ? h->c : 0;
-  out->pairs = h->has_list ? h->pairs[h->cur].as<int32_t>() : nullptr;
-  out->sep = h->sep.as<double>();
-  out->tang_disp = h->has_list ? h->hist[h->cur].as<double>() : nullptr;
-  out->force = h->force.as<double>();
-  out->share = h->share.as<double>();
+  out->num_pairs = h->list.has_list ? h->list.c : 0;
+  out->pairs = h->list.has_list ? h->pairs[h->cur].as<int32_t>() : nullptr;
+  out->sep = h->list.sep.as<double>();
+  out->tang_disp = h->list.has_list ? h->hist[h->cur].as<double>() : nullptr;
+  out->force = h->list.force.as<double>();
+  out->share = h->list.share.as<double>();
   out->node_force = h->node_force.as<double>();
-  out->seg = h->seg.as<double>();
-  out->aabb = h->aabb.as<double>();
+  out->seg = h->list.seg.as<double>();
+  out->aabb = h->list.aabb.as<double>();
   out->velocity_prev = h->vel_prev.as<double>();
   return MHIP_SUCCESS;
 }

@@ -188,42 +188,14 @@ __device__ inline double pow_three_halves(double x) {
   return p + p_lo;
 }
 
-// ---- segment rows (filament_contact.hip, segment_contact.hip) ------------------------------------------------------
-// seg[i] = (p0, p1, r, 0): one 64-byte line, read as four double2
-struct SegmentRow {
-  V3 p0, p1;
-  double r;
-};
-__device__ inline SegmentRow load_segment(const double* __restrict__ seg, size_t i) {
-  const double2* q = reinterpret_cast<const double2*>(seg + 8 * i);  // a 64-byte line
-  const double2 a = q[0], b = q[1], c = q[2], d = q[3];
-  return {{a.x, a.y, b.x}, {b.y, c.x, c.y}, d.x};
+// (hertz_friction.hip, and the row writers of segment_linkers.hpp)
+__device__ inline bool row_is_pos_zero(const double* p, size_t c) {  // the three words of row c are all +0.0
+  return (__double_as_longlong(p[3 * c]) | __double_as_longlong(p[3 * c + 1]) | __double_as_longlong(p[3 * c + 2])) == 0;
 }
-// what the right end node receives of the linker force Fs acting at cp; the left one receives Fs - this (RED :206-221).
-// The `+` inside term2 is the reference's (the velocity map has `-`): DESIGN.md 5k.
-__device__ inline V3 segment_share(V3 x0, V3 x1, V3 cp, V3 Fs) {
-  const V3 lc = cp - x0, lr = x1 - x0;
-  const double iL = 1.0 / norm(lr);
-  const V3 t = lr * iL;
-  const V3 term1 = (dot(t, Fs) * lc) * iL;
-  const V3 term2 = (dot(lc, t) * (Fs + dot(t, Fs) * t)) * iL;
-  return term2 - term1;
-}
-
 // The frictional Hertzian law of one contact (sep <= 0, or NaN), after the contact-point velocities
 // (SpherocylinderSegmentSpherocylinderSegmentFrictionalHertzianContact.cpp:468-511): rel = v_cp,j - v_cp,i, n the
 // normal from i to j, td the pair's history row.  force is the one on body i; td the new history row.
 // hertz_friction.hip (rigid rods) and filament_contact.hip (flexible segments) call this one text.
-__device__ inline bool row_is_pos_zero(const double* p, size_t c) {  // the three words of row c are all +0.0
-  return (__double_as_longlong(p[3 * c]) | __double_as_longlong(p[3 * c + 1]) | __double_as_longlong(p[3 * c + 2])) == 0;
-}
-__device__ inline void store_row_nan(double* p, size_t c) {
-  const double q = __builtin_nan("");
-  store3(p, c, V3{q, q, q});
-}
-__device__ inline void reset_row(double* p, size_t c) {  // +0.0, written only where it is not +0.0 already
-  if (!row_is_pos_zero(p, c)) store3(p, c, V3{0.0, 0.0, 0.0});
-}
 struct FrictionContact {
   V3 force, td;
   bool capped;

@@ -8,10 +8,7 @@
 //                  end-segment correction (HP1.cpp:4395-4434, :4451-4490)                            one segment per lane
 //   node gather    each body adds the sums of its (segment, side) entries: no atomic on a force       one body per lane
 // Orders, byte counts and the wider WCA box: include/mundy_hip_segment_contact.h, DESIGN.md 5s.
-#include "mhip_internal.hpp"
-#include "force_device.hpp"
-#include "geom_device.hpp"
-
+#include "segment_linkers.hpp"
 #include "../../include/mundy_hip_segment_contact.h"
 
 #include <algorithm>
@@ -30,29 +27,16 @@ __global__ void __launch_bounds__(kBlock)
     const int2 ab = ends[e];  // checked against [0, n) at creation
     const V3 x0 = load3(x, ab.x), x1 = load3(x, ab.y);
     const double r = radius[e];
-    double2* q = reinterpret_cast<double2*>(seg + 8 * e);
-    q[0] = make_double2(x0.x, x0.y);
-    q[1] = make_double2(x0.z, x1.x);
-    q[2] = make_double2(x1.y, x1.z);
-    q[3] = make_double2(r, 0.0);
-    const Box b = aabb_segment(x0, x1, dmax(r, min_reach));
-    double* o = aabb + 6 * e;
-    o[0] = b.lo.x - skin, o[1] = b.lo.y - skin, o[2] = b.lo.z - skin;
-    o[3] = b.hi.x + skin, o[4] = b.hi.y + skin, o[5] = b.hi.z + skin;
+    store_segment_view(seg, aabb, e, x0, x1, r, dmax(r, min_reach), skin);
   }
 }
 
-// the two laws: the force magnitude at the signed separation s of two segments of radii ri, rj
+// the two laws: Hertz (segment_hertz, segment_linkers.hpp) at the signed separation, WCA at the centreline distance
 struct SegmentLaw {
   double E, nu, epsilon, sigma, cutoff;
 };
-__device__ inline double segment_hertz(const SegmentLaw& w, double ri, double rj, double s) {
-  const double Rs = (ri * rj) / (ri + rj);
-  const double Es = (w.E * w.E) / (w.E - w.E * w.nu * w.nu + w.E - w.E * w.nu * w.nu);
-  return hertz_force_magnitude(Es, Rs, s);
-}
-// the end-segment correction's Hertz magnitude: the same expression at sep = L - 2 r, Rs = r r / (r + r), with x^(3/2)
-// rounded once (force_device.hpp), so that it is the host's value in bits
+// the end-segment correction's Hertz magnitude: segment_hertz's expression at sep = L - 2 r, Rs = r r / (r + r), with
+// x^(3/2) rounded once (force_device.hpp), so that it is the host's value in bits
 __device__ inline double segment_hertz_end(const SegmentLaw& w, double r, double s) {
   const double Rs = (r * r) / (r + r);
   const double Es = (w.E * w.E) / (w.E - w.E * w.nu * w.nu + w.E - w.E * w.nu * w.nu);
@@ -75,35 +59,25 @@ __global__ void __launch_bounds__(kBlock)
   double dmax_ = 0.0;
   unsigned count = 0;
   for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < C; c += (size_t)gridDim.x * blockDim.x) {
-    // the list is read once per step
-    const int2 p{__builtin_nontemporal_load(pairs + 2 * c), __builtin_nontemporal_load(pairs + 2 * c + 1)};
-    if (static_cast<unsigned>(p.x) >= M || static_cast<unsigned>(p.y) >= M) {  // never dereferenced
-      sep[c] = __builtin_nan("");
-      store_row_nan(force, c);
-      store_row_nan(share, 2 * c);
-      store_row_nan(share, 2 * c + 1);
+    const int2 p = load_pair_once(pairs, c);
+    if (static_cast<unsigned>(p.x) >= M || static_cast<unsigned>(p.y) >= M) {
+      refuse_linker(sep, force, share, c);
       in_branch[c] = 1;
       continue;
     }
-    const SegmentRow a = load_segment(seg, p.x), b = load_segment(seg, p.y);
-    const SegSeg r = dist_segment_segment(a.p0, a.p1, b.p0, b.p1);
-    const double s = r.dist - (a.r + b.r);
+    const SegmentLinker k = measure_linker(seg, p);
+    const double s = k.s;
     sep[c] = s;
-    const bool in = KIND == MHIP_SEGMENT_CONTACT_HERTZ ? s < 0.0 : r.dist < law.cutoff;
+    const bool in = KIND == MHIP_SEGMENT_CONTACT_HERTZ ? s < 0.0 : k.r.dist < law.cutoff;
     in_branch[c] = in ? 1 : 0;
     if (!in) {
-      reset_row(force, c);
-      reset_row(share, 2 * c);
-      reset_row(share, 2 * c + 1);
+      reset_linker(force, share, c);
       continue;
     }
-    const V3 n = (r.cp2 - r.cp1) * (1.0 / r.dist);  // left to right (linker kernel :226); dist == 0: NaN rows
     // WCA: the distance as the reference recomputes it from the stored separation (...SegmentWCA.cpp:195-196)
-    const double fm = KIND == MHIP_SEGMENT_CONTACT_HERTZ ? segment_hertz(law, a.r, b.r, s) : segment_wca(law, s + (a.r + b.r));
-    const V3 F = (-fm) * n;  // on the left segment; the right one receives the negative
-    store3(force, c, F);
-    store3(share, 2 * c, segment_share(a.p0, a.p1, r.cp1, F));
-    store3(share, 2 * c + 1, segment_share(b.p0, b.p1, r.cp2, V3{-F.x, -F.y, -F.z}));
+    const double fm = KIND == MHIP_SEGMENT_CONTACT_HERTZ ? segment_hertz(law.E, law.nu, k.a.r, k.b.r, s)
+                                                         : segment_wca(law, s + (k.a.r + k.b.r));
+    store_linker_force(force, share, c, k, (-fm) * k.normal());
     dmax_ = -s > dmax_ ? -s : dmax_;
     ++count;
   }
@@ -111,9 +85,8 @@ __global__ void __launch_bounds__(kBlock)
   block_stat_add(count, stats + 1);
 }
 
-// One segment per lane: a0[e] = +0.0 + sum of (Fs - share), a1[e] = +0.0 + sum of share over the segment's entries in
-// ascending order (entries outside the force branch, whose rows are +0.0, are passed over: the same bits), then the end
-// correction.  sums[e] = (a0, a1): 48 bytes.
+// One segment per lane: sum_segment_entries (a linker outside the force branch is passed over on its byte of in_branch),
+// then the end correction.  sums[e] = (a0, a1): 48 bytes.
 template <int KIND>
 __global__ void __launch_bounds__(kBlock)
     k_segment_sums(size_t M, const int32_t* __restrict__ ptr, const int32_t* __restrict__ ent,
@@ -123,20 +96,8 @@ __global__ void __launch_bounds__(kBlock)
                    unsigned long long* __restrict__ stats) {
   double dmax_ = 0.0;
   for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < M; e += (size_t)gridDim.x * blockDim.x) {
-    V3 a0{0.0, 0.0, 0.0}, a1{0.0, 0.0, 0.0};
-    const int32_t lo = ptr[e], hi = ptr[e + 1];
-    for (int32_t j = lo; j < hi; ++j) {
-      const int32_t en = ent[j];
-      const size_t c = static_cast<size_t>(en >> 1);
-      // The rows of a linker outside the branch are +0.0, and a sum that started from +0.0 is never -0.0: adding them
-      // changes no bit, so one byte stands for 48 bytes of rows.
-      if (!in_branch[c]) continue;
-      const V3 F = load3(force, c);
-      const V3 Fs = (en & 1) ? V3{-F.x, -F.y, -F.z} : F;
-      const V3 sm = load3(share, static_cast<size_t>(en));  // row 2 c + side
-      a0 = a0 + (Fs - sm);
-      a1 = a1 + sm;
-    }
+    const SegmentSums q = sum_segment_entries(ptr, ent, e, force, share, [&](size_t c) { return !in_branch[c]; });
+    V3 a0 = q.a0, a1 = q.a1;
     if (end_correction[e]) {  // the missing neighbour of a chain's first or last segment (HP1.cpp:4367-4372)
       const SegmentRow s = load_segment(seg, e);
       const V3 d = s.p1 - s.p0;
@@ -181,18 +142,10 @@ using namespace mhip;
 struct mhip_segment_contacts {
   size_t n = 0, m = 0;
   mhip_segment_contact_params prm{};
-  mhip_broadphase_t bp = nullptr;
-  bool has_list = false;
-  size_t c = 0;  // length of the list
-  HandleBuffer ends, radius, end_correction, ex_ptr, ex_idx;
-  HandleBuffer seg, aabb, aabb_ref, sums;
-  HandleBuffer pairs, sep, force, share, in_branch;
+  LinkerList list;
+  HandleBuffer ends, radius, end_correction, sums;
+  HandleBuffer pairs, in_branch;
   HandleBuffer body_ptr, body_ent;  // body -> (segment << 1) | side
-  HandleBuffer inc_ptr, inc_ent;    // segment -> (linker << 1) | side
-  HandleBuffer cursor, ws;
-  ~mhip_segment_contacts() {
-    if (bp) (void)mhip_broadphase_destroy(bp);
-  }
   SegmentLaw law() const { return {prm.youngs_modulus, prm.poisson_ratio, prm.epsilon, prm.sigma, prm.cutoff}; }
   bool wca() const { return prm.kind == MHIP_SEGMENT_CONTACT_WCA; }
 };
@@ -203,7 +156,7 @@ int segment_view(mhip_segment_contacts_t h, const double* center, hipStream_t s)
   if (h->m == 0) return MHIP_SUCCESS;
   k_segment_view_ends<<<grid_for(h->m), kBlock, 0, s>>>(h->m, h->ends.as<int2>(), center, h->radius.as<double>(),
                                                         h->wca() ? 0.5 * h->prm.cutoff : 0.0, h->prm.skin,
-                                                        h->seg.as<double>(), h->aabb.as<double>());
+                                                        h->list.seg.as<double>(), h->list.aabb.as<double>());
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
 }
@@ -221,14 +174,9 @@ int mhip_segment_contacts_create(mhip_segment_contacts_t* handle, size_t n, size
   const mhip_segment_contact_params& p = *params;
   MHIP_REQUIRE(p.kind == MHIP_SEGMENT_CONTACT_HERTZ || p.kind == MHIP_SEGMENT_CONTACT_WCA, MHIP_ERR_INVALID_ARGUMENT,
                "unknown segment contact kind %d", p.kind);
-  MHIP_REQUIRE(std::isfinite(p.skin) && p.skin >= 0.0, MHIP_ERR_INVALID_ARGUMENT, "skin must be finite and >= 0, got %g",
-               p.skin);
-  if (p.kind == MHIP_SEGMENT_CONTACT_HERTZ) {
-    MHIP_REQUIRE(std::isfinite(p.youngs_modulus) && p.youngs_modulus > 0.0, MHIP_ERR_INVALID_ARGUMENT,
-                 "youngs_modulus must be finite and > 0, got %g", p.youngs_modulus);
-    MHIP_REQUIRE(p.poisson_ratio > 0.0 && p.poisson_ratio < 1.0, MHIP_ERR_INVALID_ARGUMENT,
-                 "poisson_ratio must lie in (0, 1), got %g", p.poisson_ratio);
-  } else {
+  const bool hertz = p.kind == MHIP_SEGMENT_CONTACT_HERTZ;
+  if (int e = check_linker_params(p.skin, p.youngs_modulus, p.poisson_ratio, hertz)) return e;
+  if (!hertz) {
     MHIP_REQUIRE(std::isfinite(p.epsilon) && p.epsilon >= 0.0, MHIP_ERR_INVALID_ARGUMENT,
                  "epsilon must be finite and >= 0, got %g", p.epsilon);
     MHIP_REQUIRE(std::isfinite(p.sigma) && p.sigma > 0.0, MHIP_ERR_INVALID_ARGUMENT, "sigma must be finite and > 0, got %g",
@@ -239,17 +187,15 @@ int mhip_segment_contacts_create(mhip_segment_contacts_t* handle, size_t n, size
   MHIP_REQUIRE(m == 0 || ends, MHIP_ERR_INVALID_ARGUMENT, "ends is null");
   MHIP_REQUIRE(n < (1ull << 30), MHIP_ERR_INVALID_ARGUMENT, "too many bodies for 32-bit segment ends");
   MHIP_REQUIRE(m < (1ull << 30), MHIP_ERR_INVALID_ARGUMENT, "too many segments for 31-bit incidence entries");
-  auto r_ok = [](double v) { return std::isfinite(v) && v > 0.0; };
-  MHIP_REQUIRE(radius || r_ok(radius_scalar), MHIP_ERR_INVALID_ARGUMENT, "radius must be finite and > 0, got %g",
-               radius_scalar);
+  MHIP_REQUIRE(radius || (std::isfinite(radius_scalar) && radius_scalar > 0.0), MHIP_ERR_INVALID_ARGUMENT,
+               "radius must be finite and > 0, got %g", radius_scalar);
   for (size_t e = 0; e < m; ++e) {
     const int32_t a = ends[2 * e], b = ends[2 * e + 1];
     MHIP_REQUIRE(a >= 0 && b >= 0 && static_cast<size_t>(a) < n && static_cast<size_t>(b) < n, MHIP_ERR_INVALID_ARGUMENT,
                  "segment %zu joins (%d, %d): an index outside [0, %zu)", e, a, b, n);
     MHIP_REQUIRE(a != b, MHIP_ERR_INVALID_ARGUMENT, "segment %zu joins body %d to itself", e, a);
     if (radius)
-      MHIP_REQUIRE(r_ok(radius[e]), MHIP_ERR_INVALID_ARGUMENT, "segment %zu: radius must be finite and > 0, got %g", e,
-                   radius[e]);
+      if (int err = check_segment_radius(e, radius[e])) return err;
   }
   // who may not pair with whom: for segment e every other segment incident to either of its end nodes
   // (DestroyBoundNeighbors.cpp:150-170), ascending, once each
@@ -285,29 +231,21 @@ int mhip_segment_contacts_create(mhip_segment_contacts_t* handle, size_t n, size
   h->m = m;
   h->prm = p;
   hipStream_t s = as_stream(stream);
-  if (int e = mhip_broadphase_create(&h->bp)) return e;
-  const size_t d = sizeof(double), big = std::max(n, m);
+  const size_t d = sizeof(double);
   int e = MHIP_SUCCESS;
+  // (cursor and ws serve the body incidence below as well: the larger of the two row counts)
+  if ((e = h->list.create(__func__, m, std::max(n, m), ex_ptr, ex_idx, s))) return e;
   if ((e = h->ends.reserve(m * sizeof(int2) + 8)) || (e = h->radius.reserve(m * d + 8)) ||
-      (e = h->end_correction.reserve(m + 8)) || (e = h->ex_ptr.reserve((m + 1) * sizeof(int32_t))) ||
-      (e = h->ex_idx.reserve(ex_idx.size() * sizeof(int32_t) + 8)) || (e = h->seg.reserve(8 * m * d + 8)) ||
-      (e = h->aabb.reserve(6 * m * d + 8)) || (e = h->aabb_ref.reserve(6 * m * d + 8)) ||
-      (e = h->sums.reserve(6 * m * d + 8)) || (e = h->body_ptr.reserve((n + 1) * sizeof(int32_t))) ||
-      (e = h->body_ent.reserve(2 * m * sizeof(int32_t) + 8)) || (e = h->inc_ptr.reserve((m + 1) * sizeof(int32_t))) ||
-      (e = h->cursor.reserve((big + 1) * sizeof(int32_t))) || (e = h->ws.reserve(scan_workspace_bytes(big) + 8)))
+      (e = h->end_correction.reserve(m + 8)) || (e = h->sums.reserve(6 * m * d + 8)) ||
+      (e = h->body_ptr.reserve((n + 1) * sizeof(int32_t))) || (e = h->body_ent.reserve(2 * m * sizeof(int32_t) + 8)))
     return e;
-  if ((e = upload(__func__, h->ex_ptr, ex_ptr.data(), (m + 1) * sizeof(int32_t), s))) return e;
   if (m > 0) {
     if ((e = upload(__func__, h->ends, ends, m * sizeof(int2), s))) return e;
     if ((e = upload(__func__, h->radius, rad.data(), m * d, s))) return e;
     if ((e = upload(__func__, h->end_correction, corr.data(), m, s))) return e;
-    if (!ex_idx.empty() && (e = upload(__func__, h->ex_idx, ex_idx.data(), ex_idx.size() * sizeof(int32_t), s))) return e;
   }
-  if ((e = mhip_broadphase_set_exclusions(h->bp, m, h->ex_ptr.as<int32_t>(), h->ex_idx.as<int32_t>(), ex_idx.size(),
-                                          stream)))
-    return e;
-  if ((e = build_incidence(n, m, PairEnds{h->ends.as<int2>()}, h->cursor.as<int32_t>(), h->body_ptr.as<int32_t>(),
-                           h->body_ent.as<int32_t>(), h->ws.ptr, s)))
+  if ((e = build_incidence(n, m, PairEnds{h->ends.as<int2>()}, h->list.cursor.as<int32_t>(), h->body_ptr.as<int32_t>(),
+                           h->body_ent.as<int32_t>(), h->list.ws.ptr, s)))
     return e;
   // the host arrays built here may go as soon as this returns
   if ((e = hip_status(__func__, hipStreamSynchronize(s)))) return e;
@@ -328,41 +266,19 @@ int mhip_segment_contacts_update(mhip_segment_contacts_t h, const double* center
   *rebuilt = 0;
   hipStream_t s = as_stream(stream);
   if (int e = segment_view(h, center, s)) return e;
-  const size_t m = h->m, d = sizeof(double);
+  LinkerList& l = h->list;
   int moved = 1;  // the first call builds
-  if (h->has_list && !force_rebuild)
-    if (int e = mhip_aabb_moved(m, h->aabb.as<double>(), h->aabb_ref.as<double>(), 0.5 * h->prm.skin, &moved, stream))
-      return e;
+  if (l.has_list && !force_rebuild)
+    if (int e = l.moved(h->m, h->prm.skin, &moved, s)) return e;
   if (!moved) return MHIP_SUCCESS;
   // rebuild (HP1.cpp:3053-3175): every pair of box-overlapping segments that share no node
-  mhip_broadphase_config cfg{};
-  cfg.search_kind = MHIP_SEARCH_AABB;
-  cfg.symmetric = 0;
-  cfg.buffer = 0.0;  // the boxes carry the skin
-  size_t c_new = 0;
   // (the search snapshots its `center` argument for mhip_broadphase_needs_rebuild, which this handle never asks: the
   //  boxes stand in for it, 6 m doubles where 3 m are read)
-  if (int e = mhip_broadphase_build(h->bp, &cfg, m, h->aabb.as<double>(), h->aabb.as<double>(), nullptr, &c_new, stream))
+  if (int e = l.rebuild(h->m, l.aabb.as<double>(), h->pairs, s, [&](size_t c_new) {
+        if (int e = h->in_branch.reserve(c_new + 8)) return e;
+        return c_new > 0 ? hip_status(__func__, hipMemsetAsync(h->in_branch.ptr, 0, c_new, s)) : MHIP_SUCCESS;
+      }))
     return e;
-  MHIP_REQUIRE(c_new < (1ull << 30), MHIP_ERR_RUNTIME, "too many linkers for 32-bit incidence entries");
-  int e = MHIP_SUCCESS;
-  if ((e = h->pairs.reserve(c_new * sizeof(int2) + 8)) || (e = h->inc_ent.reserve(2 * c_new * sizeof(int32_t) + 8)) ||
-      (e = h->sep.reserve(c_new * d + 8)) || (e = h->force.reserve(3 * c_new * d + 8)) ||
-      (e = h->share.reserve(6 * c_new * d + 8)) || (e = h->in_branch.reserve(c_new + 8)))
-    return e;
-  if ((e = mhip_broadphase_get_pairs(h->bp, h->pairs.as<int32_t>(), nullptr, nullptr, stream))) return e;
-  if (c_new > 0) {
-    MHIP_HIP(hipMemsetAsync(h->sep.ptr, 0, c_new * d, s));
-    MHIP_HIP(hipMemsetAsync(h->force.ptr, 0, 3 * c_new * d, s));
-    MHIP_HIP(hipMemsetAsync(h->share.ptr, 0, 6 * c_new * d, s));
-    MHIP_HIP(hipMemsetAsync(h->in_branch.ptr, 0, c_new, s));
-  }
-  if ((e = build_incidence(m, c_new, PairEnds{h->pairs.as<int2>()}, h->cursor.as<int32_t>(), h->inc_ptr.as<int32_t>(),
-                           h->inc_ent.as<int32_t>(), h->ws.ptr, s)))
-    return e;
-  if (m > 0) MHIP_HIP(hipMemcpyAsync(h->aabb_ref.ptr, h->aabb.ptr, 6 * m * d, hipMemcpyDeviceToDevice, s));
-  h->c = c_new;
-  h->has_list = true;
   *rebuilt = 1;
   return MHIP_SUCCESS;
 }
@@ -370,15 +286,16 @@ int mhip_segment_contacts_update(mhip_segment_contacts_t h, const double* center
 int mhip_segment_contacts_linker_pass(mhip_segment_contacts_t h, void* stats, mhip_stream_t stream) {
   MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "segment contacts handle is null");
   MHIP_REQUIRE(stats != nullptr, MHIP_ERR_INVALID_ARGUMENT, "stats is null");
-  MHIP_REQUIRE(h->has_list, MHIP_ERR_RUNTIME, "mhip_segment_contacts_linker_pass before mhip_segment_contacts_update");
+  MHIP_REQUIRE(h->list.has_list, MHIP_ERR_RUNTIME, "mhip_segment_contacts_linker_pass before mhip_segment_contacts_update");
   hipStream_t s = as_stream(stream);
   MHIP_HIP(hipMemsetAsync(stats, 0, 2 * sizeof(unsigned long long), s));
-  const size_t c = h->c;
+  const LinkerList& l = h->list;
+  const size_t c = l.c;
   if (h->m == 0 || c == 0) return MHIP_SUCCESS;
   dispatch<MHIP_SEGMENT_CONTACT_WCA, MHIP_SEGMENT_CONTACT_HERTZ>(h->prm.kind, [&](auto kind) {
     k_segment_linkers<decltype(kind)::value><<<grid_for(c), kBlock, 0, s>>>(
-        c, h->m, h->pairs.as<int>(), h->seg.as<double>(), h->law(), h->sep.as<double>(), h->force.as<double>(),
-        h->share.as<double>(), h->in_branch.as<uint8_t>(), static_cast<unsigned long long*>(stats));
+        c, h->m, h->pairs.as<int>(), l.seg.as<double>(), h->law(), l.sep.as<double>(), l.force.as<double>(),
+        l.share.as<double>(), h->in_branch.as<uint8_t>(), static_cast<unsigned long long*>(stats));
   });
   MHIP_LAUNCH_CHECK();
   return MHIP_SUCCESS;
@@ -388,15 +305,16 @@ int mhip_segment_contacts_reduce(mhip_segment_contacts_t h, double* force, int a
                                  mhip_stream_t stream) {
   MHIP_REQUIRE(h != nullptr, MHIP_ERR_INVALID_ARGUMENT, "segment contacts handle is null");
   MHIP_REQUIRE(force != nullptr || h->n == 0, MHIP_ERR_INVALID_ARGUMENT, "force is null");
-  MHIP_REQUIRE(h->has_list, MHIP_ERR_RUNTIME, "mhip_segment_contacts_reduce before mhip_segment_contacts_update");
+  MHIP_REQUIRE(h->list.has_list, MHIP_ERR_RUNTIME, "mhip_segment_contacts_reduce before mhip_segment_contacts_update");
   hipStream_t s = as_stream(stream);
   const size_t n = h->n, m = h->m;
+  const LinkerList& l = h->list;
   if (n == 0) return MHIP_SUCCESS;
   if (m > 0) {
     dispatch<MHIP_SEGMENT_CONTACT_WCA, MHIP_SEGMENT_CONTACT_HERTZ>(h->prm.kind, [&](auto kind) {
       k_segment_sums<decltype(kind)::value><<<grid_for(m), kBlock, 0, s>>>(
-          m, h->inc_ptr.as<int32_t>(), h->inc_ent.as<int32_t>(), h->in_branch.as<uint8_t>(), h->force.as<double>(),
-          h->share.as<double>(), h->seg.as<double>(), h->end_correction.as<uint8_t>(), h->law(), h->sums.as<double>(),
+          m, l.inc_ptr.as<int32_t>(), l.inc_ent.as<int32_t>(), h->in_branch.as<uint8_t>(), l.force.as<double>(),
+          l.share.as<double>(), l.seg.as<double>(), h->end_correction.as<uint8_t>(), h->law(), h->sums.as<double>(),
           static_cast<unsigned long long*>(stats));
     });
     MHIP_LAUNCH_CHECK();
@@ -417,7 +335,7 @@ int mhip_segment_contacts_force(mhip_segment_contacts_t h, const double* center,
   MHIP_REQUIRE(stats != nullptr, MHIP_ERR_INVALID_ARGUMENT, "stats is null");
   MHIP_REQUIRE(center != nullptr || h->m == 0, MHIP_ERR_INVALID_ARGUMENT, "center is null");
   MHIP_REQUIRE(force != nullptr || h->n == 0, MHIP_ERR_INVALID_ARGUMENT, "force is null");
-  MHIP_REQUIRE(h->has_list, MHIP_ERR_RUNTIME, "mhip_segment_contacts_force before mhip_segment_contacts_update");
+  MHIP_REQUIRE(h->list.has_list, MHIP_ERR_RUNTIME, "mhip_segment_contacts_force before mhip_segment_contacts_update");
   if (int e = segment_view(h, center, as_stream(stream))) return e;
   if (int e = mhip_segment_contacts_linker_pass(h, stats, stream)) return e;
   return mhip_segment_contacts_reduce(h, force, accumulate, stats, stream);
@@ -428,13 +346,13 @@ int mhip_segment_contacts_get(mhip_segment_contacts_t h, mhip_segment_contact_fi
   MHIP_REQUIRE(out != nullptr, MHIP_ERR_INVALID_ARGUMENT, "fields is null");
   out->num_bodies = h->n;
   out->num_segments = h->m;
-  out->num_pairs = h->has_list ? h->c : 0;
-  out->pairs = h->has_list ? h->pairs.as<int32_t>() : nullptr;
-  out->sep = h->sep.as<double>();
-  out->force = h->force.as<double>();
-  out->share = h->share.as<double>();
-  out->seg = h->seg.as<double>();
-  out->aabb = h->aabb.as<double>();
+  out->num_pairs = h->list.has_list ? h->list.c : 0;
+  out->pairs = h->list.has_list ? h->pairs.as<int32_t>() : nullptr;
+  out->sep = h->list.sep.as<double>();
+  out->force = h->list.force.as<double>();
+  out->share = h->list.share.as<double>();
+  out->seg = h->list.seg.as<double>();
+  out->aabb = h->list.aabb.as<double>();
   return MHIP_SUCCESS;
 }
 

@@ -66,6 +66,34 @@ def _finite_nonneg(value, name):
     return v
 
 
+def _finite(value, name, ok, what):
+    v = float(value)
+    if not (math.isfinite(v) and ok(v)):
+        raise ValueError("%s must be finite and %s, got %r" % (name, what, v))
+    return v
+
+
+def _read_field(ptr, rows, width, name=None):
+    """a copy of `rows` rows of `width` 8-byte words at the library pointer `ptr` as a new device tensor: float64
+    [rows, width] ([rows] for width 1), "share" viewed as [rows, 2, 3]; "pairs": int32 [rows, 2], one word per pair"""
+    if name == "pairs":
+        out, words = torch.empty((rows, 2), dtype=torch.int32, device="cuda"), rows
+    else:
+        shape = (rows, width) if width > 1 else (rows,)
+        out, words = torch.empty(shape, dtype=torch.float64, device="cuda"), rows * width
+    if words:
+        capi.check(capi.load().mhip_deep_copy(words, C.c_void_p(out.data_ptr()), C.c_void_p(ptr), _stream()))
+    return out.view(rows, 2, 3) if name == "share" else out
+
+
+def _write_field(ptr, rows, width, value, name):
+    """the inverse of _read_field for a float64 field: `value` (a device tensor of the field's size) over the library's"""
+    if name == "pairs" or value.numel() != rows * width:
+        raise ValueError("%s: expected %d float64 values" % (name, rows * width))
+    if rows:
+        capi.check(capi.load().mhip_deep_copy(rows * width, C.c_void_p(ptr), _ptr(value, name=name), _stream()))
+
+
 def check_dict_spec(spec, what, keys, optional=()):
     """a keyword given as a dict: it is one, holds no key outside `keys`, and every key not in `optional`"""
     if not isinstance(spec, dict):
@@ -2222,21 +2250,13 @@ class Filaments(_Handle):
             capi.check(capi.load().mhip_filaments_get_inertial(self._h, C.byref(got)))
             if not getattr(got, name):
                 raise RuntimeError("%s before set_inertial" % name)
-            w = 3 if name == "acceleration" else 1
-            out = torch.empty((self.n, w) if w > 1 else (self.n,), dtype=torch.float64, device="cuda")
-            if self.n:
-                capi.check(capi.load().mhip_deep_copy(self.n * w, _ptr(out), C.c_void_p(getattr(got, name)), _stream()))
-            return out
+            return _read_field(getattr(got, name), self.n, 3 if name == "acceleration" else 1)
         if name not in capi.FILAMENT_FIELDS:
             raise ValueError("unknown filament field %r" % (name,))
         fields = capi.FilamentFields()
         capi.check(capi.load().mhip_filaments_get(self._h, C.byref(fields)))
         rows = self.num_filaments if name == "phase" else self.n
-        w = self._WIDTH.get(name, 1)
-        out = torch.empty((rows, w) if w > 1 else (rows,), dtype=torch.float64, device="cuda")
-        if rows:
-            capi.check(capi.load().mhip_deep_copy(rows * w, _ptr(out), C.c_void_p(getattr(fields, name)), _stream()))
-        return out
+        return _read_field(getattr(fields, name), rows, self._WIDTH.get(name, 1))
 
 
 # ---- frictional Hertzian contacts between filament segments (mhip_filament_contacts_*) ---------------------------------
@@ -2250,21 +2270,16 @@ def check_filament_contacts(n, skin, youngs_modulus, poisson_ratio, mu, damping=
     (mundy_hip_filament_inertial.h), which reads neither mu nor the dampings"""
     if law not in FILAMENT_CONTACT_LAWS:
         raise ValueError("law must be one of %s, got %r" % (", ".join(sorted(FILAMENT_CONTACT_LAWS)), law))
-    def number(v, name, ok, what):
-        v = float(v)
-        if not (math.isfinite(v) and ok(v)):
-            raise ValueError("%s must be finite and %s, got %r" % (name, what, v))
-        return v
-    skin = number(skin, "skin", lambda v: v >= 0.0, ">= 0")
-    E = number(youngs_modulus, "youngs_modulus", lambda v: v > 0.0, "> 0")
-    nu = number(poisson_ratio, "poisson_ratio", lambda v: 0.0 < v < 1.0, "in (0, 1)")
-    mu = number(mu, "mu", lambda v: v >= 0.0, ">= 0")
+    skin = _finite(skin, "skin", lambda v: v >= 0.0, ">= 0")
+    E = _finite(youngs_modulus, "youngs_modulus", lambda v: v > 0.0, "> 0")
+    nu = _finite(poisson_ratio, "poisson_ratio", lambda v: 0.0 < v < 1.0, "in (0, 1)")
+    mu = _finite(mu, "mu", lambda v: v >= 0.0, ">= 0")
     if not (isinstance(damping, (tuple, list)) and len(damping) == 2):
         raise ValueError("damping must be (normal, tangential), got %r" % (damping,))
-    gn = number(damping[0], "damping[0]", lambda v: v >= 0.0, ">= 0")
-    gt = number(damping[1], "damping[1]", lambda v: v >= 0.0, ">= 0")
-    rho = number(density, "density", lambda v: v >= 0.0, ">= 0")
-    hdt = -1.0 if history_dt is None else number(history_dt, "history_dt", lambda v: v >= 0.0, ">= 0")
+    gn = _finite(damping[0], "damping[0]", lambda v: v >= 0.0, ">= 0")
+    gt = _finite(damping[1], "damping[1]", lambda v: v >= 0.0, ">= 0")
+    rho = _finite(density, "density", lambda v: v >= 0.0, ">= 0")
+    hdt = -1.0 if history_dt is None else _finite(history_dt, "history_dt", lambda v: v >= 0.0, ">= 0")
     if isinstance(bonded_exclusion, bool) or not isinstance(bonded_exclusion, (int, np.integer)) or bonded_exclusion < 1:
         raise ValueError("bonded_exclusion must be an integer >= 1, got %r" % (bonded_exclusion,))
     r = None
@@ -2371,24 +2386,11 @@ class FilamentContacts(_Handle):
 
     def field(self, name):
         """a copy of one field (capi.FILAMENT_CONTACT_FIELDS) as a device tensor; pairs int32 [c, 2], share [c, 2, 3]"""
-        ptr, rows, w = self._span(name)
-        if name == "pairs":
-            out = torch.empty((rows, 2), dtype=torch.int32, device="cuda")
-            words = rows  # one 8-byte word per pair
-        else:
-            out = torch.empty((rows, w) if w > 1 else (rows,), dtype=torch.float64, device="cuda")
-            words = rows * w
-        if words:
-            capi.check(capi.load().mhip_deep_copy(words, C.c_void_p(out.data_ptr()), C.c_void_p(ptr), _stream()))
-        return out.view(rows, 2, 3) if name == "share" else out
+        return _read_field(*self._span(name), name)
 
     def set_field(self, name, value):
         """overwrites one float64 field of the handle with `value` (a device tensor of the field's size): a restart"""
-        ptr, rows, w = self._span(name)
-        if name == "pairs" or value.numel() != rows * w:
-            raise ValueError("%s: expected %d float64 values" % (name, rows * w))
-        if rows:
-            capi.check(capi.load().mhip_deep_copy(rows * w, C.c_void_p(ptr), _ptr(value, name=name), _stream()))
+        _write_field(*self._span(name), value, name)
 
 
 # ---- frictionless contacts between backbone segments (mhip_segment_contacts_*, include/mundy_hip_segment_contact.h) -----
@@ -2432,10 +2434,7 @@ def check_segment_contacts(n, spec):
     ra, r0 = _spring_param(spec["radius"], m, "segment radius", True)
 
     def number(name, ok, what):
-        v = float(spec[name])
-        if not (math.isfinite(v) and ok(v)):
-            raise ValueError("%s must be finite and %s, got %r" % (name, what, v))
-        return v
+        return _finite(spec[name], name, ok, what)
     skin = number("skin", lambda v: v >= 0.0, ">= 0")
     hertz = spec["kind"] == "hertz"
     # (the parameters of the other law are carried, not checked: the library reads only its own kind's)
@@ -2544,14 +2543,4 @@ class SegmentContacts(_Handle):
             raise ValueError("unknown segment contact field %r" % (name,))
         f = self.fields()
         rows = self.num_segments if name in ("seg", "aabb") else int(f.num_pairs)
-        w = capi.SEGMENT_CONTACT_FIELDS[name]
-        if name == "pairs":
-            out = torch.empty((rows, 2), dtype=torch.int32, device="cuda")
-            words = rows  # one 8-byte word per pair
-        else:
-            out = torch.empty((rows, w) if w > 1 else (rows,), dtype=torch.float64, device="cuda")
-            words = rows * w
-        if words:
-            capi.check(capi.load().mhip_deep_copy(words, C.c_void_p(out.data_ptr()), C.c_void_p(getattr(f, name)),
-                                                  _stream()))
-        return out.view(rows, 2, 3) if name == "share" else out
+        return _read_field(getattr(f, name), rows, capi.SEGMENT_CONTACT_FIELDS[name], name)
