@@ -246,6 +246,7 @@ int mhip_aabb_moved(size_t n, const double* aabb, const double* aabb_ref, double
  *     the force -grad U of U = -1/2 k r_max^2 ln(1 - (L / r_max)^2) (the potential HP1.cpp:3323-3333 weighs): attractive.
  *     NgpHP1.cpp:1105-1122 applies the opposite sign; this library does not.  A spring with L >= r_max
  *     (or L NaN) has no force: its term is NaN and it is counted in *overstretched.
+ *   MHIP_SPRING_FENEWCA  r = r_max:           the Kremer-Grest bond; fm and its statistics: mundy_hip_bending.h
  *   with d = x_j - x_i, L = sqrt(d.d) (right fold), body i receives +fm d and body j -fm d.
  * k [m] / r [m] per spring [host], or NULL: then the scalar stands for every spring.  pairs [m][2] int32 [host].
  * create copies them, refuses (MHIP_ERR_INVALID_ARGUMENT, before any HIP call) an index outside [0, n), a spring from a
@@ -257,6 +258,7 @@ int mhip_aabb_moved(size_t n, const double* aabb, const double* aabb_ref, double
  * without force; *max_length [device, 1 double] = the longest L (+0.0 without springs), order independent. */
 #define MHIP_SPRING_HOOKEAN 0
 #define MHIP_SPRING_FENE 1
+#define MHIP_SPRING_FENEWCA 2
 typedef struct mhip_springs* mhip_springs_t;
 int mhip_springs_create(mhip_springs_t* handle, size_t n, size_t m, const int32_t* pairs /*[host] m x 2*/, int type,
                         const double* k /*[host] m or NULL*/, double k_scalar, const double* r /*[host] m or NULL*/,

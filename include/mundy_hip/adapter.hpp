@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../mundy_hip.h"
+#include "../mundy_hip_bending.h"
 #include "../mundy_hip_contact_force.h"
 #include "../mundy_hip_hydro_periphery.h"
 #include "../mundy_hip_hydro_solve.h"
@@ -1214,6 +1215,8 @@ class Springs {
   ~Springs() { mhip_springs_destroy(h_); }
   Springs(const Springs&) = delete;
   Springs& operator=(const Springs&) = delete;
+  /// MHIP_SPRING_FENEWCA only: the WCA part's epsilon and sigma (> 0; 1 and 1 until set), for every later force
+  void set_wca(double epsilon, double sigma) { check(mhip_springs_set_wca(h_, epsilon, sigma)); }
   /// force [n][3] (device); the statistics stay on the device until read
   void compute_forces(const double* center, double* force, mhip_stream_t stream = nullptr) {
     check(mhip_springs_force(h_, center, force, overstretched_.data(), max_length_.data(), stream));
@@ -1228,6 +1231,42 @@ class Springs {
   mhip_springs_t h_ = nullptr;
   DeviceArray<int> overstretched_;
   DeviceArray<double> max_length_;
+};
+
+/// Angular springs (mhip_angular_springs_*, mundy_hip_bending.h; AngularSpringsKernel.cpp:107-197): host triplets [m][3]
+/// = (end a, end b, centre c), k / rest_angle per triplet (host vectors, empty = the scalar for every triplet)
+class AngularSprings {
+ public:
+  AngularSprings(size_t num_bodies, const std::vector<int32_t>& triplets, const std::vector<double>& k, double k_scalar,
+                 const std::vector<double>& rest_angle, double rest_angle_scalar, mhip_stream_t stream = nullptr)
+      : m_(triplets.size() / 3) {
+    check(mhip_angular_springs_create(&h_, num_bodies, m_, triplets.data(), k.empty() ? nullptr : k.data(), k_scalar,
+                                      rest_angle.empty() ? nullptr : rest_angle.data(), rest_angle_scalar, stream));
+  }
+  ~AngularSprings() { mhip_angular_springs_destroy(h_); }
+  AngularSprings(const AngularSprings&) = delete;
+  AngularSprings& operator=(const AngularSprings&) = delete;
+  /// into force [n][3] (device); degenerate [device, 1 int] and max_deviation [device, 1 double]
+  void force(const double* center, double* force, bool accumulate, int* degenerate, double* max_deviation,
+             mhip_stream_t stream = nullptr) {
+    check(mhip_angular_springs_force(h_, center, force, accumulate ? 1 : 0, degenerate, max_deviation, stream));
+  }
+  /// the bodies were permuted: new_of_old [n] (device)
+  void renumber(const int32_t* new_of_old, mhip_stream_t stream = nullptr) {
+    check(mhip_angular_springs_renumber(h_, new_of_old, stream));
+  }
+  /// the cosines of the rest angles the kernel uses [m], on the host
+  std::vector<double> cos_rest() const {
+    std::vector<double> c(m_);
+    check(mhip_angular_springs_get(h_, nullptr, nullptr, c.data()));
+    return c;
+  }
+  size_t size() const { return m_; }
+  mhip_angular_springs_t handle() const { return h_; }
+
+ private:
+  mhip_angular_springs_t h_ = nullptr;
+  size_t m_;
 };
 
 /// compute_hookean_spring_forces (NgpHP1.cpp:1054-1069): force [n][3] of a Hookean spring set

@@ -62,6 +62,8 @@ struct StepStats {
   double kinetic_energy = 0.0;           // FilamentStepper::set_inertial: of the velocities the corrector wrote
   double max_spring_length = 0.0;        // SphereChainStepper: the longest spring at the start of the step
   int springs_overstretched = 0;         // SphereChainStepper: springs past their limit (FENE: L >= r_max)
+  int angular_degenerate = 0;            // ... set_angular_springs: triplets with an arm of zero length (no force)
+  double max_angle_deviation = 0.0;      // ... the largest |cos(theta) - cos(rest_angle)| at the force evaluation
   // SphereChainStepper with crosslinkers, a periphery or active springs: the step's statistics array
   int crosslinker_binds = 0, crosslinker_unbinds = 0;  // this step's KMC events
   int crosslinker_periphery_bound = 0;                 // crosslinkers bound to a periphery site after the KMC step
@@ -767,10 +769,12 @@ class DistributedSpherocylinderStepper {
 ///     reference's order (HP1.cpp:4733-4741): KMC -> active sampling -> springs -> crosslinker springs -> periphery
 ///     -> active dipoles; their statistics share one device array that resolve() downloads once
 ///   set_hydrodynamics [+ set_hydro_periphery]     u_hydro of force(), added to U_ext after the noise (:4744-4803)
+///   set_angular_springs, set_spring_wca     the bending term after the springs, and the WCA part of FENE-WCA bonds
+///     (mundy_hip_bending.h); the angular statistics have a device array of their own
 class SphereChainStepper {
  public:
   /// host arrays: center [n][3], radius [n], mob_trans [n]; spring_pairs [m][2] with one stiffness and one rest length
-  /// (Hookean) or r_max (FENE) for all, spring_type MHIP_SPRING_*; keys [n] of the noise or empty = the body indices
+  /// (Hookean) or r_max (FENE, FENE-WCA) for all, spring_type MHIP_SPRING_*; keys [n] of the noise or empty = the body indices
   /// (the counters start at 0)
   SphereChainStepper(const std::vector<double>& center, const std::vector<double>& radius,
                      const std::vector<double>& mob_trans, double dt, double search_buffer,
@@ -891,6 +895,14 @@ class SphereChainStepper {
     have_wall_ = true;
     use_stats();
   }
+  /// The WCA part of MHIP_SPRING_FENEWCA backbone springs (epsilon, sigma > 0; 1 and 1 until set)
+  void set_spring_wca(double epsilon, double sigma) { springs_.set_wca(epsilon, sigma); }
+  /// Angular springs (mech::AngularSprings; host triplets [ma][3] = (end, end, centre), one stiffness and one rest angle
+  /// for all): the term of forces() after the springs and before the crosslinker springs (SpringsUpdated.cpp:1844)
+  void set_angular_springs(const std::vector<int32_t>& triplets, double k, double rest_angle) {
+    angular_.reset(new AngularSprings(n_, triplets, {}, k, {}, rest_angle));
+    angular_stats_ = DeviceVector(2);  // (max deviation, the degenerate count in the low int of the second word)
+  }
   /// Active force dipoles (mech::ActiveSprings; host pairs [ma][2]): sampled in forces() before the springs, their
   /// force its last term, their timers advanced by resolve()
   void set_active_springs(const std::vector<int32_t>& pairs, double sigma, double kon, double koff) {
@@ -935,8 +947,8 @@ class SphereChainStepper {
   }
   /// The force stage in the reference's order (HP1.cpp:4733-4741) into force() [n][3]: crosslinker KMC, active sampling,
   /// backbone segment contacts (Hertz mode: added to the contact force that contact_forces() left there), springs (added
-  /// to what is there in Hertz mode or after the segment contacts), crosslinker springs, periphery, active dipoles, every
-  /// term after the springs added to them.  Returns force() for the caller to accumulate further
+  /// to what is there in Hertz mode or after the segment contacts), angular springs, crosslinker springs, periphery,
+  /// active dipoles, every term after the springs added to them.  Returns force() for the caller to accumulate further
   /// terms into.
   double* forces() {
     const bool first_term = hertz_ && sphere_contacts_;  // force() holds D f
@@ -954,6 +966,8 @@ class SphereChainStepper {
     } else {
       springs_.compute_forces(x, f);
     }
+    if (angular_)
+      angular_->force(x, f, true, reinterpret_cast<int*>(angular_stats_.data() + 1), angular_stats_.data());
     if (xl_) xl_->force(x, f, true, stat_int(5, 0), stat_double(4));
     if (have_wall_)
       check(mhip_periphery_force(&wall_, n_, x, radius_.data(), f, 1, stat_int(7, 0), stat_double(6), nullptr));
@@ -1055,6 +1069,7 @@ class SphereChainStepper {
   /// the optional stages' handles (null before their setter)
   const Crosslinkers* crosslinkers() const { return xl_.get(); }
   const ActiveSprings* active_springs() const { return active_.get(); }
+  const AngularSprings* angular_springs() const { return angular_.get(); }
   /// the smallest pivot of set_hydro_periphery's inversion
   double min_pivot() const { return min_pivot_; }
 
@@ -1125,6 +1140,11 @@ class SphereChainStepper {
       st.active_switches_on = i[16];
       st.active_switches_off = i[17];
     }
+    if (angular_) {
+      const std::vector<double> a = angular_stats_.download();
+      st.max_angle_deviation = a[0];
+      std::memcpy(&st.angular_degenerate, &a[1], sizeof(int));
+    }
     if (backbone_) {
       const std::vector<std::uint64_t> b = backbone_stats_.download();
       std::memcpy(&st.max_segment_overlap, &b[0], sizeof(double));
@@ -1162,6 +1182,8 @@ class SphereChainStepper {
   bool have_wall_ = false;
   mhip_periphery wall_{};
   std::unique_ptr<ActiveSprings> active_;
+  std::unique_ptr<AngularSprings> angular_;
+  DeviceVector angular_stats_;
   std::unique_ptr<Hydrodynamics> hydro_;
   std::unique_ptr<HydroPeriphery> hydro_periphery_;
   int hydro_kind_ = MHIP_HYDRO_RPYC;

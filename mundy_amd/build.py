@@ -15,7 +15,8 @@ HEADERS = ["mhip_internal.hpp", "geom_device.hpp", "ellipsoid_device.hpp", "elli
            os.path.join("..", "..", "include", "mundy_hip_periphery_binding.h"),
            os.path.join("..", "..", "include", "mundy_hip_segment_contact.h"),
            os.path.join("..", "..", "include", "mundy_hip_hydro_solve.h"),
-           os.path.join("..", "..", "include", "mundy_hip_filament_inertial.h")]
+           os.path.join("..", "..", "include", "mundy_hip_filament_inertial.h"),
+           os.path.join("..", "..", "include", "mundy_hip_bending.h")]
 # -ffp-contract=off: a*b+c stays two roundings so per-element results are bit-identical to the scalar reference order
 FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

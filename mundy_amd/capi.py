@@ -13,7 +13,7 @@ SEARCH_SPHERES, SEARCH_AABB = 0, 1
 SEARCH_METHOD_AUTO, SEARCH_METHOD_GRID, SEARCH_METHOD_MORTON_LBVH = 0, 1, 2
 SPACE_UNCONSTRAINED, SPACE_LOWER_BOUND, SPACE_UPPER_BOUND, SPACE_BOUNDED = 0, 1, 2, 3
 RESIDUAL_PROJECTED_DIFF, RESIDUAL_PROJECTED_GRADIENT = 0, 1
-SPRING_HOOKEAN, SPRING_FENE = 0, 1
+SPRING_HOOKEAN, SPRING_FENE, SPRING_FENEWCA = 0, 1, 2
 PERIPHERY_SPHERE, PERIPHERY_ELLIPSOID, PERIPHERY_ELLIPSOID_FAST = 0, 1, 2
 HYDRO_STOKES, HYDRO_RPY, HYDRO_RPYC = 0, 1, 2
 HYDRO_CHUNK = 1024  # MHIP_HYDRO_CHUNK: the width of the summation order's chunks
@@ -410,6 +410,16 @@ FILAMENT_INERTIAL_SIGNATURES = {
     "mhip_filaments_get_inertial": [_vp, C.POINTER(FilamentInertialFields)],
     "mhip_filament_contacts_set_law": [_vp, _i],
 }
+# include/mundy_hip_bending.h, a header of its own for the same reason: name -> argtypes, every function returns int
+# status.  tests/test_bending_host.py checks this table against that header and the library.
+BENDING_SIGNATURES = {
+    "mhip_springs_set_wca": [_vp, _d, _d],
+    "mhip_angular_springs_create": [C.POINTER(_vp), _sz, _sz, _vp, _vp, _d, _vp, _d, _vp],
+    "mhip_angular_springs_force": [_vp, _vp, _vp, _i, _vp, _vp, _vp],
+    "mhip_angular_springs_renumber": [_vp, _vp, _vp],
+    "mhip_angular_springs_get": [_vp, _vp, _vp, _vp],
+    "mhip_angular_springs_destroy": [_vp],
+}
 OTHER_SYMBOLS = {"mhip_last_error": ([], C.c_char_p), "mhip_version": ([], C.c_int),
                  "mhip_release_cached_workspaces": ([], C.c_int)}
 
@@ -431,7 +441,7 @@ def load():
         for name, argtypes in (list(SIGNATURES.items()) + list(PERIPHERY_SIGNATURES.items()) +
                                list(CONTACT_FORCE_SIGNATURES.items()) + list(PERIPHERY_BINDING_SIGNATURES.items()) +
                                list(SEGMENT_CONTACT_SIGNATURES.items()) + list(HYDRO_SOLVE_SIGNATURES.items()) +
-                               list(FILAMENT_INERTIAL_SIGNATURES.items())):
+                               list(FILAMENT_INERTIAL_SIGNATURES.items()) + list(BENDING_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = C.c_int

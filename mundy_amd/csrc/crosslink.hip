@@ -435,6 +435,8 @@ int mhip_crosslinkers_create(mhip_crosslinkers_t* handle, size_t n, size_t m, co
                              double unbind_rate, double kt, double capture_radius, mhip_stream_t stream) {
   MHIP_REQUIRE(handle != nullptr, MHIP_ERR_INVALID_ARGUMENT, "handle is null");
   *handle = nullptr;
+  MHIP_REQUIRE(type != MHIP_SPRING_FENEWCA, MHIP_ERR_INVALID_ARGUMENT,
+               "crosslinkers take no FENE-WCA springs: the reference's binding rates have no such branch");
   MHIP_REQUIRE(type == MHIP_SPRING_HOOKEAN || type == MHIP_SPRING_FENE, MHIP_ERR_INVALID_ARGUMENT,
                "unknown spring type %d", type);
   MHIP_REQUIRE(m == 0 || left, MHIP_ERR_INVALID_ARGUMENT, "left is null");

@@ -30,7 +30,7 @@ void dispatch_bools(bool a, bool b, F&& f) {  // f(std::bool_constant<a>{}, std:
 // A source lists item i of m at bodies: src(i, f) calls f(body, entry) for each.  build_incidence: count -> exclusive
 // scan -> fill -> per-body sort into ptr[0 .. n], ent, every body's list ascending (the fill order depends on atomic
 // arrival).  deg: n + 1 ints of scratch; ws: scan_workspace_bytes(n).  m == 0: ptr all zero, no launches.
-// Every source of the library is one of the three below, and chain.hip instantiates the build for each.
+// Every source of the library is one of the four below, and chain.hip instantiates the build for each.
 struct PairEnds {  // entry (s << 1) | side of pair s at body pairs[s][side]
   const int2* pairs;
   template <class F>
@@ -56,6 +56,21 @@ struct ListedAtBody {  // entry c at body at[c] where that is a body (>= 0: a ne
   __device__ void operator()(size_t c, F&& f) const {
     const int32_t b = at[c];
     if (b >= 0 && other[c] != b) f(b, static_cast<int32_t>(c));
+  }
+};
+// One angular spring: the two ends (roles 0 and 1) and the centre (role 2), the reference's BEAM_3 node order
+// (AngularSpringsKernel.cpp:125-133), padded to one 16-byte load.
+struct alignas(16) Triplet {
+  int32_t a, b, c, pad;
+};
+struct TripletEnds {  // entry (t << 2) | role of triplet t at its end a (role 0), end b (1) and centre c (2)
+  const Triplet* triplets;
+  template <class F>
+  __device__ void operator()(size_t t, F&& f) const {
+    const Triplet q = triplets[t];
+    f(q.a, static_cast<int32_t>(t << 2));
+    f(q.b, static_cast<int32_t>((t << 2) | 1));
+    f(q.c, static_cast<int32_t>((t << 2) | 2));
   }
 };
 template <class SRC>
@@ -136,13 +151,31 @@ __device__ inline void wave_stat_add(int v, int* dst) {
 // A spring of length L = |d| pulls with fm d.  Hookean (r = rest length): fm = k (L - r) (1 / L) (NgpHP1.cpp:1054-1069,
 // its association).  FENE (r = r_max), -grad of U = -1/2 k r_max^2 ln(1 - (L / r_max)^2): attractive, and no force (NaN)
 // at L >= r_max -- the caller counts that spring as overstretched where !(L < r).
+// FENE-WCA (r = r_max), the Kremer-Grest bond in the reference's expressions and association
+// (FENEWCASpringsKernel.cpp:147-176): the length is clamped to r_max - 1e-4 (its hard-coded epsilon_reg), so the bond
+// never goes without force -- the caller counts it as overstretched where !(L < r - kFeneWcaClamp).  The WCA cutoff
+// 2^(1/6) sigma is the handle's, computed once on the host: no pow here.
 struct SpringTerm {
   double L, fm;
 };
+struct WcaParams {
+  double epsilon = 1.0, sigma = 1.0, cutoff = 0.0;
+};
+constexpr double kFeneWcaClamp = 1e-4;
 template <int TYPE>
-__device__ inline SpringTerm spring_term(V3 d, double k, double r) {
+__device__ inline SpringTerm spring_term(V3 d, double k, double r, WcaParams w = WcaParams{}) {
   const double L = sqrt(dot(d, d));
   if (TYPE == MHIP_SPRING_HOOKEAN) return {L, k * (L - r) * (1.0 / L)};
+  if (TYPE == MHIP_SPRING_FENEWCA) {
+    const double rm = r - kFeneWcaClamp;
+    const double La = rm < L ? rm : L;  // std::min(L, rm): a NaN L stays NaN
+    const double spring = k * La / (1.0 - (La / r) * (La / r));
+    const double rho2 = w.sigma * w.sigma / (La * La);
+    const double rho6 = rho2 * rho2 * rho2;
+    const double rho12 = rho6 * rho6;
+    const double lj = La < w.cutoff ? 6.0 * 4.0 * w.epsilon * (2.0 * rho12 - rho6) / La : 0.0;
+    return {L, (spring - lj) * (1.0 / L)};
+  }
   const double q = L / r;
   return {L, (L < r) ? k / (1.0 - q * q) : __builtin_nan("")};
 }

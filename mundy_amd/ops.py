@@ -1174,6 +1174,8 @@ def integrate_euler(dt, velocity, center, quat=None):
 
 # ---- bead-spring chains with thermal noise (NgpHP1.cpp:3802-3990, BrownianMotion.cpp, SpringsUpdated.cpp) ------------
 SPRING_TYPES = {"hookean": capi.SPRING_HOOKEAN, "fene": capi.SPRING_FENE}
+# (the crosslinkers' kinds, which their checks read; a backbone spring set has the Kremer-Grest bond as well)
+BACKBONE_SPRING_TYPES = dict(SPRING_TYPES, fenewca=capi.SPRING_FENEWCA)
 
 
 def _spring_param(value, m, name, positive):
@@ -1196,8 +1198,8 @@ def _spring_param(value, m, name, positive):
 
 def check_springs(pairs, kind, k, r, n):
     """host-side validation of a spring set -> (pairs int32 [m, 2] host, type, k array / None, k0, r array / None, r0)"""
-    if kind not in SPRING_TYPES:
-        raise ValueError("spring type must be 'hookean' or 'fene', got %r" % (kind,))
+    if kind not in BACKBONE_SPRING_TYPES:
+        raise ValueError("spring type must be 'hookean', 'fene' or 'fenewca', got %r" % (kind,))
     p = pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
     if p.size == 0:
         p = p.reshape(0, 2)
@@ -1209,14 +1211,24 @@ def check_springs(pairs, kind, k, r, n):
         raise ValueError("spring pairs: a spring from a body to itself (spring %d)" % int(np.argmax(p[:, 0] == p[:, 1])))
     m = p.shape[0]
     ka, k0 = _spring_param(k, m, "spring constant k", False)
-    fene = kind == "fene"
+    fene = kind != "hookean"
     ra, r0 = _spring_param(r, m, "r_max" if fene else "rest length r0", fene)
-    return np.ascontiguousarray(p, dtype=np.int32), SPRING_TYPES[kind], ka, k0, ra, r0
+    return np.ascontiguousarray(p, dtype=np.int32), BACKBONE_SPRING_TYPES[kind], ka, k0, ra, r0
+
+
+def check_wca(kind, epsilon, sigma):
+    """host-side validation of the WCA parameters of a "fenewca" spring set -> (epsilon, sigma)"""
+    if kind != "fenewca":
+        raise ValueError("WCA epsilon and sigma belong to 'fenewca' springs, not %r" % (kind,))
+    _, eps = _spring_param(float(epsilon), 1, "WCA epsilon", True)
+    _, sig = _spring_param(float(sigma), 1, "WCA sigma", True)
+    return eps, sig
 
 
 class Springs(_Handle):
-    """A spring set between n bodies (mhip_springs_*): kind "hookean" (r = rest length) or "fene" (r = r_max); k and r
-    numbers or per-spring arrays.  force(center) -> (force [n, 3], overstretched [1] int32, max_length [1] float64), the
+    """A spring set between n bodies (mhip_springs_*): kind "hookean" (r = rest length), "fene" or "fenewca" (r = r_max;
+    the latter the Kremer-Grest bond of mundy_hip_bending.h, epsilon = sigma = 1 until set_wca); k and r numbers or
+    per-spring arrays.  force(center) -> (force [n, 3], overstretched [1] int32, max_length [1] float64), the
     two statistics left on the device.  Every body sums its terms in ascending spring index from +0.0."""
     _destroy = "mhip_springs_destroy"
 
@@ -1229,6 +1241,13 @@ class Springs(_Handle):
         capi.check(capi.load().mhip_springs_create(C.byref(h), self.n, p.shape[0], cp(p), t, cp(ka), k0, cp(ra), r0,
                                                    _stream()))
         self._h = h
+        self.wca = (1.0, 1.0) if kind == "fenewca" else None
+
+    def set_wca(self, epsilon, sigma):
+        """the WCA part of a "fenewca" set (mhip_springs_set_wca): epsilon, sigma finite and > 0, for every later force"""
+        eps, sig = check_wca(self.kind, epsilon, sigma)
+        capi.check(capi.load().mhip_springs_set_wca(self._h, eps, sig))
+        self.wca = (eps, sig)
 
     def force(self, center, out=None, stats=None):
         """stats: an optional int32 [1] / float64 [1] pair (overstretched, max_length) to write into"""
@@ -1242,6 +1261,94 @@ class Springs(_Handle):
         capi.check(capi.load().mhip_springs_force(self._h, _ptr(center, cols=3, name="center"), _ptr(f, name="out"),
                                                   C.c_void_p(over.data_ptr()), C.c_void_p(mx.data_ptr()), _stream()))
         return f, over, mx
+
+
+def check_angular_springs(n, triplets, k, rest_angle):
+    """host-side validation of an angular spring set (no library call) -> (triplets int32 [m, 3] host: end a, end b,
+    centre c; k array / None, k0, rest_angle array / None, rest_angle0)"""
+    t = triplets.detach().cpu().numpy() if isinstance(triplets, torch.Tensor) else np.asarray(triplets)
+    if t.size == 0:
+        t = t.reshape(0, 3)
+    if t.ndim != 2 or t.shape[1] != 3 or not (t.dtype.kind in "iu" or t.size == 0):
+        raise ValueError("angular spring triplets must be integers of shape [m, 3], got %s %s" % (t.dtype, t.shape))
+    if t.size and (t.min() < 0 or t.max() >= n):
+        raise ValueError("angular spring triplets: an index outside [0, %d)" % n)
+    same = (t[:, 0] == t[:, 1]) | (t[:, 0] == t[:, 2]) | (t[:, 1] == t[:, 2])
+    if same.any():
+        raise ValueError("angular spring triplets: the three bodies of triplet %d are not distinct" % int(np.argmax(same)))
+    m = t.shape[0]
+    if m >= 2 ** 29:
+        raise ValueError("angular spring triplets: %d triplets, the incidence entries hold fewer than 2^29" % m)
+    ka, k0 = _spring_param(k, m, "angular spring constant k", False)
+    aa, a0 = _spring_param(rest_angle, m, "rest angle", False)
+    vals = aa if aa is not None else np.array([a0])
+    if (vals > math.pi).any():
+        raise ValueError("rest angle must lie in [0, pi], got %r" % float(vals[vals > math.pi][0]))
+    return np.ascontiguousarray(t, dtype=np.int32), ka, k0, aa, a0
+
+
+class AngularSprings(_Handle):
+    """m angular springs between n bodies (mhip_angular_springs_*, mundy_hip_bending.h): triplets [m, 3] = (end a, end b,
+    centre c), U = 1/2 k (cos(theta) - cos(rest_angle))^2 with theta the angle at c; k and rest_angle numbers or
+    per-triplet arrays.  force(center) -> (force [n, 3], degenerate [1] int32, max_deviation [1] float64), the two
+    statistics left on the device.  Every body sums its rows in ascending triplet index from +0.0."""
+    _destroy = "mhip_angular_springs_destroy"
+
+    def __init__(self, n, triplets, k, rest_angle):
+        t, ka, k0, aa, a0 = check_angular_springs(n, triplets, k, rest_angle)
+        self.n, self.num_triplets = int(n), t.shape[0]
+        h = C.c_void_p()
+        cp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        capi.check(capi.load().mhip_angular_springs_create(C.byref(h), self.n, t.shape[0], cp(t), cp(ka), k0, cp(aa), a0,
+                                                           _stream()))
+        self._h = h
+
+    def _get(self, what):
+        m = self.num_triplets
+        out = np.empty((m, 3), dtype=np.int32) if what == 0 else np.empty(m, dtype=np.float64)
+        args = [None, None, None]
+        args[what] = out.ctypes.data_as(C.c_void_p)
+        capi.check(capi.load().mhip_angular_springs_get(self._h, *args))
+        return out
+
+    @property
+    def triplets(self):
+        """int32 [m, 3] host: the triplets as the handle holds them (after any renumbering)"""
+        return self._get(0)
+
+    @property
+    def k(self):
+        return self._get(1)
+
+    @property
+    def cos_rest(self):
+        """float64 [m] host: the cosines of the rest angles the kernel uses, to the bit"""
+        return self._get(2)
+
+    def force(self, center, out=None, accumulate=False, stats=None):
+        """written to (or, accumulate=True, added into) out [n, 3]; stats: an optional int32 [1] / float64 [1] pair
+        (degenerate, max_deviation) to write into"""
+        if tuple(center.shape) != (self.n, 3):
+            raise ValueError("center must have shape [%d, 3], got %s" % (self.n, tuple(center.shape)))
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs out")
+            out = torch.empty((self.n, 3), dtype=torch.float64, device=center.device)
+        if stats is None:
+            stats = (torch.empty(1, dtype=torch.int32, device=center.device),
+                     torch.empty(1, dtype=torch.float64, device=center.device))
+        deg, dev = stats
+        capi.check(capi.load().mhip_angular_springs_force(
+            self._h, _ptr(center, cols=3, name="center"), _ptr(out, cols=3, name="out"), 1 if accumulate else 0,
+            _ptr(deg, torch.int32, name="degenerate"), _ptr(dev, name="max_deviation"), _stream()))
+        return out, deg, dev
+
+    def renumber(self, new_of_old):
+        """the bodies were permuted: new_of_old int32 [n]"""
+        if tuple(new_of_old.shape) != (self.n,):
+            raise ValueError("new_of_old must have shape [%d], got %s" % (self.n, tuple(new_of_old.shape)))
+        capi.check(capi.load().mhip_angular_springs_renumber(self._h, _ptr(new_of_old, torch.int32, name="new_of_old"),
+                                                             _stream()))
 
 
 def _u64(t, name):
@@ -1680,6 +1787,8 @@ def check_crosslinkers(n, left, right, sites, kind, k, r, bind_rate, unbind_rate
     def host(a):
         return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
+    if kind == "fenewca":
+        raise ValueError("crosslinkers take no 'fenewca' springs: the reference's binding rates have no FENE-WCA branch")
     if kind not in SPRING_TYPES:
         raise ValueError("crosslinker spring type must be 'hookean' or 'fene', got %r" % (kind,))
     if left is None:
@@ -1732,6 +1841,8 @@ def check_periphery_sites(spec, kind, unbind_rate, capture_radius):
     capture_radius=None) for crosslinkers of spring type `kind` (no library call) -> (points float64 [P, 3] host,
     bind_rate, k, r, unbind_rate, capture_radius); unbind_rate and capture_radius default to the crosslinkers' own"""
     check_dict_spec(spec, "periphery_sites", _PERIPHERY_SITE_KEYS, optional=("unbind_rate", "capture_radius"))
+    if kind == "fenewca":
+        raise ValueError("crosslinkers take no 'fenewca' springs: the reference's binding rates have no FENE-WCA branch")
     if kind not in SPRING_TYPES:
         raise ValueError("crosslinker spring type must be 'hookean' or 'fene', got %r" % (kind,))
     pts = spec["points"]

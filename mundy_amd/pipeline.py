@@ -144,6 +144,9 @@ class StepStats:
     max_overlap: float = 0.0  # contact_model="hertz": max(0, -sep) over the step's contacts (what dt is chosen from)
     num_born: int = 0  # growth mode: bodies that divided this step (their children are rows n_before + k)
     max_spring_length: float = 0.0  # springs=: the longest spring at the start of the step
+    springs_overstretched: int = 0  # ... "fenewca": the bonds clamped at r_max - 1e-4 (the other FENE kind raises)
+    angular_degenerate: int = 0        # angular_springs=: triplets with an arm of zero length (the step raises)
+    max_angle_deviation: float = 0.0   # ... the largest |cos(theta) - cos(rest_angle)| at this step's force evaluation
     num_sliding: int = 0  # hertz_friction=: contacts whose tangential force was capped at mu |F_n| this step
     crosslinker_bound: int = 0    # crosslinkers=: doubly bound crosslinkers after this step's KMC
     crosslinker_binds: int = 0    # ... right heads that bound this step
@@ -174,7 +177,7 @@ class ContactStepper:
                  poisson_ratio=0.3, growth_rate=None, division_length=None, capacity=None, ids=None, springs=None,
                  brownian_kt=None, rng_keys=None, rng_counter=None, hertz_friction=None, hertz_damping=(0.0, 0.0),
                  hertz_density=1.0, crosslinkers=None, periphery=None, active_forces=None, hydrodynamics=None,
-                 backbone_collision=None):
+                 backbone_collision=None, angular_springs=None, spring_wca=None):
         """kind = "sphere" | "spherocylinder" | "mixed".  Mixed systems (BASELINE configs[4]) pass kinds [n] int32
         (0 sphere, 1 spherocylinder, 2 ellipsoid) and shape [n, 3] = (r,-,-) / (r,L,-) / (r1,r2,r3) instead of
         radius / length.
@@ -246,7 +249,15 @@ class ContactStepper:
         with an end node that belongs to no other segment (the reference's "first or last element in chain"), a byte mask
         [m] or False overrides it.  contact_model = "none" (only with backbone_collision): no sphere list, narrow phase,
         solve or sweep; U = U_ext, num_contacts = 0 and body_contact_force() raises -- the reference's configuration.
-        With "lcp" and "hertz" the segment term is one more force of the force stage."""
+        With "lcp" and "hertz" the segment term is one more force of the force stage.
+        springs of kind "fenewca" are the Kremer-Grest bond (FENE + WCA; mundy_hip_bending.h): r is r_max,
+        spring_wca = (epsilon, sigma), both > 0, default (1, 1) as the reference hard-codes them.  Such a bond never goes
+        without force: a step reports the clamped ones in springs_overstretched and does not raise.
+        angular_springs = (triplets [m, 3], k, rest_angle): the three-body bending term U = 1/2 k (cos(theta) -
+        cos(rest_angle))^2 of the reference's AngularSpringsKernel (ops.AngularSprings; synth.chain_triplets lists a
+        chain's triplets: end, end, centre); k >= 0 and rest_angle in [0, pi] numbers or per-triplet arrays.  A force term
+        after the springs and before the crosslinker springs; the chain step (spheres, free space), with or without
+        springs=.  A triplet with a zero arm has no force: the step raises."""
         if kind not in ("sphere", "spherocylinder", "mixed"):
             raise ValueError("kind must be 'sphere', 'spherocylinder' or 'mixed'")
         if contact_model not in ("lcp", "hertz", "none"):
@@ -275,10 +286,20 @@ class ContactStepper:
         backbone_spec = None
         if backbone_collision is not None:  # (checked before anything reaches the device)
             backbone_spec = self._check_backbone(chain_only, center.shape[0], springs, backbone_collision)
+        bending_spec = None
+        if angular_springs is not None:  # (checked before anything reaches the device)
+            bending_spec = self._check_bending(chain_only, center.shape[0], angular_springs)
+        wca_spec = None
+        if spring_wca is not None:  # (checked before anything reaches the device)
+            if not isinstance(spring_wca, (tuple, list)) or len(spring_wca) != 2:
+                raise ValueError("spring_wca must be (epsilon, sigma)")
+            if springs is None or not isinstance(springs, (tuple, list)) or len(springs) != 4:
+                raise ValueError("spring_wca needs springs=(pairs, 'fenewca', k, r_max)")
+            wca_spec = ops.check_wca(springs[1], *spring_wca)
         hydro_spec = None
         if hydrodynamics is not None:  # (checked before anything reaches the device)
             if (springs is None and brownian_kt is None and crosslinkers is None and periphery is None and
-                    active_forces is None and backbone_collision is None):
+                    active_forces is None and backbone_collision is None and angular_springs is None):
                 raise ValueError("hydrodynamics belongs to the chain step: pass springs= or brownian_kt= (0.0: no noise)")
             self._check_chain_only("hydrodynamics", "the kernels are free-space", *chain_only)
             hydro_spec = ops.check_hydrodynamics(hydrodynamics, center.shape[0])
@@ -315,7 +336,7 @@ class ContactStepper:
         elif division_length is not None or capacity is not None or ids is not None:
             raise ValueError("division_length, capacity and ids belong to growth mode: pass growth_rate")
         self.chain = (springs is not None or brownian_kt is not None or crosslinkers is not None or
-                      nucleus_spec is not None or backbone_spec is not None)
+                      nucleus_spec is not None or backbone_spec is not None or bending_spec is not None)
         if self.chain:  # (checked before anything reaches the device)
             chain_spec = self._check_chain(kind, center.shape[0], periodic_box, friction, contact_cutoff, springs,
                                            brownian_kt, rng_keys, rng_counter)
@@ -381,6 +402,8 @@ class ContactStepper:
         self.cutoff_fallbacks = 0
         self.ids = self.springs = self.rng_keys = self.rng_counter = self.crosslinkers = None
         self.xl_sources = self.xl_sites = self.periphery = self.active = self.hydro = self.backbone = None
+        self.angular = None
+        self._spring_wca = wca_spec
         if self.growth:
             self._init_growth(growth_rate, division_length, capacity, ids, search_buffer)
         if self.chain:
@@ -395,6 +418,8 @@ class ContactStepper:
             self._init_hydro(*hydro_spec)
         if backbone_spec is not None:
             self._init_backbone(backbone_spec)
+        if bending_spec is not None:
+            self._init_bending(bending_spec)
         # the springs' own term, added to F = D f or to the segment contacts' force (the spring kernel overwrites)
         if (self.hydro_contact_forces or self.backbone is not None) and self.springs is not None:
             self._spring_term = torch.zeros((n, 3), dtype=torch.float64, device=center.device)
@@ -402,7 +427,8 @@ class ContactStepper:
         # _snapshot_<mode>() / _restore_<mode>(saved) / _renumber_<mode>(perm, inv) hooks in this order
         on = dict(growth=self.growth, friction=self.hertz_friction is not None, springs=self.springs is not None,
                   crosslinkers=self.crosslinkers is not None, periphery=self.periphery is not None,
-                  active=self.active is not None, hydro=self.hydro is not None, backbone=self.backbone is not None)
+                  active=self.active is not None, hydro=self.hydro is not None, backbone=self.backbone is not None,
+                  bending=self.angular is not None)
         self._modes = [m for m, v in on.items() if v]
 
     @staticmethod
@@ -535,7 +561,7 @@ class ContactStepper:
     def _init_chain(self, spec, kt, keys, counter):
         n, dev = self.center.shape[0], self.center.device
         self._spring_spec = spec
-        self.springs = ops.Springs(n, *spec) if spec is not None else None
+        self.springs = self._new_springs() if spec is not None else None
         self.brownian_kt = kt
         self.rng_keys = (torch.arange(n, dtype=torch.int64, device=dev) if keys is None else
                          torch.from_numpy(keys).to(dev))
@@ -545,6 +571,12 @@ class ContactStepper:
         self.spring_force = torch.zeros((n, 3), dtype=torch.float64, device=dev)
         self.u_ext = torch.zeros((n, 6), dtype=torch.float64, device=dev)
         self.velocity = None
+
+    def _new_springs(self):
+        sp = ops.Springs(self.center.shape[0], *self._spring_spec)
+        if self._spring_wca is not None:
+            sp.set_wca(*self._spring_wca)
+        return sp
 
     def _snapshot_springs(self):
         return None  # (the set is fixed: nothing to save)
@@ -558,7 +590,31 @@ class ContactStepper:
         p, skind, k, r = self._spring_spec
         self._spring_spec = (np.ascontiguousarray(inv.cpu().numpy()[p], dtype=np.int32), skind, k, r)
         self.springs.close()
-        self.springs = ops.Springs(self.center.shape[0], *self._spring_spec)
+        self.springs = self._new_springs()
+
+    # -- angular springs (AngularSpringsKernel.cpp:107-197; SpringsUpdated.cpp:1843-1862) ------------------------------------
+    @staticmethod
+    def _check_bending(chain_only, n, spec):
+        ContactStepper._check_chain_only("angular_springs", "no minimum-image angles", *chain_only)
+        if not isinstance(spec, (tuple, list)) or len(spec) != 3:
+            raise ValueError("angular_springs must be (triplets, k, rest_angle)")
+        t, ka, k0, aa, a0 = ops.check_angular_springs(n, *spec)
+        return t, (ka if ka is not None else k0), (aa if aa is not None else a0)
+
+    def _init_bending(self, spec):
+        self.angular = ops.AngularSprings(self.center.shape[0], *spec)
+        # (max_angle_deviation, angular_degenerate in the low int32 of the second word): an array of its own, read with
+        # the chain step's -- the layout of that one is shared with the C++ apps and stays as it is
+        self._bending_stats = torch.zeros(2, dtype=torch.float64, device=self.center.device)
+
+    def _snapshot_bending(self):
+        return None  # (the set is fixed: nothing to save)
+
+    def _restore_bending(self, saved):
+        pass
+
+    def _renumber_bending(self, perm, inv):
+        self.angular.renumber(inv)  # the three indices of every triplet; order, k and rest angles stay
 
     # -- crosslinkers that bind and unbind (HP1.cpp:3264-3748, :4728-4739) ------------------------------------------------
     _XL_KEYS = ("left", "right", "sites", "kind", "k", "r", "bind_rate", "unbind_rate", "kt", "capture_radius", "skin",
@@ -873,13 +929,13 @@ class ContactStepper:
 
     def _force_stage(self, external_force):
         """the force stage in the reference's order (HP1.cpp:4733-4741): crosslinker KMC, active sampling, backbone
-        segment contacts, springs, crosslinker springs, periphery, active force dipoles, external force; every term after
-        the first that writes is added into self.spring_force.  The segment list is brought up to date first, on the
+        segment contacts, springs, angular springs, crosslinker springs, periphery, active force dipoles, external force;
+        every term after the first that writes is added into self.spring_force.  The segment list is brought up to date first, on the
         positions of the start of the step.  With no such term the caller's external_force (or None: no force at all) is
         returned as it is, not copied.  With hydrodynamics contact_forces the buffer already holds the contact force
         F = D f (contact_forces()), the first term as in the reference, and every term here is added to it:
-        F = (((((D f + F_backbone) + F_spring) + F_crosslinker) + F_periphery) + F_active) + F_ext, each + one rounding,
-        a term that is off left out."""
+        F = ((((((D f + F_backbone) + F_spring) + F_angular) + F_crosslinker) + F_periphery) + F_active) + F_ext, each + one
+        rounding, a term that is off left out."""
         st, force, written = self._chain_stats, self.spring_force, self.hydro_contact_forces
         if self.backbone is not None:
             self._backbone_rebuilt = self.backbone.update(self.center, force_rebuild=self._backbone_stale)
@@ -898,6 +954,11 @@ class ContactStepper:
         elif self.springs is not None:
             self.springs.force(self.center, out=force,
                                stats=(stat(st, "springs_overstretched"), stat(st, "max_spring_length")))
+            written = True
+        if self.angular is not None:  # (SpringsUpdated.cpp:1844: one execute over both spring parts)
+            bs = self._bending_stats
+            self.angular.force(self.center, out=force, accumulate=written,
+                               stats=(bs.view(torch.int32)[2:3], bs[0:1]))
             written = True
         if self.crosslinkers is not None:
             self.crosslinkers.force(self.center, out=force, accumulate=written,
@@ -1413,9 +1474,16 @@ class ContactStepper:
         """the chain step's statistics into st: one read of the statistics array, and one of the segment contacts' own"""
         got = read_stats(self._chain_stats)  # the one read of the step
         st.max_overlap, st.max_spring_length = got["max_overlap"], got["max_spring_length"]
-        if got["springs_overstretched"]:
+        st.springs_overstretched = got["springs_overstretched"]
+        # (a FENE-WCA bond is clamped, never without force: its count is reported)
+        if got["springs_overstretched"] and self.springs.kind != "fenewca":
             raise RuntimeError("%d FENE spring(s) stretched to L >= r_max: no force (reduce dt)"
                                % got["springs_overstretched"])
+        if self.angular is not None:
+            h = self._bending_stats.cpu()
+            st.max_angle_deviation, st.angular_degenerate = float(h[0]), int(h.view(torch.int32)[2])
+            if st.angular_degenerate:
+                raise RuntimeError("%d angular spring(s) with an arm of zero length: no force" % st.angular_degenerate)
         if self.crosslinkers is not None:
             st.crosslinker_binds, st.crosslinker_unbinds = got["crosslinker_binds"], got["crosslinker_unbinds"]
             self.crosslinker_bound += st.crosslinker_binds - st.crosslinker_unbinds

@@ -315,3 +315,14 @@ def backbone_segments(node_ptr):
         raise ValueError("node_ptr must be a non-decreasing 1-d array, got %r" % (node_ptr,))
     first = np.concatenate([np.arange(a, b - 1) for a, b in zip(ptr[:-1], ptr[1:])] or [np.zeros(0, np.int64)])
     return np.ascontiguousarray(np.stack([first, first + 1], axis=1).astype(np.int32))
+
+
+def chain_triplets(node_ptr):
+    """the angular springs of contiguous chains (ChainOfSprings.cpp:436-467): one for every interior bead i + 1 of a
+    chain, in the reference's BEAM_3 node order, ends first and centre last -> triplets int32 [m, 3] = (i, i + 2, i + 1),
+    in bead order"""
+    ptr = np.asarray(node_ptr, dtype=np.int64)
+    if ptr.ndim != 1 or ptr.size < 1 or (np.diff(ptr) < 0).any():
+        raise ValueError("node_ptr must be a non-decreasing 1-d array, got %r" % (node_ptr,))
+    first = np.concatenate([np.arange(a, b - 2) for a, b in zip(ptr[:-1], ptr[1:])] or [np.zeros(0, np.int64)])
+    return np.ascontiguousarray(np.stack([first, first + 2, first + 1], axis=1).astype(np.int32))
